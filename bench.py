@@ -5,7 +5,7 @@ emb_dim 64, batch 65 536, fp32, MLP [256, 128] -> 1; synthetic seeded tables / w
 A "step" = one forward of one batch through the product path (BasicNCF.forward on int64 positions ->
 ncf_score_fused through the C ABI), inputs already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -95,6 +95,15 @@ def make_model(device):
                 m.weight.uniform_(-bound, bound, generator=g)
                 m.bias.uniform_(-bound, bound, generator=g)
     return model
+
+
+def dump_outputs(directory, arrays, rank=0):
+    """--dump-outputs DIR: every array as DIR/<name>.npy in float32 (rank r > 0: <name>_rank<r>.npy)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        fname = name if rank == 0 else f"{name}_rank{rank}"
+        np.save(os.path.join(directory, fname + ".npy"), t.detach().float().cpu().numpy())
 
 
 def make_batches(device, rank, zipf_users=False):
@@ -293,20 +302,22 @@ def run_cfg2(args, ctx):
         ctx.barrier()
         t0 = time.perf_counter()
         for k in range(args.steps):
-            step(k)
+            out = step(k)
         ctx.barrier()
         elapsed = time.perf_counter() - t0
         native.check_oob(device)
+        last_out = out.clone() if getattr(args, "dump_outputs", None) else None   # what the last timed step returned
         # The same steps also as HIP-graph launches of up to 32 steps over the resident index batches (every rank its own graph: replicas
         # share nothing).  A step is one kernel either way; what the graph removes is the host's part of the FIRST step of the timed
         # region (the GPU idles behind the synchronisation until Python has walked a whole forward) — 3-7 % of a 20-step run, nothing
         # at 400 steps.  With several ranks every decision below is taken collectively (a rank that could not capture takes all of them
         # back to the eager figure), so the ranks never disagree on the number of barriers.
         elapsed_eager = ctx.max_over_ranks(elapsed)
-        elapsed_graph, graph_err, steps_per_launch = None, None, None
+        elapsed_graph, graph_err, steps_per_launch, graph_last = None, None, None, None
         if os.environ.get("NCF_CFG2_NO_GRAPH") != "1":
             gr = gouts = None
             spl = next(pl for pl in range(min(args.steps, 32), 0, -1) if args.steps % pl == 0)
+            k0 = args.steps - spl                  # the graph holds the LAST spl steps of the eager sequence: both forms end on the same step
             try:                                   # capture: no collective in here
                 cur = torch.cuda.current_stream(device)
                 side = torch.cuda.Stream(device=device)
@@ -317,10 +328,10 @@ def run_cfg2(args, ctx):
                 torch.cuda.synchronize()
                 gr = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gr):
-                    gouts = [step(k) for k in range(spl)]
+                    gouts = [step(k0 + k) for k in range(spl)]
                 gr.replay()
                 torch.cuda.synchronize()
-                if not torch.equal(gouts[spl - 1], step(spl - 1)):
+                if not torch.equal(gouts[spl - 1], step(k0 + spl - 1)):
                     raise RuntimeError("graph replay differs from the eager step")
             except Exception as exc:   # noqa: BLE001 — never take the line down: the eager timing stands
                 graph_err = str(exc)
@@ -337,7 +348,8 @@ def run_cfg2(args, ctx):
                 still = True
                 try:
                     native.check_oob(device)
-                    still = bool(torch.equal(gouts[spl - 1], step(spl - 1)) and torch.equal(gouts[0], step(0)))   # after the timed replays
+                    graph_last = gouts[spl - 1].clone()
+                    still = bool(torch.equal(gouts[spl - 1], step(k0 + spl - 1)) and torch.equal(gouts[0], step(k0)))   # after the timed replays
                 except Exception as exc:   # noqa: BLE001
                     still, graph_err = False, str(exc)
                 if not still and graph_err is None:
@@ -350,6 +362,10 @@ def run_cfg2(args, ctx):
                 graph_err = "another rank could not capture its graph"
             del gr, gouts
     elapsed = elapsed_eager if elapsed_graph is None else min(elapsed_eager, elapsed_graph)
+    if getattr(args, "dump_outputs", None):
+        # the reported form's last timed step (the graph form's output is verified bit-equal to the eager step above)
+        graph_reported = elapsed_graph is not None and elapsed_graph <= elapsed_eager
+        dump_outputs(args.dump_outputs, {"scores": graph_last if graph_reported else last_out}, rank)
 
     # --- roofline of the dominant kernel (the kernels run on torch's current stream, so torch.cuda.Event brackets them)
     packed = model._packed_mlp()
@@ -582,7 +598,14 @@ def main():
     ap.add_argument("--zipf-users", action="store_true", help="cfg2: Zipf(1.05) user ids instead of uniform ones (its own profile context)")
     ap.add_argument("--workload", default=None, choices=["cfg2", "cfg2_emb128", "cfg3", "cfg4", "cfg5", "train2"],
                     help="one config alone (cfg2 = the headline line without other_configs); default: headline + other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline path returned in its last timed step as DIR/scores.npy "
+                         "(float32, [65536, 1]; seeded inputs: identical from run to run with the same arguments)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs is not None and args.workload not in (None, "cfg2"):
+        ap.error("--dump-outputs writes the headline workload's outputs (cfg2): run it without --workload or with --workload cfg2")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus is not None and args.gpus > 1:
             sys.exit(launch_ranks(args, sys.argv[1:]))

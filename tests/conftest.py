@@ -55,8 +55,61 @@ def pytest_terminal_summary(terminalreporter, exitstatus, config):
         pass
 
 
+def hashed_weight(shape, salt, bound):
+    """Deterministic float32 weights in [-bound, bound) from an integer hash of (element index, salt): the same bits on any
+    machine and numpy version (no RNG stream involved), so a fixture can store the recipe instead of the values."""
+    n = int(np.prod(shape))
+    h = (np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B1) + np.uint64(salt) * np.uint64(0x85EBCA77)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(15)
+    h = (h * np.uint64(0x2C1B3C6D)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(12)
+    h = (h * np.uint64(0x297A2D39)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(15)
+    u = (h >> np.uint64(8)).astype(np.float64) / float(1 << 24)
+    return ((2.0 * u - 1.0) * float(bound)).astype(np.float32).reshape(shape)
+
+
+# CPU fingerprint of the goldens' summation order: fp32 linear layers (forward, and the two transposed products of backward)
+# at the shapes the goldens exercise and ATen's vectorised reductions (sums, softmax, cosine similarity), one thread, on
+# hashed inputs.  tests/golden/blas_probe.npz holds the SHA-256 of each result as computed where the goldens were made.
+BLAS_PROBE_SHAPES = [(64, 60, 8), (64, 40, 8), (700, 600, 64), (700, 400, 128), (700, 128, 256), (700, 256, 128), (48, 24, 16),
+                     (512, 64, 256), (512, 256, 1), (64, 20, 16), (16, 2094, 128), (96, 256, 128)]
+
+
+def blas_probe_arrays(torch=torch):
+    arrays = {}
+    for n, (M, K, N) in enumerate(BLAS_PROBE_SHAPES):
+        x = torch.from_numpy(hashed_weight((M, K), 7 * n + 1, 1.0))
+        w = torch.from_numpy(hashed_weight((N, K), 7 * n + 2, K ** -0.5))
+        b = torch.from_numpy(hashed_weight((N,), 7 * n + 3, 0.5))
+        g = torch.from_numpy(hashed_weight((M, N), 7 * n + 4, 1.0))
+        arrays[f"linear_{M}x{K}x{N}"] = torch.nn.functional.linear(x, w, b).numpy()
+        arrays[f"gw_{M}x{K}x{N}"] = g.t().mm(x).numpy()
+        arrays[f"gx_{M}x{K}x{N}"] = g.mm(w).numpy()
+        arrays[f"sum_{M}x{K}"] = torch.cat([x.sum(0), x.sum(1)]).numpy()
+        arrays[f"softmax_{M}x{K}"] = torch.softmax(x, dim=1).numpy()
+        arrays[f"cos_{M}x{K}"] = torch.nn.functional.cosine_similarity(x[:, None, :min(K, 64)], x[None, :8, :min(K, 64)], dim=-1).numpy()
+    return arrays
+
+
+def golden_path_blas():
+    """True when this machine (one thread) reproduces the fingerprint bit for bit: its fp32 GEMMs and reductions sum in the order
+    of the machine the goldens were made on, so the CPU oracle can be held to the goldens bit-exactly."""
+    import hashlib
+    ref = np.load(os.path.join(GOLDEN, "blas_probe.npz"), allow_pickle=False)
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        got = blas_probe_arrays()
+    finally:
+        torch.set_num_threads(n)
+    return set(got) == set(ref.files) and all(
+        hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() == str(ref[k]) for k, v in got.items())
+
+
 def load_golden(name):
-    """Returns (state_dict of torch tensors, dict of other arrays, kwargs dict or None)."""
+    """Returns (state_dict of torch tensors, dict of other arrays, kwargs dict or None).  A fixture may store some weights
+    as a recipe (``hashed_weights``: JSON list of [state key, shape, salt, bound], see hashed_weight) instead of values."""
     z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
     state, arrays = {}, {}
     for k in z.files:
@@ -66,6 +119,8 @@ def load_golden(name):
             arrays.setdefault("grads", {})[k[3:]] = torch.from_numpy(z[k])
         else:
             arrays[k] = z[k]
+    for key, shape, salt, bound in json.loads(str(arrays.pop("hashed_weights"))) if "hashed_weights" in arrays else []:
+        state[key] = torch.from_numpy(hashed_weight(tuple(shape), salt, bound))
     kwargs = json.loads(str(arrays.pop("kwargs"))) if "kwargs" in arrays else None
     return state, arrays, kwargs
 

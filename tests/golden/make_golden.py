@@ -1,13 +1,14 @@
 """Generate the golden vectors under tests/golden/ by running the REFERENCE itself on CPU.
 
-Run in the build container only (needs /root/reference, which never travels to the GPU box):
+Needs a checkout of the reference project (its path as the argument, or NCF_REFERENCE_DIR):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py <reference checkout>
+    python tests/golden/make_golden.py <reference checkout> --only g4     # the G4 fixture alone (or: --only blas_probe)
 
 Each .npz holds weights (every state_dict entry, prefixed ``w::``), inputs and the reference's
 outputs, so nothing depends on RNG-stream equality between torch versions.  Only *data* is stored:
-no reference source, no checkpoint bytes (G4 stores the SHA-256 of the shipped checkpoint and the
-inputs/outputs; the weights are re-read from /root/reference when the test runs here).
+no reference source, no checkpoint bytes (G4 runs the reference model at the shipped checkpoint's dims with
+hashed weights: the fixture stores their recipe, the inputs and the outputs).
 
 The reference imports ``torch_geometric.data.Data`` (content_providers.py:1, annotation only) and
 ``seaborn`` (plots.py:3); neither is installed, so two empty in-memory stub modules are registered
@@ -27,8 +28,21 @@ import types
 
 import numpy as np
 
-REF = "/root/reference"
+REF = os.environ.get("NCF_REFERENCE_DIR", "")   # checkout of the reference project (first argument overrides)
 OUT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(OUT))
+from conftest import blas_probe_arrays, hashed_weight  # noqa: E402  (tests/conftest.py)
+
+# G4: the dims of the reference's shipped AttentionNCF checkpoint (models/runs/AttentionNCF_with_features_attNet128_3mil.pt).
+# Its trained weights are reference content and stay out of this repository; the fixture uses hashed weights of the same shapes.
+G4_KWARGS = {"item_dim": 2094, "item_emb": 128, "user_emb": 128, "att_dense": 128, "mlp_dense_layers": [256, 128],
+             "dropout_rate": 0.2, "use_cos_sim_instead": False, "message_dropout": 0.0}
+# per-tensor bounds of the hashed weights at the trained checkpoint's scale (about sqrt(3) x its standard deviation per tensor;
+# the single-element biases at its magnitude), so that the attention weights spread as they do with trained weights
+G4_BOUNDS = {"ItemEmbeddings.0.weight": 0.3, "ItemEmbeddings.0.bias": 0.22, "UserEmbeddings.0.weight": 0.36,
+             "UserEmbeddings.0.bias": 0.4, "AttentionNet.0.weight": 0.26, "AttentionNet.0.bias": 0.13,
+             "AttentionNet.3.weight": 0.04, "AttentionNet.3.bias": 0.03, "MLP.0.weight": 0.19, "MLP.0.bias": 0.3,
+             "MLP.3.weight": 0.17, "MLP.3.bias": 0.68, "MLP.6.weight": 0.025, "MLP.6.bias": 3.3}
 
 
 def _import_reference():
@@ -57,6 +71,34 @@ def _save(name, **arrays):
     path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **arrays)
     print("wrote", path, os.path.getsize(path), "bytes")
+
+
+def golden_g4(torch, AttentionNCF):
+    """G4: AttentionNCF at the shipped checkpoint's dims (K = 2094 input features), weights from hashed_weight within
+    G4_BOUNDS; the fixture stores the recipe, the inputs and the reference's outputs."""
+    m = AttentionNCF(**G4_KWARGS).eval()
+    recipe, state = [], {}
+    for salt, (k, v) in enumerate(m.state_dict().items()):
+        recipe.append([k, list(v.shape), 1000 + salt, G4_BOUNDS[k]])
+        state[k] = torch.from_numpy(hashed_weight(tuple(v.shape), 1000 + salt, G4_BOUNDS[k]))
+    m.load_state_dict(state)
+    g = torch.Generator().manual_seed(10)
+    Fdim = G4_KWARGS["item_dim"]
+    rated = (torch.rand(16, Fdim, generator=g) < 0.02).float() + torch.rand(16, Fdim, generator=g) * 0.1
+    cand = (torch.rand(4, Fdim, generator=g) < 0.02).float() + torch.rand(4, Fdim, generator=g) * 0.1
+    um = torch.zeros(4, 16)
+    mask = torch.rand(4, 16, generator=g) < 0.6
+    um[mask] = (torch.randint(1, 11, (4, 16), generator=g).float() * 0.5 - 3.1)[mask]
+    with torch.no_grad():
+        out, att = m(cand, rated, um, return_attention_weights=True)
+    _save("g4_att_ckpt_dims", candidate_items=cand.numpy(), rated_items=rated.numpy(), user_matrix=um.numpy(),
+          out=out.numpy(), att=att.numpy(), kwargs=np.array(json.dumps(G4_KWARGS)), hashed_weights=np.array(json.dumps(recipe)))
+
+
+def golden_blas_probe(torch):
+    # SHA-256 of each product's bytes: the test only asks whether the bits are the same
+    _save("blas_probe", **{k: np.array(hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest())
+                           for k, v in blas_probe_arrays(torch).items()})
 
 
 def main():
@@ -252,24 +294,9 @@ def main():
               user2item_edge_index=gr.user2item_edge_index.numpy(), item2user_edge_index=gr.item2user_edge_index.numpy(),
               pos=pos, **extra)
 
-    # ---------------- G4: shipped checkpoint (weights NOT copied) ----------------
-    ck = os.path.join(REF, "models/runs/AttentionNCF_with_features_attNet128_3mil.pt")
-    sha = hashlib.sha256(open(ck, "rb").read()).hexdigest()
-    state, kwargs = torch.load(ck, map_location="cpu", weights_only=True)
-    m = AttentionNCF(**kwargs).eval()
-    m.load_state_dict(state)
-    g = torch.Generator().manual_seed(10)
-    Fdim = kwargs["item_dim"]
-    rated = (torch.rand(16, Fdim, generator=g) < 0.02).float() + torch.rand(16, Fdim, generator=g) * 0.1
-    cand = (torch.rand(4, Fdim, generator=g) < 0.02).float() + torch.rand(4, Fdim, generator=g) * 0.1
-    um = torch.zeros(4, 16)
-    mask = torch.rand(4, 16, generator=g) < 0.6
-    um[mask] = (torch.randint(1, 11, (4, 16), generator=g).float() * 0.5 - 3.1)[mask]
-    with torch.no_grad():
-        out, att = m(cand, rated, um, return_attention_weights=True)
-    _save("g4_att_shipped_ckpt", candidate_items=cand.numpy(), rated_items=rated.numpy(), user_matrix=um.numpy(),
-          out=out.numpy(), att=att.numpy(), kwargs=np.array(json.dumps(kwargs)),
-          ckpt_sha256=np.array(sha), ckpt_relpath=np.array("models/runs/AttentionNCF_with_features_attNet128_3mil.pt"))
+    golden_g4(torch, AttentionNCF)
+
+    golden_blas_probe(torch)
 
     # ---------------- G5: eval_ranking (eval.py:25-75) ----------------
     import pandas as pd
@@ -322,4 +349,18 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    # python tests/golden/make_golden.py <reference checkout> [--only g4|blas_probe]
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if args:
+        REF = args[0]
+    if not REF or not os.path.isdir(os.path.join(REF, "src")):
+        raise SystemExit("usage: make_golden.py <reference checkout> [--only g4|blas_probe]  (or set NCF_REFERENCE_DIR)")
+    if "--only" in sys.argv:
+        _import_reference()
+        import torch
+        from neural_collaborative_filtering.models.attention_ncf import AttentionNCF
+        torch.set_num_threads(1)
+        only = sys.argv[sys.argv.index("--only") + 1]
+        golden_g4(torch, AttentionNCF) if only == "g4" else golden_blas_probe(torch)
+    else:
+        main()

@@ -1,5 +1,4 @@
 """GPU parity tests for K3 (AttentionNCF item-item attention) against reference goldens and the CPU oracle."""
-import os
 
 import pytest
 import torch
@@ -44,15 +43,10 @@ def test_attention_golden(gpu, name):
     assert float(att[2, 3]) == 0.0            # exact-zero entry is unrated (attention_ncf.py:158)
 
 
-def test_attention_shipped_checkpoint(gpu):
-    """G4 with the reference's trained weights — only where /root/reference is mounted (never on the GPU box, since
-    reference content does not travel); kept so that a GPU-equipped build container exercises it."""
-    _, a, kw = load_golden("g4_att_shipped_ckpt")
-    ck = os.path.join("/root/reference", str(a["ckpt_relpath"]))
-    if not os.path.exists(ck):
-        pytest.skip("reference checkpoint not present on this host")
-    state, kwargs = torch.load(ck, map_location="cpu", weights_only=True)
-    m = _model(kwargs, state, gpu)
+def test_attention_checkpoint_dims(gpu):
+    """G4: the dims of the reference's shipped checkpoint (2094 input features) with hashed weights at its scale."""
+    state, a, kw = load_golden("g4_att_ckpt_dims")
+    m = _model(kw, state, gpu)
     with torch.no_grad():
         out, att = m(torch.from_numpy(a["candidate_items"]).to(gpu), torch.from_numpy(a["rated_items"]).to(gpu),
                      torch.from_numpy(a["user_matrix"]).to(gpu), return_attention_weights=True)
