@@ -108,6 +108,8 @@ SIGNATURES = {
     "ncf_l2_normalize_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p]),
     "ncf_gather_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_int, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
     "ncf_scatter_add_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
+    "ncf_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
+    "ncf_topk_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p]),
     "ncf_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _c_i64, _c_p]),
 }
@@ -1156,3 +1158,41 @@ def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
             raise ValueError("adam_step_: contiguous fp32 tensors of one size")
     _check(lib.ncf_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                              float(weight_decay), int(step), _stream(p)))
+
+
+# ------------------------------------------------------------------ top-K
+TOPK_MAX_K = 1024
+
+
+def topk_rows(scores: torch.Tensor, k: int, seen: Optional[tuple] = None):
+    """(out_score (R, k) fp32, out_idx (R, k) int32, out_count (R,) int32) of ncf_topk_rows: each row's k best columns in the order
+    of torch.sort(descending=True, stable=True) (NaN last), skipping the columns listed for the row in ``seen`` = (rowptr (R + 1)
+    int64, col int32), a CSR on the GPU.  Slots past out_count hold idx -1 / score -inf.  Outputs and workspace come from the
+    caching allocator on the current stream; no host synchronisation."""
+    lib = load_library()
+    _dev(scores, "scores")
+    if scores.dtype != torch.float32:
+        raise TypeError("topk_rows takes fp32 scores")
+    R, C, ld = _rows2d(scores, "scores")
+    k = int(k)
+    dev = scores.device
+    rowptr = col = None
+    if seen is not None:
+        rowptr, col = seen
+        _dev(rowptr, "seen rowptr")
+        _dev(col, "seen col")
+        if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.dim() != 1 or col.dim() != 1:
+            raise ValueError("seen = (rowptr int64 (R + 1), col int32)")
+        if rowptr.numel() != R + 1:
+            raise ValueError(f"seen rowptr has {rowptr.numel()} entries, {R + 1} expected")
+        rowptr, col = rowptr.contiguous(), col.contiguous()
+        if col.numel() == 0:                      # a valid CSR with no entries: nothing to skip
+            col = torch.empty(1, dtype=torch.int32, device=dev)
+    out_score = torch.empty((R, max(k, 0)), dtype=torch.float32, device=dev)
+    out_idx = torch.empty((R, max(k, 0)), dtype=torch.int32, device=dev)
+    out_count = torch.empty(R, dtype=torch.int32, device=dev)
+    nbytes = lib.ncf_topk_workspace_bytes(R, C, k)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _check(lib.ncf_topk_rows(_ptr(scores), R, C, ld, _ptr(rowptr), _ptr(col), k, _ptr(out_score), _ptr(out_idx), _ptr(out_count),
+                             _ptr(ws), nbytes, _stream(scores)))
+    return out_score, out_idx, out_count

@@ -1,0 +1,168 @@
+"""Top-K recommendation on the device: the library function behind the reference's web backend (webapp/backend.py:78-121).
+
+``top_k_items``        BasicNCF / MF (index providers): every listed user against every item (or a subset), scored block by
+                       block through the model's HIP scoring path, ranked by ncf_topk_rows.  Results stay on the device.
+``recommend_for_user`` AttentionNCF: one user given as a Series of ratings against a catalogue, with the reference's arguments,
+                       threshold rule and DataFrame columns (imdbID, score, because, attention).  Only k scores, k ids and the k
+                       winners' attention rows cross to the host.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import native
+from .neural_collaborative_filtering.models.attention_ncf import RowsOf, SparseRatings
+from .neural_collaborative_filtering.util import require_gpu
+
+# bound of one score block of top_k_items: scores (4 B) + the two int64 position columns (16 B) per (user, item) pair
+BLOCK_BYTES = 256 << 20
+_PAIR_BYTES = 4 + 16
+
+
+def _model_device(model) -> torch.device:
+    return next(model.parameters()).device
+
+
+def _eval_only(model):
+    if model.training:
+        raise RuntimeError("recommendations are computed in eval mode: call model.eval() first")
+
+
+def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
+                exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES):
+    """The ``k`` best items of every user in ``user_ids`` for a BasicNCF / MF model (int64 position inputs, the index providers').
+
+    user_ids: (B,) int64 user positions on the GPU.  item_ids: optional (I,) int64 item positions to rank (default: every item of
+    the model).  exclude: optional per-user CSR ``(rowptr (B + 1) int64, col int32)`` of columns of the ranked list to skip (with
+    ``item_ids`` absent, columns are item positions) — typically each user's training ratings.
+    Returns ``(scores (B, k) fp32, item_positions (B, k) int64, counts (B,) int32)`` on the device, each row in descending score
+    order (ties: lower column first; NaN last); slots past ``counts`` hold position -1 and score -inf.  The users are scored in
+    blocks of rows whose (user, item) score block stays under ``block_bytes``; nothing synchronises with the host."""
+    _eval_only(model)
+    require_gpu(user_ids)
+    dev = user_ids.device
+    if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
+        raise ValueError("user_ids must be a 1-D int64 tensor of user positions")
+    if item_ids is None:
+        items = torch.arange(model.item_embeddings[0].in_features, dtype=torch.int64, device=dev)
+    else:
+        require_gpu(item_ids)
+        if item_ids.dtype != torch.int64 or item_ids.dim() != 1:
+            raise ValueError("item_ids must be a 1-D int64 tensor of item positions")
+        items = item_ids.contiguous()
+    B, I = user_ids.numel(), items.numel()
+    if not 1 <= int(k) <= native.TOPK_MAX_K:
+        raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
+    if exclude is not None:
+        rowptr, col = exclude
+        require_gpu(rowptr, col)
+        if rowptr.numel() != B + 1:
+            raise ValueError(f"exclude rowptr has {rowptr.numel()} entries, {B + 1} expected")
+        rowptr, col = rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous()
+    rows_per_block = max(1, int(block_bytes) // max(1, I * _PAIR_BYTES))
+    users = user_ids.contiguous()
+    outs = []
+    with torch.no_grad():
+        for b0 in range(0, B, rows_per_block):
+            b1 = min(B, b0 + rows_per_block)
+            nb = b1 - b0
+            u = users[b0:b1].repeat_interleave(I)
+            i = items.repeat(nb)
+            scores = model(u, i).view(nb, I)
+            # the kernel reads seen_col[rowptr[r] ..]: a slice of rowptr indexes the whole col array, no rebasing
+            seen = None if exclude is None else (rowptr[b0:b1 + 1], col)
+            outs.append(native.topk_rows(scores, k, seen))
+    s = torch.cat([o[0] for o in outs]) if len(outs) != 1 else outs[0][0]
+    idx = torch.cat([o[1] for o in outs]) if len(outs) != 1 else outs[0][1]
+    cnt = torch.cat([o[2] for o in outs]) if len(outs) != 1 else outs[0][2]
+    pos = idx.to(torch.int64)
+    if item_ids is not None:
+        pos = torch.where(pos >= 0, items[pos.clamp_min(0)], pos)
+    return s, pos, cnt
+
+
+# ---------------------------------------------------------------------------------------- AttentionNCF: one user, one catalogue
+_catalogue_cache = {}
+
+
+def _catalogue(item_features, device):
+    """(features (I, F) fp32 on ``device``, pandas Index of item ids).  A DataFrame is converted once and kept by identity (the last
+    one per device), so a serving loop passes the same DataFrame and the model sees the same catalogue tensor every request — which
+    is what keeps AttentionNCF's candidate projections.  A ``(tensor, ids)`` pair is used as it is."""
+    import pandas as pd
+    if isinstance(item_features, tuple):
+        feats, ids = item_features
+        require_gpu(feats)
+        ids = pd.Index(np.asarray(ids.cpu() if torch.is_tensor(ids) else ids))
+        if feats.dim() != 2 or feats.shape[0] != len(ids):
+            raise ValueError("item_features = (tensor (I, F), ids (I,))")
+        return feats, ids
+    hit = _catalogue_cache.get(device)
+    if hit is not None and hit[0] is item_features:
+        return hit[1], hit[2]
+    feats = torch.from_numpy(np.ascontiguousarray(item_features.values, dtype=np.float32)).to(device)
+    _catalogue_cache[device] = (item_features, feats, item_features.index)
+    return feats, item_features.index
+
+
+def recommend_for_user(model, item_features, user_ratings, k=10, ignore_seen=True, explain_factor=1.5, explain_constant=0.025):
+    """The reference's ``recommend_for_user`` (webapp/backend.py:78-121) for an AttentionNCF: same arguments, same meaning, same
+    returned DataFrame columns ``imdbID, score, because, attention`` — the ``k`` best items by predicted score, each with the rated
+    items whose attention weight exceeds ``explain_factor / n_rated + explain_constant`` and those weights.
+
+    item_features: a DataFrame (index = item ids, one feature row per item) as in the reference, or ``(device tensor (I, F), ids)``.
+    user_ratings: a Series of ratings indexed by item id; the ratings are centred as ``rating - (mean + 2.5) / 2`` (backend.py:92).
+
+    Order of work: (1) the whole catalogue is scored once WITHOUT attention weights (the fast path; the catalogue tensor is the
+    same object request after request, so the model's kept candidate projections are reused); (2) ncf_topk_rows ranks it on the
+    device, skipping the rated items when ``ignore_seen`` (no reduced copy of the catalogue is built); (3) the forward runs again
+    with ``return_attention_weights=True`` on the k winners only.  A winner's reported ``score`` comes from pass (1) and its
+    ``because`` / ``attention`` from pass (2)'s weights: the two passes compute the same function for the same pair, up to fp32
+    summation order.  Ranking ties go to the item that comes first in the catalogue (the reference's sort is not stable)."""
+    import pandas as pd
+    _eval_only(model)
+    if not 1 <= int(k) <= native.TOPK_MAX_K:
+        raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
+    dev = _model_device(model)
+    feats, ids = _catalogue(item_features, dev)
+    I = feats.shape[0]
+    rated_ids = np.sort(np.unique(user_ratings.index))                                 # backend.py:88
+    rated_pos = ids.get_indexer(rated_ids)
+    if (rated_pos < 0).any():
+        raise KeyError(f"rated items not in the catalogue: {list(rated_ids[rated_pos < 0])[:5]}")
+    n_rated = len(rated_ids)
+    centred = (user_ratings.loc[rated_ids].values - ((user_ratings.mean() + 2.5) / 2)).astype(np.float32)   # backend.py:92
+    nz = np.nonzero(centred != 0)[0]          # attention_ncf.py:158: an entry that is exactly 0 counts as unrated
+    pos_dev = torch.from_numpy(rated_pos.astype(np.int64)).to(dev)
+    rated_items = feats.index_select(0, pos_dev)                                        # backend.py:89
+    rowptr = torch.tensor([0, len(nz)], dtype=torch.int64, device=dev)
+    col = torch.from_numpy(nz.astype(np.int32)).to(dev)
+    val = torch.from_numpy(centred[nz]).to(dev)
+
+    def ratings(B):      # one CSR row shared by every candidate: the reference repeats the user's row B times (backend.py:92)
+        return SparseRatings(rowptr, col, val, n_rated, pair_row=torch.zeros(B, dtype=torch.int64, device=dev))
+
+    with torch.no_grad():
+        scores = model(feats, rated_items, ratings(I)).view(1, I)
+        seen = (torch.tensor([0, n_rated], dtype=torch.int64, device=dev), pos_dev.to(torch.int32)) if ignore_seen else None
+        top_s, top_i, top_n = native.topk_rows(scores, k, seen)
+        winners = top_i[0].to(torch.int64).clamp_min(0)       # slots past the count rerun item 0 and are dropped below
+        _, att = model(RowsOf(feats, winners), rated_items, ratings(winners.numel()), return_attention_weights=True)
+        n = int(top_n.item())
+        top_s, top_i, att = top_s[0, :n].cpu().numpy(), top_i[0, :n].cpu().numpy(), att[:n].cpu().numpy()
+
+    exp_thr = explain_factor * (1 / max(n_rated, 1)) + explain_constant             # backend.py:105
+    mask = att > exp_thr
+    if ignore_seen:        # the row label the reference's frame carries: the position in the catalogue without the rated items
+        label = top_i - np.searchsorted(np.sort(rated_pos), top_i)
+    else:
+        label = top_i
+    return pd.DataFrame(data={
+        'imdbID': ids[top_i],
+        'score': top_s,
+        'because': [rated_ids[m] for m in mask],
+        'attention': [att[i, m] for i, m in enumerate(mask)],
+    }, index=label)

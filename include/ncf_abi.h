@@ -506,6 +506,27 @@ int ncf_adam_step(float* dev_p, const float* dev_g, float* dev_m, float* dev_v, 
                   float eps, float weight_decay, int64_t step, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-row top-K with exclusion — the ranking step of a recommendation request.
+ * Replaces: DataFrame.sort_values(by='score', ascending=False).iloc[:k] over the whole score vector after
+ *           item_features.drop(user_ratings.index) — webapp/backend.py:84, 113-118.
+ * dev_scores: (rows, cols) fp32, row-major, leading dimension ld >= cols; never written.
+ * dev_seen_rowptr (rows + 1, int64) / dev_seen_col (int32): optional CSR of the columns each row must skip (both NULL = none);
+ *   ids need not be sorted, duplicates and ids outside [0, cols) are ignored.
+ * Per row: dev_out_score / dev_out_idx (rows, k) — the first out_count[row] = min(k, cols - excluded) entries are the row's best
+ *   columns in the order of torch.sort(descending=True, stable=True) over the remaining columns (equal scores: lower column
+ *   first; -0.0 == +0.0; NaN below every number including -inf, NaNs by column); the remaining slots hold idx -1, score -inf.
+ *   Scores are the input's bits.  Deterministic: no atomics decide an order.
+ * Supported: 1 <= k <= 1024 (NCF_EINVAL otherwise), 1 <= cols <= 2^24 and rows <= 65536 (NCF_EUNSUPPORTED otherwise); nothing is
+ *   launched on a refusal.  Rows longer than 8192 columns are split over workgroups (per-tile candidates in the workspace, then a
+ *   merge launch); the workspace (ncf_topk_workspace_bytes; 16-byte aligned; 0 bytes for cols <= 8192) is bounded by processing
+ *   the rows in chunks.
+ * ------------------------------------------------------------------------------------------------ */
+size_t ncf_topk_workspace_bytes(int64_t rows, int64_t cols, int k);
+int ncf_topk_rows(const float* dev_scores, int64_t rows, int64_t cols, int64_t ld, const int64_t* dev_seen_rowptr,
+                  const int32_t* dev_seen_col, int k, float* dev_out_score, int32_t* dev_out_idx, int32_t* dev_out_count,
+                  void* dev_workspace, size_t workspace_bytes, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Calibration probe — the bf16 MFMA rate the chip SUSTAINS on random operands (it lowers its clock under matrix load), so that
  * bench.py can state a kernel's fraction of it next to the fraction of the 2.5 PFLOP/s datasheet figure.  Not part of scoring.
  * Launches `blocks` 512-thread workgroups; every wave issues iters * 32 v_mfma_f32_16x16x32_bf16 (16 384 flop each) on register
