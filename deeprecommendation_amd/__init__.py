@@ -1,5 +1,5 @@
 """MI355X (gfx950) path of the NCF models.  The recommendation functions are re-exported here, imported on first use."""
-_RECOMMEND = ("top_k_items", "recommend_for_user")
+_RECOMMEND = ("top_k_items", "recommend_for_user", "seen_items")
 
 
 def __getattr__(name):

@@ -1,0 +1,367 @@
+// Fused dot-product score-and-select (ncf_dot_topk): the k best items of each listed user for a dot-product readout (MF,
+// GraphNCF(use_dot_product=True)), without a B x I score matrix.  The scores are made in registers by f32 MFMA and filtered
+// against a running per-user threshold before anything leaves the workgroup; only k keys per (user, column tile) are written.
+//
+// Scores: bit-identical to gather_dot_kernel<false> (gather.hip) for the same pair.  That kernel sums 16 fmaf chains (chain s
+// over e = s, s+16, s+32, ... in increasing e, from +0.f) and adds them in a fixed tree (q_l = p_l + p_{l+8}, r_l = q_l + q_{l+4},
+// t_l = r_l + r_{l+2}, score = t_0 + t_1).  Here each chain has its own 16 x 16 accumulator tile (16 users x 16 items) and
+// v_mfma_f32_16x16x4_f32 advances it by kDtKS elements of the chain per step: K slot q of step j holds element 16 (kDtKS j + q) + s,
+// so the K order inside one instruction is the chain's order (f32 MFMA is an exact fmaf chain over its K slots).  The 15 tree
+// adds run on the VALU.
+//
+// Shape: a 256-thread workgroup owns 64 users (16 per wave) x one tile of tile_cols ranked-list columns.  The waves are
+// independent (no workgroup barrier): each holds its 16 user rows in registers for the whole tile and walks the tile 16 items at
+// a time (item rows read straight from global memory, one item-row block ahead; the four waves read the same rows, so three of
+// four reads are L1 hits).  Per user the wave keeps kDtCap candidate keys in LDS and a threshold: a key is kept when it beats the
+// threshold and its column is not excluded (an LDS bitmap of the user's excluded columns, rebuilt every kDtChunk columns).  A user
+// whose buffer cannot take another 16 keys is re-selected down to k (wave-wide bitwise search for the k-th key, then
+// compaction); the k-th key becomes the threshold.  At the end of the tile each user's k best keys go to the workspace in the
+// layout topk_tile_kernel's merge levels read (kp keys per tile, 0-padded), and those levels finish the ranking; the last one
+// recovers the score from the key (topk_unmap), which is the caller's bits for every non-NaN score (a dot product from +0.f is
+// never -0.0).
+#include "topk_common.h"
+
+namespace ncf {
+
+constexpr int kDtWaves = 4;
+constexpr int kDtThreads = kDtWaves * kWave;
+constexpr int kDtUsers = 16;                       // users per wave (the MFMA M dimension)
+constexpr int kDtBlockUsers = kDtWaves * kDtUsers; // users per workgroup
+constexpr int kDtCap = 256;                        // candidate keys per user
+constexpr int kDtMaxK = 128;                       // fused limit on k (a re-select must free >= 16 + some slots)
+constexpr int kDtMaxD = 256;                       // fused limit on the embedding width (user rows live in registers)
+constexpr int kDtChunk = 2048;                     // columns per exclusion bitmap
+constexpr int kDtKS = 4;                           // chain elements per MFMA step (the instruction's K)
+constexpr int64_t kDtTargetBlocks = 512;           // tile_cols shrinks (8192 -> 2048) until the grid reaches this
+
+struct DtWaveShared {
+    unsigned long long buf[kDtUsers][kDtCap];
+    uint32_t bitmap[kDtUsers][kDtChunk / 32];
+    unsigned long long thr[kDtUsers];
+    int cnt[kDtUsers];
+};
+
+// order this wave's LDS accesses (the LDS serves one wave's instructions in order; the fence keeps the compiler from moving
+// memory operations across it)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
+
+// 16 floats of a row starting at element e0 (elements >= D read as 0)
+__device__ __forceinline__ void load_block(const float* __restrict__ row, int e0, int D, bool vec, float (&v)[16]) {
+    if (vec && e0 + 16 <= D) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const f32x4 q = *reinterpret_cast<const f32x4*>(row + e0 + 4 * h);
+            v[4 * h] = q[0]; v[4 * h + 1] = q[1]; v[4 * h + 2] = q[2]; v[4 * h + 3] = q[3];
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < 16; ++s) v[s] = e0 + s < D ? row[e0 + s] : 0.f;
+    }
+}
+
+// J steps of kDtKS chain elements: lane (row l & 15, slot q = l >> 4) holds block kDtKS j + q of its row (zeros past D / q >= kDtKS)
+template <int J>
+__device__ __forceinline__ void load_frag(const float* row, int D, bool vec, int q, float (&v)[J][16]) {
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        if (row && q < kDtKS) load_block(row, 16 * (kDtKS * j + q), D, vec, v[j]);
+        else {
+#pragma unroll
+            for (int s = 0; s < 16; ++s) v[j][s] = 0.f;
+        }
+    }
+}
+
+// The largest key T with #{v >= T} >= keep over the wave's 4 x 64 keys (0 = empty; at least `keep` nonzero keys present).
+__device__ unsigned long long wave_kth(const unsigned long long (&v)[4], int keep) {
+    unsigned long long prefix = 0ull;
+    for (int bit = 63; bit >= 0; --bit) {
+        const unsigned long long cand = prefix | (1ull << bit);
+        int c = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c += __popcll(__ballot(v[i] >= cand));
+        if (c < keep) continue;
+        prefix = cand;
+        if (c == keep) {                 // exactly `keep` keys are >= cand: the smallest of them is the answer
+            unsigned long long m = ~0ull;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (v[i] >= cand) m = min(m, v[i]);
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) m = min(m, shfl_xor_u64(m, o));
+            return m;
+        }
+    }
+    return prefix;
+}
+
+// keep the `keep` best of user u's candidates; the k-th becomes the threshold
+__device__ void reselect(DtWaveShared& sh, int u, int keep, int lane) {
+    const int n = sh.cnt[u];
+    unsigned long long v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = lane + 64 * i < n ? sh.buf[u][lane + 64 * i] : 0ull;
+    const unsigned long long kth = wave_kth(v, keep);
+    wave_lds_sync();
+    int base = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const bool f = v[i] != 0ull && v[i] >= kth;
+        const unsigned long long m = __ballot(f);
+        if (f) sh.buf[u][base + lanes_below(m)] = v[i];
+        base += __popcll(m);
+    }
+    if (lane == 0) {
+        sh.cnt[u] = keep;
+        sh.thr[u] = kth;
+    }
+    wave_lds_sync();
+}
+
+template <int J>
+__global__ __launch_bounds__(kDtThreads) void dot_topk_kernel(
+    const float* __restrict__ tabA, int64_t rowsA, int64_t ldA, const float* __restrict__ tabB, int64_t rowsB, int64_t ldB,
+    const int64_t* __restrict__ idxA, const int64_t* __restrict__ idxB, int64_t cols, int D, const int64_t* __restrict__ seen_rowptr,
+    const int32_t* __restrict__ seen_col, int64_t row0, int64_t nrows, int tiles, int tile_cols, int k, int kp,
+    unsigned long long* __restrict__ out_keys, int64_t n_out, int32_t* oob) {
+    __shared__ DtWaveShared shw[kDtWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    DtWaveShared& sh = shw[wave];
+    const int tile = blockIdx.x % tiles;
+    const int64_t u0 = (int64_t)(blockIdx.x / tiles) * kDtBlockUsers + wave * kDtUsers;   // first local row of this wave
+    if (u0 >= nrows) return;
+    const int nu = (int)min((int64_t)kDtUsers, nrows - u0);
+    const int r16 = lane & 15, q = lane >> 4;
+    const bool vecA = (ldA & 3) == 0 && (reinterpret_cast<uintptr_t>(tabA) & 15u) == 0;
+    const bool vecB = (ldB & 3) == 0 && (reinterpret_cast<uintptr_t>(tabB) & 15u) == 0;
+
+    // this lane's user row (A operand: row r16)
+    const float* arow = nullptr;
+    if (r16 < nu) {
+        const int64_t r = row0 + u0 + r16;
+        const int64_t ia = idxA ? idxA[r] : r;
+        if (ia >= 0 && ia < rowsA) arow = tabA + ia * ldA;
+        else if (oob && q == 0) *oob = 1;
+    }
+    float a[J][16];
+    load_frag<J>(arow, D, vecA, q, a);
+
+    if (lane < kDtUsers) {
+        sh.cnt[lane] = 0;
+        sh.thr[lane] = 0ull;
+    }
+    const int64_t c0 = (int64_t)tile * tile_cols, c1 = min(cols, c0 + tile_cols);
+    const int steps = (int)((c1 - c0 + 15) >> 4);
+    const bool excl = seen_rowptr != nullptr;
+
+    auto item_row = [&](int g) -> const float* {
+        const int64_t c = c0 + (int64_t)g * 16 + r16;
+        if (g >= steps || c >= c1) return nullptr;
+        const int64_t ib = idxB ? idxB[c] : c;
+        if (ib >= 0 && ib < rowsB) return tabB + ib * ldB;
+        if (oob && q == 0) *oob = 1;
+        return nullptr;
+    };
+    float b[J][16];
+    load_frag<J>(item_row(0), D, vecB, q, b);
+
+    for (int g = 0; g < steps; ++g) {
+        const int64_t cbase = c0 + (int64_t)g * 16;
+        if (excl && ((cbase - c0) % kDtChunk) == 0) {          // rebuild the exclusion bitmap for columns [cbase, cbase + kDtChunk)
+            wave_lds_sync();
+            for (int w = lane; w < kDtUsers * (kDtChunk / 32); w += kWave) (&sh.bitmap[0][0])[w] = 0u;
+            wave_lds_sync();
+            for (int u = 0; u < nu; ++u) {
+                const int64_t r = row0 + u0 + u;
+                const int64_t pb = seen_rowptr[r], pe = seen_rowptr[r + 1];
+                for (int64_t p = pb + lane; p < pe; p += kWave) {
+                    const int64_t c = (int64_t)seen_col[p] - cbase;     // ids outside the chunk (or the list) do nothing
+                    if (c >= 0 && c < kDtChunk) atomicOr(&sh.bitmap[u][c >> 5], 1u << (c & 31));
+                }
+            }
+            wave_lds_sync();
+        }
+        float bn[J][16];
+        load_frag<J>(item_row(g + 1), D, vecB, q, bn);        // next item block in flight during this one's MFMAs
+
+        f32x4 acc[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+#pragma unroll
+            for (int s = 0; s < 16; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j][s], b[j][s], acc[s], 0, 0, 0);
+
+        // lane holds item column r16 of users 4q .. 4q+3 (C/D layout: col = lane & 15, row = 4 (lane >> 4) + reg)
+        const int64_t c = cbase + r16;
+        const uint32_t low = 0xFFFFFFFFu - (uint32_t)c;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int u = 4 * q + rr;
+            float p[16];
+#pragma unroll
+            for (int s = 0; s < 16; ++s) p[s] = acc[s][rr];
+            float qq[8], rs[4];
+#pragma unroll
+            for (int l = 0; l < 8; ++l) qq[l] = p[l] + p[l + 8];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) rs[l] = qq[l] + qq[l + 4];
+            const float score = (rs[0] + rs[2]) + (rs[1] + rs[3]);
+            const unsigned long long key = ((unsigned long long)topk_map(score) << 32) | low;
+            bool pass = u < nu && c < c1 && key > sh.thr[u];
+            if (pass && excl) {
+                const int off = (int)((c - c0) % kDtChunk);
+                pass = !((sh.bitmap[u][off >> 5] >> (off & 31)) & 1u);
+            }
+            if (pass) {
+                const int slot = atomicAdd(&sh.cnt[u], 1);     // < kDtCap: a user had <= kDtCap - 16 before this step
+                sh.buf[u][slot] = key;
+            }
+        }
+        wave_lds_sync();
+        unsigned long long full = __ballot(lane < kDtUsers && sh.cnt[lane] > kDtCap - 16);
+        while (full) {
+            const int u = __builtin_ctzll(full);
+            full &= full - 1;
+            reselect(sh, u, k, lane);
+        }
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+#pragma unroll
+            for (int s = 0; s < 16; ++s) b[j][s] = bn[j][s];
+    }
+
+    // each user's k best keys of this tile, unsorted, 0-padded to kp
+    for (int u = 0; u < nu; ++u) {
+        if (sh.cnt[u] > k) reselect(sh, u, k, lane);
+        const int n = sh.cnt[u];
+        unsigned long long* dst = out_keys + (u0 + u) * n_out + (int64_t)tile * kp;
+        for (int s = lane; s < kp; s += kWave) dst[s] = s < n ? sh.buf[u][s] : 0ull;
+    }
+}
+
+// The launch plan: column tiles of the fused level, then the merge levels of topk_tile_kernel over kp keys per tile.
+struct DotTopkPlan {
+    int tile_cols;
+    int64_t tiles0;
+    int merges;              // merge launches (>= 1: the last one sorts and writes the result)
+    int64_t mtiles[8];
+    int kp;
+    int64_t n1, n2;          // keys per row in the two ping-pong buffers
+    int64_t chunk;           // rows per chunk
+};
+
+static DotTopkPlan dot_topk_plan(int64_t rows, int64_t cols, int k) {
+    DotTopkPlan p{};
+    p.kp = (k + 1) & ~1;
+    const int64_t ublocks = (rows + kDtBlockUsers - 1) / kDtBlockUsers;
+    p.tile_cols = kTopkTile;
+    while (p.tile_cols > kDtChunk && ublocks * ((cols + p.tile_cols - 1) / p.tile_cols) < kDtTargetBlocks) p.tile_cols >>= 1;
+    p.tiles0 = (cols + p.tile_cols - 1) / p.tile_cols;
+    p.n1 = p.tiles0 * p.kp;
+    int64_t n = p.n1;
+    p.merges = 0;
+    while (true) {
+        const int64_t t = (n + kTopkTile - 1) / kTopkTile;
+        p.mtiles[p.merges++] = t;
+        if (t == 1) break;
+        n = t * p.kp;
+    }
+    p.n2 = p.merges > 1 ? p.mtiles[0] * p.kp : 0;
+    const int64_t per_row = (p.n1 + p.n2) * 8;
+    int64_t chunk = max((int64_t)1, min(rows, (int64_t)(kTopkChunkBytes / per_row)));
+    if (chunk < rows && chunk > kDtBlockUsers) chunk -= chunk % kDtBlockUsers;   // whole user blocks per chunk
+    p.chunk = chunk;
+    return p;
+}
+
+static int dot_topk_check(int64_t rows, int64_t cols, int D, int k, const char* what) {
+    if (k < 1 || k > kTopkMaxK) return fail(NCF_EINVAL, "%s: k = %d is outside 1 .. %d", what, k, kTopkMaxK);
+    if (k > kDtMaxK) return fail(NCF_EUNSUPPORTED, "%s: k = %d is above the fused limit %d", what, k, kDtMaxK);
+    if (D < 1 || D > kDtMaxD) return fail(NCF_EUNSUPPORTED, "%s: width D = %d is outside the fused range 1 .. %d", what, D, kDtMaxD);
+    if (cols < 1 || cols > kTopkMaxCols)
+        return fail(NCF_EUNSUPPORTED, "%s: cols = %lld is outside 1 .. %lld", what, (long long)cols, (long long)kTopkMaxCols);
+    if (rows < 0 || rows > kTopkMaxRows)
+        return fail(NCF_EUNSUPPORTED, "%s: rows = %lld is outside 0 .. %lld", what, (long long)rows, (long long)kTopkMaxRows);
+    return NCF_OK;
+}
+
+template <int J>
+static void launch_dot_topk(unsigned blocks, hipStream_t s, const float* tabA, int64_t rowsA, int64_t ldA, const float* tabB,
+                            int64_t rowsB, int64_t ldB, const int64_t* idxA, const int64_t* idxB, int64_t cols, int D,
+                            const int64_t* seen_rowptr, const int32_t* seen_col, int64_t r0, int64_t nr, const DotTopkPlan& p, int k,
+                            unsigned long long* out, int32_t* oob) {
+    hipLaunchKernelGGL((dot_topk_kernel<J>), dim3(blocks), dim3(kDtThreads), 0, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols,
+                       D, seen_rowptr, seen_col, r0, nr, (int)p.tiles0, p.tile_cols, k, p.kp, out, p.n1, oob);
+}
+
+}  // namespace ncf
+
+using namespace ncf;
+
+extern "C" size_t ncf_dot_topk_workspace_bytes(int64_t rows, int64_t cols, int D, int k) {
+    if (dot_topk_check(rows, cols, D, k, "ncf_dot_topk_workspace_bytes") != NCF_OK || rows == 0) return 0;
+    const DotTopkPlan p = dot_topk_plan(rows, cols, k);
+    return (size_t)(p.chunk * (p.n1 + p.n2) * 8);
+}
+
+extern "C" int ncf_dot_topk(const float* tabA, int64_t rowsA, int64_t ldA, const float* tabB, int64_t rowsB, int64_t ldB,
+                            const int64_t* idxA, const int64_t* idxB, int64_t rows, int64_t cols, int D, const int64_t* seen_rowptr,
+                            const int32_t* seen_col, int k, float* out_score, int32_t* out_idx, int32_t* out_count, void* workspace,
+                            size_t workspace_bytes, int32_t* oob, ncf_stream_t stream) {
+    const int rc = dot_topk_check(rows, cols, D, k, "ncf_dot_topk");
+    if (rc != NCF_OK) return rc;
+    if (rows == 0) return NCF_OK;
+    if (!tabA || !tabB || !out_score || !out_idx || !out_count) return fail(NCF_EINVAL, "ncf_dot_topk: null argument");
+    if (ldA < D || ldB < D) return fail(NCF_EINVAL, "ncf_dot_topk: leading dimension smaller than D = %d", D);
+    if (!idxA && rows > rowsA) return fail(NCF_EINVAL, "ncf_dot_topk: rows = %lld > rowsA without idxA", (long long)rows);
+    if (!idxB && cols > rowsB) return fail(NCF_EINVAL, "ncf_dot_topk: cols = %lld > rowsB without idxB", (long long)cols);
+    if ((seen_rowptr == nullptr) != (seen_col == nullptr))
+        return fail(NCF_EINVAL, "ncf_dot_topk: seen_rowptr and seen_col are given together or not at all");
+    const DotTopkPlan p = dot_topk_plan(rows, cols, k);
+    const size_t need = (size_t)(p.chunk * (p.n1 + p.n2) * 8);
+    if (workspace_bytes < need)
+        return fail(NCF_EWORKSPACE, "ncf_dot_topk: workspace of %zu bytes, %zu needed (ncf_dot_topk_workspace_bytes)", workspace_bytes, need);
+    if (!workspace || !aligned16(workspace)) return fail(NCF_EINVAL, "ncf_dot_topk: workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* bufA = (unsigned long long*)workspace;
+    unsigned long long* bufB = bufA + p.chunk * p.n1;
+    const int J = (D + 16 * kDtKS - 1) / (16 * kDtKS);
+    for (int64_t r0 = 0; r0 < rows; r0 += p.chunk) {
+        const int64_t nr = min(p.chunk, rows - r0);
+        const unsigned blocks = (unsigned)(((nr + kDtBlockUsers - 1) / kDtBlockUsers) * p.tiles0);
+        switch (J) {
+            case 1: launch_dot_topk<1>(blocks, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, D, seen_rowptr, seen_col, r0, nr, p, k, bufA, oob); break;
+            case 2: launch_dot_topk<2>(blocks, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, D, seen_rowptr, seen_col, r0, nr, p, k, bufA, oob); break;
+            case 3: launch_dot_topk<3>(blocks, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, D, seen_rowptr, seen_col, r0, nr, p, k, bufA, oob); break;
+            default: launch_dot_topk<4>(blocks, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, D, seen_rowptr, seen_col, r0, nr, p, k, bufA, oob); break;
+        }
+        // merge levels: topk_tile_kernel over the fused level's kp keys per tile; the last one sorts and writes (score from the key)
+        unsigned long long* in = bufA;
+        unsigned long long* out = bufB;
+        int64_t n_in = p.n1;
+        for (int L = 0; L < p.merges; ++L) {
+            const int64_t t = p.mtiles[L];
+            if (L == p.merges - 1) {
+                hipLaunchKernelGGL((topk_tile_kernel<false, true>), dim3((unsigned)(t * nr)), dim3(kTopkThreads), 0, s, nullptr, 0, 0, nullptr,
+                                   nullptr, in, n_in, (int)t, r0, k, p.kp, nullptr, 0, out_score, out_idx, out_count);
+            } else {
+                const int64_t n_out = t * p.kp;
+                hipLaunchKernelGGL((topk_tile_kernel<false, false>), dim3((unsigned)(t * nr)), dim3(kTopkThreads), 0, s, nullptr, 0, 0,
+                                   nullptr, nullptr, in, n_in, (int)t, r0, k, p.kp, out, n_out, out_score, out_idx, out_count);
+                unsigned long long* tmp = in;
+                in = out;
+                out = tmp;
+                n_in = n_out;
+            }
+        }
+    }
+    return check_launch("ncf_dot_topk");
+}

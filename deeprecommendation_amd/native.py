@@ -110,6 +110,9 @@ SIGNATURES = {
     "ncf_scatter_add_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
     "ncf_topk_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p]),
+    "ncf_dot_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_int]),
+    "ncf_dot_topk": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_int, _c_p,
+                              _c_p, _c_p, _c_p, _c_size, _c_p, _c_p]),
     "ncf_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _c_i64, _c_p]),
 }
@@ -1195,4 +1198,55 @@ def topk_rows(scores: torch.Tensor, k: int, seen: Optional[tuple] = None):
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     _check(lib.ncf_topk_rows(_ptr(scores), R, C, ld, _ptr(rowptr), _ptr(col), k, _ptr(out_score), _ptr(out_idx), _ptr(out_count),
                              _ptr(ws), nbytes, _stream(scores)))
+    return out_score, out_idx, out_count
+
+
+DOT_TOPK_MAX_K = 128     # the fused kernel's limits (include/ncf_abi.h ncf_dot_topk); outside them it returns NCF_EUNSUPPORTED
+DOT_TOPK_MAX_D = 256
+
+
+def _seen_csr(seen, R, dev):
+    if seen is None:
+        return None, None
+    rowptr, col = seen
+    _dev(rowptr, "seen rowptr")
+    _dev(col, "seen col")
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.dim() != 1 or col.dim() != 1:
+        raise ValueError("seen = (rowptr int64 (R + 1), col int32)")
+    if rowptr.numel() != R + 1:
+        raise ValueError(f"seen rowptr has {rowptr.numel()} entries, {R + 1} expected")
+    rowptr, col = rowptr.contiguous(), col.contiguous()
+    if col.numel() == 0:                      # a valid CSR with no entries: nothing to skip
+        col = torch.empty(1, dtype=torch.int32, device=dev)
+    return rowptr, col
+
+
+def dot_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], k: int,
+             seen: Optional[tuple] = None):
+    """ncf_dot_topk: for each user row tabA[idxA[r]] (tabA[r] with idxA None) the k best columns c of the list idxB (every row of
+    tabB with idxB None) by <user row, tabB[idxB[c]]> — exactly ``topk_rows(gather_dot(...).view(B, I), k, seen)``, bit for bit,
+    without the B x I score matrix.  Returns (out_score (B, k) fp32, out_idx (B, k) int32 columns of the list, out_count (B,)
+    int32) like topk_rows.  fp32 tables only; k <= DOT_TOPK_MAX_K and width <= DOT_TOPK_MAX_D, else NativeError with code
+    NCF_EUNSUPPORTED and nothing launched.  Outputs and workspace from the caching allocator on the current stream; no sync."""
+    lib = load_library()
+    _dev(tabA, "tabA"), _dev(tabB, "tabB")
+    if tabA.dtype != torch.float32 or tabB.dtype != torch.float32:
+        raise TypeError("dot_topk takes fp32 tables")
+    rowsA, D, ldA = _rows2d(tabA, "tabA")
+    rowsB, DB, ldB = _rows2d(tabB, "tabB")
+    if D != DB:
+        raise ValueError("dot_topk needs equal widths")
+    idxA, idxB = _idx(idxA), _idx(idxB)
+    B = idxA.numel() if idxA is not None else rowsA
+    I = idxB.numel() if idxB is not None else rowsB
+    k = int(k)
+    dev = tabA.device
+    rowptr, col = _seen_csr(seen, B, dev)
+    out_score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    out_idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    out_count = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = lib.ncf_dot_topk_workspace_bytes(B, I, D, k)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    _check(lib.ncf_dot_topk(_ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, I, D, _ptr(rowptr), _ptr(col),
+                            k, _ptr(out_score), _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
     return out_score, out_idx, out_count

@@ -1,7 +1,9 @@
 """Top-K recommendation on the device: the library function behind the reference's web backend (webapp/backend.py:78-121).
 
-``top_k_items``        BasicNCF / MF (index providers): every listed user against every item (or a subset), scored block by
-                       block through the model's HIP scoring path, ranked by ncf_topk_rows.  Results stay on the device.
+``top_k_items``        BasicNCF / MF (index providers) and GraphNCF: every listed user against every item (or a subset), scored
+                       block by block through the model's HIP scoring path and ranked by ncf_topk_rows — or, for a dot-product
+                       readout, scored and ranked in one pass by ncf_dot_topk (no score matrix).  Results stay on the device.
+``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
 ``recommend_for_user`` AttentionNCF: one user given as a Series of ratings against a catalogue, with the reference's arguments,
                        threshold rule and DataFrame columns (imdbID, score, because, attention).  Only k scores, k ids and the k
                        winners' attention rows cross to the host.
@@ -31,23 +33,56 @@ def _eval_only(model):
         raise RuntimeError("recommendations are computed in eval mode: call model.eval() first")
 
 
-def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
-                exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES):
-    """The ``k`` best items of every user in ``user_ids`` for a BasicNCF / MF model (int64 position inputs, the index providers').
+def _graph_model(model) -> bool:
+    from .neural_collaborative_filtering.models.gnn_ncf import GraphNCF
+    return isinstance(model, GraphNCF)
 
-    user_ids: (B,) int64 user positions on the GPU.  item_ids: optional (I,) int64 item positions to rank (default: every item of
-    the model).  exclude: optional per-user CSR ``(rowptr (B + 1) int64, col int32)`` of columns of the ranked list to skip (with
-    ``item_ids`` absent, columns are item positions) — typically each user's training ratings.
+
+def _dot_readout(model) -> bool:
+    from .neural_collaborative_filtering.models.mf import MF
+    return isinstance(model, MF) or (_graph_model(model) and model.MLP is None)
+
+
+def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
+                exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES, *, graph=None,
+                fused: Optional[bool] = None):
+    """The ``k`` best items of every user in ``user_ids`` for a BasicNCF / MF / GraphNCF model (int64 position inputs).
+
+    user_ids: (B,) int64 user positions on the GPU — for a GraphNCF node positions as in ``GraphNCF.forward`` (users come after
+    the ``graph.num_items`` items).  item_ids: optional (I,) int64 item positions to rank (default: every item of the model; for
+    a GraphNCF every item node ``0 .. graph.num_items - 1``).  exclude: optional per-user CSR ``(rowptr (B + 1) int64, col
+    int32)`` of columns of the ranked list to skip (with ``item_ids`` absent, columns are item positions) — typically each
+    user's training ratings (``seen_items`` builds it from a graph).  graph: the GraphData a GraphNCF is evaluated on; required
+    for a GraphNCF and refused for any other model.
+    fused: how a dot-product readout (MF, GraphNCF with ``use_dot_product=True``) is ranked.  ``None``: GraphNCF-dot through the
+    fused score-and-select kernel (``native.dot_topk``: no score matrix), everything else score-then-select; ``True``: the fused
+    kernel for MF too (refused for a model with an MLP readout); ``False``: score-then-select everywhere.  Both routes give the
+    same bits; where the fused kernel's limits (k <= 128, width <= 256) do not hold it falls back to score-then-select.
     Returns ``(scores (B, k) fp32, item_positions (B, k) int64, counts (B,) int32)`` on the device, each row in descending score
-    order (ties: lower column first; NaN last); slots past ``counts`` hold position -1 and score -inf.  The users are scored in
-    blocks of rows whose (user, item) score block stays under ``block_bytes``; nothing synchronises with the host."""
+    order (ties: lower column first; NaN last); slots past ``counts`` hold position -1 and score -inf.  Score-then-select scores
+    the users in blocks of rows whose (user, item) score block stays under ``block_bytes``; nothing synchronises with the host."""
     _eval_only(model)
     require_gpu(user_ids)
     dev = user_ids.device
     if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
         raise ValueError("user_ids must be a 1-D int64 tensor of user positions")
+    is_graph = _graph_model(model)
+    if is_graph and graph is None:
+        raise ValueError("a GraphNCF ranks items on a graph: pass graph=")
+    if not is_graph and graph is not None:
+        raise ValueError(f"graph= is only taken by a GraphNCF, not by {type(model).__name__}")
+    if fused and not _dot_readout(model):
+        raise ValueError(f"fused=True needs a dot-product readout; {type(model).__name__} here scores through an MLP")
+    if fused and getattr(model, "scoring_dtype", torch.float32) != torch.float32:
+        raise ValueError("fused=True takes fp32 tables: the model scores in " + str(model.scoring_dtype))
+    use_fused = bool(fused) if fused is not None else (is_graph and _dot_readout(model))
+    if is_graph:
+        graph = graph.to(dev)
+        n_items = graph.num_items
+    else:
+        n_items = model.item_embeddings[0].in_features
     if item_ids is None:
-        items = torch.arange(model.item_embeddings[0].in_features, dtype=torch.int64, device=dev)
+        items = torch.arange(n_items, dtype=torch.int64, device=dev)
     else:
         require_gpu(item_ids)
         if item_ids.dtype != torch.int64 or item_ids.dim() != 1:
@@ -62,26 +97,75 @@ def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.
         if rowptr.numel() != B + 1:
             raise ValueError(f"exclude rowptr has {rowptr.numel()} entries, {B + 1} expected")
         rowptr, col = rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous()
-    rows_per_block = max(1, int(block_bytes) // max(1, I * _PAIR_BYTES))
     users = user_ids.contiguous()
-    outs = []
-    with torch.no_grad():
-        for b0 in range(0, B, rows_per_block):
-            b1 = min(B, b0 + rows_per_block)
-            nb = b1 - b0
-            u = users[b0:b1].repeat_interleave(I)
-            i = items.repeat(nb)
-            scores = model(u, i).view(nb, I)
-            # the kernel reads seen_col[rowptr[r] ..]: a slice of rowptr indexes the whole col array, no rebasing
-            seen = None if exclude is None else (rowptr[b0:b1 + 1], col)
-            outs.append(native.topk_rows(scores, k, seen))
-    s = torch.cat([o[0] for o in outs]) if len(outs) != 1 else outs[0][0]
-    idx = torch.cat([o[1] for o in outs]) if len(outs) != 1 else outs[0][1]
-    cnt = torch.cat([o[2] for o in outs]) if len(outs) != 1 else outs[0][2]
+    out = None
+    if use_fused:
+        out = _fused_top_k(model, graph, users, item_ids is None, items, n_items, int(k),
+                           None if exclude is None else (rowptr, col))
+    if out is None:
+        score = (lambda u, i: model(graph, u, i)) if is_graph else model
+        rows_per_block = max(1, int(block_bytes) // max(1, I * _PAIR_BYTES))
+        outs = []
+        with torch.no_grad():
+            for b0 in range(0, B, rows_per_block):
+                b1 = min(B, b0 + rows_per_block)
+                nb = b1 - b0
+                u = users[b0:b1].repeat_interleave(I)
+                i = items.repeat(nb)
+                scores = score(u, i).view(nb, I)
+                # the kernel reads seen_col[rowptr[r] ..]: a slice of rowptr indexes the whole col array, no rebasing
+                seen = None if exclude is None else (rowptr[b0:b1 + 1], col)
+                outs.append(native.topk_rows(scores, k, seen))
+        out = tuple(torch.cat([o[j] for o in outs]) if len(outs) != 1 else outs[0][j] for j in range(3))
+    s, idx, cnt = out
     pos = idx.to(torch.int64)
     if item_ids is not None:
         pos = torch.where(pos >= 0, items[pos.clamp_min(0)], pos)
     return s, pos, cnt
+
+
+def _fused_top_k(model, graph, users, all_items, items, n_items, k, seen):
+    """native.dot_topk over the model's (user table, item table); None where the fused kernel's limits do not hold (the caller
+    then scores and selects, which gives the same bits)."""
+    if k > native.DOT_TOPK_MAX_K:
+        return None
+    with torch.no_grad():
+        cache = model._refresh()
+        if graph is not None:
+            combined = model.propagate_all(graph, cache)
+            tabA, tabB = combined, combined
+            if all_items:                   # the first n_items rows are the item nodes: rank them in place, no id list
+                tabB, items = combined[:n_items], None
+        else:
+            tabA = model._table("user", model.user_embeddings[0], cache)
+            tabB = model._table("item", model.item_embeddings[0], cache)
+            if all_items:
+                items = None
+        if tabA.shape[1] > native.DOT_TOPK_MAX_D:
+            return None
+        return native.dot_topk(tabA, users, tabB, items, k, seen)
+
+
+def seen_items(graph, user_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exclusion CSR ``(rowptr (B + 1) int64, col int32)`` of each listed user's training interactions — the item ends of
+    the graph's ``user2item`` edges whose source is that user — in the column space of ``top_k_items``' default item list (item
+    positions ``0 .. graph.num_items - 1``).  user_ids: (B,) int64 node positions on the GPU, as ``top_k_items`` takes them.
+    Built on the device with torch ops; a row lists its items in edge order (duplicate edges repeat)."""
+    require_gpu(user_ids)
+    if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
+        raise ValueError("user_ids must be a 1-D int64 tensor of user node positions")
+    dev = user_ids.device
+    ei = graph.user2item_edge_index.to(dev)
+    src, dst = ei[0].to(torch.int64), ei[1].to(torch.int64)
+    order = torch.argsort(src, stable=True)
+    s_src, s_dst = src[order], dst[order]
+    lo = torch.searchsorted(s_src, user_ids)
+    cnt = torch.searchsorted(s_src, user_ids, right=True) - lo
+    rowptr = torch.zeros(user_ids.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(cnt, 0, out=rowptr[1:])
+    row = torch.repeat_interleave(torch.arange(user_ids.numel(), device=dev), cnt)
+    pos = lo[row] + torch.arange(row.numel(), device=dev) - rowptr[row]
+    return rowptr, s_dst[pos].to(torch.int32)
 
 
 # ---------------------------------------------------------------------------------------- AttentionNCF: one user, one catalogue

@@ -527,6 +527,31 @@ int ncf_topk_rows(const float* dev_scores, int64_t rows, int64_t cols, int64_t l
                   void* dev_workspace, size_t workspace_bytes, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fused dot-product top-K (csrc/dot_topk.hip) — "rank every item for these users" for a dot-product readout (MF, GraphNCF with
+ * use_dot_product=True): ncf_gather_dot over every (user, item) pair followed by ncf_topk_rows, without the B x I score matrix.
+ * For each row r < rows (user row a = tabA[idxA[r]], or tabA[r] with idxA NULL) and each column c < cols of the ranked list (item
+ * row tabB[idxB[c]], or tabB[c] with idxB NULL), score(r, c) = <a, tabB[..]> over D fp32 elements, BIT-IDENTICAL to what
+ * ncf_gather_dot (NCF_F32) returns for that pair: 16 fmaf chains (chain s over e = s, s+16, ... in increasing e, from +0.f), then
+ * q_l = p_l + p_{l+8}, r_l = q_l + q_{l+4}, t_l = r_l + r_{l+2}, score = t_0 + t_1.  The output is ncf_topk_rows' over that
+ * score matrix: per row the k best columns by the 64-bit key (map(score) << 32 | ~c) — descending score, ties to the lower
+ * column, NaN last — skipping the columns listed for the row in the optional CSR (dev_seen_rowptr (rows + 1) int64,
+ * dev_seen_col int32; unsorted, duplicates and ids outside [0, cols) ignored).  dev_out_score / dev_out_idx: rows x k,
+ * dev_out_count: rows; slots past the count hold idx -1 and score -inf.  An output score is recovered from its key: the caller's
+ * bits for every non-NaN score; a NaN score ranks last but its payload is not kept.
+ * Out-of-range ids in idxA / idxB read as zero rows and set *dev_oob_flag (when non-NULL), as in ncf_gather_dot.
+ * Supported: 1 <= k <= 128 and 1 <= D <= 256 (the fused kernel's limits; NCF_EUNSUPPORTED otherwise, and for k outside the ABI
+ *   range 1 .. 1024 NCF_EINVAL: take ncf_gather_dot + ncf_topk_rows, which give the same answer), 1 <= cols <= 2^24, rows <= 65536;
+ *   ldA, ldB >= D.  Nothing is launched on a refusal.  The workspace (ncf_dot_topk_workspace_bytes, 16-byte aligned, never 0 for
+ *   rows > 0) holds k keys per row and column tile; rows are processed in chunks that keep it near 256 MB.  No host
+ *   synchronisation: the call captures into a HIP graph.
+ * ------------------------------------------------------------------------------------------------ */
+size_t ncf_dot_topk_workspace_bytes(int64_t rows, int64_t cols, int D, int k);
+int ncf_dot_topk(const float* dev_tabA, int64_t rowsA, int64_t ldA, const float* dev_tabB, int64_t rowsB, int64_t ldB,
+                 const int64_t* dev_idxA, const int64_t* dev_idxB, int64_t rows, int64_t cols, int D, const int64_t* dev_seen_rowptr,
+                 const int32_t* dev_seen_col, int k, float* dev_out_score, int32_t* dev_out_idx, int32_t* dev_out_count,
+                 void* dev_workspace, size_t workspace_bytes, int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Calibration probe — the bf16 MFMA rate the chip SUSTAINS on random operands (it lowers its clock under matrix load), so that
  * bench.py can state a kernel's fraction of it next to the fraction of the 2.5 PFLOP/s datasheet figure.  Not part of scoring.
  * Launches `blocks` 512-thread workgroups; every wave issues iters * 32 v_mfma_f32_16x16x32_bf16 (16 384 flop each) on register
