@@ -41,17 +41,6 @@ struct DtWaveShared {
     int cnt[kDtUsers];
 };
 
-// order this wave's LDS accesses (the LDS serves one wave's instructions in order; the fence keeps the compiler from moving
-// memory operations across it)
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
-
 // 16 floats of a row starting at element e0 (elements >= D read as 0)
 __device__ __forceinline__ void load_block(const float* __restrict__ row, int e0, int D, bool vec, float (&v)[16]) {
     if (vec && e0 + 16 <= D) {
@@ -77,29 +66,6 @@ __device__ __forceinline__ void load_frag(const float* row, int D, bool vec, int
             for (int s = 0; s < 16; ++s) v[j][s] = 0.f;
         }
     }
-}
-
-// The largest key T with #{v >= T} >= keep over the wave's 4 x 64 keys (0 = empty; at least `keep` nonzero keys present).
-__device__ unsigned long long wave_kth(const unsigned long long (&v)[4], int keep) {
-    unsigned long long prefix = 0ull;
-    for (int bit = 63; bit >= 0; --bit) {
-        const unsigned long long cand = prefix | (1ull << bit);
-        int c = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) c += __popcll(__ballot(v[i] >= cand));
-        if (c < keep) continue;
-        prefix = cand;
-        if (c == keep) {                 // exactly `keep` keys are >= cand: the smallest of them is the answer
-            unsigned long long m = ~0ull;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (v[i] >= cand) m = min(m, v[i]);
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) m = min(m, shfl_xor_u64(m, o));
-            return m;
-        }
-    }
-    return prefix;
 }
 
 // keep the `keep` best of user u's candidates; the k-th becomes the threshold

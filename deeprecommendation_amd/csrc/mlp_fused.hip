@@ -14,7 +14,7 @@
 //   The K order inside an 8-wide group is permuted identically for A and B, which only changes the fp32
 //   summation order (exact FMA chain, one rounding per product).
 // Bound: fp32 MFMA (157.3 TFLOP/s).  FLOP per pair = 2 * (K0*N1 + N1*N2 + N2)  (131 328 at 128-256-128-1).
-#include "ncf_common.h"
+#include "mlp_fused.h"
 
 #ifndef NCF_X_DEPTH
 #define NCF_X_DEPTH 4       // measured (interleaved A/B, cfg 2): 2 -> 72.4 us, 3 -> 70.0 us, 4 -> 69.5 us
@@ -683,29 +683,6 @@ __global__ void copy_or_zero_kernel(const float* __restrict__ src, int n, float*
     if (i < n) dst[i] = src ? src[i] : 0.f;
 }
 
-// blob layout (floats): Wp1[N1*K0] b1[N1] (Wp2[N2*N1] b2[N2])? wl[Nlast] bl[1] pad
-struct BlobLayout {
-    size_t wp1, b1, wp2, b2, wl, bl, total;
-};
-static BlobLayout blob_layout(const int* dims, int n_layers) {
-    BlobLayout L{};
-    const size_t K0 = dims[0], N1 = dims[1];
-    size_t off = 0;
-    L.wp1 = off; off += N1 * K0;
-    L.b1 = off; off += N1;
-    size_t last = N1;
-    if (n_layers == 3) {
-        const size_t N2 = dims[2];
-        L.wp2 = off; off += N2 * N1;
-        L.b2 = off; off += N2;
-        last = N2;
-    }
-    L.wl = off; off += last;
-    L.bl = off; off += 4;  // keep 16-byte granularity
-    L.total = off;
-    return L;
-}
-
 typedef void (*fused_fn)(FusedArgs);
 #ifndef NCF_SMALL_TILES
 #define NCF_SMALL_TILES 768   // below this many 32-pair tiles the 4-waves-per-tile kernel is used (measured crossover)
@@ -758,11 +735,6 @@ static void launch_inst(const FusedArgs& a, hipStream_t s) {
     }
     launch_main(a);
 }
-
-#define NCF_FUSED_INSTANCES(X) \
-    X(64, 256, 128) X(64, 256, 0) X(64, 128, 0) X(64, 128, 64) \
-    X(128, 256, 128) X(128, 256, 0) X(128, 128, 0) X(128, 128, 64) \
-    X(256, 256, 128) X(256, 256, 0) X(256, 128, 0)
 
 static bool fused_dispatch(int K0, int N1, int N2, const FusedArgs* a, hipStream_t s) {
 #define X(k, n1, n2) \

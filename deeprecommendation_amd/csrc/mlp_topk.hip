@@ -1,0 +1,499 @@
+// Fused MLP score-and-select (ncf_mlp_topk): the k best items of each listed user for an MLP readout (BasicNCF: cat(user, item);
+// GraphNCF(use_dot_product=False): cat(item, user)), without the B x I pair id columns or score matrix.
+//
+// Scores: bit-identical to score_fused_f32_kernel (mlp_fused.hip) for the same pair and packed blob.  That kernel computes every
+// layer transposed (pair on the MFMA column, neuron on the accumulator rows, v_mfma_f32_32x32x2_f32), starts layer 1's accumulator
+// at b1 and runs the k-steps of the concat's first part (q < EA/8, rows of tabA) before those of the second part.  An MFMA column
+// depends only on its own B operands, so after step EA/8 - 1 the accumulator of a pair is a function of its first-part row alone:
+//   prefix pass   mlp_prefix_kernel runs exactly those first EA/8 k-steps (same Wp1 fragments, same j order, from b1) once per
+//                 first-part row (32 rows per wave tile) and writes the N1-float state in neuron order: per listed user in the
+//                 user-first order, per ranked column in the item-first order.
+//   main kernel   one wave = one user x a range of ranked columns, 32 columns (one MFMA tile) at a time.  Layer 1's accumulator
+//                 starts from the prefix state (user-first: the user's state, broadcast over the columns and loaded like b1;
+//                 item-first: each column's own state), the remaining Q1 - EA/8 k-steps take the second part's rows (item rows
+//                 per column, or the user row broadcast), then layer 2 and the 1-wide layer run as in the fused kernel, with its
+//                 weight prefetch schedule, bias + ReLU and the final partial + shfl_xor(partial, 32) + bl.  The same instructions
+//                 run on the same operands in the same order, so every score has the fused scorer's bits; the first part's FLOP
+//                 (2 EA N1 per pair) is paid once per row instead of once per pair.
+// Selection: per wave, the user's candidate keys (map(score) << 32 | ~column, the topk.hip order) live in LDS behind a running k-th
+// key threshold; excluded columns are skipped through an LDS bitmap of the range.  A buffer that cannot take another 32 keys is
+// re-selected down to k (wave_kth).  Each (user, range) writes its k best keys in the layout topk_tile_kernel's merge levels read
+// (kp keys per range, 0-padded), and those levels finish the ranking; the last one recovers each score from its key (topk_unmap).
+// A fused-MLP score is never -0.0: `partial` starts at +0.f, an fmaf onto +0 and an exact cancellation both give +0 in
+// round-to-nearest, so partial is never -0 and partial + bl is -0 only if both are.  The recovered bits are therefore the caller's
+// for every non-NaN score; NaN payloads are not kept (a NaN ranks last and comes back as a NaN).
+#include "mlp_fused.h"
+#include "topk_common.h"
+
+namespace ncf {
+
+constexpr int kMtWaves = 4;                      // waves per workgroup (independent: no workgroup barrier)
+constexpr int kMtThreads = kMtWaves * kWave;
+constexpr int kMtCols = 32;                      // columns per wave tile (the MFMA N dimension)
+constexpr int kMtCap = 256;                      // candidate keys per wave (= wave_kth's 4 x 64)
+constexpr int kMtMaxK = 128;                     // fused limit on k (a re-select must free >= 32 + some slots)
+constexpr int64_t kMtTargetWaves = 2048;         // range shrinks (8192 -> 32 columns) until the grid has this many waves
+
+__device__ __forceinline__ f32x4 mt_ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// State of layer 1 after the first part's k-steps for n first-part rows tab[idx[p]] (tab[p] with idx NULL):
+// state[p][n] = (b1 + W1[:, :EA] . row)[n], accumulated in score_fused_f32_kernel's order.  Out-of-range ids read row 0 scaled
+// by zero (as the fused kernel does) and set the flag.
+template <int K0, int N1>
+__global__ __launch_bounds__(256) void mlp_prefix_kernel(const float* __restrict__ tab, int64_t rows, int64_t ld,
+                                                         const int64_t* __restrict__ idx, int64_t n, int EA,
+                                                         const float* __restrict__ Wp1, const float* __restrict__ b1,
+                                                         float* __restrict__ state, int32_t* oob) {
+    constexpr int NT1 = N1 / 32;
+    const int lane = threadIdx.x & 63;
+    const int m = lane & 31, h = lane >> 5;
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile * 32 >= n) return;
+    const int64_t p = tile * 32 + m;
+    const int64_t pc = p < n ? p : n - 1;
+    const int64_t ia = idx ? idx[pc] : pc;
+    const bool ok = (ia >= 0) & (ia < rows);
+    if (!ok && oob) *oob = 1;
+    const float* row = tab + (ok ? ia : 0) * ld + 4 * h;
+    const float z = ok ? 1.f : 0.f;
+    f32x16 acc[NT1];
+#pragma unroll
+    for (int nt = 0; nt < NT1; ++nt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 bb = mt_ldg4(b1 + 32 * nt + 8 * g + 4 * h);
+            acc[nt][4 * g + 0] = bb[0]; acc[nt][4 * g + 1] = bb[1];
+            acc[nt][4 * g + 2] = bb[2]; acc[nt][4 * g + 3] = bb[3];
+        }
+    const f32x4* wp = reinterpret_cast<const f32x4*>(Wp1) + lane;
+    const int qa = EA / 8;
+    for (int q = 0; q < qa; ++q) {
+        const f32x4 xb = mt_ldg4(row + 8 * q) * z;
+#pragma unroll
+        for (int nt = 0; nt < NT1; ++nt) {
+            const f32x4 w = wp[(q * NT1 + nt) * 64];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], xb[j], acc[nt], 0, 0, 0);
+        }
+    }
+    if (p >= n) return;
+    float* dst = state + p * N1 + 4 * h;
+#pragma unroll
+    for (int nt = 0; nt < NT1; ++nt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<f32x4*>(dst + 32 * nt + 8 * g) =
+                f32x4{acc[nt][4 * g + 0], acc[nt][4 * g + 1], acc[nt][4 * g + 2], acc[nt][4 * g + 3]};
+}
+
+struct MtArgs {
+    const float* tabB; int64_t rowsB; int64_t ldB;   // the concat's second part (items user-first, users item-first)
+    const int64_t* idxU; const int64_t* idxI;         // user ids (read here item-first only), item ids (read here user-first only)
+    int user_first;
+    int64_t cols; int EA;
+    const float* state;                               // prefix state: per global row (user-first) or per column (item-first)
+    const float* Wp1; const float* Wp2; const float* b2; const float* wl; const float* bl;
+    const int64_t* seen_rowptr; const int32_t* seen_col;
+    int64_t row0, nrows; int tiles, tile_cols, k, kp;
+    unsigned long long* out_keys; int64_t n_out;
+    int32_t* oob;
+};
+
+struct MtWaveShared {
+    unsigned long long buf[kMtCap];
+    uint32_t bitmap[kTopkTile / 32];
+};
+
+// keep the `keep` best of the wave's cnt candidates; returns the k-th key (the new threshold)
+__device__ unsigned long long mt_reselect(MtWaveShared& sh, int cnt, int keep, int lane) {
+    unsigned long long v[4];
+    wave_lds_sync();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = lane + 64 * i < cnt ? sh.buf[lane + 64 * i] : 0ull;
+    const unsigned long long kth = wave_kth(v, keep);
+    wave_lds_sync();
+    int base = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const bool f = v[i] != 0ull && v[i] >= kth;
+        const unsigned long long m = __ballot(f);
+        if (f) sh.buf[base + lanes_below(m)] = v[i];
+        base += __popcll(m);
+    }
+    wave_lds_sync();
+    return kth;
+}
+
+template <int K0, int N1, int N2>
+__global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(MtArgs a) {
+    constexpr int NT1 = N1 / 32, Q1 = K0 / 8;
+    constexpr int NT2 = N2 / 32, Q2 = N1 / 8;
+    __shared__ MtWaveShared shw[kMtWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    MtWaveShared& sh = shw[wave];
+    const int m = lane & 31, h = lane >> 5;
+    const int64_t unit = (int64_t)blockIdx.x * kMtWaves + wave;
+    if (unit >= a.nrows * a.tiles) return;               // whole wave exits together
+    const int64_t uloc = unit / a.tiles, r = a.row0 + uloc;
+    const int range = (int)(unit % a.tiles);
+    const int64_t c0 = (int64_t)range * a.tile_cols, c1 = min(a.cols, c0 + a.tile_cols);
+    const bool excl = a.seen_rowptr != nullptr;
+    if (excl) {                                          // the user's excluded columns inside [c0, c1)
+        for (int w = lane; w < a.tile_cols / 32; w += kWave) sh.bitmap[w] = 0u;
+        wave_lds_sync();
+        const int64_t pb = a.seen_rowptr[r], pe = a.seen_rowptr[r + 1];
+        for (int64_t p = pb + lane; p < pe; p += kWave) {
+            const int64_t c = (int64_t)a.seen_col[p] - c0;   // duplicates and ids outside the range do nothing
+            if (c >= 0 && c < c1 - c0) atomicOr(&sh.bitmap[c >> 5], 1u << (c & 31));
+        }
+        wave_lds_sync();
+    }
+    // item-first: the user is the second part, one row broadcast to every column
+    const float* urow = nullptr;
+    float zU = 1.f;
+    if (!a.user_first) {
+        const int64_t iu = a.idxU ? a.idxU[r] : r;
+        const bool ok = (iu >= 0) & (iu < a.rowsB);
+        if (!ok && a.oob) *a.oob = 1;
+        urow = a.tabB + (ok ? iu : 0) * a.ldB + 4 * h;
+        zU = ok ? 1.f : 0.f;
+    }
+    const int qa = a.EA / 8, Qr = Q1 - qa;               // k-steps done by the prefix pass / left here (Qr >= 1)
+    const float bl0 = a.bl[0];
+    unsigned long long thr = 0ull;
+    int cnt = 0;
+
+    for (int64_t cb = c0; cb < c1; cb += kMtCols) {
+        // The bias / weight pointers are made opaque per tile: hoisted out of the tile loop, the loop-invariant b2, wl and first
+        // weight loads would hold ~160 VGPRs for the whole loop and spill.
+        const float* Wp1 = a.Wp1;
+        const float* Wp2 = a.Wp2;
+        const float* b2 = a.b2;
+        const float* wl = a.wl;
+        asm volatile("" : "+s"(Wp1), "+s"(Wp2), "+s"(b2), "+s"(wl));
+        const int64_t c = cb + m;
+        const int64_t cc = c < c1 ? c : c1 - 1;
+        const float* srow;
+        const float* xrow;
+        float zx;
+        if (a.user_first) {
+            srow = a.state + r * N1;
+            const int64_t ib = a.idxI ? a.idxI[cc] : cc;
+            const bool ok = (ib >= 0) & (ib < a.rowsB);
+            if (!ok && a.oob) *a.oob = 1;
+            xrow = a.tabB + (ok ? ib : 0) * a.ldB + 4 * h;
+            zx = ok ? 1.f : 0.f;
+        } else {
+            srow = a.state + cc * N1;
+            xrow = urow;
+            zx = zU;
+        }
+
+        // ---- layer 1: acc1 = prefix state + the second part's k-steps (score_fused_f32_kernel's steps qa .. Q1 - 1) ----
+        f32x16 acc1[NT1];
+#pragma unroll
+        for (int nt = 0; nt < NT1; ++nt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 bb = mt_ldg4(srow + 32 * nt + 8 * g + 4 * h);
+                acc1[nt][4 * g + 0] = bb[0]; acc1[nt][4 * g + 1] = bb[1];
+                acc1[nt][4 * g + 2] = bb[2]; acc1[nt][4 * g + 3] = bb[3];
+            }
+        {
+            // Qr is a runtime count, so the steps run in a loop of step pairs with two weight buffers (a fully unrolled loop with
+            // per-step guards keeps both versions of every ring register live and spills).  As in the fused kernel, the next
+            // step's weight load for tile nt is issued right behind tile nt's MFMAs, and the row chunks two and three steps ahead
+            // are issued after the step's weight loads, so the in-order vmcnt wait for the next weights never waits for them.
+            // Look-ahead loads past the last step re-read the last step's data (in bounds, unused) instead of branching.
+            const f32x4* wp = reinterpret_cast<const f32x4*>(Wp1) + (int64_t)qa * NT1 * 64 + lane;  // + (s*NT1 + nt)*64
+            auto mfma_step = [&](const f32x4 (&w)[NT1], f32x4 (&wn)[NT1], int sn, f32x4 xv) {
+                const f32x4 xb = xv * zx;                // zero an out-of-range row at use time
+#pragma unroll
+                for (int nt = 0; nt < NT1; ++nt) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[nt][j], xb[j], acc1[nt], 0, 0, 0);
+                    wn[nt] = wp[(sn * NT1 + nt) * 64];
+                }
+            };
+            f32x4 wA[NT1], wB[NT1];
+            f32x4 x0, x1, x2, x3;
+#pragma unroll
+            for (int nt = 0; nt < NT1; ++nt) wA[nt] = wp[nt * 64];
+            x0 = mt_ldg4(xrow);
+            x1 = mt_ldg4(xrow + 8 * min(1, Qr - 1));
+            int s = 0;
+            for (; s + 1 < Qr; s += 2) {
+                mfma_step(wA, wB, s + 1, x0);
+                x2 = mt_ldg4(xrow + 8 * min(s + 2, Qr - 1));
+                x3 = mt_ldg4(xrow + 8 * min(s + 3, Qr - 1));
+#pragma unroll
+                for (int nt = 0; nt < NT1; ++nt) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
+                }
+                __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                mfma_step(wB, wA, min(s + 2, Qr - 1), x1);
+#pragma unroll
+                for (int nt = 0; nt < NT1; ++nt) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                x0 = x2;
+                x1 = x3;
+            }
+            if (s < Qr) {                                // odd count: the last step (wA, x0 hold it)
+                const f32x4 xb = x0 * zx;
+#pragma unroll
+                for (int nt = 0; nt < NT1; ++nt)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wA[nt][j], xb[j], acc1[nt], 0, 0, 0);
+            }
+        }
+
+        float partial = 0.f;
+        if constexpr (N2 > 0) {
+            // ---- layer 2: acc2 = b2 + W2 . relu(acc1) ----
+            f32x16 acc2[NT2];
+#pragma unroll
+            for (int nt = 0; nt < NT2; ++nt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 bb = mt_ldg4(b2 + 32 * nt + 8 * g + 4 * h);
+                    acc2[nt][4 * g + 0] = bb[0]; acc2[nt][4 * g + 1] = bb[1];
+                    acc2[nt][4 * g + 2] = bb[2]; acc2[nt][4 * g + 3] = bb[3];
+                }
+            const f32x4* wp = reinterpret_cast<const f32x4*>(Wp2) + lane;
+            f32x4 w[2][NT2];
+#pragma unroll
+            for (int nt = 0; nt < NT2; ++nt) w[0][nt] = wp[nt * 64];
+#pragma unroll
+            for (int q = 0; q < Q2; ++q) {
+                const int cur = q & 1, nxt = cur ^ 1;
+                const int kb = q >> 2, g = q & 3;
+                f32x4 hv;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) hv[j] = fmaxf(acc1[kb][4 * g + j], 0.f);
+#pragma unroll
+                for (int nt = 0; nt < NT2; ++nt) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
+                    if (q + 1 < Q2) w[nxt][nt] = wp[((q + 1) * NT2 + nt) * 64];
+                }
+#pragma unroll
+                for (int nt = 0; nt < NT2; ++nt) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // ---- last layer (1 wide): bl + sum_n wl[n] * relu(acc2[n]) ----
+#pragma unroll
+            for (int nt = 0; nt < NT2; ++nt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 ww = mt_ldg4(wl + 32 * nt + 8 * g + 4 * h);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc2[nt][4 * g + j], 0.f), partial);
+                }
+        } else {
+#pragma unroll
+            for (int nt = 0; nt < NT1; ++nt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 ww = mt_ldg4(wl + 32 * nt + 8 * g + 4 * h);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc1[nt][4 * g + j], 0.f), partial);
+                }
+        }
+        partial += __shfl_xor(partial, 32);              // the two lane halves hold complementary neuron rows
+        const float score = partial + bl0;
+
+        // ---- select: lanes of half 0 hold columns cb + m ----
+        const unsigned long long key = ((unsigned long long)topk_map(score) << 32) | (0xFFFFFFFFu - (uint32_t)c);
+        bool pass = h == 0 && c < c1 && key > thr;
+        if (pass && excl) {
+            const int off = (int)(c - c0);
+            pass = !((sh.bitmap[off >> 5] >> (off & 31)) & 1u);
+        }
+        const unsigned long long mk = __ballot(pass);
+        if (pass) sh.buf[cnt + lanes_below(mk)] = key;   // cnt <= kMtCap - 32 before this tile
+        cnt += __popcll(mk);
+        if (cnt > kMtCap - kMtCols) {
+            thr = mt_reselect(sh, cnt, a.k, lane);
+            cnt = a.k;
+        }
+    }
+
+    // this range's k best keys, unsorted, 0-padded to kp
+    if (cnt > a.k) {
+        mt_reselect(sh, cnt, a.k, lane);
+        cnt = a.k;
+    }
+    wave_lds_sync();
+    unsigned long long* dst = a.out_keys + uloc * a.n_out + (int64_t)range * a.kp;
+    for (int s = lane; s < a.kp; s += kWave) dst[s] = s < cnt ? sh.buf[s] : 0ull;
+}
+
+// The launch plan: column ranges of the fused level, then the merge levels of topk_tile_kernel over kp keys per range.
+struct MlpTopkPlan {
+    int tile_cols;
+    int64_t tiles0;
+    int merges;              // merge launches (>= 1: the last one sorts and writes the result)
+    int64_t mtiles[8];
+    int kp;
+    int64_t n1, n2;          // keys per row in the two ping-pong buffers
+    int64_t chunk;           // rows per chunk
+    size_t state_bytes;      // prefix state at the front of the workspace
+};
+
+static MlpTopkPlan mlp_topk_plan(int64_t rows, int64_t cols, int N1, int user_first, int k) {
+    MlpTopkPlan p{};
+    p.kp = (k + 1) & ~1;
+    p.tile_cols = kTopkTile;
+    while (p.tile_cols > kMtCols && rows * ((cols + p.tile_cols - 1) / p.tile_cols) < kMtTargetWaves) p.tile_cols >>= 1;
+    p.tiles0 = (cols + p.tile_cols - 1) / p.tile_cols;
+    p.n1 = p.tiles0 * p.kp;
+    int64_t n = p.n1;
+    p.merges = 0;
+    while (true) {
+        const int64_t t = (n + kTopkTile - 1) / kTopkTile;
+        p.mtiles[p.merges++] = t;
+        if (t == 1) break;
+        n = t * p.kp;
+    }
+    p.n2 = p.merges > 1 ? p.mtiles[0] * p.kp : 0;
+    const int64_t per_row = (p.n1 + p.n2) * 8;
+    p.chunk = max((int64_t)1, min(rows, (int64_t)(kTopkChunkBytes / per_row)));
+    p.state_bytes = (size_t)(user_first ? rows : cols) * N1 * sizeof(float);
+    return p;
+}
+
+static bool mt_dispatch(int K0, int N1, int N2, bool launch, unsigned blocks, hipStream_t s, const MtArgs* a) {
+#define X(k0, n1, n2) \
+    if (K0 == k0 && N1 == n1 && N2 == n2) { if (launch) hipLaunchKernelGGL((mlp_topk_kernel<k0, n1, n2>), dim3(blocks), dim3(kMtThreads), 0, s, *a); return true; }
+    NCF_FUSED_INSTANCES(X)
+#undef X
+    return false;
+}
+
+static bool mt_shape_ok(int dtype, int EA, int EB, int n_layers, const int* dims) {
+    if (dtype != NCF_F32 || !dims) return false;
+    if (n_layers != 2 && n_layers != 3) return false;
+    if (dims[n_layers] != 1) return false;
+    if (EA < 8 || EB < 8 || EA % 8 || EB % 8 || EA + EB != dims[0]) return false;   // both parts present
+    return mt_dispatch(dims[0], dims[1], n_layers == 3 ? dims[2] : 0, false, 0, nullptr, nullptr);
+}
+
+static int mt_check(int64_t rows, int64_t cols, int k, const char* what) {
+    if (k < 1 || k > kTopkMaxK) return fail(NCF_EINVAL, "%s: k = %d is outside 1 .. %d", what, k, kTopkMaxK);
+    if (k > kMtMaxK) return fail(NCF_EUNSUPPORTED, "%s: k = %d is above the fused limit %d", what, k, kMtMaxK);
+    if (cols < 1 || cols > kTopkMaxCols)
+        return fail(NCF_EUNSUPPORTED, "%s: cols = %lld is outside 1 .. %lld", what, (long long)cols, (long long)kTopkMaxCols);
+    if (rows < 0 || rows > kTopkMaxRows)
+        return fail(NCF_EUNSUPPORTED, "%s: rows = %lld is outside 0 .. %lld", what, (long long)rows, (long long)kTopkMaxRows);
+    return NCF_OK;
+}
+
+static size_t mt_workspace(const MlpTopkPlan& p) { return p.state_bytes + (size_t)(p.chunk * (p.n1 + p.n2) * 8); }
+
+}  // namespace ncf
+
+using namespace ncf;
+
+extern "C" int ncf_mlp_topk_supported(int dtype, int EA, int EB, int n_layers, const int* dims, int k) {
+    return (mt_shape_ok(dtype, EA, EB, n_layers, dims) && k >= 1 && k <= kMtMaxK) ? 1 : 0;
+}
+
+extern "C" size_t ncf_mlp_topk_workspace_bytes(int64_t rows, int64_t cols, int user_first, int n_layers, const int* dims, int k) {
+    if (mt_check(rows, cols, k, "ncf_mlp_topk_workspace_bytes") != NCF_OK || rows == 0) return 0;
+    if (!dims || (n_layers != 2 && n_layers != 3) || dims[1] < 32 || dims[1] % 32) return 0;
+    return mt_workspace(mlp_topk_plan(rows, cols, dims[1], user_first, k));
+}
+
+extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t ldA, const void* tabB, int64_t rowsB, int64_t ldB,
+                            int EA, int EB, int user_first, const int64_t* user_ids, const int64_t* item_ids, int64_t rows,
+                            int64_t cols, int n_layers, const int* dims, const void* packed, const int64_t* seen_rowptr,
+                            const int32_t* seen_col, int k, float* out_score, int32_t* out_idx, int32_t* out_count, void* workspace,
+                            size_t workspace_bytes, int32_t* oob, ncf_stream_t stream) {
+    const int rc = mt_check(rows, cols, k, "ncf_mlp_topk");
+    if (rc != NCF_OK) return rc;
+    if (!mt_shape_ok(dtype, EA, EB, n_layers, dims))
+        return fail(NCF_EUNSUPPORTED, "ncf_mlp_topk: no fused instance for dtype=%d EA=%d EB=%d layers=%d", dtype, EA, EB, n_layers);
+    if (rows == 0) return NCF_OK;
+    if (!tabA || !tabB || !packed || !out_score || !out_idx || !out_count) return fail(NCF_EINVAL, "ncf_mlp_topk: null argument");
+    if (ldA < EA || ldB < EB || ldA % 4 || ldB % 4 || !aligned16(tabA) || !aligned16(tabB) || !aligned16(packed))
+        return fail(NCF_EINVAL, "ncf_mlp_topk: tables must be 16-byte aligned with ld %% 4 == 0");
+    user_first = user_first ? 1 : 0;
+    const int64_t nUrows = user_first ? rowsA : rowsB, nIrows = user_first ? rowsB : rowsA;
+    if (!user_ids && rows > nUrows) return fail(NCF_EINVAL, "ncf_mlp_topk: rows = %lld > user table rows without user ids", (long long)rows);
+    if (!item_ids && cols > nIrows) return fail(NCF_EINVAL, "ncf_mlp_topk: cols = %lld > item table rows without item ids", (long long)cols);
+    if ((seen_rowptr == nullptr) != (seen_col == nullptr))
+        return fail(NCF_EINVAL, "ncf_mlp_topk: seen_rowptr and seen_col are given together or not at all");
+    const int K0 = dims[0], N1 = dims[1], N2 = n_layers == 3 ? dims[2] : 0;
+    const MlpTopkPlan p = mlp_topk_plan(rows, cols, N1, user_first, k);
+    const size_t need = mt_workspace(p);
+    if (workspace_bytes < need)
+        return fail(NCF_EWORKSPACE, "ncf_mlp_topk: workspace of %zu bytes, %zu needed (ncf_mlp_topk_workspace_bytes)", workspace_bytes, need);
+    if (!workspace || !aligned16(workspace)) return fail(NCF_EINVAL, "ncf_mlp_topk: workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const BlobLayout L = blob_layout(dims, n_layers);
+    const float* P = (const float*)packed;
+    float* state = (float*)workspace;
+    unsigned long long* bufA = (unsigned long long*)((char*)workspace + p.state_bytes);
+    unsigned long long* bufB = bufA + p.chunk * p.n1;
+
+    // prefix pass over the first part's rows: the listed users (user-first) or the ranked items (item-first)
+    const int64_t npre = user_first ? rows : cols;
+    const unsigned pblocks = (unsigned)(((npre + 31) / 32 + 3) / 4);
+#define X(k0, n1, n2) \
+    if (K0 == k0 && N1 == n1 && N2 == n2) \
+        hipLaunchKernelGGL((mlp_prefix_kernel<k0, n1>), dim3(pblocks), dim3(256), 0, s, (const float*)tabA, rowsA, ldA, \
+                           user_first ? user_ids : item_ids, npre, EA, P + L.wp1, P + L.b1, state, oob);
+    NCF_FUSED_INSTANCES(X)
+#undef X
+
+    MtArgs a{};
+    a.tabB = (const float*)tabB; a.rowsB = rowsB; a.ldB = ldB;
+    a.idxU = user_ids; a.idxI = item_ids;
+    a.user_first = user_first;
+    a.cols = cols; a.EA = EA;
+    a.state = state;
+    a.Wp1 = P + L.wp1;
+    a.Wp2 = n_layers == 3 ? P + L.wp2 : nullptr; a.b2 = n_layers == 3 ? P + L.b2 : nullptr;
+    a.wl = P + L.wl; a.bl = P + L.bl;
+    a.seen_rowptr = seen_rowptr; a.seen_col = seen_col;
+    a.tiles = (int)p.tiles0; a.tile_cols = p.tile_cols; a.k = k; a.kp = p.kp;
+    a.out_keys = bufA; a.n_out = p.n1;
+    a.oob = oob;
+    for (int64_t r0 = 0; r0 < rows; r0 += p.chunk) {
+        const int64_t nr = min(p.chunk, rows - r0);
+        a.row0 = r0; a.nrows = nr;
+        const unsigned blocks = (unsigned)((nr * p.tiles0 + kMtWaves - 1) / kMtWaves);
+        mt_dispatch(K0, N1, N2, true, blocks, s, &a);
+        // merge levels: topk_tile_kernel over the fused level's kp keys per range; the last one sorts and writes (score from the key)
+        unsigned long long* in = bufA;
+        unsigned long long* out = bufB;
+        int64_t n_in = p.n1;
+        for (int lv = 0; lv < p.merges; ++lv) {
+            const int64_t t = p.mtiles[lv];
+            if (lv == p.merges - 1) {
+                hipLaunchKernelGGL((topk_tile_kernel<false, true>), dim3((unsigned)(t * nr)), dim3(kTopkThreads), 0, s, nullptr, 0, 0, nullptr,
+                                   nullptr, in, n_in, (int)t, r0, k, p.kp, nullptr, 0, out_score, out_idx, out_count);
+            } else {
+                const int64_t n_out = t * p.kp;
+                hipLaunchKernelGGL((topk_tile_kernel<false, false>), dim3((unsigned)(t * nr)), dim3(kTopkThreads), 0, s, nullptr, 0, 0,
+                                   nullptr, nullptr, in, n_in, (int)t, r0, k, p.kp, out, n_out, out_score, out_idx, out_count);
+                unsigned long long* tmp = in;
+                in = out;
+                out = tmp;
+                n_in = n_out;
+            }
+        }
+    }
+    return check_launch("ncf_mlp_topk");
+}

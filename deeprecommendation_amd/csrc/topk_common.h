@@ -1,5 +1,6 @@
-// Shared pieces of the per-row top-K (topk.hip: ncf_topk_rows; dot_topk.hip: ncf_dot_topk): the key map, the tile select
-// kernel, the launch plan.  See topk.hip for the ordering contract and the kernel shape.  Internal: not part of the ABI.
+// Shared pieces of the per-row top-K (topk.hip: ncf_topk_rows; dot_topk.hip: ncf_dot_topk; mlp_topk.hip: ncf_mlp_topk): the key
+// map, the wave-wide candidate helpers of the fused kernels, the tile select kernel, the launch plan.  See topk.hip for the
+// ordering contract and the kernel shape.  Internal: not part of the ABI.
 #pragma once
 #include "ncf_common.h"
 
@@ -33,6 +34,40 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 // (key >> top) == (ref >> top), with top = 64 meaning "no bits": true
 __device__ __forceinline__ bool topk_high_eq(unsigned long long key, unsigned long long ref, int top) {
     return top >= 64 || ((key ^ ref) >> top) == 0;
+}
+
+// order this wave's LDS accesses (the LDS serves one wave's instructions in order; the fence keeps the compiler from moving
+// memory operations across it)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
+
+// The largest key T with #{v >= T} >= keep over the wave's 4 x 64 keys (0 = empty; at least `keep` nonzero keys present).
+__device__ unsigned long long wave_kth(const unsigned long long (&v)[4], int keep) {
+    unsigned long long prefix = 0ull;
+    for (int bit = 63; bit >= 0; --bit) {
+        const unsigned long long cand = prefix | (1ull << bit);
+        int c = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c += __popcll(__ballot(v[i] >= cand));
+        if (c < keep) continue;
+        prefix = cand;
+        if (c == keep) {                 // exactly `keep` keys are >= cand: the smallest of them is the answer
+            unsigned long long m = ~0ull;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (v[i] >= cand) m = min(m, v[i]);
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) m = min(m, shfl_xor_u64(m, o));
+            return m;
+        }
+    }
+    return prefix;
 }
 
 struct TopkShared {

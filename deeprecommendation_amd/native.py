@@ -113,6 +113,10 @@ SIGNATURES = {
     "ncf_dot_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_int]),
     "ncf_dot_topk": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_int, _c_p,
                               _c_p, _c_p, _c_p, _c_size, _c_p, _c_p]),
+    "ncf_mlp_topk_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_p, _c_int]),
+    "ncf_mlp_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_int, _c_p, _c_int]),
+    "ncf_mlp_topk": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_i64,
+                              _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p]),
     "ncf_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _c_i64, _c_p]),
 }
@@ -1249,4 +1253,48 @@ def dot_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
     _check(lib.ncf_dot_topk(_ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, I, D, _ptr(rowptr), _ptr(col),
                             k, _ptr(out_score), _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
+    return out_score, out_idx, out_count
+
+
+MLP_TOPK_MAX_K = 128     # the fused MLP kernel's limit on k (include/ncf_abi.h ncf_mlp_topk)
+
+
+def mlp_topk_supported(packed: PackedMLP, EA: int, EB: int, k: int) -> bool:
+    """Whether ncf_mlp_topk has a kernel for this packed MLP, split (EA, EB) and k."""
+    return bool(load_library().ncf_mlp_topk_supported(packed.dt, EA, EB, packed.n_layers, _dims_array(packed.dims), int(k)))
+
+
+def mlp_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], packed: PackedMLP,
+             k: int, seen: Optional[tuple] = None, user_first: bool = True):
+    """ncf_mlp_topk: the k best items of each user for an MLP readout over cat(tabA[idxA[.]], tabB[idxB[.]]) (id lists None =
+    every row).  user_first=True: the users are the first part (rows of the result = idxA, ranked columns = idxB); False: the items
+    are (columns = idxA, rows = idxB).  Exactly ``topk_rows(score_fused(...).view(B, I), k, seen)`` over every (user, item) pair,
+    bit for bit, without the pair id columns or the score matrix.  Returns (out_score (B, k) fp32, out_idx (B, k) int32 columns
+    of the list, out_count (B,) int32) like topk_rows.  A shape without a fused instance, a bf16 blob or k > MLP_TOPK_MAX_K raise
+    NativeError with code NCF_EUNSUPPORTED and launch nothing.  Outputs and workspace from the caching allocator on the current
+    stream; no sync."""
+    lib = load_library()
+    _dev(tabA, "tabA"), _dev(tabB, "tabB")
+    rowsA, EA, ldA = _rows2d(tabA, "tabA")
+    rowsB, EB, ldB = _rows2d(tabB, "tabB")
+    if tabA.dtype != tabB.dtype:
+        raise TypeError("mlp_topk: both tables must have one dtype")
+    if tabA.dtype != packed.dtype:
+        raise TypeError(f"tables are {tabA.dtype} but the MLP was packed for {packed.dtype}")
+    idxA, idxB = _idx(idxA), _idx(idxB)
+    nA = idxA.numel() if idxA is not None else rowsA
+    nB = idxB.numel() if idxB is not None else rowsB
+    user_ids, item_ids, B, I = (idxA, idxB, nA, nB) if user_first else (idxB, idxA, nB, nA)
+    k = int(k)
+    dev = tabA.device
+    rowptr, col = _seen_csr(seen, B, dev)
+    out_score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    out_idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    out_count = torch.empty(B, dtype=torch.int32, device=dev)
+    d = _dims_array(packed.dims)
+    nbytes = lib.ncf_mlp_topk_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, k)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    _check(lib.ncf_mlp_topk(packed.dt, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, EA, EB, 1 if user_first else 0, _ptr(user_ids),
+                            _ptr(item_ids), B, I, packed.n_layers, d, _ptr(packed.blob), _ptr(rowptr), _ptr(col), k, _ptr(out_score),
+                            _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
     return out_score, out_idx, out_count

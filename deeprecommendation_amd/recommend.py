@@ -1,8 +1,9 @@
 """Top-K recommendation on the device: the library function behind the reference's web backend (webapp/backend.py:78-121).
 
 ``top_k_items``        BasicNCF / MF (index providers) and GraphNCF: every listed user against every item (or a subset), scored
-                       block by block through the model's HIP scoring path and ranked by ncf_topk_rows — or, for a dot-product
-                       readout, scored and ranked in one pass by ncf_dot_topk (no score matrix).  Results stay on the device.
+                       block by block through the model's HIP scoring path and ranked by ncf_topk_rows — or scored and ranked in
+                       one pass (no score matrix) by ncf_dot_topk for a dot-product readout and by ncf_mlp_topk for an MLP
+                       readout.  Results stay on the device.
 ``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
 ``recommend_for_user`` AttentionNCF: one user given as a Series of ratings against a catalogue, with the reference's arguments,
                        threshold rule and DataFrame columns (imdbID, score, because, attention).  Only k scores, k ids and the k
@@ -54,10 +55,13 @@ def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.
     int32)`` of columns of the ranked list to skip (with ``item_ids`` absent, columns are item positions) — typically each
     user's training ratings (``seen_items`` builds it from a graph).  graph: the GraphData a GraphNCF is evaluated on; required
     for a GraphNCF and refused for any other model.
-    fused: how a dot-product readout (MF, GraphNCF with ``use_dot_product=True``) is ranked.  ``None``: GraphNCF-dot through the
-    fused score-and-select kernel (``native.dot_topk``: no score matrix), everything else score-then-select; ``True``: the fused
-    kernel for MF too (refused for a model with an MLP readout); ``False``: score-then-select everywhere.  Both routes give the
-    same bits; where the fused kernel's limits (k <= 128, width <= 256) do not hold it falls back to score-then-select.
+    fused: how the scores are ranked.  ``None``: GraphNCF-dot through the fused dot-product score-and-select kernel
+    (``native.dot_topk``), and an MLP readout (BasicNCF, GraphNCF with ``use_dot_product=False``) through the fused MLP
+    score-and-select kernel (``native.mlp_topk``), neither of which writes a score matrix; MF score-then-select.  ``True``: the
+    fused dot-product kernel for MF too (refused for a model with an MLP readout); ``False``: score-then-select everywhere.  All
+    routes give the same bits.  Where a fused kernel's limits do not hold it falls back to score-then-select: k <= 128 for both;
+    width <= 256 for the dot kernel; for the MLP kernel fp32 scoring, no folded first layer and an MLP shape with an
+    ``ncf_score_fused`` instance.
     Returns ``(scores (B, k) fp32, item_positions (B, k) int64, counts (B,) int32)`` on the device, each row in descending score
     order (ties: lower column first; NaN last); slots past ``counts`` hold position -1 and score -inf.  Score-then-select scores
     the users in blocks of rows whose (user, item) score block stays under ``block_bytes``; nothing synchronises with the host."""
@@ -99,9 +103,11 @@ def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.
         rowptr, col = rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous()
     users = user_ids.contiguous()
     out = None
+    seen = None if exclude is None else (rowptr, col)
     if use_fused:
-        out = _fused_top_k(model, graph, users, item_ids is None, items, n_items, int(k),
-                           None if exclude is None else (rowptr, col))
+        out = _fused_top_k(model, graph, users, item_ids is None, items, n_items, int(k), seen)
+    elif fused is None and not _dot_readout(model):
+        out = _fused_mlp_top_k(model, graph, users, item_ids is None, items, n_items, int(k), seen)
     if out is None:
         score = (lambda u, i: model(graph, u, i)) if is_graph else model
         rows_per_block = max(1, int(block_bytes) // max(1, I * _PAIR_BYTES))
@@ -144,6 +150,32 @@ def _fused_top_k(model, graph, users, all_items, items, n_items, k, seen):
         if tabA.shape[1] > native.DOT_TOPK_MAX_D:
             return None
         return native.dot_topk(tabA, users, tabB, items, k, seen)
+
+
+def _fused_mlp_top_k(model, graph, users, all_items, items, n_items, k, seen):
+    """native.mlp_topk over the model's MLP readout — BasicNCF: cat(user table, item table), the users first; GraphNCF:
+    cat(item node rows, user node rows) of the propagated table, the items first.  None where the fused kernel does not apply
+    (bf16 scoring, a folded first layer, an MLP shape without a fused instance, k > 128); the caller then scores and selects,
+    which gives the same bits."""
+    if k > native.MLP_TOPK_MAX_K or model.scoring_dtype != torch.float32 or model.fold_first_layer:
+        return None
+    with torch.no_grad():
+        cache = model._refresh()
+        packed = model._packed_mlp("MLP", cache)
+        if packed is None:
+            return None
+        if graph is not None:
+            combined = model.propagate_all(graph, cache)
+            tabA, idxA, tabB, idxB, user_first = combined, items, combined, users, False
+            if all_items:                   # the first n_items rows are the item nodes: rank them in place, no id list
+                tabA, idxA = combined[:n_items], None
+        else:
+            tabA = model._table("user", model.user_embeddings[0], cache)
+            tabB = model._table("item", model.item_embeddings[0], cache)
+            idxA, idxB, user_first = users, None if all_items else items, True
+        if not native.mlp_topk_supported(packed, tabA.shape[1], tabB.shape[1], k):
+            return None
+        return native.mlp_topk(tabA, idxA, tabB, idxB, packed, k, seen, user_first=user_first)
 
 
 def seen_items(graph, user_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

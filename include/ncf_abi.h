@@ -552,6 +552,36 @@ int ncf_dot_topk(const float* dev_tabA, int64_t rowsA, int64_t ldA, const float*
                  void* dev_workspace, size_t workspace_bytes, int32_t* dev_oob_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fused MLP top-K (csrc/mlp_topk.hip) — "rank every item for these users" for an MLP readout (BasicNCF: cat(user, item);
+ * GraphNCF with use_dot_product=False: cat(item, user)): ncf_score_fused over every (user, item) pair followed by ncf_topk_rows,
+ * without the pair id columns or the B x I score matrix.  The concat's first part (EA wide) comes from dev_tabA, the second (EB
+ * wide) from dev_tabB; user_first != 0 says the user is the first part (rows of tabA, items rows of tabB), 0 that the item is
+ * (items rows of tabA, users rows of tabB).  Row r < rows is user dev_user_ids[r] (r with NULL), column c < cols of the ranked
+ * list is item dev_item_ids[c] (c with NULL).  score(r, c) is BIT-IDENTICAL to what ncf_score_fused (NCF_F32) returns for that
+ * pair with the same packed blob (ncf_mlp_pack; n_layers, dims as there): the first part's share of layer 1 runs once per row
+ * of the first part (in the fused scorer's operation order) instead of once per pair.  The output is ncf_topk_rows' over that
+ * score matrix, as in ncf_dot_topk: keys (map(score) << 32 | ~c), ties to the lower column, NaN last, the columns listed for the
+ * row in the optional CSR (dev_seen_rowptr (rows + 1) int64, dev_seen_col int32; duplicates and ids outside [0, cols) ignored)
+ * skipped; out_score / out_idx rows x k, out_count rows, slots past the count idx -1 / score -inf.  Scores are recovered from
+ * keys: the caller's bits for every non-NaN score (a fused-MLP score is never -0.0); a NaN ranks last, its payload not kept.
+ * Out-of-range user or item ids read as zero rows and set *dev_oob_flag (when non-NULL), as in ncf_score_fused.
+ * Supported (ncf_mlp_topk_supported): dtype NCF_F32, a (K0 = EA + EB, dims) shape with an ncf_score_fused instance, EA and EB
+ *   both >= 8 and multiples of 8, 1 <= k <= 128; NCF_EUNSUPPORTED otherwise (k outside the ABI range 1 .. 1024: NCF_EINVAL) —
+ *   take ncf_score_fused + ncf_topk_rows, which give the same answer.  1 <= cols <= 2^24, rows <= 65536; tables 16-byte aligned
+ *   with ld % 4 == 0.  Nothing is launched on a refusal.  The workspace (ncf_mlp_topk_workspace_bytes, 16-byte aligned, never 0
+ *   for rows > 0) holds the first part's layer-1 state (dims[1] floats per user, or per column when user_first == 0) and k keys
+ *   per row and column range; rows are processed in chunks that keep the key part near 256 MB.  No host synchronisation: the
+ *   call captures into a HIP graph.
+ * ------------------------------------------------------------------------------------------------ */
+int ncf_mlp_topk_supported(int dtype, int EA, int EB, int n_layers, const int* dims, int k);
+size_t ncf_mlp_topk_workspace_bytes(int64_t rows, int64_t cols, int user_first, int n_layers, const int* dims, int k);
+int ncf_mlp_topk(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, const void* dev_tabB, int64_t rowsB, int64_t ldB,
+                 int EA, int EB, int user_first, const int64_t* dev_user_ids, const int64_t* dev_item_ids, int64_t rows,
+                 int64_t cols, int n_layers, const int* dims, const void* dev_packed, const int64_t* dev_seen_rowptr,
+                 const int32_t* dev_seen_col, int k, float* dev_out_score, int32_t* dev_out_idx, int32_t* dev_out_count,
+                 void* dev_workspace, size_t workspace_bytes, int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Calibration probe — the bf16 MFMA rate the chip SUSTAINS on random operands (it lowers its clock under matrix load), so that
  * bench.py can state a kernel's fraction of it next to the fraction of the 2.5 PFLOP/s datasheet figure.  Not part of scoring.
  * Launches `blocks` 512-thread workgroups; every wave issues iters * 32 v_mfma_f32_16x16x32_bf16 (16 384 flop each) on register
