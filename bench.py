@@ -5,9 +5,14 @@ emb_dim 64, batch 65 536, fp32, MLP [256, 128] -> 1; synthetic seeded tables / w
 A "step" = one forward of one batch through the product path (BasicNCF.forward on int64 positions ->
 ncf_score_fused through the C ABI), inputs already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given and prints the line.  `--full` adds everything else, after the headline measurement: the live
+`roofline` / `gather_roofline` launches, cfg 2's `variants`, the CPU baselines and `other_configs`.  The secondary
+configs (`--workload cfgK`) run with `--full` only.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment STARTS the N ranks itself: this process, before it has made
 any GPU call, runs the torch.distributed.run command above as a child and exits with its code (a process that has
@@ -16,7 +21,7 @@ touched the GPU is never re-exec'd).  Under torchrun, WORLD_SIZE must equal --gp
 N > 1, headline line: replicas (pairs are independent; tables + MLP replicated, the batch is split, no
 data-path collective) -> weak scaling, value = N * 65 536 * K / max-over-ranks time.
 
-`other_configs` (default run only; `--workload cfg2` prints the headline line alone, `--workload cfgK` that config alone):
+`other_configs` (`--full` without `--workload` only; `--workload cfg2` prints the headline line alone, `--workload cfgK` that config alone):
   N = 1: cfg 3 (AttentionNCF), cfg 4 (LightGCN propagation, 100 M directed edges), cfg 5 (bf16 emb 128, the 28 GB of
          tables on one GPU), each with its own `roofline` and `cpu_baseline`;
   N > 1: the two configs that SHARD — cfg 5 (row-sharded tables, all-to-all over RCCL; pipelined / serial / de-duplicating
@@ -367,6 +372,35 @@ def run_cfg2(args, ctx):
         graph_reported = elapsed_graph is not None and elapsed_graph <= elapsed_eager
         dump_outputs(args.dump_outputs, {"scores": graph_last if graph_reported else last_out}, rank)
 
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "scored user-item pairs/sec",
+            "value": world * B * args.steps / elapsed,
+            "unit": "pairs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": warm,
+            "warmup_requested": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": "cfg2: BasicNCF 1M users x 100k items, emb_dim=64, batch=65536/GPU, fp32, MLP 128-256-128-1"
+                                   + (" [Zipf(1.05) user ids]" if ctxname == "cfg2zipf" else "")
+                                   + (" [first MLP layer FOLDED into 256-wide tables: 65 792 executed FLOP and 2068 B per pair]" if args.fold else ""),
+                       "parallelism": f"replicas x{world} (tables+MLP replicated, batch split, no collective)",
+                       "step_form": ("HIP-graph launches of %d steps over the resident index batches" % steps_per_launch
+                                     if elapsed_graph is not None and elapsed_graph <= elapsed_eager else "one forward per step, enqueued from Python"),
+                       "eager_ms_per_step": elapsed_eager / args.steps * 1e3,
+                       "graph_ms_per_step": None if elapsed_graph is None else elapsed_graph / args.steps * 1e3, "graph_error": graph_err,
+                       "full": args.full},
+        }
+    if not args.full:
+        return line
+
     # --- roofline of the dominant kernel (the kernels run on torch's current stream, so torch.cuda.Event brackets them)
     packed = model._packed_mlp()
     tu, ti = model._table("user", model.user_embeddings[0]), model._table("item", model.item_embeddings[0])
@@ -469,29 +503,7 @@ def run_cfg2(args, ctx):
 
     if rank != 0:
         return None
-    total_pairs = world * B * args.steps
-    line = {
-        "metric": "scored user-item pairs/sec",
-        "value": total_pairs / elapsed,
-        "unit": "pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": warm,
-        "warmup_requested": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "cfg2: BasicNCF 1M users x 100k items, emb_dim=64, batch=65536/GPU, fp32, MLP 128-256-128-1"
-                               + (" [Zipf(1.05) user ids]" if ctxname == "cfg2zipf" else "")
-                               + (" [first MLP layer FOLDED into 256-wide tables: 65 792 executed FLOP and 2068 B per pair]" if args.fold else ""),
-                   "parallelism": f"replicas x{world} (tables+MLP replicated, batch split, no collective)",
-                   "step_form": ("HIP-graph launches of %d steps over the resident index batches" % steps_per_launch
-                                 if elapsed_graph is not None and elapsed_graph <= elapsed_eager else "one forward per step, enqueued from Python"),
-                   "eager_ms_per_step": elapsed_eager / args.steps * 1e3,
-                   "graph_ms_per_step": None if elapsed_graph is None else elapsed_graph / args.steps * 1e3, "graph_error": graph_err},
+    line.update({
         "roofline": {"kernel": "score_fused_f32_kernel<128,256,128>", "bound": "mfma", "achieved": achieved_tf,
                      "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved_tf / PEAK_F32_MFMA_TFLOPS,
                      "traffic": kt_f["traffic"], "us_per_launch": kt_f["us"], "us_per_launch_basis": kt_f["basis"],
@@ -510,7 +522,7 @@ def run_cfg2(args, ctx):
                             "ids": "Zipf(1.05) users" if ctxname == "cfg2zipf" else "uniform",
                             "algorithmic_bytes_per_pair": GATHER_BYTES_PER_PAIR, "algorithmic_bytes_per_launch": GATHER_BYTES_PER_PAIR * B,
                             "frac_of_measured_copy_ceiling": ((variants or {}).get("gather_measured_ceilings") or {}).get("gather_frac_of_copy_ceiling")},
-    }
+    })
     if variants is not None:
         line["variants"] = variants
     if fold_info is not None:
@@ -601,11 +613,16 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline path returned in its last timed step as DIR/scores.npy "
                          "(float32, [65536, 1]; seeded inputs: identical from run to run with the same arguments)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also take the live roofline launches, cfg2's variants, the CPU baselines and "
+                         "other_configs (a plain run measures the headline alone); the secondary --workload configs need it")
     args = ap.parse_args()
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be >= 1")
     if args.dump_outputs is not None and args.workload not in (None, "cfg2"):
         ap.error("--dump-outputs writes the headline workload's outputs (cfg2): run it without --workload or with --workload cfg2")
+    if args.workload not in (None, "cfg2") and not args.full:
+        ap.error(f"--workload {args.workload} is a secondary config: it runs with --full only")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus is not None and args.gpus > 1:
             sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -630,7 +647,7 @@ def main():
         line = fn(sized(st, wu), ctx)
     else:
         line = run_cfg2(sized(400, 40), ctx)
-        if args.workload is None:
+        if args.workload is None and args.full:
             others = {}
             if ctx.rank == 0:
                 line["other_configs"] = others

@@ -58,6 +58,30 @@ def test_dump_outputs_is_refused_for_a_secondary_workload(tmp_path):
     assert not (tmp_path / "out").exists()
 
 
+def test_secondary_workload_needs_full():
+    r = _run(["--workload", "cfg3"], NO_GPU)
+    assert r.returncode != 0
+    assert "--workload cfg3 is a secondary config: it runs with --full only" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_alone(gpu):
+    """A plain run prints the headline line without what --full adds, and spends less than 30 s outside its steps."""
+    import time
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)], timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([s for s in r.stdout.splitlines() if s.startswith("{")][-1])
+    assert line["metric"] == "scored user-item pairs/sec" and line["unit"] == "pairs/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["steps"] == steps and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["config"]["full"] is False
+    for key in ("roofline", "gather_roofline", "variants", "cpu_baseline", "cpu_baseline_reference_formulation", "other_configs"):
+        assert key not in line
+    assert wall - (steps + warmup) * line["ms_per_step"] * 1e-3 < 30.0
+
+
 @pytest.mark.gpu
 def test_dump_outputs_holds_the_last_timed_step(gpu, tmp_path):
     """--dump-outputs DIR: the scores of the last of the --steps timed steps (40 steps over the 16 cycled index batches: the

@@ -14,10 +14,10 @@ cd $ROOT
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE"
 for C in $CTXS; do
   case $C in
-    cfg2)     ARGS="bench.py --workload cfg2 --steps 60 --warmup 10 --no-cpu-baseline --no-variants" ;;
-    cfg2zipf) ARGS="bench.py --workload cfg2 --steps 60 --warmup 10 --no-cpu-baseline --no-variants --zipf-users" ;;
-    cfg5_b*)  export NCF_CFG5_LOCAL_BATCH=${C#cfg5_b}; ARGS="bench.py --workload cfg5 --steps 30 --warmup 5 --no-cpu-baseline --no-variants" ;;
-    *)        unset NCF_CFG5_LOCAL_BATCH; ARGS="bench.py --workload $C --no-cpu-baseline --no-variants" ;;
+    cfg2)     ARGS="bench.py --full --workload cfg2 --steps 60 --warmup 10 --no-cpu-baseline --no-variants" ;;
+    cfg2zipf) ARGS="bench.py --full --workload cfg2 --steps 60 --warmup 10 --no-cpu-baseline --no-variants --zipf-users" ;;
+    cfg5_b*)  export NCF_CFG5_LOCAL_BATCH=${C#cfg5_b}; ARGS="bench.py --full --workload cfg5 --steps 30 --warmup 5 --no-cpu-baseline --no-variants" ;;
+    *)        unset NCF_CFG5_LOCAL_BATCH; ARGS="bench.py --full --workload $C --no-cpu-baseline --no-variants" ;;
   esac
   OUT=$ROOT/gpurun_out/prof_${TAG}_$C
   mkdir -p $OUT
