@@ -3,7 +3,7 @@
 Needs a checkout of the reference project (its path as the argument, or NCF_REFERENCE_DIR):
 
     python tests/golden/make_golden.py <reference checkout>
-    python tests/golden/make_golden.py <reference checkout> --only g4     # the G4 fixture alone (or: --only blas_probe)
+    python tests/golden/make_golden.py <reference checkout> --only g4     # the G4 fixture alone (or: --only g3_peaked, blas_probe)
 
 Each .npz holds weights (every state_dict entry, prefixed ``w::``), inputs and the reference's
 outputs, so nothing depends on RNG-stream equality between torch versions.  Only *data* is stored:
@@ -19,6 +19,8 @@ Round 3 adds the deterministic train-mode pins:
   g3_att_train_*   AttentionNCF in .train() with dropout_rate=0.0 / message_dropout=None: target masking (:195-205)
   g7_grads_*       loss = MSELoss(reduction='sum') (datasets/base.py:19-20,31-32), .backward(): every parameter gradient
   g8_create_graph_*  content_providers/graph_providers.py:10-66 create_graph, binary and weighted
+
+and the peaked-softmax pins (golden_g3_peaked): g3_att_peaked_e64, g3_att_peaked_none, g3_att_train_peaked.
 """
 import hashlib
 import json
@@ -71,6 +73,105 @@ def _save(name, **arrays):
     path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **arrays)
     print("wrote", path, os.path.getsize(path), "bytes")
+
+
+# attention_ncf.py:195-205: in training a candidate that equals one of the rated rows (isclose on the embeddings) is
+# masked out of its own softmax row.  Candidates 0..n_self-1 ARE rated rows of the batch; the loss is the reference's
+# MSELoss(reduction='sum') against y (datasets/base.py:19-20,31-32) and every parameter gradient is stored.
+def _att_train_case(torch, AttentionNCF, tag, Fdim, IE, UE, B, I, n_self, seed, mlp, density=0.5, att_scale=None, **kw):
+    torch.manual_seed(seed)
+    m = AttentionNCF(item_dim=Fdim, item_emb=IE, user_emb=UE, mlp_dense_layers=mlp, dropout_rate=0.0,
+                     message_dropout=None, **kw).train()
+    extra = {}
+    if att_scale is not None:                             # peaked softmax: AttentionNet's last Linear scaled (see golden_g3_peaked)
+        with torch.no_grad():
+            m.AttentionNet[-1].weight.mul_(att_scale)
+        extra["att_scale"] = np.array(float(att_scale))
+        hook = _logit_hook(m, extra)
+    g = torch.Generator().manual_seed(seed + 1)
+    rated = torch.rand(I, Fdim, generator=g)
+    cand = torch.rand(B, Fdim, generator=g)
+    self_cols = torch.randperm(I, generator=g)[:n_self]
+    cand[:n_self] = rated[self_cols]                      # these candidates are rated items of the batch
+    um = torch.zeros(B, I)
+    mask = torch.rand(B, I, generator=g) < density
+    um[mask] = (torch.randint(1, 11, (B, I), generator=g).float() * 0.5 - 2.9)[mask]
+    for b in range(n_self):                               # the user HAS rated the candidate (that is what gets masked)
+        um[b, self_cols[b]] = 1.35 if b % 2 == 0 else -0.65
+    um[B - 1] = 0.0                                       # all-unrated row in train mode
+    if n_self > 1:                                        # a row whose ONLY rated entry is the candidate itself -> all -inf -> 0
+        um[1] = 0.0
+        um[1, self_cols[1]] = 0.85
+    y = torch.randint(1, 11, (B,), generator=g).float() * 0.5
+    out, att = m(cand, rated, um, return_attention_weights=True)
+    if att_scale is not None:
+        hook.remove()
+    loss = torch.nn.MSELoss(reduction='sum')(out, y.view(-1, 1).float())
+    loss.backward()
+    grads = {"g::" + k: p.grad.detach().numpy().copy() for k, p in m.named_parameters()}
+    assert all(np.isfinite(v).all() for v in grads.values())
+    _save(tag, candidate_items=cand.numpy(), rated_items=rated.numpy(), user_matrix=um.numpy(), y=y.numpy(),
+          self_cols=self_cols.numpy(), out=out.detach().numpy(), att=att.numpy(), loss=np.array(loss.item()),
+          kwargs=np.array(json.dumps(m.kwargs)), **_state_arrays(m), **grads, **extra)
+
+
+def _logit_hook(m, store):
+    """Forward hook on AttentionNet: its output is the reference's raw logits attOut (attention_ncf.py:179), one per valid pair of
+    the batch in row-major (pair, rated item) order; stored as ``logits``."""
+    return m.AttentionNet.register_forward_hook(lambda mod, inp, out: store.__setitem__("logits", out.detach().reshape(-1).numpy().copy()))
+
+
+# G3 peaked: AttentionNet's last Linear (the one that produces the logit) multiplied by PEAK_SCALE, so that the softmax is as peaked
+# as with trained weights: one rated item takes almost all the weight, the logits of a row spread over tens of units and most exp
+# terms underflow.  PEAK_SCALE is the smallest round value with a median row max weight >= 0.9 and a per-row logit spread >= 60 in
+# g3_att_peaked_e64 (tests/test_attention_peaked_fixtures.py checks both).
+PEAK_SCALE = 500.0
+# the train fixture's scale: its rows are shorter (~75 entries) and its gradients go through the softmax derivative, whose fp32 rounding
+# grows with the logits: at 500 the reference's own gradients lie 0.5-0.8 of the 1e-5 bar from their float64 values, at 300 the median
+# row max weight is still 0.8
+TRAIN_PEAK_SCALE = 300.0
+
+
+def golden_g3_peaked(torch, AttentionNCF):
+    """g3_att_peaked_e64: the dims where the grouped / entry-split / tail kernels all apply (F = 50, IE = UE = 64, A = 128, MLP
+    [256, 128]), 8 users x 32 candidates in the reference's call shape (a user's row repeated per candidate), 400 rated items: six
+    users rate 300-360 of them (rows of 5-6 tiles of 64), one rates a single item, one none; ratings of both signs.
+    g3_att_peaked_none: the linear AttentionNet (att_dense=None) scaled the same way.  g3_att_train_peaked: the train-mode recipe
+    (target mask, gradients of MSELoss(sum)) with the scaled AttentionNet.  Every fixture stores the reference's raw logits."""
+    def eval_case(tag, Fdim, IE, A, mlp, users, per_user, I, counts, seed):
+        # hashed weights at PyTorch's default Linear scale (bound 1 / sqrt(fan_in)) stored as their recipe, except AttentionNet's scaled
+        # output weight, stored as values
+        m = AttentionNCF(item_dim=Fdim, item_emb=IE, user_emb=IE, att_dense=A, mlp_dense_layers=mlp).eval()
+        recipe, state, peaked = [], {}, "AttentionNet.%d.weight" % (len(m.AttentionNet) - 1)
+        for salt, (k, v) in enumerate(m.state_dict().items()):
+            fan_in = int(m.state_dict()[k.replace(".bias", ".weight")].shape[1])
+            state[k] = torch.from_numpy(hashed_weight(tuple(v.shape), seed * 100 + salt, fan_in ** -0.5))
+            if k == peaked:
+                state[k] = state[k] * PEAK_SCALE
+            else:
+                recipe.append([k, list(v.shape), seed * 100 + salt, fan_in ** -0.5])
+        m.load_state_dict(state)
+        g = torch.Generator().manual_seed(seed + 1)
+        rated = torch.rand(I, Fdim, generator=g)
+        cand = torch.rand(users * per_user, Fdim, generator=g)
+        rows = torch.zeros(users, I)
+        for u, n in enumerate(counts):
+            cols = torch.randperm(I, generator=g)[:n]
+            rows[u, cols] = torch.randint(1, 11, (n,), generator=g).float() * 0.5 - 2.9     # -2.4 .. 2.1, never 0
+        um = rows[torch.arange(users * per_user) // per_user].contiguous()                # the user's row once per candidate
+        extra = {}
+        hook = _logit_hook(m, extra)
+        with torch.no_grad():
+            out, att = m(cand, rated, um, return_attention_weights=True)
+        hook.remove()
+        _save(tag, candidate_items=cand.numpy(), rated_items=rated.numpy(), user_matrix=um.numpy(), out=out.numpy(), att=att.numpy(),
+              att_scale=np.array(PEAK_SCALE), kwargs=np.array(json.dumps(m.kwargs)), hashed_weights=np.array(json.dumps(recipe)),
+              **{"w::" + peaked: state[peaked].numpy()}, **extra)
+
+    eval_case("g3_att_peaked_e64", 50, 64, 128, [256, 128], 8, 32, 400, [340, 300, 360, 1, 320, 0, 350, 310], 107)
+    eval_case("g3_att_peaked_none", 20, 16, None, [32, 16], 6, 4, 120, [100, 90, 1, 0, 110, 70], 108)
+    _att_train_case(torch, AttentionNCF, "g3_att_train_peaked", 48, 64, 64, 40, 150, 9, 205, [64], density=0.5,
+                    att_scale=TRAIN_PEAK_SCALE, att_dense=128)
 
 
 def golden_g4(torch, AttentionNCF):
@@ -208,36 +309,8 @@ def main():
               out=out.numpy(), att=att.numpy(), kwargs=np.array(json.dumps(m.kwargs)), **_state_arrays(m))
 
     # ---------------- G3-train: AttentionNCF.train(), deterministic (dropout 0, no message dropout) ----------------
-    # attention_ncf.py:195-205: in training a candidate that equals one of the rated rows (isclose on the embeddings) is
-    # masked out of its own softmax row.  Candidates 0..n_self-1 ARE rated rows of the batch; the loss is the reference's
-    # MSELoss(reduction='sum') against y (datasets/base.py:19-20,31-32) and every parameter gradient is stored.
-    def att_train_case(tag, Fdim, IE, UE, B, I, n_self, seed, mlp, density=0.5, **kw):
-        torch.manual_seed(seed)
-        m = AttentionNCF(item_dim=Fdim, item_emb=IE, user_emb=UE, mlp_dense_layers=mlp, dropout_rate=0.0,
-                         message_dropout=None, **kw).train()
-        g = torch.Generator().manual_seed(seed + 1)
-        rated = torch.rand(I, Fdim, generator=g)
-        cand = torch.rand(B, Fdim, generator=g)
-        self_cols = torch.randperm(I, generator=g)[:n_self]
-        cand[:n_self] = rated[self_cols]                      # these candidates are rated items of the batch
-        um = torch.zeros(B, I)
-        mask = torch.rand(B, I, generator=g) < density
-        um[mask] = (torch.randint(1, 11, (B, I), generator=g).float() * 0.5 - 2.9)[mask]
-        for b in range(n_self):                               # the user HAS rated the candidate (that is what gets masked)
-            um[b, self_cols[b]] = 1.35 if b % 2 == 0 else -0.65
-        um[B - 1] = 0.0                                       # all-unrated row in train mode
-        if n_self > 1:                                        # a row whose ONLY rated entry is the candidate itself -> all -inf -> 0
-            um[1] = 0.0
-            um[1, self_cols[1]] = 0.85
-        y = torch.randint(1, 11, (B,), generator=g).float() * 0.5
-        out, att = m(cand, rated, um, return_attention_weights=True)
-        loss = torch.nn.MSELoss(reduction='sum')(out, y.view(-1, 1).float())
-        loss.backward()
-        grads = {"g::" + k: p.grad.detach().numpy().copy() for k, p in m.named_parameters()}
-        assert all(np.isfinite(v).all() for v in grads.values())
-        _save(tag, candidate_items=cand.numpy(), rated_items=rated.numpy(), user_matrix=um.numpy(), y=y.numpy(),
-              self_cols=self_cols.numpy(), out=out.detach().numpy(), att=att.numpy(), loss=np.array(loss.item()),
-              kwargs=np.array(json.dumps(m.kwargs)), **_state_arrays(m), **grads)
+    def att_train_case(*args, **kw):
+        _att_train_case(torch, AttentionNCF, *args, **kw)
 
     att_train_case("g3_att_train_dense8", 20, 16, 16, 8, 12, 3, 201, [32, 16], att_dense=8)
     att_train_case("g3_att_train_cos", 20, 16, 16, 8, 12, 3, 202, [32, 16], use_cos_sim_instead=True)
@@ -294,6 +367,8 @@ def main():
               user2item_edge_index=gr.user2item_edge_index.numpy(), item2user_edge_index=gr.item2user_edge_index.numpy(),
               pos=pos, **extra)
 
+    golden_g3_peaked(torch, AttentionNCF)
+
     golden_g4(torch, AttentionNCF)
 
     golden_blas_probe(torch)
@@ -349,18 +424,23 @@ def main():
 
 
 if __name__ == "__main__":
-    # python tests/golden/make_golden.py <reference checkout> [--only g4|blas_probe]
+    # python tests/golden/make_golden.py <reference checkout> [--only g4|g3_peaked|blas_probe]
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     if args:
         REF = args[0]
     if not REF or not os.path.isdir(os.path.join(REF, "src")):
-        raise SystemExit("usage: make_golden.py <reference checkout> [--only g4|blas_probe]  (or set NCF_REFERENCE_DIR)")
+        raise SystemExit("usage: make_golden.py <reference checkout> [--only g4|g3_peaked|blas_probe]  (or set NCF_REFERENCE_DIR)")
     if "--only" in sys.argv:
         _import_reference()
         import torch
         from neural_collaborative_filtering.models.attention_ncf import AttentionNCF
         torch.set_num_threads(1)
         only = sys.argv[sys.argv.index("--only") + 1]
-        golden_g4(torch, AttentionNCF) if only == "g4" else golden_blas_probe(torch)
+        if only == "g4":
+            golden_g4(torch, AttentionNCF)
+        elif only == "g3_peaked":
+            golden_g3_peaked(torch, AttentionNCF)
+        else:
+            golden_blas_probe(torch)
     else:
         main()

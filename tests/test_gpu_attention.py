@@ -762,3 +762,77 @@ def test_attn_candidates_random_shapes(gpu):
             assert ids.numel() == B and torch.equal(torch.sort(ids).values, torch.arange(B, device=gpu)), tag
             assert torch.equal(who[ids], torch.sort(who).values), tag          # listed row by row
     native.check_oob(gpu)
+
+
+# ----------------------------------------------------------------------------- peaked softmax (g3_att_peaked_*), every route of the model
+def _assert_within(got, ref, extra, tag):
+    """assert_close's bar (1e-5 of each element + a tenth of that on the largest) widened element by element by ``extra``."""
+    from conftest import record_error
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape
+    bar = 1e-5 * ref.abs() + 1e-6 * ref.abs().max() + extra
+    err = (got - ref).abs()
+    k = int((err / bar).argmax())
+    record_error(tag, float(err.flatten()[k]), float(bar.flatten()[k]))
+    assert bool((err <= bar).all()), f"{tag}: max abs err {float(err.max()):.3e}, worst {float((err / bar).max()):.2f} of the bar"
+
+
+@pytest.mark.parametrize("name", ["g3_att_peaked_e64", "g3_att_peaked_none"])
+def test_attention_peaked_golden_every_route(gpu, monkeypatch, kernel_option, name):
+    """The reference's peaked-softmax fixtures through every route of the model: the plain call with the dense user matrix (on-stream
+    CSR, grouped kernels), return_attention_weights (weights too), the per-pair CSR (attn_kernel), and for e64 the shared-row
+    SparseRatings (8 rated sets): attn_candidates -> entry-split kernel with the default nsplit > 1 -> partials merged by attn_tail,
+    checked by counting the calls — and the same batch with attn_grouped_kernel forced to lds and to scalar.
+
+    Bar: the default, widened element by element by the condition estimate of test_attention_peaked_fixtures.peaked_condition — the
+    first-order effect of the fp32 rounding of the logits (sums of terms much larger than themselves here), measured on the stored
+    reference logits and allowed once for the reference and once for the kernel.  The softmax, merge and weighted sum themselves are
+    pinned at the default bar with exact logits in test_gpu_attention_softmax.py."""
+    from deeprecommendation_amd import native
+    from deeprecommendation_amd.neural_collaborative_filtering.models.attention_ncf import SparseRatings
+    from test_attention_peaked_fixtures import peaked_condition
+    state, a, kw = load_golden(name)
+    _, _, d_out, d_w = peaked_condition(name)
+    m = _model(kw, state, gpu)
+    cand, rated, um = (torch.from_numpy(a[k]).to(gpu) for k in ("candidate_items", "rated_items", "user_matrix"))
+    ref_out, ref_att = torch.from_numpy(a["out"]), torch.from_numpy(a["att"])
+    with torch.no_grad():
+        _assert_within(m(cand, rated, um), ref_out, d_out, "dense")
+        out, att = m(cand.clone(), rated, um, return_attention_weights=True)
+        _assert_within(out, ref_out, d_out, "weights:out")
+        _assert_within(att, ref_att, d_w, "weights:att")
+        assert float(att[(um != 0).sum(1) == 0].abs().sum()) == 0.0
+        per_pair = SparseRatings.from_dense(um, share_identical_rows=False)
+        assert per_pair.pair_row is None
+        _assert_within(m(cand.clone(), rated, per_pair), ref_out, d_out, "per_pair")
+        shared = SparseRatings.from_dense(um)
+        assert shared.pair_row is not None and shared.rowptr.numel() - 1 == torch.unique(um, dim=0).shape[0]
+        if name == "g3_att_peaked_none":
+            _assert_within(m(cand.clone(), rated, shared), ref_out, d_out, "shared")    # ATT_LINEAR: per-pair kernel on the expanded rows
+            return
+        calls = []
+        for fn in ("attn_candidates", "attn_forward_grouped", "default_attn_nsplit", "attn_tail"):
+            real = getattr(native, fn)
+
+            def wrap(*args, _real=real, _fn=fn, **kw_):
+                res = _real(*args, **kw_)
+                if _fn == "default_attn_nsplit":
+                    calls.append((_fn, res))
+                elif _fn == "attn_tail":
+                    calls.append((_fn, args[1].nsplit if isinstance(args[1], native.AttnPartials) else 0))
+                else:
+                    calls.append((_fn, None))
+                return res
+            monkeypatch.setattr(native, fn, wrap)
+        out = m(cand.clone(), rated, shared)
+        names = [c[0] for c in calls]
+        assert names == ["attn_candidates", "default_attn_nsplit", "attn_forward_grouped", "attn_tail"], names   # nsplit: inside the grouped call
+        nsplit = calls[1][1]
+        assert nsplit > 1 and calls[3][1] == nsplit          # the entry-split kernel left nsplit > 1 partials and attn_tail merged them
+        _assert_within(out, ref_out, d_out, "shared:split+tail")
+        for kernel in ("lds", "scalar"):
+            kernel_option("attn_grouped_kernel", kernel)
+            calls.clear()
+            out = m(cand.clone(), rated, shared)
+            assert "attn_forward_grouped" in [c[0] for c in calls] and ("attn_tail", 0) in calls
+            _assert_within(out, ref_out, d_out, f"shared:{kernel}")

@@ -1,0 +1,399 @@
+"""K3's softmax on peaked rows, every kernel path, against a float64 reference with EXACT logits.
+
+AttentionNCF's attention kernels keep an online softmax state (running max m, sum of exponentials l, weighted feature sum O) per
+pair, per tile and, in the entry-split form, per slice of the rated set; the slices are merged by attn_combine_kernel or inside
+attn_tail.  All of that only matters when the softmax is peaked: one entry takes almost all the weight, the logits of a row spread
+over tens of units, most exp terms underflow, and the row maximum sits anywhere in the row.
+
+The inputs here are built so that every logit is exact in fp32 whatever the summation order: dyadic operands with few significant
+bits (pc odd multiples of 1/32, pr multiples of 1/16, w1 multiples of 1/16; two designed columns with w1 = +1 and -1 carry the
+row's designed logit t: relu(P + t/2) - relu(P - t/2) = t), so no sum ever rounds and pc + pr is never exactly 0 (no relu kink).
+For ATT_MLP_SCALED pc, pr carry 2^-64 and w1 2^64 (exact).  The kernel and the float64 reference then see identical logits, and
+only the softmax, the merge and the weighted sum are tested: the bar stays at the repository's 1e-5.
+
+Rows: a dominant entry (+60) first, last, in a middle tile and in the last slice; two exactly equal maxima in different slices;
+all logits in [82, 92] (exp overflows without the max subtraction) and in [-200, -190] (0/0 without it); a leader with the rest
+87-110 below (the fp32 underflow / flush range of exp); a whole slice 120+ below the global max (merge factor 0, finite l and O);
+one entry; none; lengths 0, 1, 63, 64, 65, 300, 1000; ratings of both signs, negative on some leaders.
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import record_error
+from test_gpu_basic import assert_close
+
+pytestmark = pytest.mark.gpu
+
+ATT_MLP, ATT_LINEAR, ATT_COS, ATT_MLP_SCALED = 0, 1, 2, 3     # include/ncf_abi.h (native.ATT_*)
+SCALE_LOG2 = 64                                               # native.ATT_SCALE_LOG2
+P_DESIGN = 512.0 + 1.0 / 32                                   # pc on the two designed columns
+B1 = 0.125
+
+# (name, length): the designed cases of the rated sets
+ROWS = [("lead_first", 300), ("lead_last", 300), ("lead_mid_tile", 300), ("lead_last_slice", 1000), ("tie_two_slices", 1000),
+        ("hot", 300), ("cold", 300), ("underflow_band", 300), ("dead_slice", 1000), ("single", 1), ("empty", 0),
+        ("len63", 63), ("len64", 64), ("len65", 65), ("neg_lead_1000", 1000)]
+TIE = (10, 900)                    # tie_two_slices: entries with identical pr rows (tiles 0 and 14)
+
+
+# ------------------------------------------------------------------------------------------------ float64 reference (CPU)
+def masked_softmax64(s, rowptr):
+    """Row softmax over the CSR entries ``s`` (float64, -inf = masked); a row without a finite entry gets zeros (the reference's
+    F.softmax over -inf + nan_to_num, attention_ncf.py:208-209)."""
+    s = s.double()
+    w = torch.zeros_like(s)
+    rp = rowptr.tolist()
+    for r in range(len(rp) - 1):
+        x = s[rp[r]:rp[r + 1]]
+        if x.numel() and bool(torch.isfinite(x).any()):
+            e = torch.exp(x - x.max())
+            w[rp[r]:rp[r + 1]] = e / e.sum()
+    return w
+
+
+def scores64(mode, pc, pr, w1, b1, normalize=True):
+    """Logits of pairs ``pc`` (P, A) against entries ``pr`` (n, A): (P, n) float64.  MLP / MLP_SCALED: b1 + sum_a w1[a] relu(pc + pr);
+    LINEAR (A = 1): pc + pr; COS: dot of the L2-normalised rows (eps 1e-12; ``normalize=False``: the kernels' contract, rows given
+    normalised — what the backward differentiates)."""
+    if mode == ATT_LINEAR:
+        return pc[:, None, 0] + pr[None, :, 0]
+    if mode == ATT_COS:
+        if normalize:
+            pc, pr = torch.nn.functional.normalize(pc, dim=1, eps=1e-12), torch.nn.functional.normalize(pr, dim=1, eps=1e-12)
+        return pc @ pr.t()
+    return torch.relu(pc[:, None, :] + pr[None]) @ w1 + b1
+
+
+def attention64(mode, pc, pr, w1, b1, rowptr, col, val, pair_row, feat, bias, normalize=True):
+    """out (B, Fdim) = sum_e w_e val_e feat[col_e] + bias per pair (bias alone for an empty set), the weights and the logits in the
+    expanded per-pair CSR layout (pair b's entries, pairs in order), all float64 and differentiable in pc, pr, w1, feat."""
+    B, I = pc.shape[0], pr.shape[0]
+    rp = rowptr.tolist()
+    out = [None] * B
+    wts, logits = [None] * B, [None] * B
+    for r in range(len(rp) - 1):
+        pairs = (pair_row == r).nonzero().view(-1)
+        if not pairs.numel():
+            continue
+        c, v = col[rp[r]:rp[r + 1]].long(), val[rp[r]:rp[r + 1]].double()
+        ok = (c >= 0) & (c < I)
+        cc = c.clamp(0, max(I - 1, 0))
+        if c.numel():
+            s = scores64(mode, pc[pairs], pr[cc], w1, b1, normalize)
+            s = torch.where(ok[None], s, torch.full_like(s, -float("inf")))
+            w = torch.softmax(s, 1).nan_to_num(0.0) if bool(ok.any()) else torch.zeros_like(s)
+            o = (w * v) @ feat[cc] + bias
+        else:
+            s = w = torch.zeros((pairs.numel(), 0), dtype=torch.float64)
+            o = bias.expand(pairs.numel(), -1) + 0 * feat.sum() + 0 * pc[pairs].sum()
+        for k, b in enumerate(pairs.tolist()):
+            out[b], wts[b], logits[b] = o[k], w[k], s[k]
+    return torch.stack(out), torch.cat(wts), torch.cat(logits)
+
+
+# ------------------------------------------------------------------------------------------------ the designed inputs
+def _design(rng):
+    """Per row: the designed logits t (multiples of 1/16) and the ratings."""
+    noise = lambda n: rng.integers(-160, 161, n) / 16.0            # [-10, 10]
+    val = lambda n: rng.integers(1, 11, n) * 0.5 - 2.9             # -2.4 .. 2.1, never 0
+    rows = []
+    for name, n in ROWS:
+        t, v = noise(n), val(n)
+        if name == "lead_first":
+            t[0] = 70.0
+        elif name == "lead_last":
+            t[-1], v[-1] = 70.0, -1.9
+        elif name == "lead_mid_tile":
+            t[145], v[145] = 70.0, -0.4
+        elif name == "lead_last_slice":
+            t[990] = 70.0
+        elif name == "tie_two_slices":
+            t[TIE[0]] = t[TIE[1]] = 70.0
+            v[TIE[1]] = -v[TIE[0]] + 0.5
+        elif name == "hot":
+            t = rng.integers(82 * 16, 92 * 16 + 1, n) / 16.0
+        elif name == "cold":
+            t = rng.integers(-200 * 16, -190 * 16 + 1, n) / 16.0
+        elif name == "underflow_band":
+            t = -(87.0 + rng.integers(0, 23 * 16 + 1, n) / 16.0)
+            t[37], v[37] = 0.0, -2.4
+        elif name == "dead_slice":
+            t[512:] = noise(n - 512) - 130.0                      # tiles 8..15: >= 120 below the row max
+        elif name == "single":
+            t[:] = 5.0
+        elif name in ("len63", "len64", "len65"):
+            t[int(rng.integers(0, n))] = 70.0
+        elif name == "neg_lead_1000":
+            t[700], v[700] = 70.0, -2.4
+        rows.append((name, t, v.astype(np.float32)))
+    return rows
+
+
+@functools.lru_cache(maxsize=None)
+def make_case(mode, seed=7):
+    """CPU tensors of one batch: pc (B, A), pr (I, A), w1, b1, CSR (rowptr, col, val) of the designed rows, pair_row (B,), feat
+    (I, Fdim), bias; and the float64 reference (out, weights, logits).  Row 0 has 70 pairs (several workgroups of every group size),
+    the others 1 .. 9, in random pair order."""
+    rng = np.random.default_rng(seed + 17 * mode)
+    rows = _design(rng)
+    A = {ATT_LINEAR: 1, ATT_COS: 64}.get(mode, 128)
+    Fdim = 64
+    lens = [len(t) for _, t, _ in rows]
+    I = sum(lens) + 16                                              # every row its own items, 16 nobody rated
+    rowptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    rowptr[1:] = np.cumsum(lens)
+    col = np.arange(sum(lens), dtype=np.int32)
+    t_all = np.concatenate([t for _, t, _ in rows])
+    val = np.concatenate([v for _, _, v in rows])
+    counts = [70] + [1 + int(rng.integers(0, 9)) for _ in rows[1:]]
+    pair_row = np.repeat(np.arange(len(rows)), counts)
+    rng.shuffle(pair_row)
+    B = len(pair_row)
+    if mode in (ATT_MLP, ATT_MLP_SCALED):
+        pc = (2 * rng.integers(-32, 32, (B, A)) + 1) / 32.0
+        pr = rng.integers(-32, 33, (I, A)) / 16.0
+        w1 = rng.integers(-1, 2, A) / 16.0
+        pc[:, 0] = pc[:, 1] = P_DESIGN
+        pr[:, 0], pr[:, 1] = 0.0, 0.0
+        pr[:len(t_all), 0], pr[:len(t_all), 1] = t_all / 2, -t_all / 2
+        w1[0], w1[1] = 1.0, -1.0
+        b1 = B1
+    elif mode == ATT_LINEAR:
+        pc = (2 * rng.integers(-32, 32, (B, 1)) + 1) / 32.0
+        pr = rng.integers(-16, 17, (I, 1)) / 16.0
+        pr[:len(t_all), 0] += t_all
+        w1, b1 = None, 0.0
+    else:                                                           # COS: unit rows of four +-1/2 (exact norms), some zero rows
+        def unit(n):
+            x = np.zeros((n, A))
+            for i in range(n):
+                x[i, rng.choice(A, 4, replace=False)] = rng.choice([-0.5, 0.5], 4)
+            return x
+        pc, pr = unit(B), unit(I)
+        pc[int(np.flatnonzero(pair_row == 0)[0])] = 0.0                # a pair with a zero-norm candidate row: all logits 0
+        pr[rowptr[1] + 3::7] = 0.0                                    # zero-norm rated rows
+        w1, b1 = None, 0.0
+    s = rowptr[ROWS.index(("tie_two_slices", 1000))]
+    pr[s + TIE[1]] = pr[s + TIE[0]]                                  # the two maxima are the very same logit for every pair
+    if mode == ATT_MLP_SCALED:
+        pc, pr, w1 = pc * 2.0 ** -SCALE_LOG2, pr * 2.0 ** -SCALE_LOG2, w1 * 2.0 ** SCALE_LOG2
+    g = torch.Generator().manual_seed(seed)
+    case = dict(mode=mode, A=A, Fdim=Fdim, I=I, B=B,
+                pc=torch.tensor(pc, dtype=torch.float32), pr=torch.tensor(pr, dtype=torch.float32),
+                w1=None if w1 is None else torch.tensor(w1, dtype=torch.float32), b1=b1,
+                rowptr=torch.from_numpy(rowptr), col=torch.from_numpy(col), val=torch.from_numpy(val),
+                pair_row=torch.from_numpy(pair_row.astype(np.int64)),
+                feat=torch.randn(I, Fdim, generator=g), bias=torch.randn(Fdim, generator=g))
+    out, w, s64 = attention64(mode, *(_f64(case[k]) for k in ("pc", "pr", "w1")), b1, case["rowptr"], case["col"], case["val"],
+                              case["pair_row"], _f64(case["feat"]), _f64(case["bias"]))
+    fin = torch.isfinite(s64)
+    assert torch.equal(s64[fin], s64[fin].float().double())         # every logit is exact in fp32: the kernels see the same values
+    case.update(out64=out, w64=w, s64=s64)
+    return case
+
+
+def _f64(t):
+    return None if t is None else t.double()
+
+
+def _dev(case, gpu):
+    return {k: (v.to(gpu) if isinstance(v, torch.Tensor) else v) for k, v in case.items()}
+
+
+def _check_design(case):
+    """The designed properties hold on the logits the kernels see (per pair, in the expanded layout)."""
+    s, rp = case["s64"], case["rowptr"]
+    lens = (rp[1:] - rp[:-1])[case["pair_row"]]
+    start = torch.cumsum(lens, 0) - lens
+    if case["mode"] not in (ATT_MLP, ATT_MLP_SCALED):
+        return
+    for b in range(case["B"]):
+        name = ROWS[int(case["pair_row"][b])][0]
+        x = s[int(start[b]):int(start[b] + lens[b])]
+        if name == "hot":
+            assert float(x.max()) > 88.8 and float(x.min()) > 75.0      # e^x overflows fp32 above 88.72
+        elif name == "cold":
+            assert float(x.max()) < -180.0
+        elif name == "underflow_band":
+            y = (x - x.max()).sort().values
+            assert float(y[-2]) <= -80.0
+        elif name == "dead_slice":
+            assert float(x[512:].max()) <= float(x.max()) - 120.0
+        elif name == "tie_two_slices":
+            assert float(x[TIE[0]]) == float(x[TIE[1]]) == float(x.max())
+        elif name.startswith("lead") or name == "neg_lead_1000":
+            top = x.sort(descending=True).values
+            assert float(top[0] - top[1]) >= 45.0
+
+
+def _expanded(c):
+    from deeprecommendation_amd.neural_collaborative_filtering.models.attention_ncf import SparseRatings
+    return SparseRatings(c["rowptr"], c["col"], c["val"], c["I"], pair_row=c["pair_row"]).expanded()
+
+
+@pytest.fixture(scope="module")
+def native(gpu):
+    from deeprecommendation_amd import native as n
+    n.load_library()
+    assert (n.ATT_MLP, n.ATT_LINEAR, n.ATT_COS, n.ATT_MLP_SCALED, n.ATT_SCALE_LOG2) == (ATT_MLP, ATT_LINEAR, ATT_COS, ATT_MLP_SCALED, SCALE_LOG2)
+    return n
+
+
+MODES = {"mlp": ATT_MLP, "mlp_scaled": ATT_MLP_SCALED, "linear": ATT_LINEAR, "cos": ATT_COS}
+
+
+# ------------------------------------------------------------------------------------------------ per-pair kernel
+@pytest.mark.parametrize("mode_name", ["mlp", "mlp_scaled", "linear", "cos"])
+def test_attn_forward_per_pair_peaked(native, gpu, mode_name):
+    """ncf_attn_forward (attn_kernel: one wave per pair, the whole row) on the expanded per-pair CSR: output and weights."""
+    case = make_case(MODES[mode_name])
+    _check_design(case)
+    c = _dev(case, gpu)
+    ex = _expanded(c)
+    run = lambda: native.attn_forward(c["mode"], c["pc"], c["pr"], c["w1"], c["b1"], ex.rowptr, ex.col, ex.val, c["feat"], out_bias=c["bias"])
+    out, w = run()
+    assert_close(out, case["out64"])
+    assert_close(w, case["w64"])
+    out2, w2 = run()
+    assert torch.equal(out, out2) and torch.equal(w, w2)
+
+
+# ------------------------------------------------------------------------------------------------ grouped kernels (one workgroup per group)
+@pytest.mark.parametrize("weights", [False, True])
+@pytest.mark.parametrize("kernel", ["lds", "scalar"])
+@pytest.mark.parametrize("mode_name", ["mlp", "mlp_scaled", "cos"])
+def test_attn_forward_grouped_peaked(native, gpu, kernel_option, mode_name, kernel, weights):
+    """ncf_attn_forward_grouped with attn_grouped_kernel = lds (LDS-broadcast form) and = scalar (scalar-operand form), with and
+    without the weights (expanded-CSR layout) — a forced form takes every call, so the entry-split form does not run here."""
+    kernel_option("attn_grouped_kernel", kernel)
+    case = make_case(MODES[mode_name])
+    c = _dev(case, gpu)
+    for ppw in (8, 32):
+        run = lambda: native.attn_forward_grouped(c["mode"], c["pc"], c["pr"], c["w1"], c["b1"], c["rowptr"], c["col"], c["val"],
+                                                  c["pair_row"], c["feat"], out_bias=c["bias"], pairs_per_wg=ppw, return_weights=weights)
+        res, res2 = run(), run()
+        out, out2 = (res[0], res2[0]) if weights else (res, res2)
+        assert_close(out, case["out64"])
+        assert torch.equal(out, out2)
+        if weights:
+            assert_close(res[1], case["w64"])
+            assert torch.equal(res[1], res2[1])
+
+
+# ------------------------------------------------------------------------------------------------ entry-split form + attn_combine_kernel
+@pytest.mark.parametrize("ppw", [5, 16, 32, 64])
+@pytest.mark.parametrize("nsplit", [1, 2, 4, 8, 9, 16, 64])
+def test_attn_split_merged_peaked(native, gpu, nsplit, ppw):
+    """ncf_attn_forward_split (ATT_MLP_SCALED, the model's mode), merged by attn_combine_kernel: nsplit 1 .. 64 (64 slices: more
+    slices than the 16 tiles of the longest row, so most slices are empty), groups of 5 .. 64 pairs."""
+    case = make_case(ATT_MLP_SCALED)
+    c = _dev(case, gpu)
+    assert native.attn_split_supported(c["mode"], c["A"], c["Fdim"], ppw)
+    run = lambda: native.attn_forward_grouped(c["mode"], c["pc"], c["pr"], c["w1"], c["b1"], c["rowptr"], c["col"], c["val"], c["pair_row"],
+                                              c["feat"], out_bias=c["bias"], pairs_per_wg=ppw, nsplit=nsplit)
+    out = run()
+    assert_close(out, case["out64"])
+    assert torch.equal(out, run())
+    empty = (c["rowptr"][1:] - c["rowptr"][:-1])[c["pair_row"]] == 0
+    assert torch.equal(out[empty], c["bias"].expand(int(empty.sum()), c["Fdim"]))
+
+
+@pytest.mark.parametrize("mode_name", ["mlp", "cos"])
+@pytest.mark.parametrize("nsplit", [1, 9])
+def test_attn_split_merged_peaked_other_modes(native, gpu, mode_name, nsplit):
+    case = make_case(MODES[mode_name])
+    c = _dev(case, gpu)
+    run = lambda: native.attn_forward_grouped(c["mode"], c["pc"], c["pr"], c["w1"], c["b1"], c["rowptr"], c["col"], c["val"], c["pair_row"],
+                                              c["feat"], out_bias=c["bias"], pairs_per_wg=32, nsplit=nsplit)
+    out = run()
+    assert_close(out, case["out64"])
+    assert torch.equal(out, run())
+
+
+# ------------------------------------------------------------------------------------------------ entry-split partials merged by attn_tail
+@pytest.mark.parametrize("nsplit", [2, 8, 9, 16])
+def test_attn_split_partials_merged_by_tail_peaked(native, gpu, nsplit):
+    """leave_partials=True: the slices' (m, l, O) stay in the workspace and ncf_attn_tail merges them (nsplit 9 and 16 take its loop
+    for more than 8 slices), adds UserEmbeddings' bias, and runs cat(candidate_emb, user_emb) -> MLP [256, 128] -> 1.  Against float64
+    of the merged user embedding followed by the same MLP."""
+    case = make_case(ATT_MLP_SCALED)
+    c = _dev(case, gpu)
+    B, E = c["B"], c["Fdim"]
+    g = torch.Generator().manual_seed(nsplit)
+    cand = torch.randn(B, E, generator=g)
+    W1 = torch.randn(256, 2 * E, generator=g) / (2 * E) ** 0.5
+    W2 = torch.randn(128, 256, generator=g) / 256 ** 0.5
+    b1, b2 = torch.randn(256, generator=g) * 0.1, torch.randn(128, generator=g) * 0.1
+    w3, b3 = torch.randn(128, generator=g) / 128 ** 0.5, 0.37
+    assert native.attn_tail_supported(E, E, 256, 128)
+    parts = native.attn_forward_grouped(c["mode"], c["pc"], c["pr"], c["w1"], c["b1"], c["rowptr"], c["col"], c["val"], c["pair_row"],
+                                        c["feat"], out_bias=c["bias"], pairs_per_wg=16, nsplit=nsplit, leave_partials=True)
+    assert isinstance(parts, native.AttnPartials) and parts.nsplit == nsplit
+    args = (cand.to(gpu), parts, c["bias"], W1.to(gpu), b1.to(gpu), W2.to(gpu), b2.to(gpu), w3.to(gpu), b3)
+    out = native.attn_tail(*args)
+    h = torch.relu(torch.cat((cand.double(), case["out64"]), 1) @ W1.double().t() + b1.double())
+    h = torch.relu(h @ W2.double().t() + b2.double())
+    assert_close(out, h @ w3.double().view(-1, 1) + b3)
+    assert torch.equal(out, native.attn_tail(*args))
+
+
+# ------------------------------------------------------------------------------------------------ backward
+@pytest.mark.parametrize("mode_name", ["mlp", "mlp_scaled", "cos"])
+def test_attn_backward_peaked(native, gpu, mode_name):
+    """ncf_attn_backward (no dropout) against float64 autograd of the reference function (COS: the dot of the given rows, the kernels'
+    contract — the training path normalises before it).
+
+    d_feat = sum over pairs of w_e val_e dout_b is well conditioned: the default bar.  d_pc, d_pr and d_w1 go through the softmax
+    derivative g_e = w_e (dv_e - sum_j w_j dv_j), dv_e = val_e feat[col_e] . dout_b, which cancels on a peaked row (w_1 ~ 1: dv_1 -
+    sum_j w_j dv_j ~ 0).  Their per-element bar is rtol x T, T = the float64 sum of the absolute values of the terms of that element
+    (|g_e| taken as w_e (|dv_e| + sum_j w_j |dv_j|), times |w1[a]| relu'(pc + pr) for d_pc / d_pr, relu(pc + pr) for d_w1, the
+    other operand's |row| for COS): an fp32 sum of those terms in any order is within a few ulp of T of the exact value, while a
+    bar relative to the (cancelled) result would ask for more than fp32 holds.  Plus the same sum with every g_e replaced by
+    2^-126 (1 + |dv_e| + sum_j w_j |dv_j|): the weights of the entries 87+ below the leader are below fp32's normal range, where
+    exp and the products that follow flush to 0 or keep only a few bits."""
+    mode = MODES[mode_name]
+    case = make_case(mode)
+    c = _dev(case, gpu)
+    ex = _expanded(c)
+    _, wts = native.attn_forward(mode, c["pc"], c["pr"], c["w1"], c["b1"], ex.rowptr, ex.col, ex.val, c["feat"], out_bias=c["bias"])
+    g = torch.Generator().manual_seed(mode)
+    dout = torch.randn(c["B"], c["Fdim"], generator=g)
+    d_pc, d_pr, d_w1, d_feat = native.attn_backward(mode, c["pc"], c["pr"], c["w1"], ex.rowptr, ex.col, ex.val, c["feat"], wts, dout.to(gpu))
+    # float64 autograd
+    pc, pr, feat = (case[k].double().requires_grad_(True) for k in ("pc", "pr", "feat"))
+    w1 = case["w1"].double().requires_grad_(True) if case["w1"] is not None else None
+    out, w, _ = attention64(mode, pc, pr, w1, case["b1"], case["rowptr"], case["col"], case["val"], case["pair_row"], feat,
+                            case["bias"].double(), normalize=False)
+    leaves = [pc, pr, feat] + ([w1] if w1 is not None else [])
+    grads = torch.autograd.grad((out * dout.double()).sum(), leaves)
+    assert_close(d_feat, grads[2])
+    # T: the sum of the absolute values of the terms, entry by entry in the expanded layout
+    col = ex.col.long().cpu()
+    owner = torch.repeat_interleave(torch.arange(c["B"]), (ex.rowptr[1:] - ex.rowptr[:-1]).cpu())
+    pcd, prd = case["pc"].double(), case["pr"].double()
+    dv = case["val"][ex.shared_entry.cpu()].double() * (case["feat"].double()[col] * dout.double()[owner]).sum(1)
+    w = w.detach()
+    wabs = torch.zeros(c["B"], dtype=torch.float64).index_add_(0, owner, w * dv.abs())[owner]
+    G = 1e-5 * w * (dv.abs() + wabs) + 2.0 ** -126 * (1.0 + dv.abs() + wabs)        # rtol x |terms| + the fp32 flush floor
+    if mode == ATT_COS:
+        T_pc = torch.zeros_like(pcd).index_add_(0, owner, G[:, None] * prd[col].abs())
+        T_pr = torch.zeros_like(prd).index_add_(0, col, G[:, None] * pcd[owner].abs())
+        T = [(d_pc, grads[0], T_pc, "d_pc"), (d_pr, grads[1], T_pr, "d_pr")]
+    else:
+        h = pcd[owner] + prd[col]
+        assert bool((h != 0).all())                                   # no relu kink: the derivative is defined everywhere
+        act = (h > 0).double() * case["w1"].double().abs()
+        T_pc = torch.zeros_like(pcd).index_add_(0, owner, G[:, None] * act)
+        T_pr = torch.zeros_like(prd).index_add_(0, col, G[:, None] * act)
+        T_w1 = (G[:, None] * torch.relu(h)).sum(0)
+        T = [(d_pc, grads[0], T_pc, "d_pc"), (d_pr, grads[1], T_pr, "d_pr"), (d_w1, grads[3], T_w1, "d_w1")]
+    for got, ref, bar, what in T:
+        got = got.detach().cpu().double()
+        assert got.shape == ref.shape, what
+        err = (got - ref).abs()
+        k = int((err / bar.clamp_min(1e-300)).argmax())
+        record_error(what, float(err.flatten()[k]), float(bar.flatten()[k]))
+        assert bool((err <= bar).all()), f"{what}: max err {float(err.max()):.3e}, worst {float((err / bar.clamp_min(1e-300)).max()):.2f} of its bar"

@@ -77,7 +77,8 @@ def test_mf():
     assert_golden(out2, ref)
 
 
-@pytest.mark.parametrize("name", ["g3_att_dense8", "g3_att_none", "g3_att_cos", "g3_att_vec64", "g3_att_vec128"])
+@pytest.mark.parametrize("name", ["g3_att_dense8", "g3_att_none", "g3_att_cos", "g3_att_vec64", "g3_att_vec128",
+                                  "g3_att_peaked_e64", "g3_att_peaked_none"])
 def test_attention(name):
     state, a, kw = load_golden(name)
     out, att = O.attention_ncf_forward(state, torch.from_numpy(a["candidate_items"]),
@@ -85,6 +86,8 @@ def test_attention(name):
                                        use_cos_sim_instead=kw["use_cos_sim_instead"], return_attention_weights=True)
     assert_golden(out, torch.from_numpy(a["out"]))
     assert_golden(att, torch.from_numpy(a["att"]))
+    if name.startswith("g3_att_peaked"):             # peaked softmax; its designed rows: test_attention_peaked_fixtures.py
+        return
     if name.startswith("g3_att_vec"):
         assert float(att[0].abs().sum()) == 0.0
         return
@@ -197,7 +200,8 @@ def test_c_kernel_order_oracle_agrees_with_reference_level_oracle():
 
 
 # ---------------- round 3: deterministic train-mode pins (target mask, gradients) ----------------
-@pytest.mark.parametrize("name", ["g3_att_train_dense8", "g3_att_train_cos", "g3_att_train_vec64", "g3_att_train_ue50"])
+@pytest.mark.parametrize("name", ["g3_att_train_dense8", "g3_att_train_cos", "g3_att_train_vec64", "g3_att_train_ue50",
+                                  "g3_att_train_peaked"])
 def test_attention_train_mode_target_mask_and_gradients(name):
     """attention_ncf.py:195-205 (train-only target mask) and the gradients of MSELoss(sum) (datasets/base.py:31-32)."""
     state, a, kw = load_golden(name)

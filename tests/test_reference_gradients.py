@@ -14,7 +14,7 @@ import torch
 
 from conftest import load_golden, onehot, record_error
 
-ATT_CASES = ["g3_att_train_dense8", "g3_att_train_cos", "g3_att_train_vec64", "g3_att_train_ue50"]
+ATT_CASES = ["g3_att_train_dense8", "g3_att_train_cos", "g3_att_train_vec64", "g3_att_train_ue50", "g3_att_train_peaked"]
 BASIC_CASES = ["g7_grads_basic_small", "g7_grads_basic_e64", "g7_grads_basic_h256", "g7_grads_mf"]
 
 
