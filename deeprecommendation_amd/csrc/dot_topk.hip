@@ -16,9 +16,9 @@
 // threshold and its column is not excluded (an LDS bitmap of the user's excluded columns, rebuilt every kDtChunk columns).  A user
 // whose buffer cannot take another 16 keys is re-selected down to k (wave-wide bitwise search for the k-th key, then
 // compaction); the k-th key becomes the threshold.  At the end of the tile each user's k best keys go to the workspace in the
-// layout topk_tile_kernel's merge levels read (kp keys per tile, 0-padded), and those levels finish the ranking; the last one
-// recovers the score from the key (topk_unmap), which is the caller's bits for every non-NaN score (a dot product from +0.f is
-// never -0.0).
+// layout topk_tile_kernel's merge levels read (kp keys per tile, 0-padded), and those levels (topk_merge, topk.hip) finish the
+// ranking; the last one recovers the score from the key (topk_unmap), which is the caller's bits for every non-NaN score (a dot
+// product from +0.f is never -0.0).
 #include "topk_common.h"
 
 namespace ncf {
@@ -71,19 +71,7 @@ __device__ __forceinline__ void load_frag(const float* row, int D, bool vec, int
 // keep the `keep` best of user u's candidates; the k-th becomes the threshold
 __device__ void reselect(DtWaveShared& sh, int u, int keep, int lane) {
     const int n = sh.cnt[u];
-    unsigned long long v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = lane + 64 * i < n ? sh.buf[u][lane + 64 * i] : 0ull;
-    const unsigned long long kth = wave_kth(v, keep);
-    wave_lds_sync();
-    int base = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const bool f = v[i] != 0ull && v[i] >= kth;
-        const unsigned long long m = __ballot(f);
-        if (f) sh.buf[u][base + lanes_below(m)] = v[i];
-        base += __popcll(m);
-    }
+    const unsigned long long kth = wave_reselect(sh.buf[u], n, keep, lane);
     if (lane == 0) {
         sh.cnt[u] = keep;
         sh.thr[u] = kth;
@@ -213,59 +201,23 @@ __global__ __launch_bounds__(kDtThreads) void dot_topk_kernel(
     }
 }
 
-// The launch plan: column tiles of the fused level, then the merge levels of topk_tile_kernel over kp keys per tile.
-struct DotTopkPlan {
-    int tile_cols;
-    int64_t tiles0;
-    int merges;              // merge launches (>= 1: the last one sorts and writes the result)
-    int64_t mtiles[8];
-    int kp;
-    int64_t n1, n2;          // keys per row in the two ping-pong buffers
-    int64_t chunk;           // rows per chunk
-};
-
-static DotTopkPlan dot_topk_plan(int64_t rows, int64_t cols, int k) {
-    DotTopkPlan p{};
-    p.kp = (k + 1) & ~1;
+// The fused level's column tiles: tile_cols shrinks (8192 -> kDtChunk) until the grid reaches kDtTargetBlocks
+static int dot_topk_tile_cols(int64_t rows, int64_t cols) {
     const int64_t ublocks = (rows + kDtBlockUsers - 1) / kDtBlockUsers;
-    p.tile_cols = kTopkTile;
-    while (p.tile_cols > kDtChunk && ublocks * ((cols + p.tile_cols - 1) / p.tile_cols) < kDtTargetBlocks) p.tile_cols >>= 1;
-    p.tiles0 = (cols + p.tile_cols - 1) / p.tile_cols;
-    p.n1 = p.tiles0 * p.kp;
-    int64_t n = p.n1;
-    p.merges = 0;
-    while (true) {
-        const int64_t t = (n + kTopkTile - 1) / kTopkTile;
-        p.mtiles[p.merges++] = t;
-        if (t == 1) break;
-        n = t * p.kp;
-    }
-    p.n2 = p.merges > 1 ? p.mtiles[0] * p.kp : 0;
-    const int64_t per_row = (p.n1 + p.n2) * 8;
-    int64_t chunk = max((int64_t)1, min(rows, (int64_t)(kTopkChunkBytes / per_row)));
-    if (chunk < rows && chunk > kDtBlockUsers) chunk -= chunk % kDtBlockUsers;   // whole user blocks per chunk
-    p.chunk = chunk;
-    return p;
+    int tile_cols = kTopkTile;
+    while (tile_cols > kDtChunk && ublocks * ((cols + tile_cols - 1) / tile_cols) < kDtTargetBlocks) tile_cols >>= 1;
+    return tile_cols;
+}
+
+// the merge levels after it, over kp keys per tile, in chunks of whole user blocks
+static TopkMerge dot_topk_plan(int64_t rows, int64_t cols, int tile_cols, int k) {
+    return topk_merge_plan(rows, (cols + tile_cols - 1) / tile_cols * topk_kp(k), k, kDtBlockUsers);
 }
 
 static int dot_topk_check(int64_t rows, int64_t cols, int D, int k, const char* what) {
-    if (k < 1 || k > kTopkMaxK) return fail(NCF_EINVAL, "%s: k = %d is outside 1 .. %d", what, k, kTopkMaxK);
-    if (k > kDtMaxK) return fail(NCF_EUNSUPPORTED, "%s: k = %d is above the fused limit %d", what, k, kDtMaxK);
+    if (const int rc = topk_check_k(what, k, kDtMaxK)) return rc;
     if (D < 1 || D > kDtMaxD) return fail(NCF_EUNSUPPORTED, "%s: width D = %d is outside the fused range 1 .. %d", what, D, kDtMaxD);
-    if (cols < 1 || cols > kTopkMaxCols)
-        return fail(NCF_EUNSUPPORTED, "%s: cols = %lld is outside 1 .. %lld", what, (long long)cols, (long long)kTopkMaxCols);
-    if (rows < 0 || rows > kTopkMaxRows)
-        return fail(NCF_EUNSUPPORTED, "%s: rows = %lld is outside 0 .. %lld", what, (long long)rows, (long long)kTopkMaxRows);
-    return NCF_OK;
-}
-
-template <int J>
-static void launch_dot_topk(unsigned blocks, hipStream_t s, const float* tabA, int64_t rowsA, int64_t ldA, const float* tabB,
-                            int64_t rowsB, int64_t ldB, const int64_t* idxA, const int64_t* idxB, int64_t cols, int D,
-                            const int64_t* seen_rowptr, const int32_t* seen_col, int64_t r0, int64_t nr, const DotTopkPlan& p, int k,
-                            unsigned long long* out, int32_t* oob) {
-    hipLaunchKernelGGL((dot_topk_kernel<J>), dim3(blocks), dim3(kDtThreads), 0, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols,
-                       D, seen_rowptr, seen_col, r0, nr, (int)p.tiles0, p.tile_cols, k, p.kp, out, p.n1, oob);
+    return topk_check_size(what, rows, cols);
 }
 
 }  // namespace ncf
@@ -274,60 +226,43 @@ using namespace ncf;
 
 extern "C" size_t ncf_dot_topk_workspace_bytes(int64_t rows, int64_t cols, int D, int k) {
     if (dot_topk_check(rows, cols, D, k, "ncf_dot_topk_workspace_bytes") != NCF_OK || rows == 0) return 0;
-    const DotTopkPlan p = dot_topk_plan(rows, cols, k);
-    return (size_t)(p.chunk * (p.n1 + p.n2) * 8);
+    return topk_merge_bytes(dot_topk_plan(rows, cols, dot_topk_tile_cols(rows, cols), k));
 }
 
 extern "C" int ncf_dot_topk(const float* tabA, int64_t rowsA, int64_t ldA, const float* tabB, int64_t rowsB, int64_t ldB,
                             const int64_t* idxA, const int64_t* idxB, int64_t rows, int64_t cols, int D, const int64_t* seen_rowptr,
                             const int32_t* seen_col, int k, float* out_score, int32_t* out_idx, int32_t* out_count, void* workspace,
                             size_t workspace_bytes, int32_t* oob, ncf_stream_t stream) {
-    const int rc = dot_topk_check(rows, cols, D, k, "ncf_dot_topk");
-    if (rc != NCF_OK) return rc;
+    if (const int rc = dot_topk_check(rows, cols, D, k, "ncf_dot_topk")) return rc;
     if (rows == 0) return NCF_OK;
     if (!tabA || !tabB || !out_score || !out_idx || !out_count) return fail(NCF_EINVAL, "ncf_dot_topk: null argument");
     if (ldA < D || ldB < D) return fail(NCF_EINVAL, "ncf_dot_topk: leading dimension smaller than D = %d", D);
     if (!idxA && rows > rowsA) return fail(NCF_EINVAL, "ncf_dot_topk: rows = %lld > rowsA without idxA", (long long)rows);
     if (!idxB && cols > rowsB) return fail(NCF_EINVAL, "ncf_dot_topk: cols = %lld > rowsB without idxB", (long long)cols);
-    if ((seen_rowptr == nullptr) != (seen_col == nullptr))
-        return fail(NCF_EINVAL, "ncf_dot_topk: seen_rowptr and seen_col are given together or not at all");
-    const DotTopkPlan p = dot_topk_plan(rows, cols, k);
-    const size_t need = (size_t)(p.chunk * (p.n1 + p.n2) * 8);
-    if (workspace_bytes < need)
-        return fail(NCF_EWORKSPACE, "ncf_dot_topk: workspace of %zu bytes, %zu needed (ncf_dot_topk_workspace_bytes)", workspace_bytes, need);
-    if (!workspace || !aligned16(workspace)) return fail(NCF_EINVAL, "ncf_dot_topk: workspace must be 16-byte aligned");
+    const int tile_cols = dot_topk_tile_cols(rows, cols);
+    const int tiles0 = (int)((cols + tile_cols - 1) / tile_cols);
+    const TopkMerge p = dot_topk_plan(rows, cols, tile_cols, k);
+    if (const int rc = topk_check_buffers("ncf_dot_topk", "ncf_dot_topk_workspace_bytes", seen_rowptr, seen_col, workspace, workspace_bytes,
+                                          topk_merge_bytes(p)))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* bufA = (unsigned long long*)workspace;
-    unsigned long long* bufB = bufA + p.chunk * p.n1;
+    unsigned long long* keys = (unsigned long long*)workspace;
     const int J = (D + 16 * kDtKS - 1) / (16 * kDtKS);
     for (int64_t r0 = 0; r0 < rows; r0 += p.chunk) {
         const int64_t nr = min(p.chunk, rows - r0);
-        const unsigned blocks = (unsigned)(((nr + kDtBlockUsers - 1) / kDtBlockUsers) * p.tiles0);
+        const unsigned blocks = (unsigned)(((nr + kDtBlockUsers - 1) / kDtBlockUsers) * tiles0);
+#define LAUNCH(J_)                                                                                                                       \
+    hipLaunchKernelGGL((dot_topk_kernel<J_>), dim3(blocks), dim3(kDtThreads), 0, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, \
+                       D, seen_rowptr, seen_col, r0, nr, tiles0, tile_cols, k, p.kp, keys, p.n1, oob)
         switch (J) {
-            case 1: launch_dot_topk<1>(blocks, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, D, seen_rowptr, seen_col, r0, nr, p, k, bufA, oob); break;
-            case 2: launch_dot_topk<2>(blocks, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, D, seen_rowptr, seen_col, r0, nr, p, k, bufA, oob); break;
-            case 3: launch_dot_topk<3>(blocks, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, D, seen_rowptr, seen_col, r0, nr, p, k, bufA, oob); break;
-            default: launch_dot_topk<4>(blocks, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, D, seen_rowptr, seen_col, r0, nr, p, k, bufA, oob); break;
+            case 1: LAUNCH(1); break;
+            case 2: LAUNCH(2); break;
+            case 3: LAUNCH(3); break;
+            default: LAUNCH(4); break;
         }
-        // merge levels: topk_tile_kernel over the fused level's kp keys per tile; the last one sorts and writes (score from the key)
-        unsigned long long* in = bufA;
-        unsigned long long* out = bufB;
-        int64_t n_in = p.n1;
-        for (int L = 0; L < p.merges; ++L) {
-            const int64_t t = p.mtiles[L];
-            if (L == p.merges - 1) {
-                hipLaunchKernelGGL((topk_tile_kernel<false, true>), dim3((unsigned)(t * nr)), dim3(kTopkThreads), 0, s, nullptr, 0, 0, nullptr,
-                                   nullptr, in, n_in, (int)t, r0, k, p.kp, nullptr, 0, out_score, out_idx, out_count);
-            } else {
-                const int64_t n_out = t * p.kp;
-                hipLaunchKernelGGL((topk_tile_kernel<false, false>), dim3((unsigned)(t * nr)), dim3(kTopkThreads), 0, s, nullptr, 0, 0,
-                                   nullptr, nullptr, in, n_in, (int)t, r0, k, p.kp, out, n_out, out_score, out_idx, out_count);
-                unsigned long long* tmp = in;
-                in = out;
-                out = tmp;
-                n_in = n_out;
-            }
-        }
+#undef LAUNCH
+        // merge levels over the fused level's kp keys per tile; the last one sorts and writes (score from the key)
+        topk_merge(p, keys, nullptr, 0, r0, nr, k, out_score, out_idx, out_count, s);
     }
     return check_launch("ncf_dot_topk");
 }

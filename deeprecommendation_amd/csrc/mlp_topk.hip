@@ -17,8 +17,9 @@
 //                 (2 EA N1 per pair) is paid once per row instead of once per pair.
 // Selection: per wave, the user's candidate keys (map(score) << 32 | ~column, the topk.hip order) live in LDS behind a running k-th
 // key threshold; excluded columns are skipped through an LDS bitmap of the range.  A buffer that cannot take another 32 keys is
-// re-selected down to k (wave_kth).  Each (user, range) writes its k best keys in the layout topk_tile_kernel's merge levels read
-// (kp keys per range, 0-padded), and those levels finish the ranking; the last one recovers each score from its key (topk_unmap).
+// re-selected down to k (wave_reselect).  Each (user, range) writes its k best keys in the layout topk_tile_kernel's merge levels
+// read (kp keys per range, 0-padded), and those levels (topk_merge, topk.hip) finish the ranking; the last one recovers each score
+// from its key (topk_unmap).
 // A fused-MLP score is never -0.0: `partial` starts at +0.f, an fmaf onto +0 and an exact cancellation both give +0 in
 // round-to-nearest, so partial is never -0 and partial + bl is -0 only if both are.  The recovered bits are therefore the caller's
 // for every non-NaN score; NaN payloads are not kept (a NaN ranks last and comes back as a NaN).
@@ -104,26 +105,6 @@ struct MtWaveShared {
     uint32_t bitmap[kTopkTile / 32];
 };
 
-// keep the `keep` best of the wave's cnt candidates; returns the k-th key (the new threshold)
-__device__ unsigned long long mt_reselect(MtWaveShared& sh, int cnt, int keep, int lane) {
-    unsigned long long v[4];
-    wave_lds_sync();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = lane + 64 * i < cnt ? sh.buf[lane + 64 * i] : 0ull;
-    const unsigned long long kth = wave_kth(v, keep);
-    wave_lds_sync();
-    int base = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const bool f = v[i] != 0ull && v[i] >= kth;
-        const unsigned long long m = __ballot(f);
-        if (f) sh.buf[base + lanes_below(m)] = v[i];
-        base += __popcll(m);
-    }
-    wave_lds_sync();
-    return kth;
-}
-
 template <int K0, int N1, int N2>
 __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(MtArgs a) {
     constexpr int NT1 = N1 / 32, Q1 = K0 / 8;
@@ -162,6 +143,14 @@ __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(MtArgs a) {
     const float bl0 = a.bl[0];
     unsigned long long thr = 0ull;
     int cnt = 0;
+    // keep the wave's k best candidates; returns the k-th key (the new threshold)
+    auto reselect = [&]() {
+        wave_lds_sync();
+        const unsigned long long kth = wave_reselect(sh.buf, cnt, a.k, lane);
+        wave_lds_sync();
+        cnt = a.k;
+        return kth;
+    };
 
     for (int64_t cb = c0; cb < c1; cb += kMtCols) {
         // The bias / weight pointers are made opaque per tile: hoisted out of the tile loop, the loop-invariant b2, wl and first
@@ -323,54 +312,31 @@ __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(MtArgs a) {
         const unsigned long long mk = __ballot(pass);
         if (pass) sh.buf[cnt + lanes_below(mk)] = key;   // cnt <= kMtCap - 32 before this tile
         cnt += __popcll(mk);
-        if (cnt > kMtCap - kMtCols) {
-            thr = mt_reselect(sh, cnt, a.k, lane);
-            cnt = a.k;
-        }
+        if (cnt > kMtCap - kMtCols) thr = reselect();
     }
 
     // this range's k best keys, unsorted, 0-padded to kp
-    if (cnt > a.k) {
-        mt_reselect(sh, cnt, a.k, lane);
-        cnt = a.k;
-    }
+    if (cnt > a.k) reselect();
     wave_lds_sync();
     unsigned long long* dst = a.out_keys + uloc * a.n_out + (int64_t)range * a.kp;
     for (int s = lane; s < a.kp; s += kWave) dst[s] = s < cnt ? sh.buf[s] : 0ull;
 }
 
-// The launch plan: column ranges of the fused level, then the merge levels of topk_tile_kernel over kp keys per range.
-struct MlpTopkPlan {
-    int tile_cols;
-    int64_t tiles0;
-    int merges;              // merge launches (>= 1: the last one sorts and writes the result)
-    int64_t mtiles[8];
-    int kp;
-    int64_t n1, n2;          // keys per row in the two ping-pong buffers
-    int64_t chunk;           // rows per chunk
-    size_t state_bytes;      // prefix state at the front of the workspace
-};
+// The fused level's column ranges: tile_cols shrinks (8192 -> kMtCols) until the grid has kMtTargetWaves waves
+static int mlp_topk_tile_cols(int64_t rows, int64_t cols) {
+    int tile_cols = kTopkTile;
+    while (tile_cols > kMtCols && rows * ((cols + tile_cols - 1) / tile_cols) < kMtTargetWaves) tile_cols >>= 1;
+    return tile_cols;
+}
 
-static MlpTopkPlan mlp_topk_plan(int64_t rows, int64_t cols, int N1, int user_first, int k) {
-    MlpTopkPlan p{};
-    p.kp = (k + 1) & ~1;
-    p.tile_cols = kTopkTile;
-    while (p.tile_cols > kMtCols && rows * ((cols + p.tile_cols - 1) / p.tile_cols) < kMtTargetWaves) p.tile_cols >>= 1;
-    p.tiles0 = (cols + p.tile_cols - 1) / p.tile_cols;
-    p.n1 = p.tiles0 * p.kp;
-    int64_t n = p.n1;
-    p.merges = 0;
-    while (true) {
-        const int64_t t = (n + kTopkTile - 1) / kTopkTile;
-        p.mtiles[p.merges++] = t;
-        if (t == 1) break;
-        n = t * p.kp;
-    }
-    p.n2 = p.merges > 1 ? p.mtiles[0] * p.kp : 0;
-    const int64_t per_row = (p.n1 + p.n2) * 8;
-    p.chunk = max((int64_t)1, min(rows, (int64_t)(kTopkChunkBytes / per_row)));
-    p.state_bytes = (size_t)(user_first ? rows : cols) * N1 * sizeof(float);
-    return p;
+// the merge levels after it, over kp keys per range
+static TopkMerge mlp_topk_plan(int64_t rows, int64_t cols, int tile_cols, int k) {
+    return topk_merge_plan(rows, (cols + tile_cols - 1) / tile_cols * topk_kp(k), k);
+}
+
+// the prefix state at the front of the workspace: N1 floats per user (user-first) or per ranked column (item-first)
+static size_t mlp_state_bytes(int64_t rows, int64_t cols, int N1, int user_first) {
+    return (size_t)(user_first ? rows : cols) * N1 * sizeof(float);
 }
 
 static bool mt_dispatch(int K0, int N1, int N2, bool launch, unsigned blocks, hipStream_t s, const MtArgs* a) {
@@ -390,16 +356,9 @@ static bool mt_shape_ok(int dtype, int EA, int EB, int n_layers, const int* dims
 }
 
 static int mt_check(int64_t rows, int64_t cols, int k, const char* what) {
-    if (k < 1 || k > kTopkMaxK) return fail(NCF_EINVAL, "%s: k = %d is outside 1 .. %d", what, k, kTopkMaxK);
-    if (k > kMtMaxK) return fail(NCF_EUNSUPPORTED, "%s: k = %d is above the fused limit %d", what, k, kMtMaxK);
-    if (cols < 1 || cols > kTopkMaxCols)
-        return fail(NCF_EUNSUPPORTED, "%s: cols = %lld is outside 1 .. %lld", what, (long long)cols, (long long)kTopkMaxCols);
-    if (rows < 0 || rows > kTopkMaxRows)
-        return fail(NCF_EUNSUPPORTED, "%s: rows = %lld is outside 0 .. %lld", what, (long long)rows, (long long)kTopkMaxRows);
-    return NCF_OK;
+    if (const int rc = topk_check_k(what, k, kMtMaxK)) return rc;
+    return topk_check_size(what, rows, cols);
 }
-
-static size_t mt_workspace(const MlpTopkPlan& p) { return p.state_bytes + (size_t)(p.chunk * (p.n1 + p.n2) * 8); }
 
 }  // namespace ncf
 
@@ -412,7 +371,7 @@ extern "C" int ncf_mlp_topk_supported(int dtype, int EA, int EB, int n_layers, c
 extern "C" size_t ncf_mlp_topk_workspace_bytes(int64_t rows, int64_t cols, int user_first, int n_layers, const int* dims, int k) {
     if (mt_check(rows, cols, k, "ncf_mlp_topk_workspace_bytes") != NCF_OK || rows == 0) return 0;
     if (!dims || (n_layers != 2 && n_layers != 3) || dims[1] < 32 || dims[1] % 32) return 0;
-    return mt_workspace(mlp_topk_plan(rows, cols, dims[1], user_first, k));
+    return mlp_state_bytes(rows, cols, dims[1], user_first) + topk_merge_bytes(mlp_topk_plan(rows, cols, mlp_topk_tile_cols(rows, cols), k));
 }
 
 extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t ldA, const void* tabB, int64_t rowsB, int64_t ldB,
@@ -432,20 +391,18 @@ extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t 
     const int64_t nUrows = user_first ? rowsA : rowsB, nIrows = user_first ? rowsB : rowsA;
     if (!user_ids && rows > nUrows) return fail(NCF_EINVAL, "ncf_mlp_topk: rows = %lld > user table rows without user ids", (long long)rows);
     if (!item_ids && cols > nIrows) return fail(NCF_EINVAL, "ncf_mlp_topk: cols = %lld > item table rows without item ids", (long long)cols);
-    if ((seen_rowptr == nullptr) != (seen_col == nullptr))
-        return fail(NCF_EINVAL, "ncf_mlp_topk: seen_rowptr and seen_col are given together or not at all");
     const int K0 = dims[0], N1 = dims[1], N2 = n_layers == 3 ? dims[2] : 0;
-    const MlpTopkPlan p = mlp_topk_plan(rows, cols, N1, user_first, k);
-    const size_t need = mt_workspace(p);
-    if (workspace_bytes < need)
-        return fail(NCF_EWORKSPACE, "ncf_mlp_topk: workspace of %zu bytes, %zu needed (ncf_mlp_topk_workspace_bytes)", workspace_bytes, need);
-    if (!workspace || !aligned16(workspace)) return fail(NCF_EINVAL, "ncf_mlp_topk: workspace must be 16-byte aligned");
+    const int tile_cols = mlp_topk_tile_cols(rows, cols);
+    const TopkMerge p = mlp_topk_plan(rows, cols, tile_cols, k);
+    const size_t state_bytes = mlp_state_bytes(rows, cols, N1, user_first);
+    if (const int rc = topk_check_buffers("ncf_mlp_topk", "ncf_mlp_topk_workspace_bytes", seen_rowptr, seen_col, workspace, workspace_bytes,
+                                          state_bytes + topk_merge_bytes(p)))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     const BlobLayout L = blob_layout(dims, n_layers);
     const float* P = (const float*)packed;
     float* state = (float*)workspace;
-    unsigned long long* bufA = (unsigned long long*)((char*)workspace + p.state_bytes);
-    unsigned long long* bufB = bufA + p.chunk * p.n1;
+    unsigned long long* keys = (unsigned long long*)((char*)workspace + state_bytes);
 
     // prefix pass over the first part's rows: the listed users (user-first) or the ranked items (item-first)
     const int64_t npre = user_first ? rows : cols;
@@ -467,33 +424,16 @@ extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t 
     a.Wp2 = n_layers == 3 ? P + L.wp2 : nullptr; a.b2 = n_layers == 3 ? P + L.b2 : nullptr;
     a.wl = P + L.wl; a.bl = P + L.bl;
     a.seen_rowptr = seen_rowptr; a.seen_col = seen_col;
-    a.tiles = (int)p.tiles0; a.tile_cols = p.tile_cols; a.k = k; a.kp = p.kp;
-    a.out_keys = bufA; a.n_out = p.n1;
+    a.tiles = (int)((cols + tile_cols - 1) / tile_cols); a.tile_cols = tile_cols; a.k = k; a.kp = p.kp;
+    a.out_keys = keys; a.n_out = p.n1;
     a.oob = oob;
     for (int64_t r0 = 0; r0 < rows; r0 += p.chunk) {
         const int64_t nr = min(p.chunk, rows - r0);
         a.row0 = r0; a.nrows = nr;
-        const unsigned blocks = (unsigned)((nr * p.tiles0 + kMtWaves - 1) / kMtWaves);
+        const unsigned blocks = (unsigned)((nr * a.tiles + kMtWaves - 1) / kMtWaves);
         mt_dispatch(K0, N1, N2, true, blocks, s, &a);
-        // merge levels: topk_tile_kernel over the fused level's kp keys per range; the last one sorts and writes (score from the key)
-        unsigned long long* in = bufA;
-        unsigned long long* out = bufB;
-        int64_t n_in = p.n1;
-        for (int lv = 0; lv < p.merges; ++lv) {
-            const int64_t t = p.mtiles[lv];
-            if (lv == p.merges - 1) {
-                hipLaunchKernelGGL((topk_tile_kernel<false, true>), dim3((unsigned)(t * nr)), dim3(kTopkThreads), 0, s, nullptr, 0, 0, nullptr,
-                                   nullptr, in, n_in, (int)t, r0, k, p.kp, nullptr, 0, out_score, out_idx, out_count);
-            } else {
-                const int64_t n_out = t * p.kp;
-                hipLaunchKernelGGL((topk_tile_kernel<false, false>), dim3((unsigned)(t * nr)), dim3(kTopkThreads), 0, s, nullptr, 0, 0,
-                                   nullptr, nullptr, in, n_in, (int)t, r0, k, p.kp, out, n_out, out_score, out_idx, out_count);
-                unsigned long long* tmp = in;
-                in = out;
-                out = tmp;
-                n_in = n_out;
-            }
-        }
+        // merge levels over the fused level's kp keys per range; the last one sorts and writes (score from the key)
+        topk_merge(p, keys, nullptr, 0, r0, nr, k, out_score, out_idx, out_count, s);
     }
     return check_launch("ncf_mlp_topk");
 }

@@ -1182,24 +1182,9 @@ def topk_rows(scores: torch.Tensor, k: int, seen: Optional[tuple] = None):
         raise TypeError("topk_rows takes fp32 scores")
     R, C, ld = _rows2d(scores, "scores")
     k = int(k)
-    dev = scores.device
-    rowptr = col = None
-    if seen is not None:
-        rowptr, col = seen
-        _dev(rowptr, "seen rowptr")
-        _dev(col, "seen col")
-        if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.dim() != 1 or col.dim() != 1:
-            raise ValueError("seen = (rowptr int64 (R + 1), col int32)")
-        if rowptr.numel() != R + 1:
-            raise ValueError(f"seen rowptr has {rowptr.numel()} entries, {R + 1} expected")
-        rowptr, col = rowptr.contiguous(), col.contiguous()
-        if col.numel() == 0:                      # a valid CSR with no entries: nothing to skip
-            col = torch.empty(1, dtype=torch.int32, device=dev)
-    out_score = torch.empty((R, max(k, 0)), dtype=torch.float32, device=dev)
-    out_idx = torch.empty((R, max(k, 0)), dtype=torch.int32, device=dev)
-    out_count = torch.empty(R, dtype=torch.int32, device=dev)
+    rowptr, col = _seen_csr(seen, R, scores.device)
     nbytes = lib.ncf_topk_workspace_bytes(R, C, k)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    out_score, out_idx, out_count, ws = _topk_outputs(R, k, nbytes, scores.device)
     _check(lib.ncf_topk_rows(_ptr(scores), R, C, ld, _ptr(rowptr), _ptr(col), k, _ptr(out_score), _ptr(out_idx), _ptr(out_count),
                              _ptr(ws), nbytes, _stream(scores)))
     return out_score, out_idx, out_count
@@ -1207,6 +1192,16 @@ def topk_rows(scores: torch.Tensor, k: int, seen: Optional[tuple] = None):
 
 DOT_TOPK_MAX_K = 128     # the fused kernel's limits (include/ncf_abi.h ncf_dot_topk); outside them it returns NCF_EUNSUPPORTED
 DOT_TOPK_MAX_D = 256
+
+
+def _topk_outputs(R, k, nbytes, dev):
+    """(out_score (R, k) fp32, out_idx (R, k) int32, out_count (R,) int32, workspace of at least nbytes) of a top-K call, from the
+    caching allocator."""
+    out_score = torch.empty((R, max(k, 0)), dtype=torch.float32, device=dev)
+    out_idx = torch.empty((R, max(k, 0)), dtype=torch.int32, device=dev)
+    out_count = torch.empty(R, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    return out_score, out_idx, out_count, ws
 
 
 def _seen_csr(seen, R, dev):
@@ -1246,11 +1241,8 @@ def dot_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     k = int(k)
     dev = tabA.device
     rowptr, col = _seen_csr(seen, B, dev)
-    out_score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    out_idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    out_count = torch.empty(B, dtype=torch.int32, device=dev)
     nbytes = lib.ncf_dot_topk_workspace_bytes(B, I, D, k)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    out_score, out_idx, out_count, ws = _topk_outputs(B, k, nbytes, dev)
     _check(lib.ncf_dot_topk(_ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, I, D, _ptr(rowptr), _ptr(col),
                             k, _ptr(out_score), _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
     return out_score, out_idx, out_count
@@ -1288,12 +1280,9 @@ def mlp_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     k = int(k)
     dev = tabA.device
     rowptr, col = _seen_csr(seen, B, dev)
-    out_score = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    out_idx = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    out_count = torch.empty(B, dtype=torch.int32, device=dev)
     d = _dims_array(packed.dims)
     nbytes = lib.ncf_mlp_topk_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, k)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    out_score, out_idx, out_count, ws = _topk_outputs(B, k, nbytes, dev)
     _check(lib.ncf_mlp_topk(packed.dt, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, EA, EB, 1 if user_first else 0, _ptr(user_ids),
                             _ptr(item_ids), B, I, packed.n_layers, d, _ptr(packed.blob), _ptr(rowptr), _ptr(col), k, _ptr(out_score),
                             _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))

@@ -136,20 +136,10 @@ def _fused_top_k(model, graph, users, all_items, items, n_items, k, seen):
     if k > native.DOT_TOPK_MAX_K:
         return None
     with torch.no_grad():
-        cache = model._refresh()
-        if graph is not None:
-            combined = model.propagate_all(graph, cache)
-            tabA, tabB = combined, combined
-            if all_items:                   # the first n_items rows are the item nodes: rank them in place, no id list
-                tabB, items = combined[:n_items], None
-        else:
-            tabA = model._table("user", model.user_embeddings[0], cache)
-            tabB = model._table("item", model.item_embeddings[0], cache)
-            if all_items:
-                items = None
-        if tabA.shape[1] > native.DOT_TOPK_MAX_D:
+        user_tab, item_tab, items = _fused_tables(model, graph, model._refresh(), all_items, items, n_items)
+        if user_tab.shape[1] > native.DOT_TOPK_MAX_D:
             return None
-        return native.dot_topk(tabA, users, tabB, items, k, seen)
+        return native.dot_topk(user_tab, users, item_tab, items, k, seen)
 
 
 def _fused_mlp_top_k(model, graph, users, all_items, items, n_items, k, seen):
@@ -164,18 +154,23 @@ def _fused_mlp_top_k(model, graph, users, all_items, items, n_items, k, seen):
         packed = model._packed_mlp("MLP", cache)
         if packed is None:
             return None
-        if graph is not None:
-            combined = model.propagate_all(graph, cache)
-            tabA, idxA, tabB, idxB, user_first = combined, items, combined, users, False
-            if all_items:                   # the first n_items rows are the item nodes: rank them in place, no id list
-                tabA, idxA = combined[:n_items], None
-        else:
-            tabA = model._table("user", model.user_embeddings[0], cache)
-            tabB = model._table("item", model.item_embeddings[0], cache)
-            idxA, idxB, user_first = users, None if all_items else items, True
+        user_tab, item_tab, items = _fused_tables(model, graph, cache, all_items, items, n_items)
+        user_first = graph is None          # GraphNCF's MLP reads cat(item, user): the items are the first part
+        tabA, idxA, tabB, idxB = (user_tab, users, item_tab, items) if user_first else (item_tab, items, user_tab, users)
         if not native.mlp_topk_supported(packed, tabA.shape[1], tabB.shape[1], k):
             return None
         return native.mlp_topk(tabA, idxA, tabB, idxB, packed, k, seen, user_first=user_first)
+
+
+def _fused_tables(model, graph, cache, all_items, items, n_items):
+    """(user table, item table, item ids or None) of a fused route: a GraphNCF's propagated node table (its first n_items rows are
+    the item nodes: all items are ranked in place, without an id list), else the model's user and item embedding tables."""
+    if graph is not None:
+        combined = model.propagate_all(graph, cache)
+        return (combined, combined[:n_items], None) if all_items else (combined, combined, items)
+    user_tab = model._table("user", model.user_embeddings[0], cache)
+    item_tab = model._table("item", model.item_embeddings[0], cache)
+    return user_tab, item_tab, None if all_items else items
 
 
 def seen_items(graph, user_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
