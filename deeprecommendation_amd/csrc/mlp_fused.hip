@@ -182,92 +182,19 @@ __global__ __launch_bounds__(NCF_WG_WAVES * 64, NCF_MIN_WAVES) void score_fused_
 #if NCF_STAMP
     const unsigned long long st_rL1 = __builtin_amdgcn_s_memrealtime();
 #endif
-    float partial = 0.f;
+    float score;
     if constexpr (N2 > 0) {
-        // ---- layer 2: acc2 = b2 + W2 . relu(acc1) ; acc1 registers are the B operands ----
-        f32x16 acc2[NT2];
-#pragma unroll
-        for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 bb = ldg4(a.b2 + 32 * nt + 8 * g + 4 * h);
-                acc2[nt][4 * g + 0] = bb[0]; acc2[nt][4 * g + 1] = bb[1];
-                acc2[nt][4 * g + 2] = bb[2]; acc2[nt][4 * g + 3] = bb[3];
-            }
-        const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wp2) + lane;
-        f32x4 w[2][NT2];
-#pragma unroll
-        for (int nt = 0; nt < NT2; ++nt) w[0][nt] = wp[nt * 64];
-#pragma unroll
-        for (int q = 0; q < Q2; ++q) {  // q = 4*kb + g : k-block kb of H1 (= tile kb of acc1), group g
-            const int cur = q & 1, nxt = cur ^ 1;
-            const int kb = q >> 2, g = q & 3;
-            f32x4 hv;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) hv[j] = fmaxf(acc1[kb][4 * g + j], 0.f);  // ReLU (util.py:15)
-            if (NCF_PAIR && NT2 % 2 == 0) {
-#pragma unroll
-                for (int nt = 0; nt < NT2; nt += 2) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
-                        acc2[nt + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt + 1][j], hv[j], acc2[nt + 1], 0, 0, 0);
-                    }
-                    if (q + 1 < Q2) {
-                        w[nxt][nt] = NCF_ABLATE_LOADS ? w[cur][nt] : wp[((q + 1) * NT2 + nt) * 64];
-                        w[nxt][nt + 1] = NCF_ABLATE_LOADS ? w[cur][nt + 1] : wp[((q + 1) * NT2 + nt + 1) * 64];
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int nt = 0; nt < NT2; ++nt) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
-                    if (q + 1 < Q2) w[nxt][nt] = NCF_ABLATE_LOADS ? w[cur][nt] : wp[((q + 1) * NT2 + nt) * 64];
-                }
-            }
-            if (!NCF_ABLATE_LOADS) {
-                if (NCF_PAIR && NT2 % 2 == 0) {
-#pragma unroll
-                    for (int nt = 0; nt < NT2; nt += 2) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-                    }
-                } else {
-#pragma unroll
-                    for (int nt = 0; nt < NT2; ++nt) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        // ---- layer 2 (acc1's registers are the B operands) and the 1-wide layer: mlp_fused.h ----
+        f32x16 acc2[N2 / 32];
+        fused_layer2<N1, N2, NCF_PAIR != 0, NCF_ABLATE_LOADS != 0>(acc1, acc2, a.b2, a.Wp2, lane);
 #if NCF_STAMP
         if (a.dbg && lane == 0) a.dbg[tile * 4 + 0] = __builtin_amdgcn_s_memrealtime();  // end of layer 2
 #endif
-        // ---- last layer (1 wide): out = bl + sum_n wl[n] * relu(acc2[n]) ----
-#pragma unroll
-        for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 ww = ldg4(a.wl + 32 * nt + 8 * g + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc2[nt][4 * g + j], 0.f), partial);
-            }
+        score = fused_last_layer(acc2, a.wl, a.bl, lane);
     } else {
-#pragma unroll
-        for (int nt = 0; nt < NT1; ++nt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 ww = ldg4(a.wl + 32 * nt + 8 * g + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc1[nt][4 * g + j], 0.f), partial);
-            }
+        score = fused_last_layer(acc1, a.wl, a.bl, lane);
     }
-    partial += __shfl_xor(partial, 32);  // the two lane halves hold complementary neuron rows
-    if (h == 0 && p < a.B) a.out[p] = partial + a.bl[0];
+    if (h == 0 && p < a.B) a.out[p] = score;
 #if NCF_STAMP
     if (a.dbg && lane == 0) {
         const unsigned long long st_t1 = __builtin_amdgcn_s_memtime(), st_r1 = __builtin_amdgcn_s_memrealtime();

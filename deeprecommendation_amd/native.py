@@ -94,6 +94,10 @@ SIGNATURES = {
     "ncf_edge_softmax_csr": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_edge_softmax_segmented_workspace_bytes": (_c_size, [_c_i64, _c_i64]),
     "ncf_edge_softmax_segmented": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_size, _c_p]),
+    "ncf_score_fused_partial_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_p]),
+    "ncf_layer1_partial": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "ncf_score_fused_partial": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64,
+                                         _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "ncf_score_folded_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "ncf_score_folded": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p,
                                   _c_p, _c_p, _c_p]),
@@ -460,6 +464,53 @@ def score_fused(tabA: torch.Tensor, idxA, tabB: Optional[torch.Tensor], idxB, pa
     _check(lib.ncf_score_fused(_dt(tabA), _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, EA, EB,
                                packed.n_layers, _dims_array(packed.dims), _ptr(packed.blob), _ptr(out),
                                _ptr(_oob_flag(tabA.device)), _stream(tabA)))
+    return out
+
+
+def partial_supported(EA: int, EB: int, packed: PackedMLP) -> bool:
+    """ncf_score_fused_partial has a kernel for tables of EA / EB columns scored by ``packed`` (fp32 only)."""
+    return packed.dt == NCF_F32 and bool(load_library().ncf_score_fused_partial_supported(
+        NCF_F32, int(EA), int(EB), packed.n_layers, _dims_array(packed.dims)))
+
+
+def layer1_partial(tabA: torch.Tensor, packed: PackedMLP, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """P (rowsA + 1, N1) fp32: layer 1's accumulators after table A's k-groups, for every row of ``tabA`` and (last row) for an
+    out-of-range id — what score_fused_partial starts from.  Depends on tabA and the packed W1 / b1 only: build once per weight
+    version.  Current stream, no sync."""
+    lib = load_library()
+    _dev(tabA, "tabA")
+    rowsA, EA, ldA = _rows2d(tabA, "tabA")
+    EB, N1 = packed.dims[0] - EA, packed.dims[1]
+    if out is None:
+        out = torch.empty((rowsA + 1, N1), dtype=torch.float32, device=tabA.device)
+    if out.shape[0] < rowsA + 1 or out.shape[1] < N1:
+        raise ValueError(f"layer1_partial: out must hold ({rowsA + 1}, {N1}) floats")
+    _, _, ldP = _rows2d(out, "out")
+    _check(lib.ncf_layer1_partial(_dt(tabA), _ptr(tabA), rowsA, ldA, EA, EB, packed.n_layers, _dims_array(packed.dims),
+                                  _ptr(packed.blob), _ptr(out), ldP, _stream(tabA)))
+    return out
+
+
+def score_fused_partial(P: torch.Tensor, tabA: torch.Tensor, idxA, tabB: torch.Tensor, idxB, packed: PackedMLP,
+                        out: Optional[torch.Tensor] = None, B: Optional[int] = None) -> torch.Tensor:
+    """Bit for bit score_fused(tabA, idxA, tabB, idxB, packed), with layer 1 started from P = layer1_partial(tabA, packed)."""
+    lib = load_library()
+    _dev(tabA, "tabA"), _dev(tabB, "tabB"), _dev(P, "P")
+    rowsA, EA, ldA = _rows2d(tabA, "tabA")
+    rowsB, EB, ldB = _rows2d(tabB, "tabB")
+    _, _, ldP = _rows2d(P, "P")
+    if P.dtype != torch.float32 or P.shape[0] != rowsA + 1 or P.shape[1] != packed.dims[1]:
+        raise ValueError(f"P must be fp32 ({rowsA + 1}, {packed.dims[1]}), built by layer1_partial from this tabA")
+    idxA, idxB = _idx(idxA), _idx(idxB)
+    if B is None:
+        B = idxA.numel() if idxA is not None else (idxB.numel() if idxB is not None else rowsA)
+    if out is None:
+        out = torch.empty((B, 1), dtype=torch.float32, device=tabA.device)
+    if tabA.dtype != packed.dtype:
+        raise TypeError(f"tables are {tabA.dtype} but the MLP was packed for {packed.dtype}")
+    _check(lib.ncf_score_fused_partial(_dt(tabA), _ptr(P), ldP, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA),
+                                       _ptr(idxB), B, EA, EB, packed.n_layers, _dims_array(packed.dims), _ptr(packed.blob),
+                                       _ptr(out), _ptr(_oob_flag(tabA.device)), _stream(tabA)))
     return out
 
 

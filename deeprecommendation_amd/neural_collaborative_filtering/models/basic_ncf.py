@@ -21,6 +21,20 @@ class _ScoringMixin:
 
     scoring_dtype = torch.float32
     fold_first_layer = False
+    partial_first_layer = None      # None = automatic (see _partial), True = whenever supported, False = never
+    partial_max_bytes = None        # cap on the partial table; None = min(4 GiB, free device memory / 4) at build time
+    PARTIAL_MIN_ROUNDS = 1          # automatic mode: batches of at least this many rounds of 4 x CUs 32-pair tiles
+
+    def set_partial_first_layer(self, enabled=None, max_bytes=None):
+        """Partial first layer (frozen weights, bit-identical): layer 1's accumulators after the user table's k-groups are
+        stored once per weight version for every row of that table (native.layer1_partial) and each pair's layer 1 starts
+        from them (native.score_fused_partial): 3/4 of the MFMAs per pair at 128-256-128-1.  ``None`` (default) = automatic:
+        fp32 table scoring of a large enough batch, from the second forward of a weight version on, never built inside a
+        stream capture, and only while the table fits ``max_bytes``.  ``True`` = whenever supported, ``False`` = never."""
+        self.partial_first_layer = None if enabled is None else bool(enabled)
+        self.partial_max_bytes = max_bytes
+        self._native_ver = None
+        return self
 
     def set_fold_first_layer(self, enabled: bool = True):
         """Opt-in inference-time folding (frozen weights): relu(W1·cat(a, b) + b1) == relu(PA[ia] + PB[ib]) with
@@ -100,6 +114,47 @@ class _ScoringMixin:
         hit = cache[key]
         return None if hit is None else hit[:3]
 
+    def _partial(self, tabA, idxA, tabB, packed, mlp_name, cache):
+        """The partial-first-layer table P for (tabA, packed), or None when this forward takes native.score_fused.  P and
+        the count of forwards that could have used it live in the _refresh() cache, so the next weight version drops them.
+        Only a table that this cache owns qualifies (P is keyed on its address; a per-forward tensor's address is reused
+        by the caching allocator)."""
+        mode = self.partial_first_layer
+        if mode is False or self.fold_first_layer or idxA is None or tabB is None or tabA.dtype != torch.float32:
+            return None
+        key = ("partial", mlp_name, tabA.data_ptr())
+        ent = cache.get(key)
+        if ent is None:
+            owned = any(v is tabA or (isinstance(v, tuple) and any(x is tabA for x in v)) for v in cache.values())
+            ok = owned and native.partial_supported(tabA.shape[1], tabB.shape[1], packed)
+            ent = cache[key] = {"ok": ok, "seen": 0, "P": None}
+        if not ent["ok"]:
+            return None
+        P = ent["P"]
+        if P is None:
+            ent["seen"] += 1
+            if mode is None:
+                dev = tabA.device
+                round_pairs = 4 * 32 * torch.cuda.get_device_properties(dev).multi_processor_count
+                if ent["seen"] < 2 or idxA.numel() < self.PARTIAL_MIN_ROUNDS * round_pairs:
+                    return None
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            nbytes = (tabA.shape[0] + 1) * packed.dims[1] * 4
+            cap = self.partial_max_bytes
+            if cap is None:
+                cap = min(4 << 30, torch.cuda.mem_get_info(tabA.device)[0] // 4)
+            if nbytes > cap:
+                return None
+            try:
+                P = ent["P"] = native.layer1_partial(tabA, packed)
+            except native.NativeError as e:
+                if e.code != native.NCF_EUNSUPPORTED:
+                    raise
+                ent["ok"] = False
+                return None
+        return P
+
     def _score(self, tabA, idxA, tabB, idxB, mlp_name="MLP", cache=None):
         """gather(A) ‖ gather(B) -> MLP -> (B,1): fused kernel when the shape has an instance, else K1 + K2."""
         EA = tabA.shape[1]
@@ -109,8 +164,12 @@ class _ScoringMixin:
             if folded is not None:
                 PA, PB, tail = folded
                 return native.score_folded(PA, idxA, PB, idxB, tail)
+        cache = self._refresh() if cache is None else cache
         packed = self._packed_mlp(mlp_name, cache)
         if packed is not None and tabA.dtype == packed.dtype and packed.supports(EA, EB):
+            P = self._partial(tabA, idxA, tabB, packed, mlp_name, cache)
+            if P is not None:
+                return native.score_fused_partial(P, tabA, idxA, tabB, idxB, packed)
             return native.score_fused(tabA, idxA, tabB, idxB, packed)
         if tabA.dtype != torch.float32:
             raise native.NativeError(native.NCF_EUNSUPPORTED, f"no bf16 kernel for EA={EA} EB={EB} MLP {getattr(packed, 'dims', None)}")

@@ -173,6 +173,27 @@ int ncf_score_fused(int dtype,
                     int n_layers, const int* dims, const void* dev_packed,
                     float* dev_out, int32_t* dev_oob_flag, ncf_stream_t stream);
 
+/* Partial first layer (frozen weights), BIT-IDENTICAL to ncf_score_fused: layer 1's MFMA chain of every neuron starts from
+ * b1 and runs over table A's EA/8 k-groups first, so after them it holds a value that depends on the row of A only.
+ * ncf_layer1_partial writes that value for every row of A, plus row rowsA for an out-of-range id, as the fp32 table
+ * P (rowsA + 1, N1), ldP >= N1, with the same MFMA instructions; build it once per weight version.
+ * ncf_score_fused_partial then returns exactly what ncf_score_fused returns for the same arguments while issuing layer 1
+ * over table B's groups only (3/4 of the MFMAs of a tile at 128-256-128-1).  Small batches and a ragged last round of
+ * 4 x CUs tiles go to ncf_score_fused's own kernels, as there.  Out-of-range ids set *dev_oob_flag.
+ * Supported (ncf_score_fused_partial_supported): dtype NCF_F32, EA > 0, EB in {32, 64, 96, 128}, and a shape that
+ * ncf_score_fused supports; else NCF_EUNSUPPORTED. */
+int ncf_score_fused_partial_supported(int dtype, int EA, int EB, int n_layers, const int* dims);
+int ncf_layer1_partial(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, int EA, int EB,
+                       int n_layers, const int* dims, const void* dev_packed,
+                       void* dev_P, int64_t ldP, ncf_stream_t stream);
+int ncf_score_fused_partial(int dtype, const void* dev_P, int64_t ldP,
+                            const void* dev_tabA, int64_t rowsA, int64_t ldA,
+                            const void* dev_tabB, int64_t rowsB, int64_t ldB,
+                            const int64_t* dev_idxA, const int64_t* dev_idxB,
+                            int64_t B, int EA, int EB,
+                            int n_layers, const int* dims, const void* dev_packed,
+                            float* dev_out, int32_t* dev_oob_flag, ncf_stream_t stream);
+
 /* Opt-in inference-time folding of the first MLP layer into the tables (frozen weights):
  *   relu(W1 . cat(a, b) + b1) == relu(PA[ia] + PB[ib])  with  PA = TA . W1[:, :EA]^T + b1  (rowsA, N1)  and
  *   PB = TB . W1[:, EA:]^T  (rowsB, N1), both built once by the caller (ncf_mlp_forward with n_layers = 1).

@@ -1,0 +1,86 @@
+"""Dev tool (GPU box): interleaved in-process A/B of native.score_fused against native.score_fused_partial at the cfg-2 shape
+(1 M users x 100 k items, E = 64, MLP 128-256-128-1), back to back, plus the build time of the partial table P.
+
+    python tools/ab_partial.py [--batches 16384,32768,40000,65536,262144] [--reps 50] [--rounds 8]
+
+Every batch size is checked bit for bit (partial == fused) before it is timed.  NCF_HIP_LIBRARY selects a variant build
+(tools/ab_build.sh) for kernel-parameter sweeps."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from deeprecommendation_amd import native  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="16384,32768,40000,65536,262144")
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=8)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    U, I, E, H = 1_000_000, 100_000, 64, (256, 128)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    tu = torch.randn(U, E, device=dev, generator=g) * 0.05
+    ti = torch.randn(I, E, device=dev, generator=g) * 0.05
+    dims = [2 * E, *H, 1]
+    ws = [(torch.rand(dims[i + 1], dims[i], device=dev, generator=g) * 2 - 1) / dims[i] ** 0.5 for i in range(3)]
+    bs = [(torch.rand(dims[i + 1], device=dev, generator=g) * 2 - 1) / dims[i] ** 0.5 for i in range(3)]
+    packed = native.PackedMLP(ws, bs)
+
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    P = native.layer1_partial(tu, packed)
+    torch.cuda.synchronize()
+    build = []
+    for _ in range(5):
+        e0.record()
+        native.layer1_partial(tu, packed, out=P)
+        e1.record()
+        torch.cuda.synchronize()
+        build.append(e0.elapsed_time(e1) * 1e3)
+    result = {"P_bytes": P.numel() * 4, "P_build_us": sorted(build)[len(build) // 2], "batches": {}}
+    print(f"P: {P.shape[0]} x {P.shape[1]} fp32 = {P.numel() * 4 / 2**30:.2f} GiB, build median {result['P_build_us']:.0f} us", flush=True)
+
+    for Bsz in [int(b) for b in args.batches.split(",")]:
+        batches = [(torch.randint(0, U, (Bsz,), device=dev, generator=g), torch.randint(0, I, (Bsz,), device=dev, generator=g))
+                   for _ in range(8)]
+        out_f = torch.empty(Bsz, 1, device=dev)
+        out_p = torch.empty(Bsz, 1, device=dev)
+        variants = {
+            "fused": lambda k: native.score_fused(tu, batches[k % 8][0], ti, batches[k % 8][1], packed, out=out_f),
+            "partial": lambda k: native.score_fused_partial(P, tu, batches[k % 8][0], ti, batches[k % 8][1], packed, out=out_p),
+        }
+        for k in range(8):
+            variants["fused"](k)
+            variants["partial"](k)
+            if not torch.equal(out_f, out_p):
+                raise SystemExit(f"B={Bsz} batch {k}: partial differs from fused (max |diff| {(out_f - out_p).abs().max().item():.3e})")
+        times = {n: [] for n in variants}
+        for _ in range(args.rounds):
+            for n, fn in variants.items():
+                for k in range(5):
+                    fn(k)
+                e0.record()
+                for k in range(args.reps):
+                    fn(k)
+                e1.record()
+                torch.cuda.synchronize()
+                times[n].append(e0.elapsed_time(e1) * 1e3 / args.reps)
+        med = {n: sorted(t)[len(t) // 2] for n, t in times.items()}
+        spread = {n: (min(t), max(t)) for n, t in times.items()}
+        result["batches"][Bsz] = {"fused_us": med["fused"], "partial_us": med["partial"], "speedup": med["fused"] / med["partial"],
+                                  "fused_range": spread["fused"], "partial_range": spread["partial"]}
+        print(f"B={Bsz:7d}: fused {med['fused']:8.2f} us [{spread['fused'][0]:.2f}, {spread['fused'][1]:.2f}]  "
+              f"partial {med['partial']:8.2f} us [{spread['partial'][0]:.2f}, {spread['partial'][1]:.2f}]  "
+              f"x{med['fused'] / med['partial']:.3f}  (bit-identical)", flush=True)
+    native.check_oob(dev)
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
