@@ -123,6 +123,8 @@ SIGNATURES = {
                               _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p]),
     "ncf_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _c_i64, _c_p]),
+    "ncf_negative_cdf": (_c_int, [_c_p, _c_i64, _c_p, ctypes.c_float, _c_p, _c_p, _c_p]),
+    "ncf_sample_negatives": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, ctypes.c_uint32, _c_i64, _c_p, _c_p, _c_p]),
 }
 
 _lib = None
@@ -1216,6 +1218,54 @@ def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
             raise ValueError("adam_step_: contiguous fp32 tensors of one size")
     _check(lib.ncf_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                              float(weight_decay), int(step), _stream(p)))
+
+
+# ------------------------------------------------------------------ negative sampling (pair-wise training)
+def _csr_rowptr(rowptr: torch.Tensor, what: str) -> int:
+    _dev(rowptr, what)
+    if rowptr.dtype != torch.int64 or rowptr.dim() != 1 or not rowptr.is_contiguous() or rowptr.numel() < 1:
+        raise ValueError(f"{what} must be a contiguous 1-D int64 tensor of rows + 1 entries")
+    return rowptr.numel() - 1
+
+
+def negative_cdf(rowptr: torch.Tensor, rating: torch.Tensor, w: float, out: Optional[torch.Tensor] = None,
+                 flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ncf_negative_cdf: every row's normalised inclusive prefix of its weights (1 when w == 0, rating ** w otherwise), each row
+    ending in exactly 1.0 — np.random.choice's CDF for _negative_sampling_probs (datasets/base.py:57-70).  ``flag`` (int32, 1
+    element; default: the device's out-of-range flag) is set when a row's total is not finite and positive.  No synchronisation."""
+    lib = load_library()
+    rows = _csr_rowptr(rowptr, "rowptr")
+    _dev(rating, "rating")
+    if rating.dtype != torch.float32 or rating.dim() != 1 or not rating.is_contiguous():
+        raise ValueError("rating must be a contiguous 1-D fp32 tensor")
+    if out is None:
+        out = torch.empty_like(rating)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rating.numel():
+        raise ValueError("out must be a contiguous fp32 tensor of the ratings' length")
+    flag = _oob_flag(rating.device) if flag is None else flag
+    _check(lib.ncf_negative_cdf(_ptr(rowptr), rows, _ptr(rating), float(w), _ptr(out), _ptr(flag), _stream(rating)))
+    return out
+
+
+def sample_negatives(rowptr: torch.Tensor, cdf: torch.Tensor, neg: torch.Tensor, pick: torch.Tensor, seed: int, slot0: int = 0,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ncf_sample_negatives: out[b] = neg[rowptr[r] + j] (int64) for r = pick[b], j = searchsorted(cdf row r, u_b, 'right') with u_b
+    the header's hash of (seed, slot0 + b).  A pick outside the rows writes -1 and sets the out-of-range flag (IndexError at the
+    next check_oob).  No synchronisation."""
+    lib = load_library()
+    rows = _csr_rowptr(rowptr, "rowptr")
+    _dev(cdf, "cdf"), _dev(neg, "neg")
+    if cdf.dtype != torch.float32 or not cdf.is_contiguous() or neg.dtype != torch.int32 or not neg.is_contiguous() or cdf.numel() != neg.numel():
+        raise ValueError("cdf (fp32) and neg (int32) must be contiguous and of one length")
+    pick = _idx(pick)
+    n = pick.numel()
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=cdf.device)
+    if out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != n:
+        raise ValueError("out must be a contiguous int64 tensor of n entries")
+    _check(lib.ncf_sample_negatives(_ptr(rowptr), _ptr(cdf), _ptr(neg), rows, _ptr(pick), n, int(seed) & 0xFFFFFFFF, int(slot0), _ptr(out),
+                                    _ptr(_oob_flag(cdf.device)), _stream(cdf)))
+    return out
 
 
 # ------------------------------------------------------------------ top-K

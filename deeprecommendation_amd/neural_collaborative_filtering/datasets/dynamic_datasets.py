@@ -1,9 +1,9 @@
-"""DynamicPointwiseDataset (reference datasets/dynamic_datasets.py:6-40): the user profile is built per batch from the
-user's rated items by the provider's ``collate_interacted_items``."""
+"""DynamicPointwiseDataset / DynamicRankingDataset (reference datasets/dynamic_datasets.py): the user profile is built per
+batch from the user's rated items by the provider's ``collate_interacted_items``."""
 import numpy as np
 import torch
 
-from .base import PointwiseDataset, ResidentInputs
+from .base import PointwiseDataset, RankingDataset, ResidentInputs
 from ..models.attention_ncf import SparseRatings
 
 
@@ -52,3 +52,23 @@ class DynamicPointwiseDataset(PointwiseDataset):
             out, att = res
             return out, y_batch, cand_ids, rated_ids, att, user_matrix
         return res, y_batch
+
+
+class DynamicRankingDataset(RankingDataset):
+    """Reference dynamic_datasets.py:43-61: the provider's collate with ``for_ranking=True`` (the negative's profile in the last
+    slot), two model calls per batch; the DataLoader loop (negatives drawn on the host)."""
+
+    def __init__(self, file_or_frame, dynamic_provider):
+        super().__init__(file_or_frame)
+        self.dynamic_provider = dynamic_provider
+
+    def use_collate(self):
+        return lambda batch: self.dynamic_provider.collate_interacted_items(batch, for_ranking=True)
+
+    @staticmethod
+    def do_forward(model, batch, device):
+        cand_ids, rated_ids, candidate_items1, rated_items, user_matrix, candidate_items2 = batch
+        rated, um = rated_items.float().to(device), _dev(user_matrix, device)
+        out1 = model(candidate_items1.float().to(device), rated, um)
+        out2 = model(candidate_items2.float().to(device), rated, um)
+        return out1, out2

@@ -1,9 +1,9 @@
-"""FixedPointwiseDataset (reference datasets/fixed_datasets.py:8-30): fixed user / item vectors from a ContentProvider.
-The collate emits int64 tensors when the provider returns positions (table path) and float tensors otherwise."""
+"""FixedPointwiseDataset / FixedRankingDataset (reference datasets/fixed_datasets.py): fixed user / item vectors from a
+ContentProvider.  The collates emit int64 tensors when the provider returns positions (table path) and float tensors otherwise."""
 import numpy as np
 import torch
 
-from .base import PointwiseDataset, ResidentInputs
+from .base import PointwiseDataset, RankingDataset, ResidentInputs
 
 
 def _to_tensor(x):
@@ -41,3 +41,53 @@ class FixedPointwiseDataset(PointwiseDataset):
         if user_vec.dtype != torch.int64:
             user_vec, item_vec = user_vec.float(), item_vec.float()
         return model(user_vec.to(device), item_vec.to(device)), y_batch
+
+
+class FixedRankingDataset(RankingDataset):
+    """Reference fixed_datasets.py:33-57: (user, positive, negative) profiles from a ContentProvider, two model calls per batch."""
+
+    def __init__(self, file_or_frame, content_provider):
+        super().__init__(file_or_frame)
+        self.content_provider = content_provider
+
+    def use_collate(self):
+        cp = self.content_provider
+
+        def custom_collate(batch):
+            users, items1, items2 = zip(*batch)
+            return (_to_tensor(cp.get_user_profile(userID=users)), _to_tensor(cp.get_item_profile(itemID=items1)),
+                    _to_tensor(cp.get_item_profile(itemID=items2)))
+
+        return custom_collate
+
+    def resident_pairs(self, device=None):
+        """Over an index provider with a device lookup (``IndexProvider.device_lookup``): the user / positive id columns and the
+        negatives' ids go up once and become positions once, on the device (an unknown id becomes -1: IndexError at the
+        epoch's check); a batch is a gather plus one ``sample_negatives`` call."""
+        cp = self.content_provider
+        if device is None or torch.device(device).type != "cuda" or not hasattr(cp, "device_lookup"):
+            return None
+        if str(device) in self._resident:
+            return self._resident[str(device)]
+        if not all(np.issubdtype(a.dtype, np.integer) for a in (self._u, self._pos, self._neg_ids)):
+            return None
+        probe = np.asarray(cp.get_user_profile(userID=self._u[:1]))
+        if not (np.issubdtype(probe.dtype, np.integer) and probe.ndim == 1):
+            return None   # dense profile rows (one-hot / features): built batch by batch
+        lookup = cp.device_lookup(device)
+        if lookup is None:
+            return None
+        dev = torch.device(device)
+        users, positives = lookup(torch.from_numpy(self._u.astype(np.int64)).to(dev), torch.from_numpy(self._pos.astype(np.int64)).to(dev))
+        _, negs = lookup(torch.zeros(0, dtype=torch.int64, device=dev), torch.from_numpy(self._neg_ids.astype(np.int64)).to(dev))
+        return self._resident_pairs(dev, users.contiguous(), positives.contiguous(), negs.to(torch.int32))
+
+    @staticmethod
+    def do_forward(model, batch, device):
+        user_vec, item1_vec, item2_vec = batch
+        if user_vec.dtype != torch.int64:
+            user_vec, item1_vec, item2_vec = user_vec.float(), item1_vec.float(), item2_vec.float()
+        user_vec = user_vec.to(device)
+        out1 = model(user_vec, item1_vec.to(device))
+        out2 = model(user_vec, item2_vec.to(device))
+        return out1, out2

@@ -527,6 +527,38 @@ int ncf_adam_step(float* dev_p, const float* dev_g, float* dev_m, float* dev_v, 
                   float eps, float weight_decay, int64_t step, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Negative sampling for pair-wise (BPR) training (csrc/negsample.hip).
+ * Replaces: RankingDataset.__getitem__'s per-sample draw — DataFrame.iloc, probs = r ** w / sum(r ** w) over the row's
+ *           negatives (_negative_sampling_probs, type 'sum_dynamic'), np.random.choice(negative_movieIds, p=probs) —
+ *           datasets/base.py:57-78.
+ * The negatives are one CSR with a row per training sample: dev_rowptr (rows + 1, int64), the negatives' item positions
+ * dev_neg (int32) and their ratings dev_rating (fp32), nnz = rowptr[rows] entries each.
+ *
+ * ncf_negative_cdf: dev_cdf (nnz fp32) = each row's normalised inclusive prefix of its weights, np.random.choice's
+ *   cdf = cumsum(p); cdf /= cdf[-1].  The weight of an entry is 1 when w == 0 (numpy's 0 ** 0 == 1), powf(r, w) otherwise.
+ *   Prefixes are exact integer sums of the weights in 64-bit fixed point against the row's largest weight (2^-S of it, S =
+ *   62 - bit length of the row's length: S >= 46 up to 2^16 entries; a positive weight never quantises below one unit), each
+ *   divided by the row's total in double and rounded to fp32: every row is non-decreasing, ends in exactly 1.0f, and an entry
+ *   of weight 0 repeats its predecessor's value (a leading one is 0.0f).  A row whose fp32 sum of weights is not finite and
+ *   positive (an empty row, all weights 0, a NaN or an overflow) sets *dev_flag = 1 and gets the uniform prefix (k + 1) / n.
+ *   Rows of any length; one wave per row.  NCF_EINVAL for w < 0 or NaN, rows < 0 or a NULL pointer.
+ * ncf_sample_negatives: one draw per listed sample.  Sample b < n uses row r = dev_pick[b] and slot s = slot0 + b:
+ *       x = lowbias32((uint32)s * 0x9E3779B1 ^ seed)
+ *       x = lowbias32(x ^ (uint32)(s >> 32) * 0x85EBCA77 ^ 0x68E31DA4)
+ *       u = (x >> 8) * 2^-24                                  (exact in fp32, in [0, 1))
+ *   with lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32 arithmetic; the mix of
+ *   the dropout masks of ncf_spmm_csr_dropout / ncf_attn_forward_dropout).  j = the number of entries of row r's CDF that are
+ *   <= u (searchsorted(cdf_row, u, side='right'), at most the row's length - 1), and dev_out[b] = dev_neg[rowptr[r] + j] (int64).
+ *   A pick outside [0, rows) or an empty row writes -1 and sets *dev_oob_flag (when non-NULL).  No atomics: the same inputs
+ *   give the same bits.  n == 0 launches nothing; NCF_EINVAL for negative sizes, slot0 < 0 or a NULL pointer.
+ * Neither call launches anything when it refuses.
+ * ------------------------------------------------------------------------------------------------ */
+int ncf_negative_cdf(const int64_t* dev_rowptr, int64_t rows, const float* dev_rating, float w, float* dev_cdf, int32_t* dev_flag,
+                     ncf_stream_t stream);
+int ncf_sample_negatives(const int64_t* dev_rowptr, const float* dev_cdf, const int32_t* dev_neg, int64_t rows, const int64_t* dev_pick,
+                         int64_t n, uint32_t seed, int64_t slot0, int64_t* dev_out, int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-row top-K with exclusion — the ranking step of a recommendation request.
  * Replaces: DataFrame.sort_values(by='score', ascending=False).iloc[:k] over the whole score vector after
  *           item_features.drop(user_ratings.index) — webapp/backend.py:84, 113-118.
