@@ -416,7 +416,7 @@ class AttentionNCF(_ScoringMixin, NCF):
         if self.training and self.message_dropout is not None:
             att = F.dropout(att, p=self.message_dropout, training=True)
             att = torch.where(att == 0, torch.full_like(att, -float('inf')), att)
-        scores = torch.full((B, I), -float('inf'), dtype=torch.float32, device=att.device)
+        scores = torch.full((B, I), -float('inf'), dtype=att.dtype, device=att.device)     # fp32, or fp64 for a .double() module
         scores[valid] = att
         if self.training:
             # the candidate itself must not attend to itself while fitting its rating (:195-205)

@@ -242,9 +242,23 @@ int ncf_spmm_csr(int dtype, const int64_t* dev_segptr, const int32_t* dev_row_of
  * counter-based hash of (seed, edge id, feature): element (e, f) of the mask is a pure function of the three, so
  *   forward   y  = sum_e coef_e * mask(id_e, :) / (1 - p') * z[col_e]        (CSR by destination, dev_edge_id = NULL: id = position)
  *   backward  dz = the same call on the CSR by SOURCE with dev_edge_id[.] = each entry's position in the forward CSR
- * use the same mask without storing it.  p' = round(p * 65536) / 65536 (the keep test is on 16 hash bits).  The masks are
- * NOT torch's Philox stream: a seeded run differs from the reference's in the (random) masks drawn, not in their law.
- * Only edge-level calls take a mask (the partial-sum tree levels of split rows go through ncf_spmm_csr).  p = 0: ncf_spmm_csr. */
+ * use the same mask without storing it.  The masks are NOT torch's Philox stream: a seeded run differs from the reference's in
+ * the (random) masks drawn, not in their law.  Only edge-level calls take a mask (the partial-sum tree levels of split rows go
+ * through ncf_spmm_csr).
+ *
+ * THE MASK (part of this ABI, shared with ncf_attn_forward_dropout / ncf_attn_backward; restated in numpy by
+ * tests/dropout_mask_ref.py, which the kernels are held to element by element).  For entry e, taken modulo 2^32, and 16-byte
+ * chunk c (features 4c .. 4c+3), in uint32 arithmetic:
+ *       h0 = lowbias32(e * 0x9E3779B1 ^ seed ^ c * 0x85EBCA77)
+ *       h1 = lowbias32(h0 ^ 0x68E31DA4)
+ *   with lowbias32 as under ncf_sample_negatives below.  Features 4c, 4c+1, 4c+2, 4c+3 are KEPT iff
+ *       h0 & 0xFFFF,  h0 >> 16,  h1 & 0xFFFF,  h1 >> 16      respectively are >= thr,
+ *       thr = (uint32)(p * 65536.f + 0.5f)   evaluated in fp32 (halves round up), clamped to 65535,
+ *   so the drop probability is p' = thr / 65536.  Kept values are multiplied by the fp32 quotient 65536.f / (float)(65536 - thr)
+ *   (= 1 / (1 - p') rounded to fp32, NOT 1 / (1 - p)); dropped ones are 0.  thr = 0 (p < 2^-17, p = 0 included) takes the plain
+ *   kernel: the result is ncf_spmm_csr's bit for bit.  p outside [0, 1) or NaN: NCF_EINVAL.
+ *   e here: entry k of the call's CSR has e = dev_edge_id[k] when dev_edge_id is given, else e = k, its position in dev_col
+ *   (for the forward call that is the position in the CSR by destination, whatever segment or tree level handles it). */
 int ncf_spmm_csr_dropout(int dtype, const int64_t* dev_segptr, const int32_t* dev_row_of, int64_t n_seg,
                          const int32_t* dev_col, const float* dev_coef,
                          const void* dev_z, int64_t Nz, int64_t ldz, int D,
@@ -324,7 +338,13 @@ int ncf_attn_forward(int mode,
 /* Training-step forms of ncf_attn_forward (the reference differentiates attention_ncf.py:176-216 through autograd):
  *   ncf_attn_forward_dropout  NCF_ATT_MLP with AttentionNet's hidden Dropout(p) active (attention_ncf.py:112-117: one mask element
  *       per (pair, rated entry, hidden unit), kept values scaled by 1 / (1 - p')): the mask is regenerated in the kernel from a
- *       counter-based hash of (seed, CSR entry, unit) — NOT torch's Philox stream, same law.  p' = round(p * 65536) / 65536.
+ *       counter-based hash of (seed, CSR entry, unit) — NOT torch's Philox stream, same law.  The mask, thr, p' and the fp32
+ *       scale are exactly those written out under ncf_spmm_csr_dropout (THE MASK), with e = the entry's position in the per-pair
+ *       CSR passed to the call (index into dev_col / dev_val / dev_weights, not the position inside its row) and chunk c = hidden
+ *       units 4c .. 4c+3; the score is s_e = b1 + sum_a w1[a] * relu(pc[b,a] + pr[col_e,a]) * scale * keep(e, a).  thr = 0 runs the
+ *       plain kernels (bit for bit ncf_attn_forward / the p = 0 backward).  With thr > 0 the call needs NCF_ATT_MLP or
+ *       NCF_ATT_MLP_SCALED (the same kernel: the exact power-of-two operand scales commute with the mask), A % 4 == 0, A <= 256
+ *       and ldpc, ldpr % 4 == 0; anything else (cosine, linear) is NCF_EUNSUPPORTED and launches nothing.
  *   ncf_attn_backward         gradients of ncf_attn_forward[_dropout] given dev_weights (the attention weights the forward wrote)
  *       and dev_dout (B, Fdim) = d loss / d dev_out_feat:
  *         dev_d_pc (B, A)            written
