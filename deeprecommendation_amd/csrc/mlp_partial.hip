@@ -19,6 +19,15 @@
 #ifndef NCF_PART_PF
 #define NCF_PART_PF 2       // P tiles (32 neurons = one 128-byte line per pair) requested ahead of their first MFMA
 #endif
+#ifndef NCF_PART_LDS
+#define NCF_PART_LDS 1      // 1: instances whose layer-1 image fits twice in a CU's LDS read it from there; 0: all stream it (A/B builds)
+#endif
+#ifndef NCF_PART_LDS_PF
+#define NCF_PART_LDS_PF 2   // P tiles requested ahead in the LDS form (the only loads on its vector-memory queue); swept 1 .. 8
+#endif
+#ifndef NCF_PART_ABLATE
+#define NCF_PART_ABLATE 0   // diagnostic, wrong results, timing only: bit 0 = every pair reads P row rowsA (one L2-resident row),
+#endif                      // bit 1 = the layer-1 weight fragment is never reloaded
 #ifndef NCF_PART_HYBRID_MAX_PERMILLE
 #define NCF_PART_HYBRID_MAX_PERMILLE 500  // a batch, or a ragged last round, of at most this share of a round goes to ncf_score_fused
 #endif
@@ -94,7 +103,8 @@ __global__ __launch_bounds__(256) void layer1_partial_kernel(PartialBuildArgs a)
 // Scoring from P.  Layer 1 runs nt-outer: accumulator tile nt starts from P tile nt and takes its QB*4 dependent MFMAs in
 // one go (the chain of every accumulator is the fused kernel's: ascending q, then j).  The pair's QB chunks of table B
 // stay in registers for all tiles; the weight fragment of (group qa + t, tile nt) is streamed through a ring of WD
-// fragments; P tile nt + PF is loaded straight into the not-yet-live acc1[nt + PF] at the end of tile nt.
+// fragments (streaming form) or read from an LDS image (LDS form, below); P tile nt + PF is loaded straight into the
+// not-yet-live acc1[nt + PF] at the end of tile nt.
 struct PartialArgs {
     const float* P; int64_t rowsA; int64_t ldP;
     const float* tabB; int64_t rowsB; int64_t ldB;
@@ -105,25 +115,45 @@ struct PartialArgs {
     float* out; int32_t* oob;
 };
 
-template <int QB, int N1, int N2>
+// LDS form (LDS = true, partial_in_lds): table B's half of Wp1 is copied once per workgroup into an LDS image in step order
+// (step s = nt*QB + t at wlds[s*64 + lane]: one conflict-free ds_read_b128 per step, counted on lgkmcnt), so the vector-memory
+// queue holds the P gathers alone in the loop and a P tile asked PF tiles ahead really has PF tiles of MFMAs to arrive in: vmcnt
+// retires in issue order, and in the streaming form every weight wait also waits for the P tile issued before that fragment.
+// The fill loads are issued before every P load (writing them to LDS never waits for HBM) and the one barrier is reached by
+// every wave of the workgroup, dead ones included; nothing after it synchronises.
+constexpr bool partial_in_lds(int QB, int N1) { return NCF_PART_LDS && QB * (N1 / 32) <= 80; }  // KiB; two workgroups share 160
+
+template <int QB, int N1, int N2, bool LDS>
 __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(PartialArgs a) {
     constexpr int NT1 = N1 / 32;
     constexpr int S = NT1 * QB;                                      // layer-1 steps of 4 MFMAs, nt-major
     constexpr int WD0 = (QB >= 16 && N1 >= 256) ? 4 : NCF_PART_WD;  // 64 VGPRs of table B leave room for 4 (else scratch)
-    constexpr int WD = WD0 < S ? WD0 : S;
-    constexpr int PF = NCF_PART_PF < 1 ? 1 : (NCF_PART_PF < NT1 ? NCF_PART_PF : NT1);
-    const int lane = threadIdx.x & 63;
+    constexpr int WD = LDS ? 2 : (WD0 < S ? WD0 : S);
+    constexpr int PF0 = LDS ? NCF_PART_LDS_PF : NCF_PART_PF;
+    constexpr int PF = PF0 < 1 ? 1 : (PF0 < NT1 ? PF0 : NT1);
+    constexpr int FILL = LDS ? S / 4 : 1;                            // fragments each of the 4 waves copies into the image
+    constexpr bool ABL_P = (NCF_PART_ABLATE & 1) != 0, ABL_W = (NCF_PART_ABLATE & 2) != 0;
+    __shared__ __attribute__((aligned(16))) f32x4 wlds[LDS ? S * 64 : 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = lane & 31, h = lane >> 5;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile * 32 >= a.B) return;  // whole wave exits together
+    const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+    const bool live = tile * 32 < a.B;
+    if (!LDS && !live) return;  // whole wave exits together; the LDS form leaves behind its barrier
     const int64_t p = tile * 32 + m;
     const int64_t pc = p < a.B ? p : a.B - 1;
 
     const int64_t ia = a.idxA ? a.idxA[pc] : pc;
     const int64_t ib = a.idxB ? a.idxB[pc] : pc;
+    const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wp1) + (int64_t)a.QA * NT1 * 64 + lane;
+    auto wfrag = [&](int s) { return wp[((s % QB) * NT1 + s / QB) * 64]; };  // step s = nt*QB + t: group qa + t, tile nt
+    f32x4 fill[FILL];
+    if constexpr (LDS) {  // steps 4i + wave; QB % 4 == 0, so (4i + wave) / QB = 4i / QB
+#pragma unroll
+        for (int i = 0; i < FILL; ++i) fill[i] = wp[(((4 * i) % QB + wave) * NT1 + (4 * i) / QB) * 64];
+    }
     const bool okA = (ia >= 0) & (ia < a.rowsA), okB = (ib >= 0) & (ib < a.rowsB);
-    if (!(okA & okB) && a.oob) *a.oob = 1;
-    const float* prow = a.P + (okA ? ia : a.rowsA) * a.ldP + 4 * h;
+    if (!(okA & okB) && a.oob && live) *a.oob = 1;
+    const float* prow = a.P + ((okA && !ABL_P) ? ia : a.rowsA) * a.ldP + 4 * h;
     const float* rowB = a.tabB + (okB ? ib : 0) * a.ldB + 4 * h;
     const float zB = okB ? 1.f : 0.f;
 
@@ -136,17 +166,27 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
             acc1[nt][4 * g + 2] = v[2]; acc1[nt][4 * g + 3] = v[3];
         }
     };
-    const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wp1) + (int64_t)a.QA * NT1 * 64 + lane;
-    auto wfrag = [&](int s) { return wp[((s % QB) * NT1 + s / QB) * 64]; };  // step s = nt*QB + t: group qa + t, tile nt
     f32x4 w[WD], x[QB];
     // Issue order = first-use order: the in-order vmcnt wait for a fragment never waits for a younger load.
     load_p(0);
+    if constexpr (!LDS) {
 #pragma unroll
-    for (int s = 0; s < WD - 1; ++s) w[s] = wfrag(s);
+        for (int s = 0; s < WD - 1; ++s) w[s] = wfrag(s);
+    }
 #pragma unroll
     for (int t = 0; t < QB; ++t) x[t] = fused_ldg4(rowB + 8 * t);
 #pragma unroll
     for (int nt = 1; nt < PF; ++nt) load_p(nt);
+    const f32x4* wq = wlds + lane;  // + s*64
+    if constexpr (LDS) {
+#pragma unroll
+        for (int i = 0; i < FILL; ++i) wlds[(4 * i + wave) * 64 + lane] = fill[i];
+        __syncthreads();
+        if (!live) return;
+        w[0] = wq[0];
+        w[1] = wq[64];
+        __builtin_amdgcn_sched_barrier(0);  // both reads stay above tile 0: its "1 DS read" groups are for steps 2 ..
+    }
 #pragma unroll
     for (int nt = 0; nt < NT1; ++nt) {
 #pragma unroll
@@ -156,13 +196,19 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[s % WD][j], xb[j], acc1[nt], 0, 0, 0);
-            if (s + WD - 1 < S) w[(s + WD - 1) % WD] = wfrag(s + WD - 1);
+            if constexpr (LDS) {  // the fragment of step s + 2 into the quad step s has just read: a full step of cover
+                if (s + 2 < S && !ABL_W) w[s % 2] = wq[(s + 2) * 64];
+            } else {
+                if (s + WD - 1 < S) w[(s + WD - 1) % WD] = ABL_W ? w[s % WD] : wfrag(s + WD - 1);
+            }
         }
         if (nt + PF < NT1) load_p(nt + PF);
+        if (!ABL_W) {
 #pragma unroll
-        for (int t = 0; t < QB; ++t) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMA
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read (next fragment)
+            for (int t = 0; t < QB; ++t) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                 // 4 MFMA
+                __builtin_amdgcn_sched_group_barrier(LDS ? 0x100 : 0x020, 1, 0);  // 1 DS / VMEM read (a later fragment)
+            }
         }
         __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);      // the P tile
         __builtin_amdgcn_sched_barrier(0);
@@ -183,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
 template <int QB, int N1, int N2>
 static void launch_partial(const PartialArgs& a, hipStream_t s) {
     const int64_t tiles = (a.B + 31) / 32;
-    hipLaunchKernelGGL((score_fused_partial_f32_kernel<QB, N1, N2>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((score_fused_partial_f32_kernel<QB, N1, N2, partial_in_lds(QB, N1)>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
 }
 
 // The reachable instances: QB = EB / 8 in {4, 8, 12, 16} with 0 < EB < K0 for a (K0, N1, N2) of NCF_FUSED_INSTANCES.  (N1, N2) =
@@ -214,6 +260,10 @@ using namespace ncf;
 
 extern "C" int ncf_score_fused_partial_supported(int dtype, int EA, int EB, int n_layers, const int* dims) {
     return partial_shape_ok(dtype, EA, EB, n_layers, dims) ? 1 : 0;
+}
+
+extern "C" int ncf_score_fused_partial_in_lds(int dtype, int EA, int EB, int n_layers, const int* dims) {
+    return partial_shape_ok(dtype, EA, EB, n_layers, dims) && partial_in_lds(EB / 8, dims[1]) ? 1 : 0;
 }
 
 extern "C" int ncf_layer1_partial(int dtype, const void* tabA, int64_t rowsA, int64_t ldA, int EA, int EB, int n_layers,
@@ -253,8 +303,9 @@ extern "C" int ncf_score_fused_partial(int dtype, const void* P, int64_t ldP, co
         return ncf_score_fused(dtype, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA ? idxA + off : nullptr, idxB ? idxB + off : nullptr,
                                n, EA, EB, n_layers, dims, packed, out + off, oob, stream);
     };
-    // The time of the one-wave-per-tile kernel is a staircase of rounds of 4 x CUs tiles (29.6-31.5 us per round at 128-256-128
-    // on an MI355X), ncf_score_fused's small-batch kernel one of half rounds (23.0 us up to 2 x CUs tiles, 31.6-31.8 up to 3 x CUs).
+    // The time of the one-wave-per-tile kernel is a staircase of rounds of 4 x CUs tiles (27.2-28.7 us per round at 128-256-128
+    // on an MI355X with layer 1's weights in LDS, 24-25 us for a second round; 29.2-31.4 us streaming them), ncf_score_fused's
+    // small-batch kernel one of half rounds (22.4-23.0 us up to 2 x CUs tiles, 31.6-31.8 up to 3 x CUs).
     // So a batch of at most half a round, and a ragged last round of at most half a round, go to ncf_score_fused (its small
     // kernel there); anything more costs a full round of this kernel.  Identity ids (NULL) cannot be offset: no split there.
     const int64_t tiles = (B + 31) / 32;

@@ -95,6 +95,7 @@ SIGNATURES = {
     "ncf_edge_softmax_segmented_workspace_bytes": (_c_size, [_c_i64, _c_i64]),
     "ncf_edge_softmax_segmented": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_size, _c_p]),
     "ncf_score_fused_partial_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_p]),
+    "ncf_score_fused_partial_in_lds": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_p]),
     "ncf_layer1_partial": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "ncf_score_fused_partial": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64,
                                          _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
@@ -472,6 +473,12 @@ def score_fused(tabA: torch.Tensor, idxA, tabB: Optional[torch.Tensor], idxB, pa
 def partial_supported(EA: int, EB: int, packed: PackedMLP) -> bool:
     """ncf_score_fused_partial has a kernel for tables of EA / EB columns scored by ``packed`` (fp32 only)."""
     return packed.dt == NCF_F32 and bool(load_library().ncf_score_fused_partial_supported(
+        NCF_F32, int(EA), int(EB), packed.n_layers, _dims_array(packed.dims)))
+
+
+def partial_in_lds(EA: int, EB: int, packed: PackedMLP) -> bool:
+    """The partial kernel of this shape reads layer 1's weights from LDS (else it streams them, or there is none)."""
+    return packed.dt == NCF_F32 and bool(load_library().ncf_score_fused_partial_in_lds(
         NCF_F32, int(EA), int(EB), packed.n_layers, _dims_array(packed.dims)))
 
 

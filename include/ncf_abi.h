@@ -181,8 +181,10 @@ int ncf_score_fused(int dtype,
  * over table B's groups only (3/4 of the MFMAs of a tile at 128-256-128-1).  Small batches and a ragged last round of
  * 4 x CUs tiles go to ncf_score_fused's own kernels, as there.  Out-of-range ids set *dev_oob_flag.
  * Supported (ncf_score_fused_partial_supported): dtype NCF_F32, EA > 0, EB in {32, 64, 96, 128}, and a shape that
- * ncf_score_fused supports; else NCF_EUNSUPPORTED. */
+ * ncf_score_fused supports; else NCF_EUNSUPPORTED.  ncf_score_fused_partial_in_lds answers 1 where the kernel of that shape
+ * keeps table B's half of layer 1's weights in LDS (EB/8 * N1/32 KiB <= 80), 0 where it streams them or has no kernel. */
 int ncf_score_fused_partial_supported(int dtype, int EA, int EB, int n_layers, const int* dims);
+int ncf_score_fused_partial_in_lds(int dtype, int EA, int EB, int n_layers, const int* dims);
 int ncf_layer1_partial(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, int EA, int EB,
                        int n_layers, const int* dims, const void* dev_packed,
                        void* dev_P, int64_t ldP, ncf_stream_t stream);

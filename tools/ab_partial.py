@@ -1,10 +1,14 @@
 """Dev tool (GPU box): interleaved in-process A/B of native.score_fused against native.score_fused_partial at the cfg-2 shape
 (1 M users x 100 k items, E = 64, MLP 128-256-128-1), back to back, plus the build time of the partial table P.
 
-    python tools/ab_partial.py [--batches 16384,32768,40000,65536,262144] [--reps 50] [--rounds 8]
+    python tools/ab_partial.py [--batches 16384,32768,40000,65536,262144] [--reps 50] [--rounds 8] [--emb 64] [--hidden 256,128]
+                               [--variants lds0=deeprecommendation_amd/libncf_hip_lds0.so,...] [--unchecked abl1,...]
 
-Every batch size is checked bit for bit (partial == fused) before it is timed.  NCF_HIP_LIBRARY selects a variant build
-(tools/ab_build.sh) for kernel-parameter sweeps."""
+Every batch size is checked bit for bit (partial == fused) before it is timed.  --variants adds one column per variant
+library (tools/ab_build.sh, e.g. `ab_build.sh lds0 mlp_partial.hip -DNCF_PART_LDS=0` for the streaming kernel everywhere): its
+ncf_score_fused_partial is timed interleaved with the loaded library's in this process, on the same P, and checked bit for
+bit first unless named in --unchecked (the NCF_PART_ABLATE builds compute wrong scores on purpose).  NCF_HIP_LIBRARY
+replaces the loaded library itself."""
 import argparse
 import json
 import os
@@ -22,16 +26,33 @@ def main():
     ap.add_argument("--batches", default="16384,32768,40000,65536,262144")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=8)
+    ap.add_argument("--emb", type=int, default=64)
+    ap.add_argument("--hidden", default="256,128")
+    ap.add_argument("--variants", default="")
+    ap.add_argument("--unchecked", default="")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    U, I, E, H = 1_000_000, 100_000, 64, (256, 128)
+    U, I, E, H = 1_000_000, 100_000, args.emb, tuple(int(h) for h in args.hidden.split(","))
+    vlibs = {}
+    for item in filter(None, args.variants.split(",")):
+        name, path = item.split("=", 1)
+        vlibs[name] = native.load_library(os.path.abspath(path))
+    unchecked = set(filter(None, args.unchecked.split(",")))
     g = torch.Generator(device=dev).manual_seed(1234)
     tu = torch.randn(U, E, device=dev, generator=g) * 0.05
     ti = torch.randn(I, E, device=dev, generator=g) * 0.05
     dims = [2 * E, *H, 1]
-    ws = [(torch.rand(dims[i + 1], dims[i], device=dev, generator=g) * 2 - 1) / dims[i] ** 0.5 for i in range(3)]
-    bs = [(torch.rand(dims[i + 1], device=dev, generator=g) * 2 - 1) / dims[i] ** 0.5 for i in range(3)]
+    nl = len(dims) - 1
+    ws = [(torch.rand(dims[i + 1], dims[i], device=dev, generator=g) * 2 - 1) / dims[i] ** 0.5 for i in range(nl)]
+    bs = [(torch.rand(dims[i + 1], device=dev, generator=g) * 2 - 1) / dims[i] ** 0.5 for i in range(nl)]
     packed = native.PackedMLP(ws, bs)
+    print(f"E = {E} + {E}, hidden {list(H)}: layer-1 weights in LDS = {native.partial_in_lds(E, E, packed)}", flush=True)
+
+    def via(lib, ia, ib, out):   # native.score_fused_partial's call, through a variant library
+        native._check(lib.ncf_score_fused_partial(native._dt(tu), native._ptr(P), P.stride(0), native._ptr(tu), U, tu.stride(0),
+                                                  native._ptr(ti), I, ti.stride(0), native._ptr(ia), native._ptr(ib), ia.numel(), E, E,
+                                                  packed.n_layers, native._dims_array(packed.dims), native._ptr(packed.blob),
+                                                  native._ptr(out), native._ptr(native._oob_flag(dev)), native._stream(tu)))
 
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     P = native.layer1_partial(tu, packed)
@@ -55,11 +76,18 @@ def main():
             "fused": lambda k: native.score_fused(tu, batches[k % 8][0], ti, batches[k % 8][1], packed, out=out_f),
             "partial": lambda k: native.score_fused_partial(P, tu, batches[k % 8][0], ti, batches[k % 8][1], packed, out=out_p),
         }
+        out_v = torch.empty(Bsz, 1, device=dev)
+        for name, lib in vlibs.items():
+            variants[name] = lambda k, lib=lib: via(lib, batches[k % 8][0], batches[k % 8][1], out_v)
         for k in range(8):
             variants["fused"](k)
-            variants["partial"](k)
-            if not torch.equal(out_f, out_p):
-                raise SystemExit(f"B={Bsz} batch {k}: partial differs from fused (max |diff| {(out_f - out_p).abs().max().item():.3e})")
+            for name in variants:
+                if name == "fused" or name in unchecked:
+                    continue
+                out = out_p if name == "partial" else out_v.fill_(float("nan"))
+                variants[name](k)
+                if not torch.equal(out_f, out):
+                    raise SystemExit(f"B={Bsz} batch {k}: {name} differs from fused (max |diff| {(out_f - out).abs().max().item():.3e})")
         times = {n: [] for n in variants}
         for _ in range(args.rounds):
             for n, fn in variants.items():
@@ -74,10 +102,13 @@ def main():
         med = {n: sorted(t)[len(t) // 2] for n, t in times.items()}
         spread = {n: (min(t), max(t)) for n, t in times.items()}
         result["batches"][Bsz] = {"fused_us": med["fused"], "partial_us": med["partial"], "speedup": med["fused"] / med["partial"],
-                                  "fused_range": spread["fused"], "partial_range": spread["partial"]}
+                                  "fused_range": spread["fused"], "partial_range": spread["partial"],
+                                  "variants": {n: {"us": med[n], "range": spread[n], "checked": n not in unchecked} for n in vlibs}}
         print(f"B={Bsz:7d}: fused {med['fused']:8.2f} us [{spread['fused'][0]:.2f}, {spread['fused'][1]:.2f}]  "
               f"partial {med['partial']:8.2f} us [{spread['partial'][0]:.2f}, {spread['partial'][1]:.2f}]  "
-              f"x{med['fused'] / med['partial']:.3f}  (bit-identical)", flush=True)
+              f"x{med['fused'] / med['partial']:.3f}  (bit-identical)"
+              + "".join(f"\n           {n:>8s} {med[n]:8.2f} us [{spread[n][0]:.2f}, {spread[n][1]:.2f}]  partial is x{med[n] / med['partial']:.3f} of it"
+                        + ("  (unchecked)" if n in unchecked else "  (bit-identical)") for n in vlibs), flush=True)
     native.check_oob(dev)
     print(json.dumps(result))
 
