@@ -258,7 +258,9 @@ def test_full_size_cfg5_properties(native, gpu, kernel_option):
     """BASELINE configs[4] at one GPU's full size (100 M x 128 and 10 M x 128 bf16 tables = 28 GB, MLP 256-256-128-1):
     size-independent properties of BOTH bf16 kernels at 65 536 and 262 144 pairs — (a) permuting the batch permutes the
     output bit-exactly, (b) extreme row ids (0, last) are read correctly, (c) the two kernels agree within the bf16
-    tolerance, (d) a subsample agrees with a float64 evaluation of the same bf16-rounded operands."""
+    tolerance, (d) a subsample agrees with a float64 evaluation of the same bf16-rounded operands.  (d) compares END TO END with a
+    reference whose h1 may differ from the kernel's by one bf16 ulp where an fp32 sum sits on a rounding boundary: that is what the
+    2e-3 bar is for.  The arithmetic itself is pinned layer by layer, and bit for bit on exact inputs, in test_gpu_bf16_contract.py."""
     free, _ = torch.cuda.mem_get_info(gpu)
     if free < 40 << 30:
         pytest.skip("needs 40 GB of free HBM")
@@ -311,7 +313,8 @@ def test_score_fused_bf16_vs_oracle(gpu, kernel_option, E, hidden, B, kernel):
     """bf16 tables / weights, fp32 accumulate: gathers are bit-exact on the bf16 table; the MLP is compared with the
     oracle evaluated on the same bf16-rounded operands — tolerance 2e-3 relative (builder-defined: BASELINE pins only
     fp32; the residual is fp32 accumulation order plus bf16 re-rounding of hidden activations that sit on a rounding
-    boundary).  All three bf16 kernels (slab-streaming, 4-wave and 8-wave weight-stationary) run every batch size, including
+    boundary: the oracle's h1 may differ from the kernel's by one bf16 ulp there, which is what this bar is for; the rounding and
+    each layer are pinned at derived bounds in test_gpu_bf16_contract.py).  All three bf16 kernels (slab-streaming, 4-wave and 8-wave weight-stationary) run every batch size, including
     the ones the library's own dispatch would hand to another kernel: 40 000 / 100 001 / 140 000 pairs give the persistent
     kernels 3-17 tiles (units) per workgroup with ragged tails; a one-hidden-layer MLP sends "ws8" to the 4-wave kernel."""
     from deeprecommendation_amd.neural_collaborative_filtering.models.basic_ncf import BasicNCF
@@ -411,7 +414,9 @@ def test_score_fused_bf16_exact_small_integers(native, gpu, kernel_option, kerne
 
 @pytest.mark.parametrize("kernel", ["stream", "ws", "ws8"])
 def test_score_fused_out_of_range_rows_read_as_zeros(native, gpu, kernel_option, kernel):
-    """ABI contract: an out-of-range id never faults; that table's part of the row is zeros and the sticky flag is set."""
+    """ABI contract: an out-of-range id never faults; that table's part of the row is zeros and the sticky flag is set.  The bf16
+    half compares end to end with an RNE reference whose h1 may differ by one bf16 ulp on a rounding boundary (hence 2e-3); the
+    exact form of the same contract is test_gpu_bf16_contract.py::test_exact_integers_out_of_range_ids."""
     kernel_option("bf16_kernel", kernel)
     g = torch.Generator().manual_seed(0)
     E, dims = 64, [128, 256, 128, 1]
