@@ -1,9 +1,14 @@
-"""MI355X (gfx950) path of the NCF models.  The recommendation functions are re-exported here, imported on first use."""
+"""MI355X (gfx950) path of the NCF models.  The recommendation and ranking-evaluation functions are re-exported here, imported on
+first use."""
 _RECOMMEND = ("top_k_items", "recommend_for_user", "seen_items")
+_RANKING_EVAL = ("rank_of_items", "ranking_metrics", "eval_full_ranking", "held_out_items")
 
 
 def __getattr__(name):
     if name in _RECOMMEND:
         from . import recommend
         return getattr(recommend, name)
+    if name in _RANKING_EVAL:
+        from . import ranking_eval
+        return getattr(ranking_eval, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

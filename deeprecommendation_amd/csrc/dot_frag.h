@@ -1,0 +1,54 @@
+// The scoring half of the fused dot-product kernels (dot_topk.hip: ncf_dot_topk; rank.hip: ncf_dot_rank): the wave shape, the
+// MFMA operand loads and the column tiling they share.  What a kernel does with the scores (candidate buffer and threshold, or
+// rank counters) is its own.  See dot_topk.hip for the chain layout that makes a score gather_dot_kernel<false>'s bit for bit.
+// Internal: not part of the ABI.
+#pragma once
+#include "topk_common.h"
+
+namespace ncf {
+
+constexpr int kDtWaves = 4;
+constexpr int kDtThreads = kDtWaves * kWave;
+constexpr int kDtUsers = 16;                       // users per wave (the MFMA M dimension)
+constexpr int kDtBlockUsers = kDtWaves * kDtUsers; // users per workgroup
+constexpr int kDtMaxD = 256;                       // fused limit on the embedding width (user rows live in registers)
+constexpr int kDtChunk = 2048;                     // columns per exclusion bitmap
+constexpr int kDtKS = 4;                           // chain elements per MFMA step (the instruction's K)
+constexpr int64_t kDtTargetBlocks = 512;           // tile_cols shrinks (8192 -> 2048) until the grid reaches this
+
+// 16 floats of a row starting at element e0 (elements >= D read as 0)
+__device__ __forceinline__ void load_block(const float* __restrict__ row, int e0, int D, bool vec, float (&v)[16]) {
+    if (vec && e0 + 16 <= D) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const f32x4 q = *reinterpret_cast<const f32x4*>(row + e0 + 4 * h);
+            v[4 * h] = q[0]; v[4 * h + 1] = q[1]; v[4 * h + 2] = q[2]; v[4 * h + 3] = q[3];
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < 16; ++s) v[s] = e0 + s < D ? row[e0 + s] : 0.f;
+    }
+}
+
+// J steps of kDtKS chain elements: lane (row l & 15, slot q = l >> 4) holds block kDtKS j + q of its row (zeros past D / q >= kDtKS)
+template <int J>
+__device__ __forceinline__ void load_frag(const float* row, int D, bool vec, int q, float (&v)[J][16]) {
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        if (row && q < kDtKS) load_block(row, 16 * (kDtKS * j + q), D, vec, v[j]);
+        else {
+#pragma unroll
+            for (int s = 0; s < 16; ++s) v[j][s] = 0.f;
+        }
+    }
+}
+
+// The fused level's column tiles: tile_cols shrinks (8192 -> kDtChunk) until the grid reaches kDtTargetBlocks
+inline int dot_topk_tile_cols(int64_t rows, int64_t cols) {
+    const int64_t ublocks = (rows + kDtBlockUsers - 1) / kDtBlockUsers;
+    int tile_cols = kTopkTile;
+    while (tile_cols > kDtChunk && ublocks * ((cols + tile_cols - 1) / tile_cols) < kDtTargetBlocks) tile_cols >>= 1;
+    return tile_cols;
+}
+
+}  // namespace ncf

@@ -19,20 +19,12 @@
 // layout topk_tile_kernel's merge levels read (kp keys per tile, 0-padded), and those levels (topk_merge, topk.hip) finish the
 // ranking; the last one recovers the score from the key (topk_unmap), which is the caller's bits for every non-NaN score (a dot
 // product from +0.f is never -0.0).
-#include "topk_common.h"
+#include "dot_frag.h"
 
 namespace ncf {
 
-constexpr int kDtWaves = 4;
-constexpr int kDtThreads = kDtWaves * kWave;
-constexpr int kDtUsers = 16;                       // users per wave (the MFMA M dimension)
-constexpr int kDtBlockUsers = kDtWaves * kDtUsers; // users per workgroup
 constexpr int kDtCap = 256;                        // candidate keys per user
 constexpr int kDtMaxK = 128;                       // fused limit on k (a re-select must free >= 16 + some slots)
-constexpr int kDtMaxD = 256;                       // fused limit on the embedding width (user rows live in registers)
-constexpr int kDtChunk = 2048;                     // columns per exclusion bitmap
-constexpr int kDtKS = 4;                           // chain elements per MFMA step (the instruction's K)
-constexpr int64_t kDtTargetBlocks = 512;           // tile_cols shrinks (8192 -> 2048) until the grid reaches this
 
 struct DtWaveShared {
     unsigned long long buf[kDtUsers][kDtCap];
@@ -40,33 +32,6 @@ struct DtWaveShared {
     unsigned long long thr[kDtUsers];
     int cnt[kDtUsers];
 };
-
-// 16 floats of a row starting at element e0 (elements >= D read as 0)
-__device__ __forceinline__ void load_block(const float* __restrict__ row, int e0, int D, bool vec, float (&v)[16]) {
-    if (vec && e0 + 16 <= D) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const f32x4 q = *reinterpret_cast<const f32x4*>(row + e0 + 4 * h);
-            v[4 * h] = q[0]; v[4 * h + 1] = q[1]; v[4 * h + 2] = q[2]; v[4 * h + 3] = q[3];
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) v[s] = e0 + s < D ? row[e0 + s] : 0.f;
-    }
-}
-
-// J steps of kDtKS chain elements: lane (row l & 15, slot q = l >> 4) holds block kDtKS j + q of its row (zeros past D / q >= kDtKS)
-template <int J>
-__device__ __forceinline__ void load_frag(const float* row, int D, bool vec, int q, float (&v)[J][16]) {
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        if (row && q < kDtKS) load_block(row, 16 * (kDtKS * j + q), D, vec, v[j]);
-        else {
-#pragma unroll
-            for (int s = 0; s < 16; ++s) v[j][s] = 0.f;
-        }
-    }
-}
 
 // keep the `keep` best of user u's candidates; the k-th becomes the threshold
 __device__ void reselect(DtWaveShared& sh, int u, int keep, int lane) {
@@ -199,14 +164,6 @@ __global__ __launch_bounds__(kDtThreads) void dot_topk_kernel(
         unsigned long long* dst = out_keys + (u0 + u) * n_out + (int64_t)tile * kp;
         for (int s = lane; s < kp; s += kWave) dst[s] = s < n ? sh.buf[u][s] : 0ull;
     }
-}
-
-// The fused level's column tiles: tile_cols shrinks (8192 -> kDtChunk) until the grid reaches kDtTargetBlocks
-static int dot_topk_tile_cols(int64_t rows, int64_t cols) {
-    const int64_t ublocks = (rows + kDtBlockUsers - 1) / kDtBlockUsers;
-    int tile_cols = kTopkTile;
-    while (tile_cols > kDtChunk && ublocks * ((cols + tile_cols - 1) / tile_cols) < kDtTargetBlocks) tile_cols >>= 1;
-    return tile_cols;
 }
 
 // the merge levels after it, over kp keys per tile, in chunks of whole user blocks

@@ -24,6 +24,7 @@
 // round-to-nearest, so partial is never -0 and partial + bl is -0 only if both are.  The recovered bits are therefore the caller's
 // for every non-NaN score; NaN payloads are not kept (a NaN ranks last and comes back as a NaN).
 #include "mlp_fused.h"
+#include "rank_common.h"
 #include "topk_common.h"
 
 namespace ncf {
@@ -105,13 +106,36 @@ struct MtWaveShared {
     uint32_t bitmap[kTopkTile / 32];
 };
 
-template <int K0, int N1, int N2>
-__global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(MtArgs a) {
+// ncf_mlp_rank: the same waves with a counting sink (rank_common.h) instead of the candidate buffer
+struct MrArgs : MtArgs {
+    const int64_t* tgt_rowptr; const unsigned long long* skey; const int32_t* sperm;   // the rows' sorted target keys and places
+    int max_targets, P;                               // targets ranked per row; its LDS slots (a power of two)
+    int32_t* rank; int32_t* ranked;
+};
+
+// the rank sinks' LDS per wave: the range's exclusion bitmap; ONE (a single target: key and counter in registers) nothing else,
+// else the row's sorted target keys and the histogram over them.  2.6 KB per wave at most, so it is static.
+template <bool ONE>
+struct MrWaveShared {
+    uint32_t bitmap[kTopkTile / 32];
+    unsigned long long buf[ONE ? 1 : kRankMaxTargets];
+    uint32_t hist[ONE ? 1 : kRankMaxTargets + 1];
+};
+
+enum { kMtSinkTopk = 0, kMtSinkRankOne = 1, kMtSinkRank = 2 };
+template <int SINK> struct MtSinkShared { typedef MrWaveShared<SINK == kMtSinkRankOne> type; };
+template <> struct MtSinkShared<kMtSinkTopk> { typedef MtWaveShared type; };
+
+// SINK says what a wave does with a score: the top-K candidate buffer behind a threshold (Args = MtArgs), a register counter
+// against the row's one target key, or a binary search into the row's sorted target keys and a bump of the histogram (MrArgs).
+template <int K0, int N1, int N2, int SINK, class Args>
+__global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(Args a) {
     constexpr int NT1 = N1 / 32, Q1 = K0 / 8;
     constexpr int NT2 = N2 / 32, Q2 = N1 / 8;
-    __shared__ MtWaveShared shw[kMtWaves];
+    typedef typename MtSinkShared<SINK>::type Shared;
+    __shared__ Shared shw[kMtWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    MtWaveShared& sh = shw[wave];
+    Shared& sh = shw[wave];
     const int m = lane & 31, h = lane >> 5;
     const int64_t unit = (int64_t)blockIdx.x * kMtWaves + wave;
     if (unit >= a.nrows * a.tiles) return;               // whole wave exits together
@@ -151,6 +175,24 @@ __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(MtArgs a) {
         cnt = a.k;
         return kth;
     };
+    [[maybe_unused]] int64_t tb = 0;                     // rank sinks: the row's first target entry and its chunk length
+    [[maybe_unused]] int tn = 0;
+    if constexpr (SINK != kMtSinkTopk) {
+        tb = a.tgt_rowptr[r];
+        tn = (int)min((int64_t)a.max_targets, a.tgt_rowptr[r + 1] - tb);
+        if constexpr (SINK == kMtSinkRankOne) {
+            thr = tn > 0 ? a.skey[tb] : kRankNoKey;     // the target's key: a column counts when its key is greater
+        } else {
+            rank_stage(sh.buf, sh.hist, a.skey + tb, tn, a.P, lane, kWave);
+            wave_lds_sync();
+        }
+        int ex = 0;                                     // ranked: the range's columns minus the excluded ones
+        if (excl)
+            for (int w = lane; w < a.tile_cols / 32; w += kWave) ex += __popc(sh.bitmap[w]);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) ex += __shfl_xor(ex, o);
+        if (lane == 0) atomicAdd(&a.ranked[r], (int)(c1 - c0) - ex);
+    }
 
     for (int64_t cb = c0; cb < c1; cb += kMtCols) {
         // The bias / weight pointers are made opaque per tile: hoisted out of the tile loop, the loop-invariant b2, wl and first
@@ -304,22 +346,47 @@ __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(MtArgs a) {
 
         // ---- select: lanes of half 0 hold columns cb + m ----
         const unsigned long long key = ((unsigned long long)topk_map(score) << 32) | (0xFFFFFFFFu - (uint32_t)c);
-        bool pass = h == 0 && c < c1 && key > thr;
-        if (pass && excl) {
-            const int off = (int)(c - c0);
-            pass = !((sh.bitmap[off >> 5] >> (off & 31)) & 1u);
+        if constexpr (SINK == kMtSinkTopk) {
+            bool pass = h == 0 && c < c1 && key > thr;
+            if (pass && excl) {
+                const int off = (int)(c - c0);
+                pass = !((sh.bitmap[off >> 5] >> (off & 31)) & 1u);
+            }
+            const unsigned long long mk = __ballot(pass);
+            if (pass) sh.buf[cnt + lanes_below(mk)] = key;   // cnt <= kMtCap - 32 before this tile
+            cnt += __popcll(mk);
+            if (cnt > kMtCap - kMtCols) thr = reselect();
+        } else {
+            bool pass = h == 0 && c < c1;
+            if (pass && excl) {
+                const int off = (int)(c - c0);
+                pass = !((sh.bitmap[off >> 5] >> (off & 31)) & 1u);
+            }
+            if constexpr (SINK == kMtSinkRankOne) {
+                cnt += (pass && key > thr) ? 1 : 0;      // private counter, reduced once after the range
+            } else if (pass) {
+                const int pos = rank_lower_bound(sh.buf, a.P, key);
+                if (pos) atomicAdd(&sh.hist[pos], 1u);
+            }
         }
-        const unsigned long long mk = __ballot(pass);
-        if (pass) sh.buf[cnt + lanes_below(mk)] = key;   // cnt <= kMtCap - 32 before this tile
-        cnt += __popcll(mk);
-        if (cnt > kMtCap - kMtCols) thr = reselect();
     }
 
-    // this range's k best keys, unsorted, 0-padded to kp
-    if (cnt > a.k) reselect();
-    wave_lds_sync();
-    unsigned long long* dst = a.out_keys + uloc * a.n_out + (int64_t)range * a.kp;
-    for (int s = lane; s < a.kp; s += kWave) dst[s] = s < cnt ? sh.buf[s] : 0ull;
+    if constexpr (SINK == kMtSinkTopk) {
+        // this range's k best keys, unsorted, 0-padded to kp
+        if (cnt > a.k) reselect();
+        wave_lds_sync();
+        unsigned long long* dst = a.out_keys + uloc * a.n_out + (int64_t)range * a.kp;
+        for (int s = lane; s < a.kp; s += kWave) dst[s] = s < cnt ? sh.buf[s] : 0ull;
+    } else if constexpr (SINK == kMtSinkRankOne) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+        if (lane == 0 && cnt && thr != kRankNoKey) atomicAdd(&a.rank[tb], cnt);   // a chunk of one: place 0
+    } else {
+        wave_lds_sync();
+        if (lane == 0) rank_suffix(sh.hist, a.P);
+        wave_lds_sync();
+        rank_flush(sh.buf, sh.hist, a.sperm + tb, tn, a.rank + tb, lane, kWave);
+    }
 }
 
 // The fused level's column ranges: tile_cols shrinks (8192 -> kMtCols) until the grid has kMtTargetWaves waves
@@ -341,10 +408,31 @@ static size_t mlp_state_bytes(int64_t rows, int64_t cols, int N1, int user_first
 
 static bool mt_dispatch(int K0, int N1, int N2, bool launch, unsigned blocks, hipStream_t s, const MtArgs* a) {
 #define X(k0, n1, n2) \
-    if (K0 == k0 && N1 == n1 && N2 == n2) { if (launch) hipLaunchKernelGGL((mlp_topk_kernel<k0, n1, n2>), dim3(blocks), dim3(kMtThreads), 0, s, *a); return true; }
+    if (K0 == k0 && N1 == n1 && N2 == n2) { if (launch) hipLaunchKernelGGL((mlp_topk_kernel<k0, n1, n2, kMtSinkTopk, MtArgs>), dim3(blocks), dim3(kMtThreads), 0, s, *a); return true; }
     NCF_FUSED_INSTANCES(X)
 #undef X
     return false;
+}
+
+static bool mr_dispatch(int K0, int N1, int N2, bool one, unsigned blocks, hipStream_t s, const MrArgs* a) {
+#define X(k0, n1, n2) \
+    if (K0 == k0 && N1 == n1 && N2 == n2) { \
+        if (one) hipLaunchKernelGGL((mlp_topk_kernel<k0, n1, n2, kMtSinkRankOne, MrArgs>), dim3(blocks), dim3(kMtThreads), 0, s, *a); \
+        else hipLaunchKernelGGL((mlp_topk_kernel<k0, n1, n2, kMtSinkRank, MrArgs>), dim3(blocks), dim3(kMtThreads), 0, s, *a); \
+        return true; \
+    }
+    NCF_FUSED_INSTANCES(X)
+#undef X
+    return false;
+}
+
+// the rank kernel's column ranges: as mlp_topk_tile_cols; a range with target chunks in LDS stays >= 512 columns (its staging,
+// suffix sum and flush are paid per range)
+static int mlp_rank_tile_cols(int64_t rows, int64_t cols, int max_targets) {
+    const int floor_cols = max_targets == 1 ? kMtCols : 512;
+    int tile_cols = kTopkTile;
+    while (tile_cols > floor_cols && rows * ((cols + tile_cols - 1) / tile_cols) < kMtTargetWaves) tile_cols >>= 1;
+    return tile_cols;
 }
 
 static bool mt_shape_ok(int dtype, int EA, int EB, int n_layers, const int* dims) {
@@ -436,4 +524,91 @@ extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t 
         topk_merge(p, keys, nullptr, 0, r0, nr, k, out_score, out_idx, out_count, s);
     }
     return check_launch("ncf_mlp_topk");
+}
+
+extern "C" int ncf_mlp_rank_supported(int dtype, int EA, int EB, int n_layers, const int* dims, int max_targets) {
+    return (mt_shape_ok(dtype, EA, EB, n_layers, dims) && max_targets >= 1 && max_targets <= kRankMaxTargets) ? 1 : 0;
+}
+
+static int mr_check(int64_t rows, int64_t cols, int max_targets, const char* what) {
+    if (const int rc = rank_check_max_targets(what, max_targets)) return rc;
+    return topk_check_size(what, rows, cols);
+}
+
+extern "C" size_t ncf_mlp_rank_workspace_bytes(int64_t rows, int64_t cols, int user_first, int n_layers, const int* dims, int64_t n_targets,
+                                               int max_targets) {
+    if (mr_check(rows, cols, max_targets, "ncf_mlp_rank_workspace_bytes") != NCF_OK || rows == 0 || n_targets < 0) return 0;
+    if (!dims || (n_layers != 2 && n_layers != 3) || dims[1] < 32 || dims[1] % 32) return 0;
+    return mlp_state_bytes(rows, cols, dims[1], user_first) + rank_ws_bytes(n_targets, true);
+}
+
+extern "C" int ncf_mlp_rank(int dtype, const void* tabA, int64_t rowsA, int64_t ldA, const void* tabB, int64_t rowsB, int64_t ldB,
+                            int EA, int EB, int user_first, const int64_t* user_ids, const int64_t* item_ids, int64_t rows,
+                            int64_t cols, int n_layers, const int* dims, const void* packed, const int64_t* seen_rowptr,
+                            const int32_t* seen_col, const int64_t* tgt_rowptr, const int32_t* tgt_col, int64_t n_targets, int max_targets,
+                            int32_t* rank, int32_t* ranked, void* workspace, size_t workspace_bytes, int32_t* oob, int32_t* overflow,
+                            ncf_stream_t stream) {
+    if (const int rc = mr_check(rows, cols, max_targets, "ncf_mlp_rank")) return rc;
+    if (!mt_shape_ok(dtype, EA, EB, n_layers, dims))
+        return fail(NCF_EUNSUPPORTED, "ncf_mlp_rank: no fused instance for dtype=%d EA=%d EB=%d layers=%d", dtype, EA, EB, n_layers);
+    if (n_targets < 0) return fail(NCF_EINVAL, "ncf_mlp_rank: n_targets = %lld", (long long)n_targets);
+    if (rows == 0) return NCF_OK;
+    if (!tabA || !tabB || !packed) return fail(NCF_EINVAL, "ncf_mlp_rank: null argument");
+    if (ldA < EA || ldB < EB || ldA % 4 || ldB % 4 || !aligned16(tabA) || !aligned16(tabB) || !aligned16(packed))
+        return fail(NCF_EINVAL, "ncf_mlp_rank: tables must be 16-byte aligned with ld %% 4 == 0");
+    user_first = user_first ? 1 : 0;
+    const int64_t nUrows = user_first ? rowsA : rowsB, nIrows = user_first ? rowsB : rowsA;
+    if (!user_ids && rows > nUrows) return fail(NCF_EINVAL, "ncf_mlp_rank: rows = %lld > user table rows without user ids", (long long)rows);
+    if (!item_ids && cols > nIrows) return fail(NCF_EINVAL, "ncf_mlp_rank: cols = %lld > item table rows without item ids", (long long)cols);
+    const int K0 = dims[0], N1 = dims[1], N2 = n_layers == 3 ? dims[2] : 0;
+    const size_t state_bytes = mlp_state_bytes(rows, cols, N1, user_first);     // N1 % 32 == 0: a multiple of 16 bytes
+    if (const int rc = rank_check_args("ncf_mlp_rank", "ncf_mlp_rank_workspace_bytes", rows, seen_rowptr, seen_col, tgt_rowptr, tgt_col,
+                                       n_targets, rank, ranked, workspace, workspace_bytes, state_bytes + rank_ws_bytes(n_targets, true)))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const BlobLayout L = blob_layout(dims, n_layers);
+    const float* P = (const float*)packed;
+    float* state = (float*)workspace;
+    const RankWs w = rank_ws_carve((char*)workspace + state_bytes, n_targets, true);
+
+    // the targets' own scores from the pair scorer, then their keys in order
+    rank_expand(user_ids, item_ids, rows, cols, tgt_rowptr, tgt_col, n_targets, w, ranked, s);
+    if (n_targets > 0) {
+        if (const int rc = ncf_score_fused(dtype, tabA, rowsA, ldA, tabB, rowsB, ldB, user_first ? w.pair_user : w.pair_item,
+                                           user_first ? w.pair_item : w.pair_user, n_targets, EA, EB, n_layers, dims, packed, w.pair_score,
+                                           oob, stream))
+            return rc;
+    }
+    rank_prepare(nullptr, 0, w.pair_score, rows, cols, seen_rowptr, seen_col, tgt_rowptr, tgt_col, max_targets, true, w, rank, overflow, s);
+
+    // prefix pass over the first part's rows, as in ncf_mlp_topk
+    const int64_t npre = user_first ? rows : cols;
+    const unsigned pblocks = (unsigned)(((npre + 31) / 32 + 3) / 4);
+#define X(k0, n1, n2) \
+    if (K0 == k0 && N1 == n1 && N2 == n2) \
+        hipLaunchKernelGGL((mlp_prefix_kernel<k0, n1>), dim3(pblocks), dim3(256), 0, s, (const float*)tabA, rowsA, ldA, \
+                           user_first ? user_ids : item_ids, npre, EA, P + L.wp1, P + L.b1, state, oob);
+    NCF_FUSED_INSTANCES(X)
+#undef X
+
+    const int tile_cols = mlp_rank_tile_cols(rows, cols, max_targets);
+    MrArgs a{};
+    a.tabB = (const float*)tabB; a.rowsB = rowsB; a.ldB = ldB;
+    a.idxU = user_ids; a.idxI = item_ids;
+    a.user_first = user_first;
+    a.cols = cols; a.EA = EA;
+    a.state = state;
+    a.Wp1 = P + L.wp1;
+    a.Wp2 = n_layers == 3 ? P + L.wp2 : nullptr; a.b2 = n_layers == 3 ? P + L.b2 : nullptr;
+    a.wl = P + L.wl; a.bl = P + L.bl;
+    a.seen_rowptr = seen_rowptr; a.seen_col = seen_col;
+    a.row0 = 0; a.nrows = rows;
+    a.tiles = (int)((cols + tile_cols - 1) / tile_cols); a.tile_cols = tile_cols;
+    a.oob = oob;
+    a.tgt_rowptr = tgt_rowptr; a.skey = w.skey; a.sperm = w.sperm;
+    a.max_targets = max_targets; a.P = rank_slots(max_targets);
+    a.rank = rank; a.ranked = ranked;
+    const unsigned blocks = (unsigned)((rows * a.tiles + kMtWaves - 1) / kMtWaves);
+    mr_dispatch(K0, N1, N2, max_targets == 1, blocks, s, &a);
+    return check_launch("ncf_mlp_rank");
 }

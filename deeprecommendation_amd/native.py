@@ -122,6 +122,16 @@ SIGNATURES = {
     "ncf_mlp_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_int, _c_p, _c_int]),
     "ncf_mlp_topk": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_i64,
                               _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p]),
+    "ncf_rank_max_targets": (_c_int, []),
+    "ncf_rank_rows_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_i64]),
+    "ncf_rank_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_size, _c_p]),
+    "ncf_dot_rank_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_i64, _c_int]),
+    "ncf_dot_rank": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p,
+                              _c_i64, _c_int, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p, _c_p]),
+    "ncf_mlp_rank_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_p, _c_int]),
+    "ncf_mlp_rank_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_int, _c_p, _c_i64, _c_int]),
+    "ncf_mlp_rank": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_i64,
+                              _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p, _c_p]),
     "ncf_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _c_i64, _c_p]),
     "ncf_negative_cdf": (_c_int, [_c_p, _c_i64, _c_p, ctypes.c_float, _c_p, _c_p, _c_p]),
@@ -1395,3 +1405,147 @@ def mlp_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
                             _ptr(item_ids), B, I, packed.n_layers, d, _ptr(packed.blob), _ptr(rowptr), _ptr(col), k, _ptr(out_score),
                             _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
     return out_score, out_idx, out_count
+
+
+# ------------------------------------------------------------------ exact ranks
+RANK_MAX_TARGETS = 128   # targets per row of a fused rank call (include/ncf_abi.h ncf_rank_max_targets); rank_rows takes any number
+DOT_RANK_MAX_D = 256     # the fused dot-product kernel's width limit, as DOT_TOPK_MAX_D
+
+_rank_overflow_flags = {}
+
+
+def _rank_overflow_flag(device) -> torch.Tensor:
+    f = _rank_overflow_flags.get(device)
+    if f is None:
+        f = torch.zeros(1, dtype=torch.int32, device=device)
+        _rank_overflow_flags[device] = f
+    return f
+
+
+def check_rank_overflow(device):
+    """Synchronising check of the sticky flag a fused rank call sets when a row has more targets than its ``max_targets``."""
+    f = _rank_overflow_flag(device)
+    if int(f.item()) != 0:
+        f.zero_()
+        raise OverflowError("a row has more targets than the max_targets the rank call was given")
+
+
+def _target_csr(targets, R, dev):
+    if targets is None:
+        raise ValueError("targets = (rowptr int64 (R + 1), col int32) is required")
+    rowptr, col = targets
+    _dev(rowptr, "targets rowptr")
+    _dev(col, "targets col")
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.dim() != 1 or col.dim() != 1:
+        raise ValueError("targets = (rowptr int64 (R + 1), col int32)")
+    if rowptr.numel() != R + 1:
+        raise ValueError(f"targets rowptr has {rowptr.numel()} entries, {R + 1} expected")
+    return rowptr.contiguous(), col.contiguous()
+
+
+def _rank_outputs(R, col, nbytes, dev, rank):
+    """(rank (n_targets,) int32, ranked (R,) int32, workspace, col and rank as the kernel takes them) of a rank call, from the caching
+    allocator.  A caller that ranks blocks of rows against one target CSR passes its own ``rank`` (every block writes its rows'
+    entries)."""
+    n = col.numel()
+    if rank is None:
+        rank = torch.empty(n, dtype=torch.int32, device=dev)
+    elif rank.dtype != torch.int32 or rank.numel() != n or not rank.is_contiguous() or rank.device != dev:
+        raise ValueError("rank must be a contiguous int32 tensor with one entry per target")
+    ranked = torch.empty(R, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    rank_arg = rank
+    if n == 0:                                  # a valid CSR with no entries: the kernels still want pointers
+        col = torch.empty(1, dtype=torch.int32, device=dev)
+        rank_arg = torch.empty(1, dtype=torch.int32, device=dev)
+    return rank, ranked, ws, col, rank_arg
+
+
+def rank_rows(scores: torch.Tensor, targets: tuple, seen: Optional[tuple] = None, rank: Optional[torch.Tensor] = None):
+    """ncf_rank_rows: ``(rank (n_targets,) int32, ranked (R,) int32)`` — for every entry of the target CSR ``targets`` = (rowptr
+    (R + 1) int64, col int32) the number of columns of its row of ``scores`` (R, C) fp32 that are not in ``seen`` (a CSR like
+    topk_rows') and come before the target in topk_rows' order, i.e. the slot the target would hold in an unbounded topk_rows
+    result; -1 for a target that is excluded or outside [0, C).  ranked[r]: the number of non-excluded columns of row r.  Entry
+    e = rowptr[r] + i of row r indexes col and rank, so a slice of a longer rowptr ranks a block of rows into a shared ``rank``.
+    Any number of targets per row.  Outputs and workspace from the caching allocator on the current stream; no sync."""
+    lib = load_library()
+    _dev(scores, "scores")
+    if scores.dtype != torch.float32:
+        raise TypeError("rank_rows takes fp32 scores")
+    R, C, ld = _rows2d(scores, "scores")
+    dev = scores.device
+    rowptr, col = _seen_csr(seen, R, dev)
+    trow, tcol = _target_csr(targets, R, dev)
+    n = tcol.numel()
+    nbytes = lib.ncf_rank_rows_workspace_bytes(R, C, n)
+    rank, ranked, ws, tcol, rank_arg = _rank_outputs(R, tcol, nbytes, dev, rank)
+    _check(lib.ncf_rank_rows(_ptr(scores), R, C, ld, _ptr(rowptr), _ptr(col), _ptr(trow), _ptr(tcol), n, _ptr(rank_arg), _ptr(ranked),
+                             _ptr(ws), nbytes, _stream(scores)))
+    return rank, ranked
+
+
+def dot_rank(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], targets: tuple,
+             max_targets: int, seen: Optional[tuple] = None, rank: Optional[torch.Tensor] = None):
+    """ncf_dot_rank: exactly ``rank_rows(gather_dot(...).view(B, I), targets, seen)`` for the users tabA[idxA[.]] against the list
+    idxB of rows of tabB (arguments as dot_topk), without the B x I score matrix.  ``max_targets`` (1 .. RANK_MAX_TARGETS) bounds the
+    targets per row and sizes the kernel's LDS; 1 is the leave-one-out form.  A row with more targets has only its first
+    max_targets ranked (the others -1) and sets the sticky flag check_rank_overflow() reads.  fp32 tables, width <= DOT_RANK_MAX_D,
+    else NativeError (NCF_EUNSUPPORTED) and nothing launched.  No sync."""
+    lib = load_library()
+    _dev(tabA, "tabA"), _dev(tabB, "tabB")
+    if tabA.dtype != torch.float32 or tabB.dtype != torch.float32:
+        raise TypeError("dot_rank takes fp32 tables")
+    rowsA, D, ldA = _rows2d(tabA, "tabA")
+    rowsB, DB, ldB = _rows2d(tabB, "tabB")
+    if D != DB:
+        raise ValueError("dot_rank needs equal widths")
+    idxA, idxB = _idx(idxA), _idx(idxB)
+    B = idxA.numel() if idxA is not None else rowsA
+    I = idxB.numel() if idxB is not None else rowsB
+    dev = tabA.device
+    rowptr, col = _seen_csr(seen, B, dev)
+    trow, tcol = _target_csr(targets, B, dev)
+    n, max_targets = tcol.numel(), int(max_targets)
+    nbytes = lib.ncf_dot_rank_workspace_bytes(B, I, D, n, max_targets)
+    rank, ranked, ws, tcol, rank_arg = _rank_outputs(B, tcol, nbytes, dev, rank)
+    _check(lib.ncf_dot_rank(_ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, I, D, _ptr(rowptr), _ptr(col),
+                            _ptr(trow), _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws), nbytes, _ptr(_oob_flag(dev)),
+                            _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
+    return rank, ranked
+
+
+def mlp_rank_supported(packed: PackedMLP, EA: int, EB: int, max_targets: int = 1) -> bool:
+    """Whether ncf_mlp_rank has a kernel for this packed MLP, split (EA, EB) and max_targets."""
+    return bool(load_library().ncf_mlp_rank_supported(packed.dt, EA, EB, packed.n_layers, _dims_array(packed.dims), int(max_targets)))
+
+
+def mlp_rank(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], packed: PackedMLP,
+             targets: tuple, max_targets: int, seen: Optional[tuple] = None, user_first: bool = True,
+             rank: Optional[torch.Tensor] = None):
+    """ncf_mlp_rank: exactly ``rank_rows(score_fused(...).view(B, I), targets, seen)`` over every (user, item) pair of an MLP readout
+    (arguments as mlp_topk), without the pair id columns or the score matrix.  max_targets and the overflow flag as dot_rank.  A
+    shape without a fused instance or a bf16 blob raise NativeError (NCF_EUNSUPPORTED) and launch nothing.  No sync."""
+    lib = load_library()
+    _dev(tabA, "tabA"), _dev(tabB, "tabB")
+    rowsA, EA, ldA = _rows2d(tabA, "tabA")
+    rowsB, EB, ldB = _rows2d(tabB, "tabB")
+    if tabA.dtype != tabB.dtype:
+        raise TypeError("mlp_rank: both tables must have one dtype")
+    if tabA.dtype != packed.dtype:
+        raise TypeError(f"tables are {tabA.dtype} but the MLP was packed for {packed.dtype}")
+    idxA, idxB = _idx(idxA), _idx(idxB)
+    nA = idxA.numel() if idxA is not None else rowsA
+    nB = idxB.numel() if idxB is not None else rowsB
+    user_ids, item_ids, B, I = (idxA, idxB, nA, nB) if user_first else (idxB, idxA, nB, nA)
+    dev = tabA.device
+    rowptr, col = _seen_csr(seen, B, dev)
+    trow, tcol = _target_csr(targets, B, dev)
+    n, max_targets = tcol.numel(), int(max_targets)
+    d = _dims_array(packed.dims)
+    nbytes = lib.ncf_mlp_rank_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, n, max_targets)
+    rank, ranked, ws, tcol, rank_arg = _rank_outputs(B, tcol, nbytes, dev, rank)
+    _check(lib.ncf_mlp_rank(packed.dt, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, EA, EB, 1 if user_first else 0, _ptr(user_ids),
+                            _ptr(item_ids), B, I, packed.n_layers, d, _ptr(packed.blob), _ptr(rowptr), _ptr(col), _ptr(trow),
+                            _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws), nbytes, _ptr(_oob_flag(dev)),
+                            _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
+    return rank, ranked

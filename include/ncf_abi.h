@@ -657,6 +657,54 @@ int ncf_mlp_topk(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, co
                  void* dev_workspace, size_t workspace_bytes, int32_t* dev_oob_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact full-catalogue ranks (csrc/rank.hip, csrc/mlp_topk.hip) — where each held-out column of a row stands among ALL of the row's
+ * non-excluded columns: the quantity behind HR@K / Recall@K / NDCG@K / MRR / AUC.  Siblings of the three top-K entry points, with
+ * the same tables, ids, exclusion CSR, key order and bit-identity of the scores; no candidate buffer, merge level or sort.
+ * Targets: a CSR (dev_tgt_rowptr (rows + 1) int64, dev_tgt_col int32 of n_targets entries in all) of columns of the ranked list.
+ *   The kernels address entry e = rowptr[r] + i of row r in dev_tgt_col and dev_rank, so a slice of a longer rowptr ranks a block of
+ *   rows against the whole col / rank arrays (n_targets = their length); entries of rows that are not listed are left untouched.
+ * dev_rank[e] (int32): the number of non-excluded columns c of the row with key(c) > key(target), key = map(score) << 32 | ~column
+ *   (descending score, -0.0 == +0.0, equal scores to the lower column, every NaN below every number and by column) — the slot the
+ *   target would hold in an unbounded ncf_topk_rows result.  The row's other targets compete like any column; duplicate targets
+ *   get the same rank; a target that is excluded or outside [0, cols) gets -1.
+ * dev_ranked[r] (int32): the number of non-excluded columns of row r.
+ * Both outputs are initialised inside the call by kernels (no memset node) and accumulated with int32 atomics over column tiles:
+ *   bit-reproducible, and a captured call gives the same answer on every replay.  Nothing is launched on a refusal.
+ * Workspace (the _workspace_bytes queries; 16-byte aligned, never 0): 12 bytes per target entry, fused calls 32; ncf_mlp_rank adds
+ *   the first part's layer-1 state as ncf_mlp_topk does.  1 <= cols <= 2^24, rows <= 65536.
+ *
+ * ncf_rank_rows: ranks the listed columns of an existing (rows, cols) fp32 score matrix (leading dimension ld).  Any number of
+ *   targets per row (processed in chunks of ncf_rank_max_targets() = 128).
+ * ncf_dot_rank / ncf_mlp_rank: arguments of ncf_dot_topk / ncf_mlp_topk.  The targets' own scores come from ncf_gather_dot /
+ *   ncf_score_fused over the (row, target) pairs, the catalogue's from the top-K kernels' scoring code: the same bits, so the result
+ *   is ncf_rank_rows' over the pair scorer's score matrix.  max_targets (1 .. 128; 0 or less NCF_EINVAL, above NCF_EUNSUPPORTED)
+ *   sizes the kernel's LDS; 1 is the leave-one-out form (target key and counter in registers).  A row with more targets than
+ *   max_targets is not truncated silently: its first max_targets entries are ranked, the others get -1 and *dev_overflow_flag
+ *   (sticky, when non-NULL) is set.  Limits as the top-K siblings: D <= 256; ncf_mlp_rank_supported() (fp32, an ncf_score_fused
+ *   instance, EA and EB multiples of 8); NCF_EUNSUPPORTED otherwise — score and take ncf_rank_rows.
+ * ------------------------------------------------------------------------------------------------ */
+int ncf_rank_max_targets(void);
+size_t ncf_rank_rows_workspace_bytes(int64_t rows, int64_t cols, int64_t n_targets);
+int ncf_rank_rows(const float* dev_scores, int64_t rows, int64_t cols, int64_t ld, const int64_t* dev_seen_rowptr,
+                  const int32_t* dev_seen_col, const int64_t* dev_tgt_rowptr, const int32_t* dev_tgt_col, int64_t n_targets,
+                  int32_t* dev_rank, int32_t* dev_ranked, void* dev_workspace, size_t workspace_bytes, ncf_stream_t stream);
+size_t ncf_dot_rank_workspace_bytes(int64_t rows, int64_t cols, int D, int64_t n_targets, int max_targets);
+int ncf_dot_rank(const float* dev_tabA, int64_t rowsA, int64_t ldA, const float* dev_tabB, int64_t rowsB, int64_t ldB,
+                 const int64_t* dev_idxA, const int64_t* dev_idxB, int64_t rows, int64_t cols, int D, const int64_t* dev_seen_rowptr,
+                 const int32_t* dev_seen_col, const int64_t* dev_tgt_rowptr, const int32_t* dev_tgt_col, int64_t n_targets,
+                 int max_targets, int32_t* dev_rank, int32_t* dev_ranked, void* dev_workspace, size_t workspace_bytes,
+                 int32_t* dev_oob_flag, int32_t* dev_overflow_flag, ncf_stream_t stream);
+int ncf_mlp_rank_supported(int dtype, int EA, int EB, int n_layers, const int* dims, int max_targets);
+size_t ncf_mlp_rank_workspace_bytes(int64_t rows, int64_t cols, int user_first, int n_layers, const int* dims, int64_t n_targets,
+                                    int max_targets);
+int ncf_mlp_rank(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, const void* dev_tabB, int64_t rowsB, int64_t ldB,
+                 int EA, int EB, int user_first, const int64_t* dev_user_ids, const int64_t* dev_item_ids, int64_t rows,
+                 int64_t cols, int n_layers, const int* dims, const void* dev_packed, const int64_t* dev_seen_rowptr,
+                 const int32_t* dev_seen_col, const int64_t* dev_tgt_rowptr, const int32_t* dev_tgt_col, int64_t n_targets,
+                 int max_targets, int32_t* dev_rank, int32_t* dev_ranked, void* dev_workspace, size_t workspace_bytes,
+                 int32_t* dev_oob_flag, int32_t* dev_overflow_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Calibration probe — the bf16 MFMA rate the chip SUSTAINS on random operands (it lowers its clock under matrix load), so that
  * bench.py can state a kernel's fraction of it next to the fraction of the 2.5 PFLOP/s datasheet figure.  Not part of scoring.
  * Launches `blocks` 512-thread workgroups; every wave issues iters * 32 v_mfma_f32_16x16x32_bf16 (16 384 flop each) on register

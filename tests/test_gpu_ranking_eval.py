@@ -1,0 +1,175 @@
+"""GPU: the public ranking evaluation (rank_of_items / eval_full_ranking) on tiny MF, BasicNCF, GraphNCF-dot and GraphNCF-MLP
+models: the fused routes and score-then-rank give identical integers; the ranks are consistent with top_k_items(k = 100) on the
+same arguments; a user above the fused cap is routed through rank_rows; bf16-scoring and folded-first-layer models take the
+unfused route and match the oracle on their own scores; training mode is refused; the metrics equal ranking_metrics of the oracle's
+ranks."""
+import numpy as np
+import pytest
+import torch
+
+from rank_ref import csr, rank_oracle
+from test_gpu_graph import _bipartite
+
+pytestmark = pytest.mark.gpu
+
+N_ITEMS, N_USERS = 700, 90
+
+
+def _model(kind, gpu):
+    """(model, graph or None, first user position)"""
+    torch.manual_seed(3)
+    if kind == "mf":
+        from deeprecommendation_amd.neural_collaborative_filtering.models.mf import MF
+        return MF(item_dim=N_ITEMS, user_dim=N_USERS, item_emb=64, user_emb=64).eval().to(gpu), None, 0
+    if kind == "basic":
+        from deeprecommendation_amd.neural_collaborative_filtering.models.basic_ncf import BasicNCF
+        return BasicNCF(item_dim=N_ITEMS, user_dim=N_USERS, item_emb=64, user_emb=64, mlp_dense_layers=[256, 128]).eval().to(gpu), None, 0
+    from deeprecommendation_amd.neural_collaborative_filtering.models.gnn_ncf import GraphNCF, GraphData
+    dot = kind == "graph_dot"
+    u2i, i2u, a1, a2 = _bipartite(N_ITEMS, N_USERS, 3000, seed=4)
+    m = GraphNCF(item_dim=N_ITEMS, user_dim=N_USERS, num_gnn_layers=2, hetero=True, node_emb=64,
+                 mlp_dense_layers=None if dot else [128], use_dot_product=dot, concat=False).eval()
+    graph = GraphData(user2item_edge_index=u2i, item2user_edge_index=i2u, user2item_edge_attr=a1, item2user_edge_attr=a2,
+                      num_items=N_ITEMS, num_users=N_USERS)
+    return m.to(gpu), graph, N_ITEMS
+
+
+def _lists(rng, B, C, big_user=None, n_big=0):
+    """Per-user exclusion lists and target lists (unique per user; some excluded, one user without targets)."""
+    seen = [rng.choice(C, int(rng.integers(0, C // 4)), replace=False).tolist() for _ in range(B)]
+    targets = [rng.choice(C, int(rng.integers(1, 6)), replace=False).tolist() for _ in range(B)]
+    targets[1] = []
+    targets[2] = targets[2] + seen[2][:1] if seen[2] else targets[2]
+    if big_user is not None:
+        targets[big_user] = rng.choice(C, n_big, replace=False).tolist()
+    return seen, targets
+
+
+def _scores(model, graph, users, items):
+    B, I = users.numel(), items.numel()
+    u, i = users.repeat_interleave(I), items.repeat(B)
+    with torch.no_grad():
+        s = model(graph, u, i) if graph is not None else model(u, i)
+    return s.view(B, I).float().cpu()
+
+
+@pytest.fixture
+def fused_calls(monkeypatch):
+    from deeprecommendation_amd import native
+    calls = {"dot_rank": 0, "mlp_rank": 0, "rank_rows": 0}
+    for name in calls:
+        real = getattr(native, name)
+
+        def counted(*a, _real=real, _name=name, **kw):
+            calls[_name] += 1
+            return _real(*a, **kw)
+
+        monkeypatch.setattr(native, name, counted)
+    return calls
+
+
+@pytest.mark.parametrize("with_items", [False, True])
+@pytest.mark.parametrize("kind", ["mf", "basic", "graph_dot", "graph_mlp"])
+def test_rank_of_items_routes_agree_and_match_top_k(gpu, fused_calls, kind, with_items):
+    from deeprecommendation_amd import eval_full_ranking, rank_of_items, ranking_metrics, top_k_items
+    model, graph, u0 = _model(kind, gpu)
+    rng = np.random.default_rng(len(kind) + int(with_items))
+    B = 40
+    users = torch.as_tensor(rng.choice(N_USERS, B, replace=False) + u0, device=gpu)
+    items = torch.as_tensor(rng.choice(N_ITEMS, 300, replace=False), device=gpu) if with_items else None
+    C = 300 if with_items else N_ITEMS
+    seen, targets = _lists(rng, B, C)
+    exclude, tg = csr(seen, gpu), csr(targets, gpu)
+    kw = dict(item_ids=items, exclude=exclude, graph=graph)
+    rank, ranked = rank_of_items(model, users, tg, **kw)
+    fused_name = "dot_rank" if kind in ("mf", "graph_dot") else "mlp_rank"
+    assert fused_calls[fused_name] == 1 and fused_calls["rank_rows"] == 0
+    rank2, ranked2 = rank_of_items(model, users, tg, fused=False, **kw)
+    assert fused_calls[fused_name] == 1 and fused_calls["rank_rows"] >= 1
+    assert torch.equal(rank, rank2) and torch.equal(ranked, ranked2)
+    rank3, _ = rank_of_items(model, users, tg, max_targets=6, block_bytes=20 * C * 7, **kw)   # given max_targets; several score blocks
+    rank4, _ = rank_of_items(model, users, tg, fused=False, block_bytes=20 * C * 7, **kw)
+    assert torch.equal(rank, rank3) and torch.equal(rank, rank4)
+
+    # consistent with top_k_items(k = 100): a target with 0 <= rank < 100 sits in that slot, no other target is in the row
+    _, pos, _ = top_k_items(model, users, 100, **kw)
+    pos, rk = pos.cpu(), rank.cpu().tolist()
+    item_of = (lambda c: int(items[c])) if with_items else (lambda c: c)
+    e = 0
+    for b in range(B):
+        row = pos[b].tolist()
+        for t in targets[b]:
+            if 0 <= rk[e] < 100:
+                assert row[rk[e]] == item_of(t)
+            else:
+                assert item_of(t) not in row
+            e += 1
+    assert rk[int(tg[0][2]) + len(targets[2]) - 1] == -1 or not seen[2]        # the excluded target
+
+    # the oracle on the model's own scores (fp32 routes are bit-equal to the model's forward), and the metrics
+    all_items = items if with_items else torch.arange(N_ITEMS, device=gpu)
+    ref_rank, ref_ranked = rank_oracle(_scores(model, graph, users, all_items), seen, targets)
+    assert torch.equal(rank.cpu(), ref_rank) and torch.equal(ranked.cpu(), ref_ranked)
+    got = eval_full_ranking(model, users, tg, exclude=exclude, cutoffs=(1, 10, 50), item_ids=items, graph=graph)
+    ref = ranking_metrics(ref_rank, tg[0].cpu(), ref_ranked, (1, 10, 50))
+    assert set(got) == set(ref)
+    for k in ref:
+        assert abs(got[k] - ref[k]) <= 1e-12, (k, got[k], ref[k])
+
+
+@pytest.mark.parametrize("kind", ["mf", "basic"])
+def test_a_user_above_the_cap_goes_through_rank_rows(gpu, fused_calls, kind):
+    from deeprecommendation_amd import native, rank_of_items
+    model, graph, u0 = _model(kind, gpu)
+    rng = np.random.default_rng(7)
+    B = 12
+    users = torch.as_tensor(rng.choice(N_USERS, B, replace=False), device=gpu)
+    seen, targets = _lists(rng, B, N_ITEMS, big_user=5, n_big=native.RANK_MAX_TARGETS + 30)
+    exclude, tg = csr(seen, gpu), csr(targets, gpu)
+    rank, ranked = rank_of_items(model, users, tg, exclude=exclude)
+    assert fused_calls["dot_rank" if kind == "mf" else "mlp_rank"] == 1 and fused_calls["rank_rows"] == 1
+    ref_rank, ref_ranked = rank_oracle(_scores(model, graph, users, torch.arange(N_ITEMS, device=gpu)), seen, targets)
+    assert torch.equal(rank.cpu(), ref_rank) and torch.equal(ranked.cpu(), ref_ranked)
+    rank2, ranked2 = rank_of_items(model, users, tg, exclude=exclude, fused=False)
+    assert torch.equal(rank, rank2) and torch.equal(ranked, ranked2)
+    native.check_rank_overflow(gpu)
+
+
+def test_models_outside_the_fused_limits_take_the_unfused_route(gpu, fused_calls):
+    from deeprecommendation_amd import rank_of_items
+    model, graph, _ = _model("basic", gpu)
+    rng = np.random.default_rng(9)
+    B = 20
+    users = torch.as_tensor(rng.choice(N_USERS, B, replace=False), device=gpu)
+    seen, targets = _lists(rng, B, N_ITEMS)
+    exclude, tg = csr(seen, gpu), csr(targets, gpu)
+    all_items = torch.arange(N_ITEMS, device=gpu)
+    for setup, undo in ((lambda: model.set_fold_first_layer(True), lambda: model.set_fold_first_layer(False)),
+                        (lambda: model.set_scoring_dtype(torch.bfloat16), lambda: model.set_scoring_dtype(torch.float32))):
+        setup()
+        before = dict(fused_calls)
+        rank, ranked = rank_of_items(model, users, tg, exclude=exclude)
+        assert fused_calls["mlp_rank"] == before["mlp_rank"] and fused_calls["rank_rows"] == before["rank_rows"] + 1
+        ref_rank, ref_ranked = rank_oracle(_scores(model, graph, users, all_items), seen, targets)
+        assert torch.equal(rank.cpu(), ref_rank) and torch.equal(ranked.cpu(), ref_ranked)
+        undo()
+
+
+def test_rank_of_items_argument_errors(gpu):
+    from deeprecommendation_amd import rank_of_items
+    model, graph, _ = _model("mf", gpu)
+    users = torch.arange(4, device=gpu)
+    tg = csr([[1], [2], [3], [4]], gpu)
+    model.train()
+    with pytest.raises(RuntimeError, match="eval"):
+        rank_of_items(model, users, tg)
+    model.eval()
+    with pytest.raises(ValueError):
+        rank_of_items(model, users, csr([[1]], gpu))
+    with pytest.raises(ValueError):
+        rank_of_items(model, users.int(), tg)
+    with pytest.raises(ValueError, match="graph"):
+        rank_of_items(model, users, tg, graph=object())
+    gm, ggraph, u0 = _model("graph_dot", gpu)
+    with pytest.raises(ValueError, match="graph"):
+        rank_of_items(gm, users + u0, tg)
