@@ -431,29 +431,26 @@ __global__ __launch_bounds__(256) void linear_rsp_kernel(const float* __restrict
     }
 }
 
-template <int NT>
-static void launch_rsp(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc,
-                       int64_t M, int K, bool relu, hipStream_t s) {
-    const int64_t tiles = (M + 31) / 32;
-    int64_t blocks = (tiles + 3) / 4;
-    if (blocks > 512) blocks = 512;                         // two 4-wave workgroups per CU, each wave loops over its tiles
-    if (relu) hipLaunchKernelGGL((linear_rsp_kernel<NT, true>), dim3((unsigned)blocks), dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, K);
-    else hipLaunchKernelGGL((linear_rsp_kernel<NT, false>), dim3((unsigned)blocks), dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, K);
+// ---------------------------------------------------------------------------------------------------------------
+// The launch rule, separate from the launches: which kernel a Linear of M rows, N outputs and K inputs runs, as a pure function
+// of (M, N, K) and the linear_kernel / linear_kslices options.  launch_linear consumes it; ncf_linear_plan returns it
+// without launching, so a test can say which kernel it ran.
+enum { LIN_NONE = 0, LIN_TILED = 1, LIN_ROWDOT = 2, LIN_RS = 3, LIN_RSP = 4 };   // the form values of ncf_linear_plan
+
+struct LinearPlan {
+    int form;           // LIN_*
+    int nt;             // rs / rsp: the kernel's NT (32-column tiles per wave); else 0
+    int ks;             // rs: K-slices of a tile; else 1
+    int col_blocks;     // gridDim.y: rs column blocks of 32 * nt outputs, tiled 64-column blocks; else 1
+    int64_t grid_x;     // gridDim.x
+};
+
+static int64_t rs_grid_x(int64_t tiles, int ks) {
+    const int waves = ks > 4 ? ks : 4, tpb = waves / ks;    // WAVES / TPB of linear_rs_kernel
+    return (tiles + tpb - 1) / tpb;
 }
 
-template <int NT, int KS>
-static void launch_rs(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc,
-                      int64_t M, int K, bool relu, hipStream_t s, int col_blocks = 1) {
-    const int64_t tiles = (M + 31) / 32;
-    constexpr int WAVES = KS > 4 ? KS : 4, TPB = WAVES / KS;
-    const dim3 grid((unsigned)((tiles + TPB - 1) / TPB), (unsigned)col_blocks);
-    if (relu) hipLaunchKernelGGL((linear_rs_kernel<NT, KS, true>), grid, dim3(WAVES * 64), 0, s, A, lda, W, ldw, bias, C, ldc, M, K);
-    else hipLaunchKernelGGL((linear_rs_kernel<NT, KS, false>), grid, dim3(WAVES * 64), 0, s, A, lda, W, ldw, bias, C, ldc, M, K);
-}
-
-template <int NT>
-static void launch_rs_nt(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc,
-                         int64_t M, int K, bool relu, hipStream_t s) {
+static LinearPlan plan_rs(int64_t M, int NT, int K) {
     const int64_t tiles = (M + 31) / 32;
     const int force = option(NCF_OPT_LINEAR_KERNEL);      // 1 = rs / 2 = rsp: A/B and tests (ncf_set_option); 0: by shape
     // persistent row-streaming form: tall problems with K a multiple of 64 (bit-identical to the one-tile-per-wave form)
@@ -464,9 +461,12 @@ static void launch_rs_nt(const float* A, int64_t lda, const float* W, int64_t ld
     // deep-and-short problems (8192 x 256 -> 128: 18.7 vs 26.0 us; the 4096 x 2094 candidate Linear).
     // Short K (<= 128) from 128 tiles: 4096 x 64 -> 128 18.3 -> 14.4 us, -> 256 28.1 -> 17.7, 16 384 x 64 -> 128 35.0 -> 14.4
     // (splitting a K of 8 or 16 steps over 4 waves only adds the LDS reduction).
-    if (K % 64 == 0 && (force ? force == 2 : (tiles >= 512 || (K <= 128 && tiles >= 128))))
-        return launch_rsp<NT>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s);
-    if constexpr (NT <= 4) {
+    if (K % 64 == 0 && (force ? force == 2 : (tiles >= 512 || (K <= 128 && tiles >= 128)))) {
+        int64_t blocks = (tiles + 3) / 4;
+        if (blocks > 512) blocks = 512;                     // two 4-wave workgroups per CU, each wave loops over its tiles
+        return {LIN_RSP, NT, 1, 1, blocks};
+    }
+    if (NT <= 4) {
         // Skinny and deep (the 4096 x 2094 -> 64 candidate Linear of AttentionNCF: 128 row tiles): one 32-column block
         // per workgroup so that tiles * NT workgroups share the chip — the rows of A are re-read once per column block
         // (from L2), each wave's MFMA chain is NT times shorter; same split-K order, bit-identical results.
@@ -478,36 +478,86 @@ static void launch_rs_nt(const float* A, int64_t lda, const float* W, int64_t ld
             // (staged A / W blocks since round 2: 4096 x 2094 -> 64 20.8 us vs 36.4 on 4 slices, 8192 rows 37.7 vs 48.1, N = 128 36.3 vs
             // 46.4, 4096 x 1030 -> 64 13.4 vs 18.1: tools/ab_skinny_linear.py)
             const bool ks8 = ksf ? ksf == 8 : K >= 1024;
-            if (ks8) return launch_rs<1, 8>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s, NT);
-            return launch_rs<1, 4>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s, NT);
+            return {LIN_RS, 1, ks8 ? 8 : 4, NT, rs_grid_x(tiles, ks8 ? 8 : 4)};
         }
-        if (tiles <= 1024 && K >= 64) return launch_rs<NT, 4>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s);
-        if (tiles <= 2048 && K >= 32) return launch_rs<NT, 2>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s);
+        if (tiles <= 1024 && K >= 64) return {LIN_RS, NT, 4, 1, rs_grid_x(tiles, 4)};
+        if (tiles <= 2048 && K >= 32) return {LIN_RS, NT, 2, 1, rs_grid_x(tiles, 2)};
     }
-    launch_rs<NT, 1>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s);
+    return {LIN_RS, NT, 1, 1, rs_grid_x(tiles, 1)};
+}
+
+static LinearPlan plan_linear(int64_t M, int N, int K) {
+    if (M == 0) return {LIN_NONE, 0, 1, 1, 0};
+    if (K >= 8 && (N == 32 || N == 64 || N == 128 || N == 256)) return plan_rs(M, N / 32, K);
+    if (N <= 8) {
+        int64_t blocks = (M * N + 15) / 16;
+        if (blocks > 16384) blocks = 16384;
+        return {LIN_ROWDOT, 0, 1, 1, blocks};
+    }
+    return {LIN_TILED, 0, 1, (N + BN - 1) / BN, (M + BM - 1) / BM};
+}
+
+template <int NT>
+static void launch_rsp(const LinearPlan& p, const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C,
+                       int64_t ldc, int64_t M, int K, bool relu, hipStream_t s) {
+    const dim3 grid((unsigned)p.grid_x);
+    if (relu) hipLaunchKernelGGL((linear_rsp_kernel<NT, true>), grid, dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, K);
+    else hipLaunchKernelGGL((linear_rsp_kernel<NT, false>), grid, dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, K);
+}
+
+template <int NT, int KS>
+static void launch_rs(const LinearPlan& p, const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C,
+                      int64_t ldc, int64_t M, int K, bool relu, hipStream_t s) {
+    constexpr int WAVES = KS > 4 ? KS : 4;
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.col_blocks);
+    if (relu) hipLaunchKernelGGL((linear_rs_kernel<NT, KS, true>), grid, dim3(WAVES * 64), 0, s, A, lda, W, ldw, bias, C, ldc, M, K);
+    else hipLaunchKernelGGL((linear_rs_kernel<NT, KS, false>), grid, dim3(WAVES * 64), 0, s, A, lda, W, ldw, bias, C, ldc, M, K);
 }
 
 static int launch_linear(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc,
                          int64_t M, int N, int K, bool relu, hipStream_t s) {
-    if (M == 0) return NCF_OK;
-    if (K >= 8 && (N == 32 || N == 64 || N == 128 || N == 256)) {
-        if (N == 32) launch_rs_nt<1>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s);
-        else if (N == 64) launch_rs_nt<2>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s);
-        else if (N == 128) launch_rs_nt<4>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s);
-        else launch_rs_nt<8>(A, lda, W, ldw, bias, C, ldc, M, K, relu, s);
+    const LinearPlan p = plan_linear(M, N, K);
+#define NCF_LIN_ARGS p, A, lda, W, ldw, bias, C, ldc, M, K, relu, s
+    switch (p.form) {
+    case LIN_NONE: return NCF_OK;
+    case LIN_RSP:
+        switch (p.nt) {
+        case 1: launch_rsp<1>(NCF_LIN_ARGS); break;
+        case 2: launch_rsp<2>(NCF_LIN_ARGS); break;
+        case 4: launch_rsp<4>(NCF_LIN_ARGS); break;
+        default: launch_rsp<8>(NCF_LIN_ARGS); break;
+        }
         return check_launch("linear_rs_f32");
+    case LIN_RS:
+        switch (p.nt * 16 + p.ks) {                         // every (NT, KS) plan_rs can return
+        case 1 * 16 + 8: launch_rs<1, 8>(NCF_LIN_ARGS); break;
+        case 1 * 16 + 4: launch_rs<1, 4>(NCF_LIN_ARGS); break;
+        case 2 * 16 + 4: launch_rs<2, 4>(NCF_LIN_ARGS); break;
+        case 4 * 16 + 4: launch_rs<4, 4>(NCF_LIN_ARGS); break;
+        case 1 * 16 + 2: launch_rs<1, 2>(NCF_LIN_ARGS); break;
+        case 2 * 16 + 2: launch_rs<2, 2>(NCF_LIN_ARGS); break;
+        case 4 * 16 + 2: launch_rs<4, 2>(NCF_LIN_ARGS); break;
+        case 1 * 16 + 1: launch_rs<1, 1>(NCF_LIN_ARGS); break;
+        case 2 * 16 + 1: launch_rs<2, 1>(NCF_LIN_ARGS); break;
+        case 4 * 16 + 1: launch_rs<4, 1>(NCF_LIN_ARGS); break;
+        case 8 * 16 + 1: launch_rs<8, 1>(NCF_LIN_ARGS); break;
+        default: return fail(NCF_ELAUNCH, "linear: no row-streaming kernel <%d, %d>", p.nt, p.ks);
+        }
+        return check_launch("linear_rs_f32");
+    case LIN_ROWDOT: {
+        const dim3 grid((unsigned)p.grid_x);
+        if (relu) hipLaunchKernelGGL(rowdot_f32_kernel<true>, grid, dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, N, K);
+        else hipLaunchKernelGGL(rowdot_f32_kernel<false>, grid, dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, N, K);
+        return check_launch("linear_f32");
     }
-    if (N <= 8) {
-        int64_t blocks = (M * N + 15) / 16;
-        if (blocks > 16384) blocks = 16384;
-        if (relu) hipLaunchKernelGGL(rowdot_f32_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, N, K);
-        else hipLaunchKernelGGL(rowdot_f32_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, N, K);
-    } else {
-        dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((N + BN - 1) / BN));
+    default: {
+        const dim3 grid((unsigned)p.grid_x, (unsigned)p.col_blocks);
         if (relu) hipLaunchKernelGGL(linear_f32_kernel<true>, grid, dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, N, K);
         else hipLaunchKernelGGL(linear_f32_kernel<false>, grid, dim3(256), 0, s, A, lda, W, ldw, bias, C, ldc, M, N, K);
+        return check_launch("linear_f32");
     }
-    return check_launch("linear_f32");
+    }
+#undef NCF_LIN_ARGS
 }
 
 }  // namespace ncf
@@ -557,6 +607,17 @@ extern "C" int ncf_mlp_forward(int dtype, const void* x, int64_t B, int64_t ldx,
         in = o;
         ldin = ldo;
     }
+    return NCF_OK;
+}
+
+extern "C" int ncf_linear_plan(int64_t M, int N, int K, int* form, int* nt, int* kslices, int* col_blocks, int64_t* grid_x) {
+    if (M < 0 || N <= 0 || K <= 0) return fail(NCF_EINVAL, "ncf_linear_plan: bad argument");
+    const LinearPlan p = plan_linear(M, N, K);
+    if (form) *form = p.form;
+    if (nt) *nt = p.nt;
+    if (kslices) *kslices = p.ks;
+    if (col_blocks) *col_blocks = p.col_blocks;
+    if (grid_x) *grid_x = p.grid_x;
     return NCF_OK;
 }
 

@@ -103,6 +103,7 @@ SIGNATURES = {
     "ncf_score_folded": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p,
                                   _c_p, _c_p, _c_p]),
     "ncf_linear_forward": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_i64, _c_p]),
+    "ncf_linear_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "ncf_gemm_tn_workspace_bytes": (_c_size, [_c_i64, _c_int, _c_int]),
     "ncf_gemm_tn": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_p, _c_i64, _c_p, _c_size, _c_p]),
     "ncf_colsum_workspace_bytes": (_c_size, [_c_i64, _c_int]),
@@ -1138,6 +1139,19 @@ def linear_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     out = torch.empty((M, N), dtype=torch.float32, device=x.device)
     _check(lib.ncf_linear_forward(NCF_F32, _ptr(x), M, ldx, _ptr(weight), _ptr(bias), K, N, 1 if relu else 0, _ptr(out), N, _stream(x)))
     return out
+
+
+LINEAR_FORMS = {0: "none", 1: "tiled", 2: "rowdot", 3: "rs", 4: "rsp"}    # ncf_linear_plan's *form
+
+
+def linear_plan(M: int, N: int, K: int):
+    """(form, nt, kslices, col_blocks, grid_x) of the kernel a Linear of M rows, N outputs and K inputs runs under the current
+    linear_kernel / linear_kslices options; form by name (LINEAR_FORMS).  Host only: no launch, no device."""
+    form, nt, ks, cb = (ctypes.c_int(0) for _ in range(4))
+    gx = ctypes.c_int64(0)
+    _check(load_library().ncf_linear_plan(int(M), int(N), int(K), ctypes.byref(form), ctypes.byref(nt), ctypes.byref(ks),
+                                          ctypes.byref(cb), ctypes.byref(gx)))
+    return LINEAR_FORMS[form.value], nt.value, ks.value, cb.value, gx.value
 
 
 # ------------------------------------------------------------------ backward (training step)

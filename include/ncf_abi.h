@@ -519,6 +519,17 @@ int ncf_l2_normalize_rows(const float* dev_x, int64_t ldx, int64_t R, int E, flo
  * ncf_mlp_forward used by the autograd wrappers, which need every layer's output (util.py:12-17 one Linear at a time). */
 int ncf_linear_forward(int dtype, const void* dev_x, int64_t M, int64_t ldx, const void* dev_W, const void* dev_b, int K, int N,
                        int relu, void* dev_out, int64_t ldo, ncf_stream_t stream);
+/* Which kernel ncf_linear_forward / a layer of ncf_mlp_forward runs for M rows, N outputs and K inputs under the current
+ * "linear_kernel" / "linear_kslices" options: the launch rule itself, answered without launching and without touching the
+ * device (like ncf_score_fused_partial_in_lds).  Any output pointer may be NULL.
+ *   *form        0 nothing (M = 0), 1 LDS-tiled kernel, 2 row-dot kernel (N <= 8), 3 row-streaming kernel, one row tile per
+ *                wave ("rs"), 4 persistent row-streaming kernel ("rsp")
+ *   *nt          forms 3 / 4: 32-column tiles per wave of the kernel launched (N / 32, or 1 with column blocks); else 0
+ *   *kslices     form 3: waves that split K of one row tile (1, 2, 4 or 8); else 1
+ *   *col_blocks  gridDim.y: form 3 column blocks of 32 * nt outputs, form 1 blocks of 64 outputs; else 1
+ *   *grid_x      gridDim.x
+ * NCF_EINVAL for M < 0, N <= 0 or K <= 0. */
+int ncf_linear_plan(int64_t M, int N, int K, int* form, int* nt, int* kslices, int* col_blocks, int64_t* grid_x);
 size_t ncf_gemm_tn_workspace_bytes(int64_t M, int N1, int N2);
 int ncf_gemm_tn(const float* dev_A, int64_t lda, const float* dev_B, int64_t ldb, int64_t M, int N1, int N2,
                 float* dev_out, int64_t ldo, void* dev_workspace, size_t workspace_bytes, ncf_stream_t stream);
