@@ -300,7 +300,8 @@ static int spmm_impl(const char* who, int dtype, const int64_t* segptr, const in
                      const float* coef, const void* z, int64_t Nz, int64_t ldz, int D, void* y, int64_t ldy, float* sum, int64_t ldsum,
                      float* partial, int fixup, const DropArgs* drop, ncf_stream_t stream) {
     if (dtype != NCF_F32) return fail(NCF_EUNSUPPORTED, "%s: fp32 only", who);
-    if (!segptr || !z || !y || n_seg < 0 || D <= 0) return fail(NCF_EINVAL, "%s: bad argument", who);
+    // a matrix without rows has nothing to read or write: its (0, D) operands may be null, like the E == 0 entries below
+    if (!segptr || n_seg < 0 || D <= 0 || (n_seg > 0 && (!z || !y))) return fail(NCF_EINVAL, "%s: bad argument", who);
     if (D % 4 || D > 256) return fail(NCF_EUNSUPPORTED, "%s: D = %d (need D %% 4 == 0 and D <= 256)", who, D);
     if (ldz % 4 || ldy % 4 || (sum && ldsum % 4) || !aligned16(z) || !aligned16(y) || (sum && !aligned16(sum)) || (partial && !aligned16(partial)))
         return fail(NCF_EINVAL, "%s: rows must be 16-byte aligned (ld %% 4 == 0)", who);
