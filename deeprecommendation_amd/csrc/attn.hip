@@ -1028,7 +1028,8 @@ __global__ __launch_bounds__(256) void l2_normalize_rows_kernel(const float* __r
         ss += __shfl_xor(ss, 2);
         ss += __shfl_xor(ss, 1);
         if (r < R) {
-            const float d = fmaxf(sqrtf(ss), 1e-12f);
+            const float nrm = sqrtf(ss);
+            const float d = nrm < 1e-12f ? 1e-12f : nrm;       // clamp_min, not fmaxf: a NaN norm stays NaN (fmaxf would return 1e-12)
             for (int e = sub; e < E; e += 16) out[r * ldo + e] = x[r * ldx + e] / d;
         }
     }

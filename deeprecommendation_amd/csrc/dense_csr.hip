@@ -197,7 +197,8 @@ extern "C" int ncf_dense_csr_rows(const float* um, int64_t ld, int64_t B, int64_
         return check_launch("ncf_dense_csr_rows (empty)");
     }
     if (B >= (1ll << 31) || I >= (1ll << 31)) return fail(NCF_EUNSUPPORTED, "ncf_dense_csr_rows: more than 2^31 rows or columns");
-    if (!um || !pair_row || !keep_cnt || !workspace) return fail(NCF_EINVAL, "ncf_dense_csr_rows: null pointer");
+    if ((!um && I > 0) || !pair_row || !keep_cnt || !workspace)     // a matrix without columns is never read: its pointer may be NULL
+        return fail(NCF_EINVAL, "ncf_dense_csr_rows: null pointer");
     if (workspace_bytes < ncf_dense_csr_workspace_bytes(B) || !aligned16(workspace))
         return fail(NCF_EWORKSPACE, "ncf_dense_csr_rows: workspace too small (ncf_dense_csr_workspace_bytes) or misaligned");
     hipStream_t s = (hipStream_t)stream;

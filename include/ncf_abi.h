@@ -459,7 +459,8 @@ int ncf_attn_tail(const float* dev_cand_emb, int64_t ldcand, int EA,
  *   an inclusive cumulative sum over dev_rowptr, IN PLACE, makes it the CSR's rowptr
  *   ncf_dense_csr_fill  -> the representatives' (col, val) in column order at rowptr[b]; dev_col / dev_val must hold rowptr[B]
  *                          entries (B * I is always enough).
- * -0.0 counts as 0 (unrated); a row containing NaN never shares.  workspace: ncf_dense_csr_workspace_bytes(B), 16-byte aligned. */
+ * -0.0 counts as 0 (unrated); a row containing NaN never shares.  workspace: ncf_dense_csr_workspace_bytes(B), 16-byte aligned.
+ * A matrix without columns (I == 0) is never read: dev_user_matrix may then be NULL in both calls; its rows are all equal and empty. */
 size_t ncf_dense_csr_workspace_bytes(int64_t B);
 int ncf_dense_csr_rows(const float* dev_user_matrix, int64_t ld, int64_t B, int64_t I, int share_rows,
                        int64_t* dev_pair_row, int64_t* dev_rowptr, void* dev_workspace, size_t workspace_bytes, ncf_stream_t stream);
@@ -502,7 +503,8 @@ int ncf_attn_candidates_packed(const float* dev_x, int64_t B, int64_t ldx, int K
                                void* dev_workspace, size_t workspace_bytes, int32_t* dev_oob_flag, ncf_stream_t stream);
 
 /* out[r, :] = x[r, :] / max(||x[r, :]||_2, 1e-12) — torch.nn.functional.normalize(p=2, dim=1) of the cosine
- * variant, models/attention_ncf.py:167-168. */
+ * variant, models/attention_ncf.py:167-168.  The clamp is torch's clamp_min, not fmaxf: a NaN norm stays NaN, so a row holding a
+ * NaN comes out all NaN (and a row holding an infinity as 0 with NaN at the infinity). */
 int ncf_l2_normalize_rows(const float* dev_x, int64_t ldx, int64_t R, int E, float* dev_out, int64_t ldout,
                           ncf_stream_t stream);
 

@@ -3,6 +3,8 @@ they must reduce to the single-GPU product path."""
 import pytest
 import torch
 
+import prep_forms_ref as R
+
 
 pytestmark = pytest.mark.gpu
 
@@ -94,24 +96,7 @@ def test_bucket_ids_kernel(gpu, world, cap, B):
     native.bucket_ids(d, rpr, total, world, cap, send, slot, counts, overflow)
     with pytest.raises(IndexError):
         native.check_oob(gpu)
-    send, slot, counts = send.cpu(), slot.cpu(), counts.cpu()
-    ok = (idx >= 0) & (idx < total)
-    owner = torch.where(ok, idx // rpr, torch.zeros_like(idx))
-    expect = torch.bincount(owner[ok], minlength=world)
-    assert torch.equal(counts.long(), expect)
-    assert int(overflow.item()) == int(bool((expect > cap).any()))
-    kept = slot >= 0
-    assert not bool(kept[~ok].any())
-    assert torch.equal(slot[kept] // cap, owner[kept])                       # the right bucket
-    assert torch.equal(send[slot[kept]], (idx - owner * rpr)[kept])          # holding the right local row
-    assert torch.unique(slot[kept]).numel() == int(kept.sum())               # one pair per slot
-    assert torch.equal(torch.bincount(owner[kept], minlength=world), torch.minimum(expect, torch.tensor(cap)))
-    used = torch.zeros(world * cap, dtype=torch.bool)
-    used[slot[kept]] = True
-    assert bool((send[~used] == 0).all())                                    # padding names local row 0
-    for o in range(world):                                                   # a bucket is filled from its start
-        n = min(int(expect[o]), cap)
-        assert bool(used[o * cap:o * cap + n].all()) and not bool(used[o * cap + n:(o + 1) * cap].any())
+    R.check_bucket_ids(idx, rpr, total, world, cap, send.cpu(), slot.cpu(), counts.cpu(), int(overflow.item()))
 
 
 @pytest.mark.parametrize("world,cap,B,zipf", [(8, 1200, 8192, False), (8, 700, 8192, True), (2, 4096, 4097, False), (3, 40, 1000, True),
@@ -146,24 +131,8 @@ def test_bucket_ids_dedup_kernel_and_bucket_gather(gpu, world, cap, B, zipf):
     else:
         native.check_oob(gpu)
     send_c, slot_c, counts_c = send.cpu().view(world, cap + 1), slot.cpu()[:B], counts.cpu()
-    ok = (idx >= 0) & (idx < total)
-    uniq = torch.unique(idx[ok])
-    expect = torch.bincount(uniq // rpr, minlength=world)
-    assert torch.equal(counts_c.long(), expect)
-    assert int(overflow.item()) == int(bool((expect > cap).any()))
-    assert torch.equal(send_c[:, 0], torch.minimum(expect, torch.tensor(cap)))          # bucket headers
-    kept = slot_c >= 0
-    assert not bool(kept[~ok].any())
-    owner = torch.where(ok, idx // rpr, torch.zeros_like(idx))
-    assert torch.equal(slot_c[kept] // cap, owner[kept])                                   # the right bucket
-    k = slot_c[kept] % cap
-    assert bool((k < send_c[owner[kept], 0]).all())                                        # inside the bucket's filled prefix
-    assert torch.equal(send_c[owner[kept], 1 + k], (idx - owner * rpr)[kept])              # holding the right local row
-    # one slot per distinct id: pairs with equal ids share it, distinct ids never do
-    assert torch.unique(slot_c[kept]).numel() == torch.unique(idx[kept]).numel()
-    assert torch.unique(torch.stack([slot_c[kept], idx[kept]]), dim=1).shape[1] == torch.unique(slot_c[kept]).numel()
-    if not bool((expect > cap).any()):
-        assert bool(kept[ok].all())
+    kept = R.check_bucket_ids_dedup(idx, rpr, total, world, cap, send.cpu(), slot_c, counts_c, int(overflow.item()))
+    owner = torch.where((idx >= 0) & (idx < total), idx // rpr, torch.zeros_like(idx))
     # the owner's side (all buckets "received" by one table here): rows of exactly the listed ids
     tab = torch.randn(rpr, 128, generator=g).to(torch.bfloat16).to(gpu)
     out = torch.full((world * cap, 128), 7.0, dtype=torch.bfloat16, device=gpu)
