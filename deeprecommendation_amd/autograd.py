@@ -46,7 +46,11 @@ class GatherColumnsFn(torch.autograd.Function):
     BasicNCF / MF construct) this is a ROW gather, and the backward scatters 4·E-byte gradient rows (full-rate atomics)
     into a zeroed [U, E] buffer whose transpose VIEW is returned: the gradient has the parameter's own strides, so Adam
     runs elementwise over the raw buffers.  For a plain contiguous [E, U] weight the column kernels are used.  torch's
-    ``W.t()[idx]`` backward goes through a sort and two table-sized copies either way."""
+    ``W.t()[idx]`` backward goes through a sort and two table-sized copies either way.
+
+    Row gradients: an id-major weight that carries a list attribute ``_ncf_row_grads`` (optim.RowSparseAdam marks its
+    parameters so) gets NO dense gradient: backward appends ``(idx, dX)`` to that list and returns None for the weight — no
+    table-sized zero fill, no scatter; the optimiser consumes the rows (native.adam_rows_)."""
 
     @staticmethod
     def forward(ctx, weight, bias, idx):
@@ -54,6 +58,7 @@ class GatherColumnsFn(torch.autograd.Function):
         ctx.wshape = tuple(weight.shape)
         ctx.has_bias = bias is not None
         ctx.row_major = weight.dim() == 2 and weight.t().is_contiguous() and not weight.is_contiguous()
+        ctx.row_grads = getattr(weight, "_ncf_row_grads", None) if ctx.row_major else None
         if ctx.row_major:
             x = native.gather_concat(weight.t(), idx)
             return x if bias is None else x.add_(bias)
@@ -66,7 +71,9 @@ class GatherColumnsFn(torch.autograd.Function):
         dW = db = None
         if ctx.needs_input_grad[0]:
             E, U = ctx.wshape
-            if ctx.row_major:
+            if ctx.row_grads is not None:
+                ctx.row_grads.append((idx, dX))
+            elif ctx.row_major:
                 dT = torch.zeros((U, E), dtype=torch.float32, device=dX.device)
                 native.scatter_add_rows(dX, idx, dT)
                 dW = dT.t()
@@ -83,11 +90,13 @@ class GatherColumnsConcatFn(torch.autograd.Function):
     activation (``basic_ncf.py:37-40``: both embedding Linears, then the concat).  Against two GatherColumnsFn + torch.cat
     it saves the concat copy forward and, backward, the two column-slice copies and one of the two bias reductions: the
     gradient rows are scattered straight from the column halves of dX (the scatter kernel takes a row stride).  Both
-    weights must be id-major (util.row_major_embedding_); the caller falls back to GatherColumnsFn + cat otherwise."""
+    weights must be id-major (util.row_major_embedding_); the caller falls back to GatherColumnsFn + cat otherwise.  A weight
+    marked with ``_ncf_row_grads`` (see GatherColumnsFn) receives ``(idx, its column half of dX)`` — a view, not a copy."""
 
     @staticmethod
     def forward(ctx, wa, ba, idx_a, wb, bb, idx_b):
         ctx.save_for_backward(idx_a, idx_b)
+        ctx.row_grads = (getattr(wa, "_ncf_row_grads", None), getattr(wb, "_ncf_row_grads", None))
         ctx.shapes = (tuple(wa.shape), tuple(wb.shape))
         ctx.has_bias = (ba is not None, bb is not None)
         x = native.gather_concat(wa.t(), idx_a, wb.t(), idx_b)
@@ -103,14 +112,21 @@ class GatherColumnsConcatFn(torch.autograd.Function):
         (ea, ua), (eb, ub) = ctx.shapes
         dX = dX.contiguous()
         d_wa = d_wb = d_ba = d_bb = None
+        rows_a, rows_b = ctx.row_grads
         if ctx.needs_input_grad[0]:
-            ta = torch.zeros((ua, ea), dtype=torch.float32, device=dX.device)
-            native.scatter_add_rows(dX[:, :ea], idx_a, ta)
-            d_wa = ta.t()
+            if rows_a is not None:
+                rows_a.append((idx_a, dX[:, :ea]))
+            else:
+                ta = torch.zeros((ua, ea), dtype=torch.float32, device=dX.device)
+                native.scatter_add_rows(dX[:, :ea], idx_a, ta)
+                d_wa = ta.t()
         if ctx.needs_input_grad[3]:
-            tb = torch.zeros((ub, eb), dtype=torch.float32, device=dX.device)
-            native.scatter_add_rows(dX[:, ea:], idx_b, tb)
-            d_wb = tb.t()
+            if rows_b is not None:
+                rows_b.append((idx_b, dX[:, ea:]))
+            else:
+                tb = torch.zeros((ub, eb), dtype=torch.float32, device=dX.device)
+                native.scatter_add_rows(dX[:, ea:], idx_b, tb)
+                d_wb = tb.t()
         if (ctx.has_bias[0] and ctx.needs_input_grad[1]) or (ctx.has_bias[1] and ctx.needs_input_grad[4]):
             db = native.colsum(dX)
             d_ba = db[:ea] if ctx.has_bias[0] and ctx.needs_input_grad[1] else None

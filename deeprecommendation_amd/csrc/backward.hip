@@ -2,6 +2,7 @@
 // gradient dW = dY^T . X as a "TN" MFMA GEMM with an ordered split over the batch, bias gradient, ReLU mask).
 // The data gradient dX = dY . W is the forward row-streaming GEMM with the transposed weight.
 #include "ncf_common.h"
+#include "adam_update.h"
 #include <math.h>
 
 namespace ncf {
@@ -178,22 +179,22 @@ __global__ __launch_bounds__(256) void scatter_add_cols_kernel(const float* __re
 // One pass of torch.optim.Adam's update (train.py:55: Adam(lr, weight_decay); amsgrad / maximize off) over one tensor:
 //   g += wd * p;  m += (1 - b1) * (g - m);  v = b2 * v + (1 - b2) * g * g;
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-// — the operation order of torch's own single-tensor path.  7 table passes (read p, g, m, v; write p, m, v) in ONE kernel;
-// torch's default (foreach) path runs ~9 elementwise kernels over the same tensors.
+// — the operation order of torch's own single-tensor path (adam_update, shared with the row-sparse kernel of adam_rows.hip).
+// 7 table passes (read p, g, m, v; write p, m, v) in ONE kernel; torch's default (foreach) path runs ~9 elementwise kernels
+// over the same tensors.
 __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, int64_t n, float lr_over_bc1, float beta1, float beta2,
-                                                        float inv_sqrt_bc2, float eps, float wd) {
+                                                        float* __restrict__ v, int64_t n, AdamCoef k) {
     const int64_t n4 = n / 4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         f32x4 pv = reinterpret_cast<const f32x4*>(p)[i], gv = reinterpret_cast<const f32x4*>(g)[i];
         f32x4 mv = reinterpret_cast<const f32x4*>(m)[i], vv = reinterpret_cast<const f32x4*>(v)[i];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float gg = wd != 0.f ? gv[j] + wd * pv[j] : gv[j];
-            mv[j] = mv[j] + (1.f - beta1) * (gg - mv[j]);
-            vv[j] = beta2 * vv[j] + (1.f - beta2) * gg * gg;
-            const float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
-            pv[j] = pv[j] - lr_over_bc1 * (mv[j] / denom);
+            float pj = pv[j], mj = mv[j], vj = vv[j];
+            adam_update(pj, mj, vj, gv[j], k);
+            pv[j] = pj;
+            mv[j] = mj;
+            vv[j] = vj;
         }
         reinterpret_cast<f32x4*>(p)[i] = pv;
         reinterpret_cast<f32x4*>(m)[i] = mv;
@@ -202,12 +203,11 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
     if (blockIdx.x == 0) {
         const int64_t i = 4 * n4 + threadIdx.x;
         if (i < n) {
-            const float gg = wd != 0.f ? g[i] + wd * p[i] : g[i];
-            const float mm = m[i] + (1.f - beta1) * (gg - m[i]);
-            const float vv = beta2 * v[i] + (1.f - beta2) * gg * gg;
-            m[i] = mm;
-            v[i] = vv;
-            p[i] = p[i] - lr_over_bc1 * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
+            float pj = p[i], mj = m[i], vj = v[i];
+            adam_update(pj, mj, vj, g[i], k);
+            m[i] = mj;
+            v[i] = vj;
+            p[i] = pj;
         }
     }
 }
@@ -327,11 +327,10 @@ extern "C" int ncf_adam_step(float* p, const float* g, float* m, float* v, int64
     if (n == 0) return NCF_OK;
     if (n < 0 || step < 1 || !p || !g || !m || !v) return fail(NCF_EINVAL, "ncf_adam_step: bad argument");
     if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v)) return fail(NCF_EINVAL, "ncf_adam_step: tensors must be 16-byte aligned");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     int64_t blocks = (n / 4 + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(lr / bc1), beta1, beta2,
-                       (float)(1.0 / sqrt(bc2)), eps, weight_decay);
+    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                       adam_coef(lr, beta1, beta2, eps, weight_decay, step));
     return check_launch("ncf_adam_step");
 }

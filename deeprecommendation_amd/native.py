@@ -135,6 +135,8 @@ SIGNATURES = {
                               _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p, _c_p]),
     "ncf_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _c_i64, _c_p]),
+    "ncf_adam_rows": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_i64, ctypes.c_float, ctypes.c_float,
+                               ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_i64, _c_p, _c_p]),
     "ncf_negative_cdf": (_c_int, [_c_p, _c_i64, _c_p, ctypes.c_float, _c_p, _c_p, _c_p]),
     "ncf_sample_negatives": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, ctypes.c_uint32, _c_i64, _c_p, _c_p, _c_p]),
 }
@@ -1249,6 +1251,33 @@ def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
             raise ValueError("adam_step_: contiguous fp32 tensors of one size")
     _check(lib.ncf_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                              float(weight_decay), int(step), _stream(p)))
+
+
+def adam_rows_(p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ids: torch.Tensor, g: torch.Tensor, lr: float, beta1: float,
+               beta2: float, eps: float, weight_decay: float, step: int):
+    """Row-sparse Adam, in place: rows ``ids`` of the id-major ``[rows, E]`` buffers ``p`` / ``m`` / ``v`` (one row stride) take ONE
+    Adam update each, with the sum of their gradient rows ``g[o]`` (``ids[o]`` = the row occurrence ``o`` belongs to; ``g`` may be
+    a column slice of a wider matrix).  Untouched rows are not read or written: weight decay and the moments' decay reach
+    touched rows only.  The ids are ordered by a stable ``torch.sort`` on the current stream; nothing synchronises with the
+    host.  Deterministic (no atomics); an id outside ``[0, rows)`` is skipped and raises at the next ``check_oob``."""
+    lib = load_library()
+    _dev(p, "p"), _dev(g, "g"), _dev(ids, "ids")
+    rows, E, ld = _rows2d(p, "p")
+    for t, what in ((m, "m"), (v, "v")):
+        _dev(t, what)
+        if t.dtype != torch.float32 or t.shape != p.shape or t.stride() != p.stride():
+            raise ValueError(f"adam_rows_: {what} must be fp32 with p's shape and strides")
+    n, Eg, ldg = _rows2d(g, "g")
+    ids = _idx(ids)
+    if p.dtype != torch.float32 or g.dtype != torch.float32 or Eg != E or ids.numel() != n:
+        raise ValueError("adam_rows_: fp32 p and g of one row width, one id per gradient row")
+    if not (p.device == m.device == v.device == g.device == ids.device):
+        raise ValueError("adam_rows_: tensors on different devices")
+    if n == 0:
+        return
+    order, perm = torch.sort(ids, stable=True)
+    _check(lib.ncf_adam_rows(_ptr(p), _ptr(m), _ptr(v), ld, rows, E, _ptr(order), _ptr(perm), n, _ptr(g), ldg, float(lr), float(beta1),
+                             float(beta2), float(eps), float(weight_decay), int(step), _ptr(_oob_flag(p.device)), _stream(p)))
 
 
 # ------------------------------------------------------------------ negative sampling (pair-wise training)

@@ -25,7 +25,15 @@ class MF(_ScoringMixin, NCF):
         if not use_native(self):
             if indexed:
                 ue, ie = self.user_embeddings[0], self.item_embeddings[0]
-                u, i = ue.weight.t()[X_user] + ue.bias, ie.weight.t()[X_item] + ie.bias
+                if (self.training and X_user.is_cuda and getattr(ue.weight, "_ncf_row_grads", None) is not None
+                        and getattr(ie.weight, "_ncf_row_grads", None) is not None):
+                    # both weights marked by optim.RowSparseAdam: the HIP gather, whose backward hands the optimiser
+                    # (ids, gradient rows) instead of building two dense table gradients
+                    from ...autograd import GatherColumnsFn
+                    u = GatherColumnsFn.apply(ue.weight, ue.bias, X_user.contiguous())
+                    i = GatherColumnsFn.apply(ie.weight, ie.bias, X_item.contiguous())
+                else:
+                    u, i = ue.weight.t()[X_user] + ue.bias, ie.weight.t()[X_item] + ie.bias
             else:
                 u, i = self.user_embeddings(X_user), self.item_embeddings(X_item)
             return torch.bmm(u.unsqueeze(1), i.unsqueeze(2)).view(-1, 1)

@@ -561,6 +561,26 @@ int ncf_scatter_add_cols(const float* dev_src, int64_t ld_src, const int64_t* de
 int ncf_adam_step(float* dev_p, const float* dev_g, float* dev_m, float* dev_v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int64_t step, ncf_stream_t stream);
 
+/* Row-sparse Adam (csrc/adam_rows.hip): the update of ncf_adam_step applied ONLY to the rows a batch touched, from the batch's
+ * per-occurrence gradient rows — no table-sized gradient, no float atomics.
+ *   dev_p, dev_m, dev_v  id-major [rows, E] buffers with one row stride ld (the buffers behind an id-major embedding weight and
+ *                        its two moments)
+ *   dev_g                [n, E] gradient rows with stride ld_g: row o is the gradient of occurrence o of the batch (a column
+ *                        half of a wider matrix is passed as it is)
+ *   dev_sorted_ids       the batch's n ids in ascending order; dev_perm[j] = the occurrence (row of dev_g, in [0, n)) that
+ *                        sorted position j came from, NULL = identity
+ * Every run of equal ids has one owner, which adds the run's gradient rows and applies one update to row id of p, m, v with
+ * the bias corrections of the tensor-wide `step` (host double arithmetic, as ncf_adam_step).  Weight decay therefore reaches
+ * touched rows only, and the moments of an untouched row do not decay.  The sum of a run is a fixed function of the sorted
+ * input (runs of up to 64 rows: left to right; longer: 64 interleaved shares, then the shares in order — see the file), so
+ * two calls on equal inputs give equal bits, and a row touched once gets the bits of ncf_adam_step on that gradient row.
+ * 16-byte accesses when E, ld, ld_g are multiples of 4 and every base is 16-byte aligned, single floats otherwise (any
+ * E >= 1).  An id outside [0, rows) is skipped and sets the sticky flag (when non-NULL).  n == 0 launches nothing;
+ * NCF_EINVAL for step < 1, E <= 0, ld < E, ld_g < E, negative sizes or a NULL p / m / v / ids / g with n > 0. */
+int ncf_adam_rows(float* dev_p, float* dev_m, float* dev_v, int64_t ld, int64_t rows, int E, const int64_t* dev_sorted_ids,
+                  const int64_t* dev_perm, int64_t n, const float* dev_g, int64_t ld_g, float lr, float beta1, float beta2, float eps,
+                  float weight_decay, int64_t step, int32_t* dev_oob_flag, ncf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Negative sampling for pair-wise (BPR) training (csrc/negsample.hip).
  * Replaces: RankingDataset.__getitem__'s per-sample draw — DataFrame.iloc, probs = r ** w / sum(r ** w) over the row's
