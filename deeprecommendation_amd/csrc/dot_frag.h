@@ -1,6 +1,8 @@
-// The scoring half of the fused dot-product kernels (dot_topk.hip: ncf_dot_topk; rank.hip: ncf_dot_rank): the wave shape, the
-// MFMA operand loads and the column tiling they share.  What a kernel does with the scores (candidate buffer and threshold, or
-// rank counters) is its own.  See dot_topk.hip for the chain layout that makes a score gather_dot_kernel<false>'s bit for bit.
+// What the fused dot-product entry points share (dot_topk.hip: ncf_dot_topk; rank.hip: ncf_dot_rank).  Device: the wave shape and
+// the MFMA operand loads of the scoring half; what a kernel does with the scores (candidate buffer and threshold, or rank
+// counters) is its own, and so is its copy of the column walk (DESIGN.md 4.22 says why).  Host: the column tiling, the number of
+// MFMA steps and the dispatch over it, and the width / size / operand refusals.  See dot_topk.hip for the chain layout that makes
+// a score gather_dot_kernel<false>'s bit for bit.
 // Internal: not part of the ABI.
 #pragma once
 #include "topk_common.h"
@@ -49,6 +51,36 @@ inline int dot_topk_tile_cols(int64_t rows, int64_t cols) {
     int tile_cols = kTopkTile;
     while (tile_cols > kDtChunk && ublocks * ((cols + tile_cols - 1) / tile_cols) < kDtTargetBlocks) tile_cols >>= 1;
     return tile_cols;
+}
+
+// ---- host side shared by the two entry points; `what` names the entry point in the error string ----
+
+// MFMA steps over a width: the J of the kernel instance
+inline int dot_steps(int D) { return (D + 16 * kDtKS - 1) / (16 * kDtKS); }
+
+// LAUNCH(J) for the instance that covers `steps` (1 .. 4: D <= kDtMaxD)
+#define NCF_DOT_DISPATCH(steps, LAUNCH) \
+    switch (steps) {                    \
+        case 1: LAUNCH(1); break;       \
+        case 2: LAUNCH(2); break;       \
+        case 3: LAUNCH(3); break;       \
+        default: LAUNCH(4); break;      \
+    }
+
+// the width and size refusals, made after the entry point's own limit (k or max_targets)
+inline int dot_check_shape(const char* what, int64_t rows, int64_t cols, int D) {
+    if (D < 1 || D > kDtMaxD) return fail(NCF_EUNSUPPORTED, "%s: width D = %d is outside the fused range 1 .. %d", what, D, kDtMaxD);
+    return topk_check_size(what, rows, cols);
+}
+
+// the operand refusals of a call with rows > 0.  outputs: the caller's output pointers that share the "null argument" refusal are all there
+inline int dot_check_operands(const char* what, const float* tabA, int64_t rowsA, int64_t ldA, const float* tabB, int64_t rowsB, int64_t ldB,
+                              const int64_t* idxA, const int64_t* idxB, int64_t rows, int64_t cols, int D, bool outputs) {
+    if (!tabA || !tabB || !outputs) return fail(NCF_EINVAL, "%s: null argument", what);
+    if (ldA < D || ldB < D) return fail(NCF_EINVAL, "%s: leading dimension smaller than D = %d", what, D);
+    if (!idxA && rows > rowsA) return fail(NCF_EINVAL, "%s: rows = %lld > rowsA without idxA", what, (long long)rows);
+    if (!idxB && cols > rowsB) return fail(NCF_EINVAL, "%s: cols = %lld > rowsB without idxB", what, (long long)cols);
+    return NCF_OK;
 }
 
 }  // namespace ncf

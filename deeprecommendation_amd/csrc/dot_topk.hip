@@ -173,8 +173,7 @@ static TopkMerge dot_topk_plan(int64_t rows, int64_t cols, int tile_cols, int k)
 
 static int dot_topk_check(int64_t rows, int64_t cols, int D, int k, const char* what) {
     if (const int rc = topk_check_k(what, k, kDtMaxK)) return rc;
-    if (D < 1 || D > kDtMaxD) return fail(NCF_EUNSUPPORTED, "%s: width D = %d is outside the fused range 1 .. %d", what, D, kDtMaxD);
-    return topk_check_size(what, rows, cols);
+    return dot_check_shape(what, rows, cols, D);
 }
 
 }  // namespace ncf
@@ -192,10 +191,9 @@ extern "C" int ncf_dot_topk(const float* tabA, int64_t rowsA, int64_t ldA, const
                             size_t workspace_bytes, int32_t* oob, ncf_stream_t stream) {
     if (const int rc = dot_topk_check(rows, cols, D, k, "ncf_dot_topk")) return rc;
     if (rows == 0) return NCF_OK;
-    if (!tabA || !tabB || !out_score || !out_idx || !out_count) return fail(NCF_EINVAL, "ncf_dot_topk: null argument");
-    if (ldA < D || ldB < D) return fail(NCF_EINVAL, "ncf_dot_topk: leading dimension smaller than D = %d", D);
-    if (!idxA && rows > rowsA) return fail(NCF_EINVAL, "ncf_dot_topk: rows = %lld > rowsA without idxA", (long long)rows);
-    if (!idxB && cols > rowsB) return fail(NCF_EINVAL, "ncf_dot_topk: cols = %lld > rowsB without idxB", (long long)cols);
+    if (const int rc = dot_check_operands("ncf_dot_topk", tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, rows, cols, D,
+                                          out_score && out_idx && out_count))
+        return rc;
     const int tile_cols = dot_topk_tile_cols(rows, cols);
     const int tiles0 = (int)((cols + tile_cols - 1) / tile_cols);
     const TopkMerge p = dot_topk_plan(rows, cols, tile_cols, k);
@@ -204,19 +202,13 @@ extern "C" int ncf_dot_topk(const float* tabA, int64_t rowsA, int64_t ldA, const
         return rc;
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* keys = (unsigned long long*)workspace;
-    const int J = (D + 16 * kDtKS - 1) / (16 * kDtKS);
     for (int64_t r0 = 0; r0 < rows; r0 += p.chunk) {
         const int64_t nr = min(p.chunk, rows - r0);
         const unsigned blocks = (unsigned)(((nr + kDtBlockUsers - 1) / kDtBlockUsers) * tiles0);
 #define LAUNCH(J_)                                                                                                                       \
     hipLaunchKernelGGL((dot_topk_kernel<J_>), dim3(blocks), dim3(kDtThreads), 0, s, tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, cols, \
                        D, seen_rowptr, seen_col, r0, nr, tiles0, tile_cols, k, p.kp, keys, p.n1, oob)
-        switch (J) {
-            case 1: LAUNCH(1); break;
-            case 2: LAUNCH(2); break;
-            case 3: LAUNCH(3); break;
-            default: LAUNCH(4); break;
-        }
+        NCF_DOT_DISPATCH(dot_steps(D), LAUNCH)
 #undef LAUNCH
         // merge levels over the fused level's kp keys per tile; the last one sorts and writes (score from the key)
         topk_merge(p, keys, nullptr, 0, r0, nr, k, out_score, out_idx, out_count, s);

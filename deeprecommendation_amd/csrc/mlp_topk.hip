@@ -23,6 +23,9 @@
 // A fused-MLP score is never -0.0: `partial` starts at +0.f, an fmaf onto +0 and an exact cancellation both give +0 in
 // round-to-nearest, so partial is never -0 and partial + bl is -0 only if both are.  The recovered bits are therefore the caller's
 // for every non-NaN score; NaN payloads are not kept (a NaN ranks last and comes back as a NaN).
+// Host side: ncf_mlp_topk and ncf_mlp_rank (the same waves with a counting sink, rank_common.h) share one front end: the operand
+// refusals (mlp_check_operands), the prefix launch with the scoring part of the kernel arguments (mlp_prefix_pass) and the column
+// ranges (mlp_tile_cols).  Each keeps what differs: the merge plan and chunk loop, or the target preparation and the sink's fields.
 #include "mlp_fused.h"
 #include "rank_common.h"
 #include "topk_common.h"
@@ -389,10 +392,13 @@ __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(Args a) {
     }
 }
 
-// The fused level's column ranges: tile_cols shrinks (8192 -> kMtCols) until the grid has kMtTargetWaves waves
-static int mlp_topk_tile_cols(int64_t rows, int64_t cols) {
+// The main kernel's column ranges: tile_cols shrinks (8192 -> floor_cols) until the grid has kMtTargetWaves waves.  Top-K and the
+// one-target rank sink go down to one MFMA tile (kMtCols); a range with target chunks in LDS stays >= kMrChunkCols columns (its
+// staging, suffix sum and flush are paid per range).
+constexpr int kMrChunkCols = 512;
+static int mlp_tile_cols(int64_t rows, int64_t cols, int floor_cols) {
     int tile_cols = kTopkTile;
-    while (tile_cols > kMtCols && rows * ((cols + tile_cols - 1) / tile_cols) < kMtTargetWaves) tile_cols >>= 1;
+    while (tile_cols > floor_cols && rows * ((cols + tile_cols - 1) / tile_cols) < kMtTargetWaves) tile_cols >>= 1;
     return tile_cols;
 }
 
@@ -426,15 +432,6 @@ static bool mr_dispatch(int K0, int N1, int N2, bool one, unsigned blocks, hipSt
     return false;
 }
 
-// the rank kernel's column ranges: as mlp_topk_tile_cols; a range with target chunks in LDS stays >= 512 columns (its staging,
-// suffix sum and flush are paid per range)
-static int mlp_rank_tile_cols(int64_t rows, int64_t cols, int max_targets) {
-    const int floor_cols = max_targets == 1 ? kMtCols : 512;
-    int tile_cols = kTopkTile;
-    while (tile_cols > floor_cols && rows * ((cols + tile_cols - 1) / tile_cols) < kMtTargetWaves) tile_cols >>= 1;
-    return tile_cols;
-}
-
 static bool mt_shape_ok(int dtype, int EA, int EB, int n_layers, const int* dims) {
     if (dtype != NCF_F32 || !dims) return false;
     if (n_layers != 2 && n_layers != 3) return false;
@@ -448,6 +445,54 @@ static int mt_check(int64_t rows, int64_t cols, int k, const char* what) {
     return topk_check_size(what, rows, cols);
 }
 
+// The refusals both entry points make after their own limit check (mt_check / mr_check), in their order; `what` names the entry
+// point.  n_targets: 0 from ncf_mlp_topk; outputs: the caller's output pointers that share the "null argument" refusal are all
+// there.  rows == 0 passes before any pointer is looked at: the caller returns NCF_OK then.
+static int mlp_check_operands(const char* what, int dtype, const void* tabA, int64_t rowsA, int64_t ldA, const void* tabB, int64_t rowsB,
+                              int64_t ldB, int EA, int EB, int user_first, const int64_t* user_ids, const int64_t* item_ids, int64_t rows,
+                              int64_t cols, int n_layers, const int* dims, const void* packed, int64_t n_targets, bool outputs) {
+    if (!mt_shape_ok(dtype, EA, EB, n_layers, dims))
+        return fail(NCF_EUNSUPPORTED, "%s: no fused instance for dtype=%d EA=%d EB=%d layers=%d", what, dtype, EA, EB, n_layers);
+    if (n_targets < 0) return fail(NCF_EINVAL, "%s: n_targets = %lld", what, (long long)n_targets);
+    if (rows == 0) return NCF_OK;
+    if (!tabA || !tabB || !packed || !outputs) return fail(NCF_EINVAL, "%s: null argument", what);
+    if (ldA < EA || ldB < EB || ldA % 4 || ldB % 4 || !aligned16(tabA) || !aligned16(tabB) || !aligned16(packed))
+        return fail(NCF_EINVAL, "%s: tables must be 16-byte aligned with ld %% 4 == 0", what);
+    const int64_t nUrows = user_first ? rowsA : rowsB, nIrows = user_first ? rowsB : rowsA;
+    if (!user_ids && rows > nUrows) return fail(NCF_EINVAL, "%s: rows = %lld > user table rows without user ids", what, (long long)rows);
+    if (!item_ids && cols > nIrows) return fail(NCF_EINVAL, "%s: cols = %lld > item table rows without item ids", what, (long long)cols);
+    return NCF_OK;
+}
+
+// Launches the prefix pass over the first part's rows (the listed users user-first, the ranked items item-first) into `state` and
+// fills the scoring part of the main kernel's arguments.  The column ranges, the rows and the sink's fields are the caller's.
+static void mlp_prefix_pass(MtArgs& a, const void* tabA, int64_t rowsA, int64_t ldA, const void* tabB, int64_t rowsB, int64_t ldB, int EA,
+                            int user_first, const int64_t* user_ids, const int64_t* item_ids, int64_t rows, int64_t cols, int n_layers,
+                            const int* dims, const void* packed, const int64_t* seen_rowptr, const int32_t* seen_col, float* state,
+                            int32_t* oob, hipStream_t s) {
+    const int K0 = dims[0], N1 = dims[1], N2 = n_layers == 3 ? dims[2] : 0;
+    const BlobLayout L = blob_layout(dims, n_layers);
+    const float* P = (const float*)packed;
+    const int64_t npre = user_first ? rows : cols;
+    const unsigned pblocks = (unsigned)(((npre + 31) / 32 + 3) / 4);
+#define X(k0, n1, n2) \
+    if (K0 == k0 && N1 == n1 && N2 == n2) \
+        hipLaunchKernelGGL((mlp_prefix_kernel<k0, n1>), dim3(pblocks), dim3(256), 0, s, (const float*)tabA, rowsA, ldA, \
+                           user_first ? user_ids : item_ids, npre, EA, P + L.wp1, P + L.b1, state, oob);
+    NCF_FUSED_INSTANCES(X)
+#undef X
+    a.tabB = (const float*)tabB; a.rowsB = rowsB; a.ldB = ldB;
+    a.idxU = user_ids; a.idxI = item_ids;
+    a.user_first = user_first ? 1 : 0;
+    a.cols = cols; a.EA = EA;
+    a.state = state;
+    a.Wp1 = P + L.wp1;
+    a.Wp2 = n_layers == 3 ? P + L.wp2 : nullptr; a.b2 = n_layers == 3 ? P + L.b2 : nullptr;
+    a.wl = P + L.wl; a.bl = P + L.bl;
+    a.seen_rowptr = seen_rowptr; a.seen_col = seen_col;
+    a.oob = oob;
+}
+
 }  // namespace ncf
 
 using namespace ncf;
@@ -459,7 +504,7 @@ extern "C" int ncf_mlp_topk_supported(int dtype, int EA, int EB, int n_layers, c
 extern "C" size_t ncf_mlp_topk_workspace_bytes(int64_t rows, int64_t cols, int user_first, int n_layers, const int* dims, int k) {
     if (mt_check(rows, cols, k, "ncf_mlp_topk_workspace_bytes") != NCF_OK || rows == 0) return 0;
     if (!dims || (n_layers != 2 && n_layers != 3) || dims[1] < 32 || dims[1] % 32) return 0;
-    return mlp_state_bytes(rows, cols, dims[1], user_first) + topk_merge_bytes(mlp_topk_plan(rows, cols, mlp_topk_tile_cols(rows, cols), k));
+    return mlp_state_bytes(rows, cols, dims[1], user_first) + topk_merge_bytes(mlp_topk_plan(rows, cols, mlp_tile_cols(rows, cols, kMtCols), k));
 }
 
 extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t ldA, const void* tabB, int64_t rowsB, int64_t ldB,
@@ -467,54 +512,25 @@ extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t 
                             int64_t cols, int n_layers, const int* dims, const void* packed, const int64_t* seen_rowptr,
                             const int32_t* seen_col, int k, float* out_score, int32_t* out_idx, int32_t* out_count, void* workspace,
                             size_t workspace_bytes, int32_t* oob, ncf_stream_t stream) {
-    const int rc = mt_check(rows, cols, k, "ncf_mlp_topk");
-    if (rc != NCF_OK) return rc;
-    if (!mt_shape_ok(dtype, EA, EB, n_layers, dims))
-        return fail(NCF_EUNSUPPORTED, "ncf_mlp_topk: no fused instance for dtype=%d EA=%d EB=%d layers=%d", dtype, EA, EB, n_layers);
+    if (const int rc = mt_check(rows, cols, k, "ncf_mlp_topk")) return rc;
+    if (const int rc = mlp_check_operands("ncf_mlp_topk", dtype, tabA, rowsA, ldA, tabB, rowsB, ldB, EA, EB, user_first, user_ids, item_ids,
+                                          rows, cols, n_layers, dims, packed, 0, out_score && out_idx && out_count))
+        return rc;
     if (rows == 0) return NCF_OK;
-    if (!tabA || !tabB || !packed || !out_score || !out_idx || !out_count) return fail(NCF_EINVAL, "ncf_mlp_topk: null argument");
-    if (ldA < EA || ldB < EB || ldA % 4 || ldB % 4 || !aligned16(tabA) || !aligned16(tabB) || !aligned16(packed))
-        return fail(NCF_EINVAL, "ncf_mlp_topk: tables must be 16-byte aligned with ld %% 4 == 0");
-    user_first = user_first ? 1 : 0;
-    const int64_t nUrows = user_first ? rowsA : rowsB, nIrows = user_first ? rowsB : rowsA;
-    if (!user_ids && rows > nUrows) return fail(NCF_EINVAL, "ncf_mlp_topk: rows = %lld > user table rows without user ids", (long long)rows);
-    if (!item_ids && cols > nIrows) return fail(NCF_EINVAL, "ncf_mlp_topk: cols = %lld > item table rows without item ids", (long long)cols);
     const int K0 = dims[0], N1 = dims[1], N2 = n_layers == 3 ? dims[2] : 0;
-    const int tile_cols = mlp_topk_tile_cols(rows, cols);
+    const int tile_cols = mlp_tile_cols(rows, cols, kMtCols);
     const TopkMerge p = mlp_topk_plan(rows, cols, tile_cols, k);
     const size_t state_bytes = mlp_state_bytes(rows, cols, N1, user_first);
     if (const int rc = topk_check_buffers("ncf_mlp_topk", "ncf_mlp_topk_workspace_bytes", seen_rowptr, seen_col, workspace, workspace_bytes,
                                           state_bytes + topk_merge_bytes(p)))
         return rc;
     hipStream_t s = (hipStream_t)stream;
-    const BlobLayout L = blob_layout(dims, n_layers);
-    const float* P = (const float*)packed;
-    float* state = (float*)workspace;
     unsigned long long* keys = (unsigned long long*)((char*)workspace + state_bytes);
-
-    // prefix pass over the first part's rows: the listed users (user-first) or the ranked items (item-first)
-    const int64_t npre = user_first ? rows : cols;
-    const unsigned pblocks = (unsigned)(((npre + 31) / 32 + 3) / 4);
-#define X(k0, n1, n2) \
-    if (K0 == k0 && N1 == n1 && N2 == n2) \
-        hipLaunchKernelGGL((mlp_prefix_kernel<k0, n1>), dim3(pblocks), dim3(256), 0, s, (const float*)tabA, rowsA, ldA, \
-                           user_first ? user_ids : item_ids, npre, EA, P + L.wp1, P + L.b1, state, oob);
-    NCF_FUSED_INSTANCES(X)
-#undef X
-
     MtArgs a{};
-    a.tabB = (const float*)tabB; a.rowsB = rowsB; a.ldB = ldB;
-    a.idxU = user_ids; a.idxI = item_ids;
-    a.user_first = user_first;
-    a.cols = cols; a.EA = EA;
-    a.state = state;
-    a.Wp1 = P + L.wp1;
-    a.Wp2 = n_layers == 3 ? P + L.wp2 : nullptr; a.b2 = n_layers == 3 ? P + L.b2 : nullptr;
-    a.wl = P + L.wl; a.bl = P + L.bl;
-    a.seen_rowptr = seen_rowptr; a.seen_col = seen_col;
+    mlp_prefix_pass(a, tabA, rowsA, ldA, tabB, rowsB, ldB, EA, user_first, user_ids, item_ids, rows, cols, n_layers, dims, packed,
+                    seen_rowptr, seen_col, (float*)workspace, oob, s);
     a.tiles = (int)((cols + tile_cols - 1) / tile_cols); a.tile_cols = tile_cols; a.k = k; a.kp = p.kp;
     a.out_keys = keys; a.n_out = p.n1;
-    a.oob = oob;
     for (int64_t r0 = 0; r0 < rows; r0 += p.chunk) {
         const int64_t nr = min(p.chunk, rows - r0);
         a.row0 = r0; a.nrows = nr;
@@ -549,26 +565,16 @@ extern "C" int ncf_mlp_rank(int dtype, const void* tabA, int64_t rowsA, int64_t 
                             int32_t* rank, int32_t* ranked, void* workspace, size_t workspace_bytes, int32_t* oob, int32_t* overflow,
                             ncf_stream_t stream) {
     if (const int rc = mr_check(rows, cols, max_targets, "ncf_mlp_rank")) return rc;
-    if (!mt_shape_ok(dtype, EA, EB, n_layers, dims))
-        return fail(NCF_EUNSUPPORTED, "ncf_mlp_rank: no fused instance for dtype=%d EA=%d EB=%d layers=%d", dtype, EA, EB, n_layers);
-    if (n_targets < 0) return fail(NCF_EINVAL, "ncf_mlp_rank: n_targets = %lld", (long long)n_targets);
+    if (const int rc = mlp_check_operands("ncf_mlp_rank", dtype, tabA, rowsA, ldA, tabB, rowsB, ldB, EA, EB, user_first, user_ids, item_ids,
+                                          rows, cols, n_layers, dims, packed, n_targets, true))
+        return rc;
     if (rows == 0) return NCF_OK;
-    if (!tabA || !tabB || !packed) return fail(NCF_EINVAL, "ncf_mlp_rank: null argument");
-    if (ldA < EA || ldB < EB || ldA % 4 || ldB % 4 || !aligned16(tabA) || !aligned16(tabB) || !aligned16(packed))
-        return fail(NCF_EINVAL, "ncf_mlp_rank: tables must be 16-byte aligned with ld %% 4 == 0");
-    user_first = user_first ? 1 : 0;
-    const int64_t nUrows = user_first ? rowsA : rowsB, nIrows = user_first ? rowsB : rowsA;
-    if (!user_ids && rows > nUrows) return fail(NCF_EINVAL, "ncf_mlp_rank: rows = %lld > user table rows without user ids", (long long)rows);
-    if (!item_ids && cols > nIrows) return fail(NCF_EINVAL, "ncf_mlp_rank: cols = %lld > item table rows without item ids", (long long)cols);
     const int K0 = dims[0], N1 = dims[1], N2 = n_layers == 3 ? dims[2] : 0;
     const size_t state_bytes = mlp_state_bytes(rows, cols, N1, user_first);     // N1 % 32 == 0: a multiple of 16 bytes
     if (const int rc = rank_check_args("ncf_mlp_rank", "ncf_mlp_rank_workspace_bytes", rows, seen_rowptr, seen_col, tgt_rowptr, tgt_col,
                                        n_targets, rank, ranked, workspace, workspace_bytes, state_bytes + rank_ws_bytes(n_targets, true)))
         return rc;
     hipStream_t s = (hipStream_t)stream;
-    const BlobLayout L = blob_layout(dims, n_layers);
-    const float* P = (const float*)packed;
-    float* state = (float*)workspace;
     const RankWs w = rank_ws_carve((char*)workspace + state_bytes, n_targets, true);
 
     // the targets' own scores from the pair scorer, then their keys in order
@@ -581,30 +587,12 @@ extern "C" int ncf_mlp_rank(int dtype, const void* tabA, int64_t rowsA, int64_t 
     }
     rank_prepare(nullptr, 0, w.pair_score, rows, cols, seen_rowptr, seen_col, tgt_rowptr, tgt_col, max_targets, true, w, rank, overflow, s);
 
-    // prefix pass over the first part's rows, as in ncf_mlp_topk
-    const int64_t npre = user_first ? rows : cols;
-    const unsigned pblocks = (unsigned)(((npre + 31) / 32 + 3) / 4);
-#define X(k0, n1, n2) \
-    if (K0 == k0 && N1 == n1 && N2 == n2) \
-        hipLaunchKernelGGL((mlp_prefix_kernel<k0, n1>), dim3(pblocks), dim3(256), 0, s, (const float*)tabA, rowsA, ldA, \
-                           user_first ? user_ids : item_ids, npre, EA, P + L.wp1, P + L.b1, state, oob);
-    NCF_FUSED_INSTANCES(X)
-#undef X
-
-    const int tile_cols = mlp_rank_tile_cols(rows, cols, max_targets);
+    const int tile_cols = mlp_tile_cols(rows, cols, max_targets == 1 ? kMtCols : kMrChunkCols);
     MrArgs a{};
-    a.tabB = (const float*)tabB; a.rowsB = rowsB; a.ldB = ldB;
-    a.idxU = user_ids; a.idxI = item_ids;
-    a.user_first = user_first;
-    a.cols = cols; a.EA = EA;
-    a.state = state;
-    a.Wp1 = P + L.wp1;
-    a.Wp2 = n_layers == 3 ? P + L.wp2 : nullptr; a.b2 = n_layers == 3 ? P + L.b2 : nullptr;
-    a.wl = P + L.wl; a.bl = P + L.bl;
-    a.seen_rowptr = seen_rowptr; a.seen_col = seen_col;
+    mlp_prefix_pass(a, tabA, rowsA, ldA, tabB, rowsB, ldB, EA, user_first, user_ids, item_ids, rows, cols, n_layers, dims, packed,
+                    seen_rowptr, seen_col, (float*)workspace, oob, s);
     a.row0 = 0; a.nrows = rows;
     a.tiles = (int)((cols + tile_cols - 1) / tile_cols); a.tile_cols = tile_cols;
-    a.oob = oob;
     a.tgt_rowptr = tgt_rowptr; a.skey = w.skey; a.sperm = w.sperm;
     a.max_targets = max_targets; a.P = rank_slots(max_targets);
     a.rank = rank; a.ranked = ranked;

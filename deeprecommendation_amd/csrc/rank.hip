@@ -423,8 +423,7 @@ void rank_prepare(const float* scores, int64_t ld, const float* pair_score, int6
 
 static int dot_rank_check(int64_t rows, int64_t cols, int D, int max_targets, const char* what) {
     if (const int rc = rank_check_max_targets(what, max_targets)) return rc;
-    if (D < 1 || D > kDtMaxD) return fail(NCF_EUNSUPPORTED, "%s: width D = %d is outside the fused range 1 .. %d", what, D, kDtMaxD);
-    return topk_check_size(what, rows, cols);
+    return dot_check_shape(what, rows, cols, D);
 }
 
 }  // namespace ncf
@@ -472,10 +471,7 @@ extern "C" int ncf_dot_rank(const float* tabA, int64_t rowsA, int64_t ldA, const
     if (const int rc = dot_rank_check(rows, cols, D, max_targets, "ncf_dot_rank")) return rc;
     if (n_targets < 0) return fail(NCF_EINVAL, "ncf_dot_rank: n_targets = %lld", (long long)n_targets);
     if (rows == 0) return NCF_OK;
-    if (!tabA || !tabB) return fail(NCF_EINVAL, "ncf_dot_rank: null argument");
-    if (ldA < D || ldB < D) return fail(NCF_EINVAL, "ncf_dot_rank: leading dimension smaller than D = %d", D);
-    if (!idxA && rows > rowsA) return fail(NCF_EINVAL, "ncf_dot_rank: rows = %lld > rowsA without idxA", (long long)rows);
-    if (!idxB && cols > rowsB) return fail(NCF_EINVAL, "ncf_dot_rank: cols = %lld > rowsB without idxB", (long long)cols);
+    if (const int rc = dot_check_operands("ncf_dot_rank", tabA, rowsA, ldA, tabB, rowsB, ldB, idxA, idxB, rows, cols, D, true)) return rc;
     if (const int rc = rank_check_args("ncf_dot_rank", "ncf_dot_rank_workspace_bytes", rows, seen_rowptr, seen_col, tgt_rowptr, tgt_col,
                                        n_targets, rank, ranked, workspace, workspace_bytes, rank_ws_bytes(n_targets, true)))
         return rc;
@@ -498,7 +494,6 @@ extern "C" int ncf_dot_rank(const float* tabA, int64_t rowsA, int64_t ldA, const
     const int P = rank_slots(max_targets);
     const int wave_bytes = (int)dot_rank_wave_bytes(seen_rowptr != nullptr, max_targets);
     const size_t lds = (size_t)wave_bytes * kDtWaves;
-    const int J = (D + 16 * kDtKS - 1) / (16 * kDtKS);
 #define LAUNCH(J_, ONE_)                                                                                                                   \
     do {                                                                                                                                   \
         if (lds > 65536)                                                                                                                   \
@@ -507,14 +502,8 @@ extern "C" int ncf_dot_rank(const float* tabA, int64_t rowsA, int64_t ldA, const
                            idxB, cols, D, seen_rowptr, seen_col, tgt_rowptr, w.skey, w.sperm, rows, tiles, tile_cols, max_targets, P,      \
                            wave_bytes, rank, ranked, oob);                                                                                 \
     } while (0)
-#define LAUNCH_J(ONE_)              \
-    switch (J) {                    \
-        case 1: LAUNCH(1, ONE_); break; \
-        case 2: LAUNCH(2, ONE_); break; \
-        case 3: LAUNCH(3, ONE_); break; \
-        default: LAUNCH(4, ONE_); break; \
-    }
-    if (one) { LAUNCH_J(true) } else { LAUNCH_J(false) }
+#define LAUNCH_J(J_) do { if (one) LAUNCH(J_, true); else LAUNCH(J_, false); } while (0)
+    NCF_DOT_DISPATCH(dot_steps(D), LAUNCH_J)
 #undef LAUNCH_J
 #undef LAUNCH
     return check_launch("ncf_dot_rank");

@@ -11,6 +11,9 @@
 // slot j is the suffix sum hist[j+1] + ... + hist[P].  Each (row, tile) adds its counts into rank / ranked with int32 atomics:
 // integer sums, so the result does not depend on the order the tiles finish in.  A row with one target keeps the key in a
 // register and a private counter instead (the leave-one-out form).
+// Here: the key, the LDS chunk helpers of the counting kernels, and the host steps of every rank call (workspace, target refusals,
+// expand, prepare).  What a fused rank call shares with its top-K sibling (operand refusals, tiling, dispatch) lives with the
+// scorer: dot_frag.h for the dot pair, mlp_topk.hip for the MLP pair.
 // Internal: not part of the ABI.
 #pragma once
 #include "topk_common.h"

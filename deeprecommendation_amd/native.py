@@ -1343,7 +1343,7 @@ def topk_rows(scores: torch.Tensor, k: int, seen: Optional[tuple] = None):
         raise TypeError("topk_rows takes fp32 scores")
     R, C, ld = _rows2d(scores, "scores")
     k = int(k)
-    rowptr, col = _seen_csr(seen, R, scores.device)
+    rowptr, col = _csr_pair(seen, R, scores.device, "seen")
     nbytes = lib.ncf_topk_workspace_bytes(R, C, k)
     out_score, out_idx, out_count, ws = _topk_outputs(R, k, nbytes, scores.device)
     _check(lib.ncf_topk_rows(_ptr(scores), R, C, ld, _ptr(rowptr), _ptr(col), k, _ptr(out_score), _ptr(out_idx), _ptr(out_count),
@@ -1365,20 +1365,59 @@ def _topk_outputs(R, k, nbytes, dev):
     return out_score, out_idx, out_count, ws
 
 
-def _seen_csr(seen, R, dev):
-    if seen is None:
+def _csr_pair(pair, R, dev, what, required=False):
+    """The CSR ``pair`` = (rowptr (R + 1) int64, col int32) of a ranking call as the kernels take it; ``what``: "seen" (None allowed:
+    nothing to skip) or "targets" (required)."""
+    if pair is None:
+        if required:
+            raise ValueError(f"{what} = (rowptr int64 (R + 1), col int32) is required")
         return None, None
-    rowptr, col = seen
-    _dev(rowptr, "seen rowptr")
-    _dev(col, "seen col")
+    rowptr, col = pair
+    if not (rowptr.is_cuda and col.is_cuda):          # the messages are formatted only when one is raised
+        _dev(rowptr, f"{what} rowptr"), _dev(col, f"{what} col")
     if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.dim() != 1 or col.dim() != 1:
-        raise ValueError("seen = (rowptr int64 (R + 1), col int32)")
+        raise ValueError(f"{what} = (rowptr int64 (R + 1), col int32)")
     if rowptr.numel() != R + 1:
-        raise ValueError(f"seen rowptr has {rowptr.numel()} entries, {R + 1} expected")
+        raise ValueError(f"{what} rowptr has {rowptr.numel()} entries, {R + 1} expected")
     rowptr, col = rowptr.contiguous(), col.contiguous()
-    if col.numel() == 0:                      # a valid CSR with no entries: nothing to skip
+    if col.numel() == 0 and not required:     # a valid exclusion CSR with no entries: nothing to skip (targets: _rank_outputs)
         col = torch.empty(1, dtype=torch.int32, device=dev)
     return rowptr, col
+
+
+def _dot_operands(fn, tabA, idxA, tabB, idxB):
+    """The operands dot_topk and dot_rank share, checked for the public function ``fn``: (the ABI arguments up to D, (B, I, D, dev))."""
+    _dev(tabA, "tabA"), _dev(tabB, "tabB")
+    if tabA.dtype != torch.float32 or tabB.dtype != torch.float32:
+        raise TypeError(f"{fn} takes fp32 tables")
+    rowsA, D, ldA = _rows2d(tabA, "tabA")
+    rowsB, DB, ldB = _rows2d(tabB, "tabB")
+    if D != DB:
+        raise ValueError(f"{fn} needs equal widths")
+    idxA, idxB = _idx(idxA), _idx(idxB)
+    B = idxA.numel() if idxA is not None else rowsA
+    I = idxB.numel() if idxB is not None else rowsB
+    return (_ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, I, D), (B, I, D, tabA.device)
+
+
+def _mlp_operands(fn, tabA, idxA, tabB, idxB, packed, user_first):
+    """The operands mlp_topk and mlp_rank share, checked for the public function ``fn``: (the ABI arguments up to the packed blob,
+    (B, I, dims array, dev)).  user_first=False: the users are tabB's rows and idxB."""
+    _dev(tabA, "tabA"), _dev(tabB, "tabB")
+    rowsA, EA, ldA = _rows2d(tabA, "tabA")
+    rowsB, EB, ldB = _rows2d(tabB, "tabB")
+    if tabA.dtype != tabB.dtype:
+        raise TypeError(f"{fn}: both tables must have one dtype")
+    if tabA.dtype != packed.dtype:
+        raise TypeError(f"tables are {tabA.dtype} but the MLP was packed for {packed.dtype}")
+    idxA, idxB = _idx(idxA), _idx(idxB)
+    nA = idxA.numel() if idxA is not None else rowsA
+    nB = idxB.numel() if idxB is not None else rowsB
+    user_ids, item_ids, B, I = (idxA, idxB, nA, nB) if user_first else (idxB, idxA, nB, nA)
+    d = _dims_array(packed.dims)
+    args = (packed.dt, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, EA, EB, 1 if user_first else 0, _ptr(user_ids), _ptr(item_ids), B, I,
+            packed.n_layers, d, _ptr(packed.blob))
+    return args, (B, I, d, tabA.device)
 
 
 def dot_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], k: int,
@@ -1389,23 +1428,13 @@ def dot_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     int32) like topk_rows.  fp32 tables only; k <= DOT_TOPK_MAX_K and width <= DOT_TOPK_MAX_D, else NativeError with code
     NCF_EUNSUPPORTED and nothing launched.  Outputs and workspace from the caching allocator on the current stream; no sync."""
     lib = load_library()
-    _dev(tabA, "tabA"), _dev(tabB, "tabB")
-    if tabA.dtype != torch.float32 or tabB.dtype != torch.float32:
-        raise TypeError("dot_topk takes fp32 tables")
-    rowsA, D, ldA = _rows2d(tabA, "tabA")
-    rowsB, DB, ldB = _rows2d(tabB, "tabB")
-    if D != DB:
-        raise ValueError("dot_topk needs equal widths")
-    idxA, idxB = _idx(idxA), _idx(idxB)
-    B = idxA.numel() if idxA is not None else rowsA
-    I = idxB.numel() if idxB is not None else rowsB
+    args, (B, I, D, dev) = _dot_operands("dot_topk", tabA, idxA, tabB, idxB)
     k = int(k)
-    dev = tabA.device
-    rowptr, col = _seen_csr(seen, B, dev)
+    rowptr, col = _csr_pair(seen, B, dev, "seen")
     nbytes = lib.ncf_dot_topk_workspace_bytes(B, I, D, k)
     out_score, out_idx, out_count, ws = _topk_outputs(B, k, nbytes, dev)
-    _check(lib.ncf_dot_topk(_ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, I, D, _ptr(rowptr), _ptr(col),
-                            k, _ptr(out_score), _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
+    _check(lib.ncf_dot_topk(*args, _ptr(rowptr), _ptr(col), k, _ptr(out_score), _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes,
+                            _ptr(_oob_flag(dev)), _stream(tabA)))
     return out_score, out_idx, out_count
 
 
@@ -1427,26 +1456,13 @@ def mlp_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     NativeError with code NCF_EUNSUPPORTED and launch nothing.  Outputs and workspace from the caching allocator on the current
     stream; no sync."""
     lib = load_library()
-    _dev(tabA, "tabA"), _dev(tabB, "tabB")
-    rowsA, EA, ldA = _rows2d(tabA, "tabA")
-    rowsB, EB, ldB = _rows2d(tabB, "tabB")
-    if tabA.dtype != tabB.dtype:
-        raise TypeError("mlp_topk: both tables must have one dtype")
-    if tabA.dtype != packed.dtype:
-        raise TypeError(f"tables are {tabA.dtype} but the MLP was packed for {packed.dtype}")
-    idxA, idxB = _idx(idxA), _idx(idxB)
-    nA = idxA.numel() if idxA is not None else rowsA
-    nB = idxB.numel() if idxB is not None else rowsB
-    user_ids, item_ids, B, I = (idxA, idxB, nA, nB) if user_first else (idxB, idxA, nB, nA)
+    args, (B, I, d, dev) = _mlp_operands("mlp_topk", tabA, idxA, tabB, idxB, packed, user_first)
     k = int(k)
-    dev = tabA.device
-    rowptr, col = _seen_csr(seen, B, dev)
-    d = _dims_array(packed.dims)
+    rowptr, col = _csr_pair(seen, B, dev, "seen")
     nbytes = lib.ncf_mlp_topk_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, k)
     out_score, out_idx, out_count, ws = _topk_outputs(B, k, nbytes, dev)
-    _check(lib.ncf_mlp_topk(packed.dt, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, EA, EB, 1 if user_first else 0, _ptr(user_ids),
-                            _ptr(item_ids), B, I, packed.n_layers, d, _ptr(packed.blob), _ptr(rowptr), _ptr(col), k, _ptr(out_score),
-                            _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
+    _check(lib.ncf_mlp_topk(*args, _ptr(rowptr), _ptr(col), k, _ptr(out_score), _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes,
+                            _ptr(_oob_flag(dev)), _stream(tabA)))
     return out_score, out_idx, out_count
 
 
@@ -1471,19 +1487,6 @@ def check_rank_overflow(device):
     if int(f.item()) != 0:
         f.zero_()
         raise OverflowError("a row has more targets than the max_targets the rank call was given")
-
-
-def _target_csr(targets, R, dev):
-    if targets is None:
-        raise ValueError("targets = (rowptr int64 (R + 1), col int32) is required")
-    rowptr, col = targets
-    _dev(rowptr, "targets rowptr")
-    _dev(col, "targets col")
-    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.dim() != 1 or col.dim() != 1:
-        raise ValueError("targets = (rowptr int64 (R + 1), col int32)")
-    if rowptr.numel() != R + 1:
-        raise ValueError(f"targets rowptr has {rowptr.numel()} entries, {R + 1} expected")
-    return rowptr.contiguous(), col.contiguous()
 
 
 def _rank_outputs(R, col, nbytes, dev, rank):
@@ -1517,8 +1520,8 @@ def rank_rows(scores: torch.Tensor, targets: tuple, seen: Optional[tuple] = None
         raise TypeError("rank_rows takes fp32 scores")
     R, C, ld = _rows2d(scores, "scores")
     dev = scores.device
-    rowptr, col = _seen_csr(seen, R, dev)
-    trow, tcol = _target_csr(targets, R, dev)
+    rowptr, col = _csr_pair(seen, R, dev, "seen")
+    trow, tcol = _csr_pair(targets, R, dev, "targets", required=True)
     n = tcol.numel()
     nbytes = lib.ncf_rank_rows_workspace_bytes(R, C, n)
     rank, ranked, ws, tcol, rank_arg = _rank_outputs(R, tcol, nbytes, dev, rank)
@@ -1535,25 +1538,14 @@ def dot_rank(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     max_targets ranked (the others -1) and sets the sticky flag check_rank_overflow() reads.  fp32 tables, width <= DOT_RANK_MAX_D,
     else NativeError (NCF_EUNSUPPORTED) and nothing launched.  No sync."""
     lib = load_library()
-    _dev(tabA, "tabA"), _dev(tabB, "tabB")
-    if tabA.dtype != torch.float32 or tabB.dtype != torch.float32:
-        raise TypeError("dot_rank takes fp32 tables")
-    rowsA, D, ldA = _rows2d(tabA, "tabA")
-    rowsB, DB, ldB = _rows2d(tabB, "tabB")
-    if D != DB:
-        raise ValueError("dot_rank needs equal widths")
-    idxA, idxB = _idx(idxA), _idx(idxB)
-    B = idxA.numel() if idxA is not None else rowsA
-    I = idxB.numel() if idxB is not None else rowsB
-    dev = tabA.device
-    rowptr, col = _seen_csr(seen, B, dev)
-    trow, tcol = _target_csr(targets, B, dev)
+    args, (B, I, D, dev) = _dot_operands("dot_rank", tabA, idxA, tabB, idxB)
+    rowptr, col = _csr_pair(seen, B, dev, "seen")
+    trow, tcol = _csr_pair(targets, B, dev, "targets", required=True)
     n, max_targets = tcol.numel(), int(max_targets)
     nbytes = lib.ncf_dot_rank_workspace_bytes(B, I, D, n, max_targets)
     rank, ranked, ws, tcol, rank_arg = _rank_outputs(B, tcol, nbytes, dev, rank)
-    _check(lib.ncf_dot_rank(_ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, I, D, _ptr(rowptr), _ptr(col),
-                            _ptr(trow), _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws), nbytes, _ptr(_oob_flag(dev)),
-                            _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
+    _check(lib.ncf_dot_rank(*args, _ptr(rowptr), _ptr(col), _ptr(trow), _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws),
+                            nbytes, _ptr(_oob_flag(dev)), _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
     return rank, ranked
 
 
@@ -1569,26 +1561,12 @@ def mlp_rank(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     (arguments as mlp_topk), without the pair id columns or the score matrix.  max_targets and the overflow flag as dot_rank.  A
     shape without a fused instance or a bf16 blob raise NativeError (NCF_EUNSUPPORTED) and launch nothing.  No sync."""
     lib = load_library()
-    _dev(tabA, "tabA"), _dev(tabB, "tabB")
-    rowsA, EA, ldA = _rows2d(tabA, "tabA")
-    rowsB, EB, ldB = _rows2d(tabB, "tabB")
-    if tabA.dtype != tabB.dtype:
-        raise TypeError("mlp_rank: both tables must have one dtype")
-    if tabA.dtype != packed.dtype:
-        raise TypeError(f"tables are {tabA.dtype} but the MLP was packed for {packed.dtype}")
-    idxA, idxB = _idx(idxA), _idx(idxB)
-    nA = idxA.numel() if idxA is not None else rowsA
-    nB = idxB.numel() if idxB is not None else rowsB
-    user_ids, item_ids, B, I = (idxA, idxB, nA, nB) if user_first else (idxB, idxA, nB, nA)
-    dev = tabA.device
-    rowptr, col = _seen_csr(seen, B, dev)
-    trow, tcol = _target_csr(targets, B, dev)
+    args, (B, I, d, dev) = _mlp_operands("mlp_rank", tabA, idxA, tabB, idxB, packed, user_first)
+    rowptr, col = _csr_pair(seen, B, dev, "seen")
+    trow, tcol = _csr_pair(targets, B, dev, "targets", required=True)
     n, max_targets = tcol.numel(), int(max_targets)
-    d = _dims_array(packed.dims)
     nbytes = lib.ncf_mlp_rank_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, n, max_targets)
     rank, ranked, ws, tcol, rank_arg = _rank_outputs(B, tcol, nbytes, dev, rank)
-    _check(lib.ncf_mlp_rank(packed.dt, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, EA, EB, 1 if user_first else 0, _ptr(user_ids),
-                            _ptr(item_ids), B, I, packed.n_layers, d, _ptr(packed.blob), _ptr(rowptr), _ptr(col), _ptr(trow),
-                            _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws), nbytes, _ptr(_oob_flag(dev)),
-                            _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
+    _check(lib.ncf_mlp_rank(*args, _ptr(rowptr), _ptr(col), _ptr(trow), _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws),
+                            nbytes, _ptr(_oob_flag(dev)), _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
     return rank, ranked

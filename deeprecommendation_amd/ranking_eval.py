@@ -22,16 +22,7 @@ import numpy as np
 import torch
 
 from . import native
-from .neural_collaborative_filtering.util import require_gpu
-from .recommend import (BLOCK_BYTES, _PAIR_BYTES, _dot_readout, _eval_only, _fused_tables, _graph_model)
-
-
-def _csr(pair, B, what):
-    rowptr, col = pair
-    require_gpu(rowptr, col)
-    if rowptr.dim() != 1 or col.dim() != 1 or rowptr.numel() != B + 1:
-        raise ValueError(f"{what} = (rowptr ({B + 1},) int64, col int32): rowptr has {rowptr.numel()} entries")
-    return rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous()
+from .recommend import BLOCK_BYTES, _csr, _dot_readout, _fused_tables, _mlp_operands, _resolve_ranked, _score_blocks
 
 
 def _take_rows(rowptr, col, rows):
@@ -45,47 +36,34 @@ def _take_rows(rowptr, col, rows):
     return new, col[entry], entry
 
 
-def _fused_ranks(model, graph, users, all_items, items, n_items, seen, targets, max_targets):
-    """The fused route over the model's tables, or None where a fused kernel's limits do not hold (the caller then scores and ranks,
-    which gives the same integers)."""
+def _fused_ranks(model, r, users, seen, targets, max_targets):
+    """The fused route over the model's tables for ``users`` (all of the ranked list's, or a row subset with its own ``seen``), or
+    None where a fused kernel's limits do not hold (the caller then scores and ranks, which gives the same integers)."""
     if getattr(model, "scoring_dtype", torch.float32) != torch.float32:
         return None
     with torch.no_grad():
-        cache = model._refresh()
         if _dot_readout(model):
-            user_tab, item_tab, ids = _fused_tables(model, graph, cache, all_items, items, n_items)
+            user_tab, item_tab, ids = _fused_tables(model, r, model._refresh())
             if user_tab.shape[1] > native.DOT_RANK_MAX_D:
                 return None
             return native.dot_rank(user_tab, users, item_tab, ids, targets, max_targets, seen)
-        if model.fold_first_layer:
+        ops = _mlp_operands(model, r, users)
+        if ops is None:
             return None
-        packed = model._packed_mlp("MLP", cache)
-        if packed is None:
-            return None
-        user_tab, item_tab, ids = _fused_tables(model, graph, cache, all_items, items, n_items)
-        user_first = graph is None          # GraphNCF's MLP reads cat(item, user): the items are the first part
-        tabA, idxA, tabB, idxB = (user_tab, users, item_tab, ids) if user_first else (item_tab, ids, user_tab, users)
+        tabA, idxA, tabB, idxB, packed, user_first = ops
         if not native.mlp_rank_supported(packed, tabA.shape[1], tabB.shape[1], max_targets):
             return None
         return native.mlp_rank(tabA, idxA, tabB, idxB, packed, targets, max_targets, seen, user_first=user_first)
 
 
-def _scored_ranks(model, graph, users, items, seen, targets, block_bytes):
+def _scored_ranks(model, r, users, seen, targets, block_bytes):
     """Score blocks of users through the model and rank each block's targets in its score rows (native.rank_rows)."""
-    score = (lambda u, i: model(graph, u, i)) if graph is not None else model
-    B, I = users.numel(), items.numel()
     trow, tcol = targets
     rank = torch.empty(tcol.numel(), dtype=torch.int32, device=users.device)
-    rows_per_block = max(1, int(block_bytes) // max(1, I * _PAIR_BYTES))
-    ranked = []
+    # the kernels read col[rowptr[r] ..] and write rank[rowptr[r] ..]: a slice of rowptr indexes the whole arrays
     with torch.no_grad():
-        for b0 in range(0, B, rows_per_block):
-            b1 = min(B, b0 + rows_per_block)
-            nb = b1 - b0
-            scores = score(users[b0:b1].repeat_interleave(I), items.repeat(nb)).view(nb, I)
-            # the kernels read col[rowptr[r] ..] and write rank[rowptr[r] ..]: a slice of rowptr indexes the whole arrays
-            blk_seen = None if seen is None else (seen[0][b0:b1 + 1], seen[1])
-            ranked.append(native.rank_rows(scores, (trow[b0:b1 + 1], tcol), blk_seen, rank=rank)[1])
+        ranked = [native.rank_rows(scores, (trow[b0:b1 + 1], tcol), None if seen is None else (seen[0][b0:b1 + 1], seen[1]), rank=rank)[1]
+                  for b0, b1, scores in _score_blocks(model, r, users, block_bytes)]
     return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])
 
 
@@ -111,32 +89,9 @@ def rank_of_items(model, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, to
     sets the sticky flag ``native.check_rank_overflow`` reads and has only its first ``max_targets`` ranked).  Users with more than
     ``native.RANK_MAX_TARGETS`` targets are split off and ranked through ``native.rank_rows``; building that row subset reads its
     size on the host."""
-    _eval_only(model)
-    require_gpu(user_ids)
-    dev = user_ids.device
-    if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
-        raise ValueError("user_ids must be a 1-D int64 tensor of user positions")
-    is_graph = _graph_model(model)
-    if is_graph and graph is None:
-        raise ValueError("a GraphNCF ranks items on a graph: pass graph=")
-    if not is_graph and graph is not None:
-        raise ValueError(f"graph= is only taken by a GraphNCF, not by {type(model).__name__}")
-    if is_graph:
-        graph = graph.to(dev)
-        n_items = graph.num_items
-    else:
-        n_items = model.item_embeddings[0].in_features
-    if item_ids is None:
-        items = torch.arange(n_items, dtype=torch.int64, device=dev)
-    else:
-        require_gpu(item_ids)
-        if item_ids.dtype != torch.int64 or item_ids.dim() != 1:
-            raise ValueError("item_ids must be a 1-D int64 tensor of item positions")
-        items = item_ids.contiguous()
-    users = user_ids.contiguous()
-    B = users.numel()
+    r = _resolve_ranked(model, user_ids, item_ids, exclude, graph)
+    users, seen, B, dev = r.users, r.seen, r.B, r.users.device
     targets = _csr(targets, B, "targets")
-    seen = None if exclude is None else _csr(exclude, B, "exclude")
     trow, tcol = targets
     if B == 0:
         return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
@@ -147,26 +102,26 @@ def rank_of_items(model, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, to
     out = None
     if fused is None or fused:
         if max_targets <= cap:
-            out = _fused_ranks(model, graph, users, item_ids is None, items, n_items, seen, targets, max(1, max_targets))
+            out = _fused_ranks(model, r, users, seen, targets, max(1, max_targets))
         else:
             # the users above the fused cap take the unfused route as a row subset, the others the fused one
             cnt = trow[1:] - trow[:-1]
             small, big = torch.nonzero(cnt <= cap).flatten(), torch.nonzero(cnt > cap).flatten()
             s_row, s_col, s_entry = _take_rows(trow, tcol, small)
             s_seen = None if seen is None else _take_rows(seen[0], seen[1], small)[:2]
-            part = _fused_ranks(model, graph, users[small].contiguous(), item_ids is None, items, n_items, s_seen, (s_row, s_col), cap) \
+            part = _fused_ranks(model, r, users[small].contiguous(), s_seen, (s_row, s_col), cap) \
                 if small.numel() else (s_col, small.to(torch.int32))
             if part is not None:
                 b_row, b_col, b_entry = _take_rows(trow, tcol, big)
                 b_seen = None if seen is None else _take_rows(seen[0], seen[1], big)[:2]
-                b_rank, b_ranked = _scored_ranks(model, graph, users[big].contiguous(), items, b_seen, (b_row, b_col), block_bytes)
+                b_rank, b_ranked = _scored_ranks(model, r, users[big].contiguous(), b_seen, (b_row, b_col), block_bytes)
                 rank = torch.empty(tcol.numel(), dtype=torch.int32, device=dev)
                 ranked = torch.empty(B, dtype=torch.int32, device=dev)
                 rank[s_entry], ranked[small] = part[0], part[1]
                 rank[b_entry], ranked[big] = b_rank, b_ranked
                 out = rank, ranked
     if out is None:
-        out = _scored_ranks(model, graph, users, items, seen, targets, block_bytes)
+        out = _scored_ranks(model, r, users, seen, targets, block_bytes)
     return out
 
 

@@ -11,7 +11,7 @@
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -44,6 +44,68 @@ def _dot_readout(model) -> bool:
     return isinstance(model, MF) or (_graph_model(model) and model.MLP is None)
 
 
+class _RankedList(NamedTuple):
+    """What top_k_items and rank_of_items rank, resolved from their shared arguments (_resolve_ranked)."""
+    graph: object                # the GraphData on the device; None for a model without one
+    users: torch.Tensor          # (B,) int64 user positions, contiguous
+    items: torch.Tensor          # (I,) int64 item positions: the ranked list's columns
+    all_items: bool              # the list is every item of the model in position order (item_ids not given)
+    n_items: int
+    seen: Optional[tuple]        # the exclusion CSR (rowptr (B + 1) int64, col int32), or None
+    B: int
+    I: int
+
+
+def _csr(pair, B, what):
+    """A per-user CSR argument ``(rowptr (B + 1), col)`` as the kernels take it: int64 / int32, contiguous."""
+    rowptr, col = pair
+    require_gpu(rowptr, col)
+    if rowptr.dim() != 1 or col.dim() != 1 or rowptr.numel() != B + 1:
+        raise ValueError(f"{what} = (rowptr ({B + 1},) int64, col int32): rowptr has {rowptr.numel()} entries")
+    return rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous()
+
+
+def _resolve_ranked(model, user_ids, item_ids, exclude, graph) -> _RankedList:
+    """The checks top_k_items and rank_of_items make on the arguments they share, and the ranked list those arguments name."""
+    _eval_only(model)
+    require_gpu(user_ids)
+    dev = user_ids.device
+    if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
+        raise ValueError("user_ids must be a 1-D int64 tensor of user positions")
+    is_graph = _graph_model(model)
+    if is_graph and graph is None:
+        raise ValueError("a GraphNCF ranks items on a graph: pass graph=")
+    if not is_graph and graph is not None:
+        raise ValueError(f"graph= is only taken by a GraphNCF, not by {type(model).__name__}")
+    if is_graph:
+        graph = graph.to(dev)
+        n_items = graph.num_items
+    else:
+        n_items = model.item_embeddings[0].in_features
+    if item_ids is None:
+        items = torch.arange(n_items, dtype=torch.int64, device=dev)
+    else:
+        require_gpu(item_ids)
+        if item_ids.dtype != torch.int64 or item_ids.dim() != 1:
+            raise ValueError("item_ids must be a 1-D int64 tensor of item positions")
+        items = item_ids.contiguous()
+    B = user_ids.numel()
+    seen = None if exclude is None else _csr(exclude, B, "exclude")
+    return _RankedList(graph, user_ids.contiguous(), items, item_ids is None, n_items, seen, B, items.numel())
+
+
+def _score_blocks(model, r: _RankedList, users, block_bytes):
+    """Yields ``(b0, b1, scores (b1 - b0, I))``: the users scored against the ranked list through the model, in blocks of rows
+    whose (user, item) score block stays under ``block_bytes``."""
+    score = (lambda u, i: model(r.graph, u, i)) if r.graph is not None else model
+    rows_per_block = max(1, int(block_bytes) // max(1, r.I * _PAIR_BYTES))
+    for b0 in range(0, users.numel(), rows_per_block):
+        b1 = min(users.numel(), b0 + rows_per_block)
+        with torch.no_grad():
+            scores = score(users[b0:b1].repeat_interleave(r.I), r.items.repeat(b1 - b0)).view(b1 - b0, r.I)
+        yield b0, b1, scores                  # outside the with: a suspended generator must not hold the grad mode
+
+
 def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
                 exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES, *, graph=None,
                 fused: Optional[bool] = None):
@@ -65,112 +127,83 @@ def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.
     Returns ``(scores (B, k) fp32, item_positions (B, k) int64, counts (B,) int32)`` on the device, each row in descending score
     order (ties: lower column first; NaN last); slots past ``counts`` hold position -1 and score -inf.  Score-then-select scores
     the users in blocks of rows whose (user, item) score block stays under ``block_bytes``; nothing synchronises with the host."""
-    _eval_only(model)
-    require_gpu(user_ids)
-    dev = user_ids.device
-    if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
-        raise ValueError("user_ids must be a 1-D int64 tensor of user positions")
-    is_graph = _graph_model(model)
-    if is_graph and graph is None:
-        raise ValueError("a GraphNCF ranks items on a graph: pass graph=")
-    if not is_graph and graph is not None:
-        raise ValueError(f"graph= is only taken by a GraphNCF, not by {type(model).__name__}")
+    r = _resolve_ranked(model, user_ids, item_ids, exclude, graph)
     if fused and not _dot_readout(model):
         raise ValueError(f"fused=True needs a dot-product readout; {type(model).__name__} here scores through an MLP")
     if fused and getattr(model, "scoring_dtype", torch.float32) != torch.float32:
         raise ValueError("fused=True takes fp32 tables: the model scores in " + str(model.scoring_dtype))
-    use_fused = bool(fused) if fused is not None else (is_graph and _dot_readout(model))
-    if is_graph:
-        graph = graph.to(dev)
-        n_items = graph.num_items
-    else:
-        n_items = model.item_embeddings[0].in_features
-    if item_ids is None:
-        items = torch.arange(n_items, dtype=torch.int64, device=dev)
-    else:
-        require_gpu(item_ids)
-        if item_ids.dtype != torch.int64 or item_ids.dim() != 1:
-            raise ValueError("item_ids must be a 1-D int64 tensor of item positions")
-        items = item_ids.contiguous()
-    B, I = user_ids.numel(), items.numel()
     if not 1 <= int(k) <= native.TOPK_MAX_K:
         raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
-    if exclude is not None:
-        rowptr, col = exclude
-        require_gpu(rowptr, col)
-        if rowptr.numel() != B + 1:
-            raise ValueError(f"exclude rowptr has {rowptr.numel()} entries, {B + 1} expected")
-        rowptr, col = rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous()
-    users = user_ids.contiguous()
     out = None
-    seen = None if exclude is None else (rowptr, col)
-    if use_fused:
-        out = _fused_top_k(model, graph, users, item_ids is None, items, n_items, int(k), seen)
+    if bool(fused) if fused is not None else (r.graph is not None and _dot_readout(model)):
+        out = _fused_top_k(model, r, int(k))
     elif fused is None and not _dot_readout(model):
-        out = _fused_mlp_top_k(model, graph, users, item_ids is None, items, n_items, int(k), seen)
+        out = _fused_mlp_top_k(model, r, int(k))
     if out is None:
-        score = (lambda u, i: model(graph, u, i)) if is_graph else model
-        rows_per_block = max(1, int(block_bytes) // max(1, I * _PAIR_BYTES))
-        outs = []
+        # the kernel reads seen_col[rowptr[r] ..]: a slice of rowptr indexes the whole col array, no rebasing
         with torch.no_grad():
-            for b0 in range(0, B, rows_per_block):
-                b1 = min(B, b0 + rows_per_block)
-                nb = b1 - b0
-                u = users[b0:b1].repeat_interleave(I)
-                i = items.repeat(nb)
-                scores = score(u, i).view(nb, I)
-                # the kernel reads seen_col[rowptr[r] ..]: a slice of rowptr indexes the whole col array, no rebasing
-                seen = None if exclude is None else (rowptr[b0:b1 + 1], col)
-                outs.append(native.topk_rows(scores, k, seen))
+            outs = [native.topk_rows(scores, k, None if r.seen is None else (r.seen[0][b0:b1 + 1], r.seen[1]))
+                    for b0, b1, scores in _score_blocks(model, r, r.users, block_bytes)]
         out = tuple(torch.cat([o[j] for o in outs]) if len(outs) != 1 else outs[0][j] for j in range(3))
     s, idx, cnt = out
     pos = idx.to(torch.int64)
-    if item_ids is not None:
-        pos = torch.where(pos >= 0, items[pos.clamp_min(0)], pos)
+    if not r.all_items:
+        pos = torch.where(pos >= 0, r.items[pos.clamp_min(0)], pos)
     return s, pos, cnt
 
 
-def _fused_top_k(model, graph, users, all_items, items, n_items, k, seen):
+def _fused_top_k(model, r: _RankedList, k):
     """native.dot_topk over the model's (user table, item table); None where the fused kernel's limits do not hold (the caller
     then scores and selects, which gives the same bits)."""
     if k > native.DOT_TOPK_MAX_K:
         return None
     with torch.no_grad():
-        user_tab, item_tab, items = _fused_tables(model, graph, model._refresh(), all_items, items, n_items)
+        user_tab, item_tab, ids = _fused_tables(model, r, model._refresh())
         if user_tab.shape[1] > native.DOT_TOPK_MAX_D:
             return None
-        return native.dot_topk(user_tab, users, item_tab, items, k, seen)
+        return native.dot_topk(user_tab, r.users, item_tab, ids, k, r.seen)
 
 
-def _fused_mlp_top_k(model, graph, users, all_items, items, n_items, k, seen):
-    """native.mlp_topk over the model's MLP readout — BasicNCF: cat(user table, item table), the users first; GraphNCF:
-    cat(item node rows, user node rows) of the propagated table, the items first.  None where the fused kernel does not apply
-    (bf16 scoring, a folded first layer, an MLP shape without a fused instance, k > 128); the caller then scores and selects,
-    which gives the same bits."""
-    if k > native.MLP_TOPK_MAX_K or model.scoring_dtype != torch.float32 or model.fold_first_layer:
+def _mlp_operands(model, r: _RankedList, users):
+    """``(tabA, idxA, tabB, idxB, packed, user_first)`` of a fused MLP readout over ``users`` and the ranked list — BasicNCF:
+    cat(user table, item table), the users first; GraphNCF: cat(item node rows, user node rows) of the propagated table, the items
+    first.  None where no fused MLP kernel applies: non-fp32 scoring, a folded first layer, no packed MLP."""
+    if getattr(model, "scoring_dtype", torch.float32) != torch.float32 or model.fold_first_layer:
+        return None
+    cache = model._refresh()
+    packed = model._packed_mlp("MLP", cache)
+    if packed is None:
+        return None
+    user_tab, item_tab, ids = _fused_tables(model, r, cache)
+    if r.graph is None:
+        return user_tab, users, item_tab, ids, packed, True
+    return item_tab, ids, user_tab, users, packed, False
+
+
+def _fused_mlp_top_k(model, r: _RankedList, k):
+    """native.mlp_topk over the model's MLP readout; None where the fused kernel does not apply (_mlp_operands, an MLP shape
+    without a fused instance, k > 128); the caller then scores and selects, which gives the same bits."""
+    if k > native.MLP_TOPK_MAX_K:
         return None
     with torch.no_grad():
-        cache = model._refresh()
-        packed = model._packed_mlp("MLP", cache)
-        if packed is None:
+        ops = _mlp_operands(model, r, r.users)
+        if ops is None:
             return None
-        user_tab, item_tab, items = _fused_tables(model, graph, cache, all_items, items, n_items)
-        user_first = graph is None          # GraphNCF's MLP reads cat(item, user): the items are the first part
-        tabA, idxA, tabB, idxB = (user_tab, users, item_tab, items) if user_first else (item_tab, items, user_tab, users)
+        tabA, idxA, tabB, idxB, packed, user_first = ops
         if not native.mlp_topk_supported(packed, tabA.shape[1], tabB.shape[1], k):
             return None
-        return native.mlp_topk(tabA, idxA, tabB, idxB, packed, k, seen, user_first=user_first)
+        return native.mlp_topk(tabA, idxA, tabB, idxB, packed, k, r.seen, user_first=user_first)
 
 
-def _fused_tables(model, graph, cache, all_items, items, n_items):
+def _fused_tables(model, r: _RankedList, cache):
     """(user table, item table, item ids or None) of a fused route: a GraphNCF's propagated node table (its first n_items rows are
     the item nodes: all items are ranked in place, without an id list), else the model's user and item embedding tables."""
-    if graph is not None:
-        combined = model.propagate_all(graph, cache)
-        return (combined, combined[:n_items], None) if all_items else (combined, combined, items)
+    if r.graph is not None:
+        combined = model.propagate_all(r.graph, cache)
+        return (combined, combined[:r.n_items], None) if r.all_items else (combined, combined, r.items)
     user_tab = model._table("user", model.user_embeddings[0], cache)
     item_tab = model._table("item", model.item_embeddings[0], cache)
-    return user_tab, item_tab, None if all_items else items
+    return user_tab, item_tab, None if r.all_items else r.items
 
 
 def seen_items(graph, user_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
