@@ -301,6 +301,7 @@ class _DynamicDeviceState:
         self.col = torch.from_numpy(np.concatenate(cols).astype(np.int32) if cols else np.zeros(0, np.int32)).to(self.device)
         self.val = torch.from_numpy(np.concatenate(vals) if vals else np.zeros(0, np.float32)).to(self.device)
         self.num_items = len(prov.item_ids)
+        self.max_row_len = int(counts.max()) if n_users else 0     # the longest CSR row: sizes a training step's per-pair buffers
 
     def _lookup(self, ids, lo, table):
         rel = ids - lo
@@ -341,8 +342,26 @@ class _DynamicDeviceState:
         positions, rated_ids is None: the rated list is the whole catalogue in provider order; the candidate rows stay an
         unevaluated selection of it)."""
         rowptr, col, val = self._chunk_csr
-        ratings = SparseRatings(rowptr, col, val, self.num_items, pair_row=rows, pairs_per_row_hint=pairs_per_row_hint)
+        ratings = SparseRatings(rowptr, col, val, self.num_items, pair_row=rows, pairs_per_row_hint=pairs_per_row_hint,
+                                max_row_len=self.max_row_len)
         return cpos, None, RowsOf(self.features, cpos), self.features, ratings, y
+
+    def train_positions(self, users, cands):
+        """``positions`` for a training file: rows of the WHOLE user base's CSR, never a chunk-local one.  The training loop holds
+        its positions for all epochs while validation passes run ``positions`` on their own chunks in between, and a training step
+        (native.pair_rows, one wave per pair) does not scale with the rows of the CSR it is handed."""
+        return self._lookup(users, self.user_lo, self.user_table), self._lookup(cands, self.item_lo, self.item_table)
+
+    def item_positions(self, items):
+        return self._lookup(items, self.item_lo, self.item_table)
+
+    def train_ratings(self, rows, pairs_per_row_hint=None):
+        return SparseRatings(self.rowptr, self.col, self.val, self.num_items, pair_row=rows, pairs_per_row_hint=pairs_per_row_hint,
+                             max_row_len=self.max_row_len)
+
+    def train_batch_at(self, rows, cpos, y, pairs_per_row_hint=None):
+        """``batch_at`` over ``train_positions``' rows."""
+        return cpos, None, RowsOf(self.features, cpos), self.features, self.train_ratings(rows, pairs_per_row_hint), y
 
     def batch(self, users, cands, y, pairs_per_row_hint=None):
         return self.batch_at(*self.positions(users, cands), y, pairs_per_row_hint)

@@ -73,6 +73,9 @@ SIGNATURES = {
     "ncf_dense_csr_workspace_bytes": (_c_size, [_c_i64]),
     "ncf_dense_csr_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_size, _c_p]),
     "ncf_dense_csr_fill": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "ncf_pair_rows_count": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    "ncf_pair_rows_fill": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int,
+                                    ctypes.c_float, ctypes.c_float, _c_p, _c_p]),
     "ncf_attn_candidates_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "ncf_attn_candidates_workspace_bytes": (_c_size, [_c_i64]),
     "ncf_attn_candidates": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_i64, _c_p, _c_i64,
@@ -793,6 +796,76 @@ def dense_to_csr(user_matrix: torch.Tensor, share_rows: bool = True):
     torch.cumsum(rowptr, 0, out=rowptr)
     _check(lib.ncf_dense_csr_fill(_ptr(user_matrix), ld, B, I, _ptr(rowptr), _ptr(pair_row), _ptr(col), _ptr(val), _stream(user_matrix)))
     return rowptr, col, val, pair_row
+
+
+_pair_rows_flags = {}
+
+
+def _pair_rows_flag(device) -> torch.Tensor:
+    """The sticky overflow flag of pair_rows calls that run inside a training step (nobody reads a per-call flag there)."""
+    f = _pair_rows_flags.get(device)
+    if f is None:
+        f = torch.zeros(1, dtype=torch.int32, device=device)
+        _pair_rows_flags[device] = f
+    return f
+
+
+def check_pair_rows(device):
+    """Synchronising check of the sticky flag a pair_rows call sets when a pair's entries did not fit its capacity."""
+    f = _pair_rows_flag(device)
+    if int(f.item()) != 0:
+        f.zero_()
+        raise OverflowError("a pair's rated entries did not fit the capacity pair_rows was given (max_row_len too small)")
+
+
+def pair_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, pair_row: torch.Tensor, capacity: int, mask=None,
+              atol: float = 1e-5, rtol: float = 1e-5, flag: Optional[torch.Tensor] = None):
+    """(out_rowptr (B+1) int64, out_col int32, out_val fp32, flag int32[1]): the per-pair CSR of a shared-row CSR (pair b uses row
+    ``pair_row[b]``), entirely on the stream (ncf_pair_rows_count + cumsum + ncf_pair_rows_fill; no host read).  out_col / out_val
+    hold ``capacity`` entries, of which out_rowptr[B] are written; an entry past capacity is dropped, out_rowptr is cut off at
+    capacity (the CSR stays consistent with its buffers) and ``flag`` is set (int32[1]: a fresh zero unless the caller passes one to accumulate in, e.g. ``_pair_rows_flag``; it is never cleared here).  ``mask`` = (cand_emb (B, E), rated_emb (I, E)): AttentionNCF's
+    train-only target mask — out_col = -1 where the pair's candidate row is torch.isclose (fp32, ``atol`` / ``rtol``) to the rated
+    item's in every element.  A pair_row outside the CSR gives an empty row and sets the sticky out-of-range flag (check_oob)."""
+    lib = load_library()
+    _dev(rowptr, "rowptr")
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float32:
+        raise TypeError("pair_rows takes an int64 rowptr, int32 columns and fp32 values")
+    if not (rowptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()) or rowptr.numel() < 1:
+        raise ValueError("pair_rows takes a contiguous CSR")
+    pair_row = _idx(pair_row)
+    R, B, capacity = rowptr.numel() - 1, pair_row.numel(), int(capacity)
+    if capacity < 0:
+        raise ValueError("capacity must be >= 0")
+    dev = rowptr.device
+    out_rowptr = torch.zeros(1, dtype=torch.int64, device=dev) if B == 0 else torch.empty(B + 1, dtype=torch.int64, device=dev)
+    out_col = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+    out_val = torch.empty(max(capacity, 1), dtype=torch.float32, device=dev)
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif flag.dtype != torch.int32 or flag.numel() != 1 or flag.device != dev:
+        raise ValueError("flag must be one int32 on the CSR's device")
+    cand = rated = None
+    I = E = ldc = ldr = 0
+    if mask is not None:
+        cand, rated = mask
+        _dev(cand, "cand_emb"), _dev(rated, "rated_emb")
+        if cand.dtype != torch.float32 or rated.dtype != torch.float32:
+            raise TypeError("pair_rows compares fp32 embeddings")
+        Bc, E, ldc = _rows2d(cand, "cand_emb")
+        I, Er, ldr = _rows2d(rated, "rated_emb")
+        if Bc != B or Er != E:
+            raise ValueError(f"mask shapes {tuple(cand.shape)} / {tuple(rated.shape)} do not fit {B} pairs")
+    if B == 0:
+        return out_rowptr, out_col, out_val, flag
+    st = _stream(rowptr)
+    _check(lib.ncf_pair_rows_count(_ptr(rowptr), R, _ptr(pair_row), B, _ptr(out_rowptr), _ptr(_oob_flag(dev)), st))
+    torch.cumsum(out_rowptr, 0, out=out_rowptr)
+    _check(lib.ncf_pair_rows_fill(_ptr(rowptr), _ptr(col), _ptr(val), R, _ptr(pair_row), B, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val),
+                                  capacity, _ptr(cand), ldc, _ptr(rated), ldr, I, E, float(atol), float(rtol), _ptr(flag), st))
+    # what did not fit was not written: the returned CSR ends at capacity (a truncated row, then empty ones), so that a kernel bounded
+    # by rowptr never reads or writes past buffers sized like out_col, whatever the flag says when somebody looks
+    torch.clamp(out_rowptr, max=capacity, out=out_rowptr)
+    return out_rowptr, out_col, out_val, flag
 
 
 def _events_us(fn, reps, settle):

@@ -11,10 +11,13 @@ from torch.utils.data import Dataset
 class ResidentInputs:
     """Whole-file model inputs for eval_model's device-resident loop: host ``tensors`` (sample order) + ``targets``;
     ``on_chunk(*device_tensors) -> inputs`` runs once per uploaded chunk (raw ids -> table positions), ``on_batch(*inputs,
-    y) -> batch`` builds the tuple ``do_forward`` receives (default: ``(*inputs, y)``)."""
+    y) -> batch`` builds the tuple ``do_forward`` receives (default: ``(*inputs, y)``).  ``train_on_chunk`` / ``train_on_batch``:
+    what train_model's resident loop uses in their place when given — it uploads the file once and keeps the chunk's inputs for
+    every epoch, so they must not depend on state an evaluation pass between two epochs replaces."""
 
-    def __init__(self, tensors, targets, on_chunk=None, on_batch=None):
+    def __init__(self, tensors, targets, on_chunk=None, on_batch=None, train_on_chunk=None, train_on_batch=None):
         self.tensors, self.targets, self.on_chunk, self.on_batch = tuple(tensors), targets, on_chunk, on_batch
+        self.train_on_chunk, self.train_on_batch = train_on_chunk or on_chunk, train_on_batch or on_batch
 
 
 class PointwiseDataset(Dataset):

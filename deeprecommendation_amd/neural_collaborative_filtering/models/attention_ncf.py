@@ -63,15 +63,20 @@ class SparseRatings:
 
     ``pair_row`` (optional, (B,) int64): the CSR then has one row per DISTINCT user of the batch and pair b uses row
     ``pair_row[b]`` — the dense matrix repeats a user's row for each of their pairs (dynamic_datasets.py:24-40); sharing
-    it is what lets the LDS-tiled attention kernel stage a user's rated rows once for all of their pairs."""
+    it is what lets the LDS-tiled attention kernel stage a user's rated rows once for all of their pairs.
+
+    ``max_row_len`` (optional, with ``pair_row``): an upper bound of the CSR's row lengths the HOST knows.  A training step then
+    builds its per-pair CSR on the stream in buffers of B * max_row_len entries (native.pair_rows) instead of reading the entry
+    count back; a row longer than the bound raises OverflowError at the epoch's flag check."""
 
     # below this average the per-pair kernel is used.  Measured at config-3 shapes (tools/ab_attn_grouped.py threshold),
     # grouped vs per-pair: 1 pair per set 335 vs 154 us, 2: 216 vs 153, 4: 128 vs 152, 8: 77 vs 151, 16+: 57 vs 147
     GROUPED_MIN_PAIRS_PER_ROW = 4
 
-    def __init__(self, rowptr, col, val, num_items, pair_row=None, pairs_per_row_hint=None):
+    def __init__(self, rowptr, col, val, num_items, pair_row=None, pairs_per_row_hint=None, max_row_len=None):
         self.rowptr, self.col, self.val, self.num_items = rowptr, col, val, int(num_items)
         self.pair_row = pair_row
+        self.max_row_len = None if max_row_len is None else int(max_row_len)
         # average number of pairs per row IN USE, when the CSR holds more rows than the batch touches (a whole user
         # base kept on the GPU, pair_row = user position): the row count then says nothing about sharing
         self.pairs_per_row_hint = pairs_per_row_hint
@@ -246,11 +251,12 @@ class AttentionNCF(_ScoringMixin, NCF):
         cache["catalog"] = (key, val, rated_items)
         return val
 
-    def forward(self, candidate_items, rated_items, user_matrix, return_attention_weights=False):
+    def forward(self, candidate_items, rated_items, user_matrix, return_attention_weights=False, pair_split=None):
+        """``pair_split`` (``forward_pairs``): the batch is the positives' pairs followed by the negatives', split at that row."""
         if not use_native(self):
             if isinstance(candidate_items, RowsOf):
                 candidate_items = candidate_items.materialise()
-            return self._forward_train(candidate_items, rated_items, user_matrix, return_attention_weights)
+            return self._forward_train(candidate_items, rated_items, user_matrix, return_attention_weights, pair_split)
         require_gpu(candidate_items, rated_items)
         cache = self._refresh()  # ONE parameter fingerprint per forward (it walks the module tree: ~12 us of host time)
         li, lu = self.ItemEmbeddings[0], self.UserEmbeddings[0]
@@ -353,7 +359,7 @@ class AttentionNCF(_ScoringMixin, NCF):
         return out
 
     # ------------------------------------------------------------------------------------------ torch training path
-    def _forward_train_hip(self, candidate_items, rated_items, user_matrix, return_attention_weights):
+    def _forward_train_hip(self, candidate_items, rated_items, user_matrix, return_attention_weights, pair_split=None):
         """attention_ncf.py:136-224 with autograd recording, on the HIP blocks: the Linear layers (LinearFn), the attention with its
         softmax and weighted sum (AttnFn: forward and backward kernels; AttentionNet's hidden dropout regenerated from a hash in
         both), the MLP (mlp_train).  The train-only target masking (:195-205, a candidate must not attend to itself) is decided
@@ -365,10 +371,20 @@ class AttentionNCF(_ScoringMixin, NCF):
         cand_emb = LinearFn.apply(cand, li.weight, li.bias, False)
         rated_emb = LinearFn.apply(rated, li.weight, li.bias, False)
         ratings = user_matrix if isinstance(user_matrix, SparseRatings) else SparseRatings.from_dense(user_matrix, share_identical_rows=False)
-        if ratings.pair_row is not None:
+        on_stream = (ratings.pair_row is not None and ratings.max_row_len is not None and not return_attention_weights
+                     and ratings.rowptr.is_cuda)
+        if on_stream:
+            # per-pair CSR and target mask in one pass on the stream (ncf_pair_rows_*): no size reaches the host, the buffers are
+            # sized by the host's bound and the kernels downstream are bounded by rowptr
+            mask = (cand_emb.detach(), rated_emb.detach()) if self.training else None
+            rowptr, col, val, _ = native.pair_rows(ratings.rowptr, ratings.col, ratings.val, ratings.pair_row.to(torch.int64).contiguous(),
+                                                   ratings.pair_row.numel() * ratings.max_row_len, mask,
+                                                   flag=native._pair_rows_flag(ratings.rowptr.device))
+        elif ratings.pair_row is not None:
             ratings = ratings.expanded()
-        rowptr, col, val = ratings.rowptr, ratings.col, ratings.val
-        if self.training and col.numel():
+        if not on_stream:
+            rowptr, col, val = ratings.rowptr, ratings.col, ratings.val
+        if not on_stream and self.training and col.numel():
             b_of = torch.repeat_interleave(torch.arange(rowptr.numel() - 1, device=col.device), rowptr[1:] - rowptr[:-1])
             same = torch.isclose(cand_emb.detach()[b_of], rated_emb.detach()[col.long()], atol=1e-5).all(dim=1)
             col = torch.where(same, torch.full_like(col, -1), col)        # a dropped entry: score -inf, weight 0 (:192-205)
@@ -387,19 +403,19 @@ class AttentionNCF(_ScoringMixin, NCF):
                 dropout = (float(drop.p), int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))    # host generator: no device sync
         proj = LinearFn.apply(rated, lu.weight, None, False)        # UserEmbeddings is linear over the weighted sum (:212-216)
         user_emb, wts = AttnFn.apply(pc, pr, w1, b1, proj, lu.bias, rowptr, col, val, mode, dropout)
-        out = mlp_train(self.MLP, torch.cat((cand_emb, user_emb), dim=1))
+        out = self._train_mlp(torch.cat((cand_emb, user_emb), dim=1), True, pair_split)
         if return_attention_weights:
             dense = SparseRatings(rowptr, ratings.col, val, ratings.num_items).to_dense(wts.detach())
             return out, dense
         return out
 
-    def _forward_train(self, candidate_items, rated_items, user_matrix, return_attention_weights):
+    def _forward_train(self, candidate_items, rated_items, user_matrix, return_attention_weights, pair_split=None):
         hip = (candidate_items.is_cuda and not getattr(self, "train_with_torch_ops", False) and not (self.training and self.message_dropout)
                and (self.use_cos_sim_instead or self.att_dense) and native.attn_backward_supported(
                    native.ATT_COS if self.use_cos_sim_instead else native.ATT_MLP,
                    self.ItemEmbeddings[0].out_features if self.use_cos_sim_instead else int(self.att_dense), self.UserEmbeddings[0].out_features))
         if hip:
-            return self._forward_train_hip(candidate_items, rated_items, user_matrix, return_attention_weights)
+            return self._forward_train_hip(candidate_items, rated_items, user_matrix, return_attention_weights, pair_split)
         if isinstance(user_matrix, SparseRatings):
             user_matrix = user_matrix.expanded()
             user_matrix = user_matrix.to_dense(user_matrix.val)
@@ -428,5 +444,23 @@ class AttentionNCF(_ScoringMixin, NCF):
         scores = F.softmax(scores, dim=1).nan_to_num(nan=0.0, posinf=0.0, neginf=0.0)
         user_feat = torch.matmul(scores * user_matrix, rated_items)
         user_emb = self.UserEmbeddings(user_feat)
-        out = self.MLP(torch.cat((cand_emb, user_emb), dim=1))
+        out = self._train_mlp(torch.cat((cand_emb, user_emb), dim=1), False, pair_split)
         return (out, scores.detach()) if return_attention_weights else out
+
+    # ------------------------------------------------------------------------------------------ pair-wise step in one forward
+    def _train_mlp(self, x, hip, pair_split=None):
+        """The MLP of a training step.  With ``pair_split`` it is applied to the two halves of the batch separately (everything
+        before it — the catalogue-side Linears above all — runs once over all 2B rows)."""
+        from ...autograd import mlp_train
+        run = (lambda t: mlp_train(self.MLP, t)) if hip else self.MLP
+        return run(x) if pair_split is None else torch.cat((run(x[:pair_split]), run(x[pair_split:])), dim=0)
+
+    def forward_pairs(self, candidate_items, rated_items, user_matrix, split):
+        """(out[:split], out[split:]) of ONE forward over the positives' pairs followed by the negatives' (a pair-wise step: the
+        rated items' embeddings and projections are computed once instead of once per call).  In a training step the MLP is applied
+        to the two halves separately, as two forwards would.  Under the BPR loss the gradient of out_neg is exactly minus that of
+        out_pos, so the output bias — and the bias of every hidden unit that is active for all pairs — has a gradient that is
+        exactly zero: two column sums over g and -g add up to that zero, where one column sum over [g; -g] leaves rounding noise,
+        which Adam turns into steps of lr (measured: MLP.0.bias 4e-2 of its largest element off after 16 steps)."""
+        out = self(candidate_items, rated_items, user_matrix, pair_split=int(split))
+        return out[:split], out[split:]

@@ -77,24 +77,27 @@ def schedule_w(epoch, break_points=(4, 8, 12, 18, 24)):
         return 3
 
 
-def _resident_training_inputs(dataset, device, batch_size):
-    """(inputs on the device, targets on the device) for the whole file, or None."""
+def _resident_training_inputs(dataset, device, batch_size, per_batch_hook=False):
+    """(inputs on the device, targets on the device, on_batch or None) for the whole file, or None.  ``on_chunk`` runs once on the
+    uploaded file, ``on_batch`` per picked batch (``ResidentInputs.train_on_*``: the forms that survive validation passes).  A
+    dataset whose batches need an ``on_batch`` hook is taken only with ``per_batch_hook`` (train_model's ``resident=True``)."""
     if torch.device(device).type != "cuda":
         return None
     res = dataset.resident_inputs(torch.device(device), batch_size)
-    if res is None or res.on_batch is not None:
+    if res is None or (res.on_batch is not None and not per_batch_hook):
         return None
     dev = [t.pin_memory().to(device, non_blocking=True) for t in (*res.tensors, res.targets)]
-    inputs = list(res.on_chunk(*dev[:-1])) if res.on_chunk is not None else dev[:-1]
-    return inputs, dev[-1]
+    inputs = list(res.train_on_chunk(*dev[:-1])) if res.train_on_chunk is not None else dev[:-1]
+    return inputs, dev[-1], res.train_on_batch
 
 
 def train_model(model, train_dataset, val_dataset: PointwiseDataset, lr, weight_decay, batch_size, val_batch_size, early_stop,
                 final_model_path='final_model.pt', checkpoint_model_path='temp.pt', max_epochs=100, patience=3, max_patience=5,
                 optimizer=None, ndcg_cutoff=10, wandb=None, num_workers=0, device=None, resident=None, shuffle=True, verbose=True):
     """train.py:21-227 for point-wise and pair-wise (ranking) training datasets.  Extra keyword arguments: ``device`` (default:
-    cuda:0 when there is one), ``resident`` (None = device-resident batches when the dataset allows, False = DataLoader loop),
-    ``shuffle`` (tests)."""
+    cuda:0 when there is one), ``resident`` (None = device-resident batches when the dataset allows, False = DataLoader loop,
+    True = device-resident batches or ValueError), ``shuffle`` (tests).  The two dynamic datasets (AttentionNCF: ``resident_opt_in``)
+    build their batches on the device only with ``resident=True``; ``None`` keeps their DataLoader loop, so no existing run changes."""
     ranking = isinstance(train_dataset, RankingDataset)
     if not (ranking or isinstance(train_dataset, PointwiseDataset)) or not isinstance(val_dataset, PointwiseDataset):
         raise NotImplementedError("train_model takes a point-wise or a ranking (pair-wise) training dataset and a point-wise "
@@ -117,11 +120,11 @@ def train_model(model, train_dataset, val_dataset: PointwiseDataset, lr, weight_
     train_graph = train_dataset.get_graph(device)
     extra = [] if train_graph is None else [train_graph]
     held = pairs = None
-    if resident is not False:
+    if resident is not False and (resident or not getattr(train_dataset, "resident_opt_in", False)):
         if ranking:
             pairs = train_dataset.resident_pairs(device) if device.type == "cuda" else None
         else:
-            held = _resident_training_inputs(train_dataset, device, batch_size)
+            held = _resident_training_inputs(train_dataset, device, batch_size, per_batch_hook=resident is True)
     if resident and held is None and pairs is None:
         raise ValueError("resident training needs a CUDA device and a dataset with on-device batches")
     loader = None
@@ -154,12 +157,14 @@ def train_model(model, train_dataset, val_dataset: PointwiseDataset, lr, weight_
             train_sum_loss = float(running.item())   # the epoch's only host synchronisation
             pairs.check()                            # the sampler's flag and the out-of-range flag, already on the host's side
         elif held is not None:
-            inputs, targets = held
+            inputs, targets, on_batch = held
             order = torch.randperm(n, device=device) if shuffle else None
             running = torch.zeros((), dtype=torch.float64, device=device)
             for s in range(0, n, batch_size):
                 pick = order[s:s + batch_size] if order is not None else slice(s, s + batch_size)
                 batch = (*[t[pick] for t in inputs], targets[pick])
+                if on_batch is not None:
+                    batch = on_batch(*batch)
                 optimizer.zero_grad()
                 out, y = do_forward(model, batch, device, *extra)
                 loss = train_dataset.calculate_loss(out, y)
@@ -167,6 +172,10 @@ def train_model(model, train_dataset, val_dataset: PointwiseDataset, lr, weight_
                 optimizer.step()
                 running += loss.detach().double()
             train_sum_loss = float(running.item())   # the epoch's only host synchronisation
+            if on_batch is not None:                 # batches built on the device: their sticky flags, already on the host's side
+                from .. import native
+                native.check_pair_rows(device)
+                native.check_oob(device)
         else:
             train_sum_loss = 0.0
             for batch in loader:

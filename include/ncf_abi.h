@@ -467,6 +467,36 @@ int ncf_dense_csr_rows(const float* dev_user_matrix, int64_t ld, int64_t B, int6
 int ncf_dense_csr_fill(const float* dev_user_matrix, int64_t ld, int64_t B, int64_t I, const int64_t* dev_rowptr,
                        const int64_t* dev_pair_row, int32_t* dev_col, float* dev_val, ncf_stream_t stream);
 
+/* Shared-row CSR -> per-pair CSR on the stream, with AttentionNCF's train-only target mask (csrc/pair_rows.hip).
+ * Replaces: SparseRatings.expanded() (repeat_interleave reads the entry count back to the host) and the mask of
+ *           models/attention_ncf.py:195-205 as torch ops (two (nnz, E) gathers for torch.isclose) in a training step.
+ * Input: a CSR of R shared rows (dev_rowptr (R + 1, int64), dev_col int32, dev_val fp32) and dev_pair_row (B, int64), the row each
+ * pair uses.  Two calls around one cumulative sum the caller runs on the stream, as ncf_dense_csr_rows / ncf_dense_csr_fill:
+ *   ncf_pair_rows_count -> dev_out_rowptr[0] = 0 and dev_out_rowptr[b + 1] = the length of shared row pair_row[b]; a row outside
+ *                          [0, R) counts 0 and sets *dev_oob_flag (when non-NULL)
+ *   an inclusive cumulative sum over dev_out_rowptr (B + 1), IN PLACE, makes it the per-pair CSR's rowptr
+ *   ncf_pair_rows_fill  -> one wave per pair: the pair's entries, in the shared row's order, copied to dev_out_col / dev_out_val at
+ *                          out_rowptr[b].  Both hold `capacity` entries; an entry at or past capacity is not written and sets
+ *                          *dev_flag = 1 (the buffers beyond rowptr[B] are never touched).
+ *   With dev_cand != NULL the fill also applies the target mask: an entry whose column c is in [0, I) gets out_col = -1 (a dropped
+ *   entry for ncf_attn_forward / ncf_attn_backward) when EVERY element e < E of row dev_cand[b * ldcand + e] is close to
+ *   dev_rated[c * ldrated + e]; its value is copied anyway.  A column outside [0, I) is copied unchanged and never compared.
+ *   "Close" is torch.isclose(cand, rated, rtol, atol) evaluated in fp32, each operation rounded on its own (the multiply is NOT
+ *   contracted into the add), with a = the candidate's element and b = the rated item's:
+ *       a == b || (isfinite(a) && isfinite(b) && fabsf(a - b) <= atol + fabsf(rtol * b))
+ *   (a NaN is close to nothing; +inf is close to +inf only).  The reference calls isclose(..., atol=1e-5): rtol is torch's 1e-5.
+ *   E % 4 == 0, E <= 256, both leading dimensions % 4 == 0 and 16-byte aligned tables take 16-byte loads; any other shape a
+ *   generic path with the same results.
+ * No atomics: the same inputs give the same bits.  B == 0 launches nothing (dev_out_rowptr[0] is then the caller's to set).
+ * NCF_EINVAL for a negative size, E < 1, a leading dimension < E, a negative or NaN tolerance or a NULL pointer; NCF_EUNSUPPORTED
+ * from B = 2^31.  Neither call launches anything when it refuses. */
+int ncf_pair_rows_count(const int64_t* dev_rowptr, int64_t R, const int64_t* dev_pair_row, int64_t B, int64_t* dev_out_rowptr,
+                        int32_t* dev_oob_flag, ncf_stream_t stream);
+int ncf_pair_rows_fill(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t R, const int64_t* dev_pair_row,
+                       int64_t B, const int64_t* dev_out_rowptr, int32_t* dev_out_col, float* dev_out_val, int64_t capacity,
+                       const float* dev_cand, int64_t ldcand, const float* dev_rated, int64_t ldrated, int64_t I, int E, float atol,
+                       float rtol, int32_t* dev_flag, ncf_stream_t stream);
+
 /* The candidate side of AttentionNCF.forward in one launch — models/attention_ncf.py:150 (ItemEmbeddings on the candidates) and
  * the candidate half of AttentionNet's first Linear (:176-179 with AttentionNet.0.weight split at the cat boundary):
  *     emb = x . Wi^T + bi   (B, N1);     pc = emb . Wc^T + b0   (B, N2)
