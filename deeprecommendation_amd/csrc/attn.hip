@@ -718,8 +718,6 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
         pcrow[k] = pcrow[0];
 #endif
     }
-    if (tid < PP) pid[tid] = tid < cnt ? pair_ids[start + tid] : -1;
-
     // MFMA roles: a job = one 16-pair x 16-feature tile of O over all 16 k-steps (4 entries each) of a tile; MT * NTILES jobs
     const int NTILES = (Fdim + 15) / 16;
     f32x4 acc[MAXNT];
@@ -734,6 +732,11 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
     int c_cur = -1, c_nxt = -1, c_nn = -1;
     float v_cur = 0.f, v_nxt = 0.f, v_nn = 0.f;
     __syncthreads();                                       // LDS zeroed before the first DMA lands
+    // pid[] is stored only HERE, below the barrier: the zeroing loop above strides over the whole allocation, pid[] included, and
+    // the thread that zeroes a pid word is in general not the thread (nor the wave) that stores it — a store above the barrier
+    // could be wiped by a late wave, and the group's outputs would then land in row 0.  The first read of pid[] is behind the
+    // next barrier (the tile loop's, or the one before the output stage when the row is empty), so no barrier is added.
+    if (tid < PP) pid[tid] = tid < cnt ? pair_ids[start + tid] : -1;
     if (ntiles > 0) {
         load_cv(beg, c_cur, v_cur);
         load_cv(beg + EC, c_nxt, v_nxt);
@@ -1135,6 +1138,47 @@ extern "C" int ncf_attn_backward(int mode, const float* pc, int64_t ldpc, const 
     return check_launch("ncf_attn_backward");
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The launch rule of ncf_attn_forward_grouped, separate from the launches: which kernel instantiation a grouped call runs, as a
+// pure function of the shape and the attn_grouped_kernel option.  ncf_attn_forward_grouped consumes it; ncf_attn_grouped_plan
+// returns it without launching, so a test can say which kernel it ran.  `mode` is NCF_ATT_MLP or NCF_ATT_COS (`scaled`: the caller
+// passed NCF_ATT_MLP_SCALED); the shape has passed the entry's argument checks (A % 4 == 0, A, Fdim <= 256, 1 <= ppw <= 32).
+enum { ATTG_NONE = 0, ATTG_SC = 1, ATTG_LDS = 2 };      // the form values of ncf_attn_grouped_plan
+
+struct AttnGroupedPlan {
+    int status;         // NCF_OK, or NCF_EUNSUPPORTED with `why`
+    int form;           // ATTG_*
+    int kmode;          // the kernel's MODE: 0 MLP, 2 cosine, 3 MLP with relu as a clamp (scalar-operand form only)
+    int a;              // scalar-operand form: CPB (16-byte chunks of a row per a-block); LDS form: FO (output registers per lane)
+    int b;              // scalar-operand form: NW (waves per workgroup); LDS form: NPF (tile pieces staged per thread)
+    size_t lds;         // dynamic LDS bytes of the launch
+    int64_t grid;       // gridDim.x
+    const char* why;
+};
+
+static AttnGroupedPlan plan_attn_grouped(int mode, bool scaled, int A, int Fdim, int64_t ldfeat, int pairs_per_wg, int64_t B, int64_t R) {
+    const bool fvec = Fdim % 4 == 0 && ldfeat % 4 == 0;
+    // upper bound on sum_r ceil(n_r / ppw): every non-empty row adds at most one partly filled workgroup, and at most
+    // min(R, B) rows are non-empty (R may be a whole user base with B pairs of a few users: device-resident evaluation)
+    const int64_t blocks = (int64_t)(unsigned)((B + pairs_per_wg - 1) / pairs_per_wg + (R < B ? R : B));
+    const int A4 = A / 4;
+    const int pp = pairs_per_wg <= 16 ? 16 : 32;
+    const int jobs = (pp / 16) * ((Fdim + 15) / 16);   // 16 x 16 output tiles of the aggregation; at most 4 per wave
+    const size_t lds2 = ((size_t)64 * (A + Fdim) + pp * 66 + pp + 2 * pp) * 4;
+    const bool sc_ok = fvec && lds2 <= 160 * 1024 && jobs <= 4 * (pp / 4);
+    const int force = option(NCF_OPT_ATTN_GROUPED_KERNEL);
+    if (sc_ok && force != 1) {
+        const int cpb = A4 % 32 == 0 ? 32 : (A4 % 16 == 0 ? 16 : (A4 % 8 == 0 ? 8 : 1));
+        return {NCF_OK, ATTG_SC, mode == NCF_ATT_MLP ? (scaled ? 3 : 0) : 2, cpb, pp / 4, lds2, blocks, ""};
+    }
+    if (force == 2) return {NCF_EUNSUPPORTED, ATTG_NONE, 0, 0, 0, lds2, 0, "the scalar-operand form needs Fdim % 4 == 0 and <= 160 KiB of LDS"};
+    const size_t lds = ((size_t)64 * (A + 4) + (size_t)64 * Fdim + (size_t)pairs_per_wg * A + A + 64 + 64) * 4;
+    if (lds > 160 * 1024) return {NCF_EUNSUPPORTED, ATTG_NONE, 0, 0, 0, lds, 0, "the tile needs more than 160 KiB of LDS"};
+    const int pieces_per_thread = (64 * (A / 4 + (fvec ? Fdim / 4 : 0)) + 511) / 512;   // <= 16 for A, Fdim <= 256
+    return {NCF_OK, ATTG_LDS, mode == NCF_ATT_MLP ? 0 : 2, Fdim <= 64 ? 1 : (Fdim <= 128 ? 2 : 4),
+            pieces_per_thread <= 4 ? 4 : (pieces_per_thread <= 8 ? 8 : 16), lds, blocks, ""};
+}
+
 extern "C" int ncf_attn_forward_grouped(int mode, const float* pc, int64_t ldpc, const float* pr, int64_t ldpr, int A,
                                         const float* w1, float b1, const int64_t* rowptr, const int32_t* col, const float* val,
                                         int64_t R, int64_t I, const int64_t* grp_ptr, const int64_t* pair_ids,
@@ -1158,11 +1202,11 @@ extern "C" int ncf_attn_forward_grouped(int mode, const float* pc, int64_t ldpc,
         return fail(NCF_EUNSUPPORTED, "ncf_attn_forward_grouped: needs A %% 4 == 0, A <= 256, Fdim <= 256 (A = %d, Fdim = %d)", A, Fdim);
     if (!aligned16(pc) || !aligned16(pr) || (w1 && !aligned16(w1)) || (Fdim % 4 == 0 && ldfeat % 4 == 0 && !aligned16(feat)))
         return fail(NCF_EINVAL, "ncf_attn_forward_grouped: operands must be 16-byte aligned");
-    const bool fvec = Fdim % 4 == 0 && ldfeat % 4 == 0;
+    const AttnGroupedPlan p = plan_attn_grouped(mode, scaled, A, Fdim, ldfeat, pairs_per_wg, B, R);
+    if (p.status != NCF_OK) return fail(p.status, "ncf_attn_forward_grouped: %s (A = %d, Fdim = %d, %zu bytes of LDS)", p.why, A, Fdim, p.lds);
     hipStream_t s = (hipStream_t)stream;
-    // upper bound on sum_r ceil(n_r / ppw): every non-empty row adds at most one partly filled workgroup, and at most
-    // min(R, B) rows are non-empty (R may be a whole user base with B pairs of a few users: device-resident evaluation)
-    const unsigned blocks = (unsigned)((B + pairs_per_wg - 1) / pairs_per_wg + (R < B ? R : B));
+    const unsigned blocks = (unsigned)p.grid;
+    const size_t lds = p.lds;
     // the dynamic-LDS limit of an instantiation is raised ONCE per device (to the 160 KiB a workgroup may declare)
     auto raise_lds = [](const void* fn, std::atomic<unsigned long long>& done) -> bool {
         int dev = 0;
@@ -1175,43 +1219,31 @@ extern "C" int ncf_attn_forward_grouped(int mode, const float* pc, int64_t ldpc,
         done.fetch_or(1ull << dev, std::memory_order_relaxed);
         return true;
     };
-    // ---- scalar-operand form (default): tiles by LDS-DMA, aggregation on the matrix cores; 4 waves for up to 16 pairs per
-    // workgroup, 8 waves for 17..32 (half the staged bytes per pair: the choice for batches that fill the chip either way) ----
-    {
-        const int A4 = A / 4;
-        const int pp = pairs_per_wg <= 16 ? 16 : 32;
-        const int jobs = (pp / 16) * ((Fdim + 15) / 16);   // 16 x 16 output tiles of the aggregation; at most 4 per wave
-        const size_t lds2 = ((size_t)64 * (A + Fdim) + pp * 66 + pp + 2 * pp) * 4;
-        const bool sc_ok = fvec && lds2 <= 160 * 1024 && aligned16(feat) && jobs <= 4 * (pp / 4);
-        const int force = option(NCF_OPT_ATTN_GROUPED_KERNEL);
-        if (sc_ok && force != 1) {
+    if (p.form == ATTG_SC) {
+        // ---- scalar-operand form (default): tiles by LDS-DMA, aggregation on the matrix cores; 4 waves for up to 16 pairs per
+        // workgroup, 8 waves for 17..32 (half the staged bytes per pair: the choice for batches that fill the chip either way) ----
 #define LAUNCH_SC(M, C)                                                                                                           \
     do {                                                                                                                       \
         static std::atomic<unsigned long long> done{0}, done2{0};                                                              \
-        if (lds2 > 64 * 1024 && !(raise_lds((const void*)attn_grouped_sc_kernel<M, C, 4>, done) &&                            \
-                                  raise_lds((const void*)attn_grouped_sc_kernel<M, C, 8>, done2)))                            \
-            return fail(NCF_EUNSUPPORTED, "ncf_attn_forward_grouped: cannot reserve %zu bytes of LDS", lds2);                  \
-        if (pp == 16)                                                                                                          \
-            hipLaunchKernelGGL((attn_grouped_sc_kernel<M, C, 4>), dim3(blocks), dim3(256), lds2, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, \
+        if (lds > 64 * 1024 && !(raise_lds((const void*)attn_grouped_sc_kernel<M, C, 4>, done) &&                             \
+                                 raise_lds((const void*)attn_grouped_sc_kernel<M, C, 8>, done2)))                             \
+            return fail(NCF_EUNSUPPORTED, "ncf_attn_forward_grouped: cannot reserve %zu bytes of LDS", lds);                   \
+        if (p.b == 4)                                                                                                          \
+            hipLaunchKernelGGL((attn_grouped_sc_kernel<M, C, 4>), dim3(blocks), dim3(256), lds, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, \
                                val, R, I, grp_ptr, pair_ids, wg_ptr, pairs_per_wg, feat, ldfeat, Fdim, out_bias, out, ldout, wts, wts_off); \
         else                                                                                                                   \
-            hipLaunchKernelGGL((attn_grouped_sc_kernel<M, C, 8>), dim3(blocks), dim3(512), lds2, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, \
+            hipLaunchKernelGGL((attn_grouped_sc_kernel<M, C, 8>), dim3(blocks), dim3(512), lds, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, \
                                val, R, I, grp_ptr, pair_ids, wg_ptr, pairs_per_wg, feat, ldfeat, Fdim, out_bias, out, ldout, wts, wts_off); \
     } while (0)
-#define LAUNCH_SC_C(M) do { if (A4 % 32 == 0) LAUNCH_SC(M, 32); else if (A4 % 16 == 0) LAUNCH_SC(M, 16); else if (A4 % 8 == 0) LAUNCH_SC(M, 8); else LAUNCH_SC(M, 1); } while (0)
-            if (mode == NCF_ATT_MLP && scaled) LAUNCH_SC_C(3);
-            else if (mode == NCF_ATT_MLP) LAUNCH_SC_C(0);
-            else LAUNCH_SC_C(2);
+#define LAUNCH_SC_C(M) do { if (p.a == 32) LAUNCH_SC(M, 32); else if (p.a == 16) LAUNCH_SC(M, 16); else if (p.a == 8) LAUNCH_SC(M, 8); else LAUNCH_SC(M, 1); } while (0)
+        if (p.kmode == 3) LAUNCH_SC_C(3);
+        else if (p.kmode == 0) LAUNCH_SC_C(0);
+        else LAUNCH_SC_C(2);
 #undef LAUNCH_SC_C
 #undef LAUNCH_SC
-            return check_launch("ncf_attn_forward_grouped");
-        }
-        if (force == 2) return fail(NCF_EUNSUPPORTED, "ncf_attn_forward_grouped: the scalar-operand form needs Fdim %% 4 == 0 and <= 160 KiB of LDS");
+        return check_launch("ncf_attn_forward_grouped");
     }
     // ---- first form: tile staged through registers, operands broadcast from LDS ----
-    const size_t lds = ((size_t)64 * (A + 4) + (size_t)64 * Fdim + (size_t)pairs_per_wg * A + A + 64 + 64) * 4;
-    if (lds > 160 * 1024) return fail(NCF_EUNSUPPORTED, "ncf_attn_forward_grouped: tile needs %zu bytes of LDS", lds);
-    const int pieces_per_thread = (64 * (A / 4 + (fvec ? Fdim / 4 : 0)) + 511) / 512;   // <= 16 for A, Fdim <= 256
 #define LAUNCH1(M, F, P)                                                                                                          \
     do {                                                                                                                       \
         static std::atomic<unsigned long long> done{0};                                                                        \
@@ -1220,14 +1252,35 @@ extern "C" int ncf_attn_forward_grouped(int mode, const float* pc, int64_t ldpc,
         hipLaunchKernelGGL((attn_grouped_kernel<M, F, P>), dim3(blocks), dim3(512), lds, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, R, I, \
                            grp_ptr, pair_ids, wg_ptr, pairs_per_wg, feat, ldfeat, Fdim, out_bias, out, ldout, wts, wts_off);   \
     } while (0)
-#define LAUNCH_P(M, F) do { if (pieces_per_thread <= 4) LAUNCH1(M, F, 4); else if (pieces_per_thread <= 8) LAUNCH1(M, F, 8); else LAUNCH1(M, F, 16); } while (0)
-#define LAUNCH_F(M) do { if (Fdim <= 64) LAUNCH_P(M, 1); else if (Fdim <= 128) LAUNCH_P(M, 2); else LAUNCH_P(M, 4); } while (0)
-    if (mode == NCF_ATT_MLP) LAUNCH_F(0);
+#define LAUNCH_P(M, F) do { if (p.b == 4) LAUNCH1(M, F, 4); else if (p.b == 8) LAUNCH1(M, F, 8); else LAUNCH1(M, F, 16); } while (0)
+#define LAUNCH_F(M) do { if (p.a == 1) LAUNCH_P(M, 1); else if (p.a == 2) LAUNCH_P(M, 2); else LAUNCH_P(M, 4); } while (0)
+    if (p.kmode == 0) LAUNCH_F(0);
     else LAUNCH_F(2);
 #undef LAUNCH_F
 #undef LAUNCH_P
 #undef LAUNCH1
     return check_launch("ncf_attn_forward_grouped");
+}
+
+extern "C" int ncf_attn_grouped_plan(int mode, int A, int Fdim, int64_t ldfeat, int pairs_per_wg, int64_t B, int64_t n_rows, int* form,
+                                     int* kernel_mode, int* cpb_or_fo, int* nw_or_npf, int64_t* lds_bytes, int64_t* grid_x) {
+    if (mode != NCF_ATT_MLP && mode != NCF_ATT_COS && mode != NCF_ATT_MLP_SCALED)
+        return fail(NCF_EUNSUPPORTED, "ncf_attn_grouped_plan: mode %d has no LDS-tiled form (use ncf_attn_forward)", mode);
+    if (B < 0 || n_rows < 0 || A <= 0 || Fdim <= 0) return fail(NCF_EINVAL, "ncf_attn_grouped_plan: bad sizes");
+    if (ldfeat < Fdim) return fail(NCF_EINVAL, "ncf_attn_grouped_plan: leading dimension smaller than row");
+    if (pairs_per_wg < 1 || pairs_per_wg > 32) return fail(NCF_EINVAL, "ncf_attn_grouped_plan: pairs_per_wg must be 1..32");
+    if (A % 4 || A > 256 || Fdim > 256)
+        return fail(NCF_EUNSUPPORTED, "ncf_attn_grouped_plan: needs A %% 4 == 0, A <= 256, Fdim <= 256 (A = %d, Fdim = %d)", A, Fdim);
+    AttnGroupedPlan p{NCF_OK, ATTG_NONE, 0, 0, 0, 0, 0, ""};
+    if (B > 0 && n_rows > 0) p = plan_attn_grouped(mode == NCF_ATT_MLP_SCALED ? NCF_ATT_MLP : mode, mode == NCF_ATT_MLP_SCALED, A, Fdim, ldfeat, pairs_per_wg, B, n_rows);
+    if (p.status != NCF_OK) return fail(p.status, "ncf_attn_grouped_plan: %s (A = %d, Fdim = %d, %zu bytes of LDS)", p.why, A, Fdim, p.lds);
+    if (form) *form = p.form;
+    if (kernel_mode) *kernel_mode = p.kmode;
+    if (cpb_or_fo) *cpb_or_fo = p.a;
+    if (nw_or_npf) *nw_or_npf = p.b;
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    if (grid_x) *grid_x = p.grid;
+    return NCF_OK;
 }
 
 extern "C" size_t ncf_group_pairs_workspace_bytes(int64_t n_rows) { return (size_t)(2 * (n_rows > 0 ? n_rows : 0) + 1) * sizeof(int); }

@@ -67,6 +67,7 @@ SIGNATURES = {
     "ncf_attn_forward_grouped": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, ctypes.c_float, _c_p, _c_p, _c_p,
                                           _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_p,
                                           _c_i64, _c_p, _c_p, _c_p]),
+    "ncf_attn_grouped_plan": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _c_int, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "ncf_group_pairs_workspace_bytes": (_c_size, [_c_i64]),
     "ncf_group_pairs": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p]),
     "ncf_group_pairs_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p]),
@@ -722,6 +723,21 @@ def attn_backward(mode: int, pc, pr, w1, rowptr, col, val, feat, wts, dout, drop
 def attn_grouped_supported(mode: int, A: int, Fdim: int) -> bool:
     """Shapes the LDS-tiled grouped kernel takes (mirrors ncf_attn_forward_grouped's NCF_EUNSUPPORTED conditions)."""
     return mode in (ATT_MLP, ATT_COS, ATT_MLP_SCALED) and A % 4 == 0 and A <= 256 and Fdim <= 256
+
+
+ATTN_GROUPED_FORMS = {0: "none", 1: "sc", 2: "lds"}    # ncf_attn_grouped_plan's *form
+
+
+def attn_grouped_plan(mode: int, A: int, Fdim: int, ldfeat: Optional[int] = None, pairs_per_wg: int = 16, B: int = 1, n_rows: int = 1):
+    """(form, kernel MODE, CPB or FO, NW or NPF, LDS bytes, grid_x) of the kernel ncf_attn_forward_grouped runs for the shape under
+    the current attn_grouped_kernel option; form by name (ATTN_GROUPED_FORMS): "sc" = attn_grouped_sc_kernel<MODE, CPB, NW>, "lds" =
+    attn_grouped_kernel<MODE, FO, NPF>.  Host only: no launch, no device.  Raises NativeError where the launch would refuse."""
+    form, km, a, b = (ctypes.c_int(0) for _ in range(4))
+    lds, gx = ctypes.c_int64(0), ctypes.c_int64(0)
+    _check(load_library().ncf_attn_grouped_plan(int(mode), int(A), int(Fdim), int(Fdim if ldfeat is None else ldfeat), int(pairs_per_wg),
+                                                int(B), int(n_rows), ctypes.byref(form), ctypes.byref(km), ctypes.byref(a),
+                                                ctypes.byref(b), ctypes.byref(lds), ctypes.byref(gx)))
+    return ATTN_GROUPED_FORMS[form.value], km.value, a.value, b.value, lds.value, gx.value
 
 
 def attn_backward_supported(mode: int, A: int, Fdim: int) -> bool:

@@ -382,8 +382,9 @@ int ncf_attn_backward(int mode,
  * order.  dev_weights (optional) receives the attention weights (models/attention_ncf.py:224) in the layout of that
  * expanded CSR: pair b's weights start at dev_weights[dev_weights_off[b]] and follow its row's entries
  * (dev_weights_off (B,) = exclusive prefix sum of the row lengths of pair_row[b]).
- * pairs_per_wg <= 16 with Fdim % 4 == 0 takes the scalar-operand form (256-thread workgroups: pc rows and w1 as scalar
- * operands through the scalar cache, tiles by LDS-DMA, aggregation on the matrix cores); 17..32 the first form.
+ * Fdim % 4 == 0 and ldfeat % 4 == 0 take the scalar-operand form (256-thread workgroups for pairs_per_wg <= 16, 512 threads for
+ * 17..32: pc rows and w1 as scalar operands through the scalar cache, tiles by LDS-DMA, aggregation on the matrix cores); other
+ * shapes the first, LDS-broadcast form.  ncf_attn_grouped_plan names the instantiation a shape runs.
  * NCF_EUNSUPPORTED (fall back to ncf_attn_forward): mode NCF_ATT_LINEAR, A % 4 != 0, A > 256, Fdim > 256. */
 int ncf_attn_forward_grouped(int mode,
                              const float* dev_pc, int64_t ldpc, const float* dev_pr, int64_t ldpr, int A,
@@ -395,6 +396,23 @@ int ncf_attn_forward_grouped(int mode,
                              const float* dev_feat, int64_t ldfeat, int Fdim, const float* dev_out_bias,
                              float* dev_out_feat, int64_t ldout,
                              float* dev_weights, const int64_t* dev_weights_off, ncf_stream_t stream);
+
+/* Which kernel ncf_attn_forward_grouped runs for a shape under the current "attn_grouped_kernel" option: the launch rule itself,
+ * answered without launching and without touching the device (like ncf_linear_plan).  Any output pointer may be NULL.
+ *   *form         0 nothing (B = 0 or n_rows = 0), 1 scalar-operand form (attn_grouped_sc_kernel<MODE, CPB, NW>), 2 LDS-broadcast
+ *                 form (attn_grouped_kernel<MODE, FO, NPF>)
+ *   *kernel_mode  the kernel's MODE: 0 MLP, 2 cosine, 3 MLP on the 2^-64-scaled operands with relu as a clamp (form 1 only; form 2
+ *                 runs NCF_ATT_MLP_SCALED as MODE 0)
+ *   *cpb_or_fo    form 1: CPB, the 16-byte chunks of a projected row per block of the score loop (32, 16, 8 or 1);
+ *                 form 2: FO, the output registers per lane (1, 2 or 4 = ceil(Fdim / 64) rounded up)
+ *   *nw_or_npf    form 1: NW, waves per workgroup (4 for pairs_per_wg <= 16, else 8); form 2: NPF, tile pieces per thread (4, 8, 16)
+ *   *lds_bytes    dynamic LDS of the launch (above 64 KiB the entry raises the kernel's limit first)
+ *   *grid_x       gridDim.x = ceil(B / pairs_per_wg) + min(n_rows, B), the bound on the number of groups
+ * Status as ncf_attn_forward_grouped's for the same shape: NCF_EINVAL for bad sizes, ldfeat < Fdim or pairs_per_wg outside 1..32;
+ * NCF_EUNSUPPORTED for NCF_ATT_LINEAR, A % 4 != 0, A > 256, Fdim > 256, a tile beyond 160 KiB of LDS, or the scalar-operand form
+ * forced on a shape it does not take (Fdim % 4 != 0 or ldfeat % 4 != 0). */
+int ncf_attn_grouped_plan(int mode, int A, int Fdim, int64_t ldfeat, int pairs_per_wg, int64_t B, int64_t n_rows,
+                          int* form, int* kernel_mode, int* cpb_or_fo, int* nw_or_npf, int64_t* lds_bytes, int64_t* grid_x);
 
 /* Builds dev_grp_ptr / dev_pair_ids / dev_wg_ptr of ncf_attn_forward_grouped from dev_pair_row (B,) = the CSR row of
  * each pair (what the dense user_matrix expresses by repeating a user's row, dynamic_datasets.py:24-40): a counting

@@ -128,6 +128,11 @@ def test_status_codes_of_the_round1_late_entries(native, gpu):
     assert args(native.ATT_MLP, 64, 0) == native.NCF_EINVAL
     assert args(native.ATT_MLP, 64, 33) == native.NCF_EINVAL
     assert not native.attn_grouped_supported(native.ATT_LINEAR, 1, 64) and native.attn_grouped_supported(native.ATT_COS, 64, 256)
+    # ncf_attn_grouped_plan (host only) refuses the same shapes with the same codes, and names a kernel for the one that runs
+    plan = lambda mode, A, ppw: lib.ncf_attn_grouped_plan(mode, A, 64, 64, ppw, 4, 1, None, None, None, None, None, None)
+    assert plan(native.ATT_LINEAR, 1, 8) == native.NCF_EUNSUPPORTED and plan(native.ATT_MLP, 6, 8) == native.NCF_EUNSUPPORTED
+    assert plan(native.ATT_MLP, 64, 0) == native.NCF_EINVAL and plan(native.ATT_MLP, 64, 33) == native.NCF_EINVAL
+    assert plan(native.ATT_MLP, 64, 8) == native.NCF_OK and native.attn_grouped_plan(native.ATT_MLP, 64, 64, 64, 8, 4, 1)[:4] == ("sc", 0, 16, 4)
     # weights requested without their offsets
     assert lib.ncf_attn_forward_grouped(native.ATT_MLP, f.data_ptr(), 64, f.data_ptr(), 64, 64, f.data_ptr(), 0.0, i64.data_ptr(), i32.data_ptr(),
                                         f.data_ptr(), 1, 64, i64.data_ptr(), i64.data_ptr(), i64.data_ptr(), 4, 8, f.data_ptr(), 64, 64, None,

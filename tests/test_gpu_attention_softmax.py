@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+from attn_forms_ref import attention64, backward_bars, masked_softmax64, scores64     # the float64 reference, shared with test_gpu_attention_forms.py
 from conftest import record_error
 from test_gpu_basic import assert_close
 
@@ -37,61 +38,6 @@ ROWS = [("lead_first", 300), ("lead_last", 300), ("lead_mid_tile", 300), ("lead_
         ("hot", 300), ("cold", 300), ("underflow_band", 300), ("dead_slice", 1000), ("single", 1), ("empty", 0),
         ("len63", 63), ("len64", 64), ("len65", 65), ("neg_lead_1000", 1000)]
 TIE = (10, 900)                    # tie_two_slices: entries with identical pr rows (tiles 0 and 14)
-
-
-# ------------------------------------------------------------------------------------------------ float64 reference (CPU)
-def masked_softmax64(s, rowptr):
-    """Row softmax over the CSR entries ``s`` (float64, -inf = masked); a row without a finite entry gets zeros (the reference's
-    F.softmax over -inf + nan_to_num, attention_ncf.py:208-209)."""
-    s = s.double()
-    w = torch.zeros_like(s)
-    rp = rowptr.tolist()
-    for r in range(len(rp) - 1):
-        x = s[rp[r]:rp[r + 1]]
-        if x.numel() and bool(torch.isfinite(x).any()):
-            e = torch.exp(x - x.max())
-            w[rp[r]:rp[r + 1]] = e / e.sum()
-    return w
-
-
-def scores64(mode, pc, pr, w1, b1, normalize=True):
-    """Logits of pairs ``pc`` (P, A) against entries ``pr`` (n, A): (P, n) float64.  MLP / MLP_SCALED: b1 + sum_a w1[a] relu(pc + pr);
-    LINEAR (A = 1): pc + pr; COS: dot of the L2-normalised rows (eps 1e-12; ``normalize=False``: the kernels' contract, rows given
-    normalised — what the backward differentiates)."""
-    if mode == ATT_LINEAR:
-        return pc[:, None, 0] + pr[None, :, 0]
-    if mode == ATT_COS:
-        if normalize:
-            pc, pr = torch.nn.functional.normalize(pc, dim=1, eps=1e-12), torch.nn.functional.normalize(pr, dim=1, eps=1e-12)
-        return pc @ pr.t()
-    return torch.relu(pc[:, None, :] + pr[None]) @ w1 + b1
-
-
-def attention64(mode, pc, pr, w1, b1, rowptr, col, val, pair_row, feat, bias, normalize=True):
-    """out (B, Fdim) = sum_e w_e val_e feat[col_e] + bias per pair (bias alone for an empty set), the weights and the logits in the
-    expanded per-pair CSR layout (pair b's entries, pairs in order), all float64 and differentiable in pc, pr, w1, feat."""
-    B, I = pc.shape[0], pr.shape[0]
-    rp = rowptr.tolist()
-    out = [None] * B
-    wts, logits = [None] * B, [None] * B
-    for r in range(len(rp) - 1):
-        pairs = (pair_row == r).nonzero().view(-1)
-        if not pairs.numel():
-            continue
-        c, v = col[rp[r]:rp[r + 1]].long(), val[rp[r]:rp[r + 1]].double()
-        ok = (c >= 0) & (c < I)
-        cc = c.clamp(0, max(I - 1, 0))
-        if c.numel():
-            s = scores64(mode, pc[pairs], pr[cc], w1, b1, normalize)
-            s = torch.where(ok[None], s, torch.full_like(s, -float("inf")))
-            w = torch.softmax(s, 1).nan_to_num(0.0) if bool(ok.any()) else torch.zeros_like(s)
-            o = (w * v) @ feat[cc] + bias
-        else:
-            s = w = torch.zeros((pairs.numel(), 0), dtype=torch.float64)
-            o = bias.expand(pairs.numel(), -1) + 0 * feat.sum() + 0 * pc[pairs].sum()
-        for k, b in enumerate(pairs.tolist()):
-            out[b], wts[b], logits[b] = o[k], w[k], s[k]
-    return torch.stack(out), torch.cat(wts), torch.cat(logits)
 
 
 # ------------------------------------------------------------------------------------------------ the designed inputs
@@ -370,26 +316,13 @@ def test_attn_backward_peaked(native, gpu, mode_name):
     leaves = [pc, pr, feat] + ([w1] if w1 is not None else [])
     grads = torch.autograd.grad((out * dout.double()).sum(), leaves)
     assert_close(d_feat, grads[2])
-    # T: the sum of the absolute values of the terms, entry by entry in the expanded layout
+    # T: the sum of the absolute values of the terms, entry by entry in the expanded layout (attn_forms_ref.backward_bars)
     col = ex.col.long().cpu()
     owner = torch.repeat_interleave(torch.arange(c["B"]), (ex.rowptr[1:] - ex.rowptr[:-1]).cpu())
-    pcd, prd = case["pc"].double(), case["pr"].double()
-    dv = case["val"][ex.shared_entry.cpu()].double() * (case["feat"].double()[col] * dout.double()[owner]).sum(1)
-    w = w.detach()
-    wabs = torch.zeros(c["B"], dtype=torch.float64).index_add_(0, owner, w * dv.abs())[owner]
-    G = 1e-5 * w * (dv.abs() + wabs) + 2.0 ** -126 * (1.0 + dv.abs() + wabs)        # rtol x |terms| + the fp32 flush floor
-    if mode == ATT_COS:
-        T_pc = torch.zeros_like(pcd).index_add_(0, owner, G[:, None] * prd[col].abs())
-        T_pr = torch.zeros_like(prd).index_add_(0, col, G[:, None] * pcd[owner].abs())
-        T = [(d_pc, grads[0], T_pc, "d_pc"), (d_pr, grads[1], T_pr, "d_pr")]
-    else:
-        h = pcd[owner] + prd[col]
-        assert bool((h != 0).all())                                   # no relu kink: the derivative is defined everywhere
-        act = (h > 0).double() * case["w1"].double().abs()
-        T_pc = torch.zeros_like(pcd).index_add_(0, owner, G[:, None] * act)
-        T_pr = torch.zeros_like(prd).index_add_(0, col, G[:, None] * act)
-        T_w1 = (G[:, None] * torch.relu(h)).sum(0)
-        T = [(d_pc, grads[0], T_pc, "d_pc"), (d_pr, grads[1], T_pr, "d_pr"), (d_w1, grads[3], T_w1, "d_w1")]
+    bars = backward_bars(mode, case["pc"], case["pr"], case["w1"], col, owner, case["val"][ex.shared_entry.cpu()], case["feat"], dout, w.detach())
+    T = [(d_pc, grads[0], bars["d_pc"], "d_pc"), (d_pr, grads[1], bars["d_pr"], "d_pr")]
+    if mode != ATT_COS:
+        T.append((d_w1, grads[3], bars["d_w1"], "d_w1"))
     for got, ref, bar, what in T:
         got = got.detach().cpu().double()
         assert got.shape == ref.shape, what
