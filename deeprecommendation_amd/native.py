@@ -95,6 +95,11 @@ SIGNATURES = {
     "ncf_attn_tail_pack_weight": (_c_int, [_c_p, _c_int, _c_int, _c_p, _c_p]),
     "ncf_attn_tail": (_c_int, [_c_p, _c_i64, _c_int, _c_p, _c_int, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_int,
                                _c_p, ctypes.c_float, _c_int, _c_p, _c_i64, _c_p]),
+    "ncf_attn_logits": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, ctypes.c_float, _c_p, _c_i64, _c_p]),
+    "ncf_attn_cross_supported": (_c_int, [_c_int]),
+    "ncf_attn_cross_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
+    "ncf_attn_cross": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_int,
+                                _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "ncf_edge_softmax_csr": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_edge_softmax_segmented_workspace_bytes": (_c_size, [_c_i64, _c_i64]),
     "ncf_edge_softmax_segmented": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_size, _c_p]),
@@ -1163,6 +1168,68 @@ def attn_forward_grouped(mode: int, pc: torch.Tensor, pr: torch.Tensor, w1: Opti
                                         _ptr(feat), ldf, Fdim, _ptr(out_bias), _ptr(out), out.stride(0), _ptr(wts), _ptr(wts_off),
                                         _stream(pc)))
     return (out, wts) if return_weights else out
+
+
+def attn_logits(mode: int, pc: torch.Tensor, pr: torch.Tensor, w1: Optional[torch.Tensor], b1: float,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The logit table of a catalogue (ncf_attn_logits): ST (I_r, I_c) fp32, ST[e, i] = the attention logit of candidate i (row of
+    ``pc``) against rated item e (row of ``pr``); modes and operands as ``attn_forward``.  One launch on the current stream."""
+    lib = load_library()
+    _dev(pc, "pc")
+    Ic, A, ldpc = _rows2d(pc, "pc")
+    Ir, A2, ldpr = _rows2d(pr, "pr")
+    if A != A2:
+        raise ValueError("attention operand shapes disagree")
+    if out is None:
+        out = torch.empty((Ir, Ic), dtype=torch.float32, device=pc.device)
+    Ir2, Ic2, ldst = _rows2d(out, "out")
+    if (Ir2, Ic2) != (Ir, Ic) or out.dtype != torch.float32:
+        raise ValueError(f"out must be ({Ir}, {Ic}) fp32")
+    _check(lib.ncf_attn_logits(int(mode), _ptr(pc), ldpc, Ic, _ptr(pr), ldpr, Ir, A, _ptr(w1), float(b1), _ptr(out), ldst, _stream(pc)))
+    return out
+
+
+def attn_cross_supported(Fdim: int) -> bool:
+    """Widths ``attn_cross`` takes (ncf_attn_cross_supported: Fdim % 32 == 0, 32 <= Fdim <= 256).  Host only."""
+    return load_library().ncf_attn_cross_supported(int(Fdim)) == 1
+
+
+def attn_cross_plan(Fdim: int, U: int = 1, I: int = 1):
+    """(nb, entry_tile, LDS bytes, grid_x) of the launch ``attn_cross`` would make: attn_cross_kernel<nb, entry_tile>.  Host only;
+    raises NativeError where the call would refuse."""
+    nb, te = ctypes.c_int(0), ctypes.c_int(0)
+    lds, gx = ctypes.c_int64(0), ctypes.c_int64(0)
+    _check(load_library().ncf_attn_cross_plan(int(Fdim), int(U), int(I), ctypes.byref(nb), ctypes.byref(te), ctypes.byref(lds), ctypes.byref(gx)))
+    return nb.value, te.value, lds.value, gx.value
+
+
+def attn_cross(ST: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, user_rows: torch.Tensor,
+               feat: torch.Tensor, out_bias: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention of the listed users against the ranked list, from the logit table (ncf_attn_cross): (U * I, Fdim), row u * I + j =
+    the user_emb of (user_rows[u], column j) — column j is table column ``cand_ids[j]``, or j without ``cand_ids`` (I = I_c).
+    ``rowptr / col / val``: the users' CSR (col = rows of ST and of feat).  An out-of-range user row or candidate id raises at the
+    next check_oob().  One launch on the current stream; nothing synchronises."""
+    lib = load_library()
+    _dev(ST, "ST")
+    Ir, Ic, ldst = _rows2d(ST, "ST")
+    Ir2, Fdim, ldf = _rows2d(feat, "feat")
+    if Ir != Ir2:
+        raise ValueError("ST and feat disagree on the number of rated items")
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float32:
+        raise TypeError("CSR must be (int64 rowptr, int32 col, fp32 val)")
+    user_rows, cand_ids = _idx(user_rows), _idx(cand_ids)
+    U = user_rows.numel()
+    I = Ic if cand_ids is None else cand_ids.numel()
+    if out is None:
+        out = torch.empty((U * I, Fdim), dtype=torch.float32, device=ST.device)
+    rows, F2, ldo = _rows2d(out, "out")
+    if rows != U * I or F2 != Fdim or out.dtype != torch.float32:
+        raise ValueError(f"out must be ({U * I}, {Fdim}) fp32")
+    _check(lib.ncf_attn_cross(_ptr(ST), ldst, Ir, Ic, _ptr(rowptr), _ptr(col), _ptr(val), rowptr.numel() - 1, _ptr(user_rows), U,
+                              _ptr(cand_ids), I, _ptr(feat), ldf, Fdim, _ptr(out_bias), _ptr(out), ldo, _ptr(_oob_flag(ST.device)),
+                              _stream(ST)))
+    return out
 
 
 def l2_normalize_rows(x: torch.Tensor) -> torch.Tensor:

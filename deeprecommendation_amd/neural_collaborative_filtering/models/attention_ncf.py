@@ -358,6 +358,130 @@ class AttentionNCF(_ScoringMixin, NCF):
             return out, ratings.to_dense(wts)
         return out
 
+    # ------------------------------------------------------------------------------------------ many users x one catalogue
+    # largest logit table (4 * I_c * I_c bytes) the cross-product route builds: 1 GiB is a catalogue of about 16k items
+    cross_table_max_bytes = 1 << 30
+    # one block of catalogue_scores: the user_emb rows (4 * UE bytes per pair), the scores and the item position of each pair
+    CATALOGUE_BLOCK_BYTES = 256 << 20
+
+    def _att_out(self, cache):
+        """(mode, w1, b1) of the attention kernels for this model, as ``forward`` passes them."""
+        if self.use_cos_sim_instead:
+            return native.ATT_COS, None, 0.0
+        if not self.att_dense:
+            return native.ATT_LINEAR, None, 0.0
+        if "att_out" not in cache:
+            l1 = self.AttentionNet[-1]
+            cache["att_out"] = ((l1.weight.detach().reshape(-1) * 2.0 ** native.ATT_SCALE_LOG2).contiguous(), float(l1.bias.detach().item()))
+        return (native.ATT_MLP_SCALED,) + cache["att_out"]
+
+    def cross_route(self, n_items: int, table=None) -> bool:
+        """Whether ``catalogue_scores`` over a catalogue of ``n_items`` takes the logit-table route.  ``table=None``: where the cross
+        kernel has an instance for ``user_emb`` and the table fits ``cross_table_max_bytes``; ``True`` outside those limits raises
+        ValueError; ``False`` is the pair route.  Host only."""
+        if table is False:
+            return False
+        UE = self.UserEmbeddings[0].out_features
+        nbytes = 4 * int(n_items) * int(n_items)
+        fits, shape = nbytes <= self.cross_table_max_bytes, native.attn_cross_supported(UE)
+        if table and not fits:
+            raise ValueError(f"the logit table of {n_items} items takes {nbytes} bytes, above AttentionNCF.cross_table_max_bytes = "
+                             f"{self.cross_table_max_bytes}")
+        if table and not shape:
+            raise ValueError(f"the cross-product attention kernel has no instance for user_emb = {UE} (a multiple of 32 in 32 .. 256)")
+        return fits and shape
+
+    def logit_table(self, item_features: torch.Tensor, cache=None):
+        """ST (I_c, I_c): the attention logit of every (rated item, candidate) pair of the catalogue (native.attn_logits), kept per
+        weight version for the last catalogue tensor seen beside ``precompute_catalog``'s entry (key: address, shape, version)."""
+        cache = self._refresh() if cache is None else cache
+        key = (item_features.data_ptr(), tuple(item_features.shape), item_features._version)
+        hit = cache.get("cross_table")
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the logit table is never built inside a stream capture: call catalogue_scores once before capturing")
+        rated_emb, pr, _ = self.precompute_catalog(item_features, cache)
+        if self.use_cos_sim_instead:
+            pc = native.l2_normalize_rows(rated_emb)
+        else:
+            wc, _, b0 = self._att_split(cache)
+            pc = native.linear(rated_emb, wc, b0)          # the candidates ARE the catalogue: same ItemEmbeddings rows
+        mode, w1, b1 = self._att_out(cache)
+        ST = native.attn_logits(mode, pc, pr, w1, b1)
+        cache["cross_table"] = (key, ST, item_features)
+        return ST
+
+    def catalogue_score_blocks(self, item_features, ratings, user_rows, item_ids=None, table=None, block_bytes=None):
+        """Yields ``(u0, u1, scores (u1 - u0, I))`` of ``catalogue_scores``, in blocks of users whose user_emb rows, scores and
+        item positions stay under ``block_bytes``.  Nothing synchronises with the host."""
+        if self.training:
+            raise RuntimeError("catalogue_scores is computed in eval mode: call model.eval() first")
+        if not isinstance(ratings, SparseRatings):
+            raise TypeError("ratings must be a SparseRatings whose rows are users and whose columns are catalogue positions")
+        if item_features.dim() != 2 or ratings.num_items != item_features.shape[0]:
+            raise ValueError(f"ratings has {ratings.num_items} columns, the catalogue {tuple(item_features.shape)} rows")
+        if user_rows.dtype != torch.int64 or user_rows.dim() != 1:
+            raise ValueError("user_rows must be a 1-D int64 tensor of rows of ratings")
+        if item_ids is not None and (item_ids.dtype != torch.int64 or item_ids.dim() != 1):
+            raise ValueError("item_ids must be a 1-D int64 tensor of catalogue positions")
+        Ic = item_features.shape[0]
+        use_table = self.cross_route(Ic, table)
+        require_gpu(item_features, ratings.rowptr, ratings.col, ratings.val, user_rows, item_ids)
+        lu = self.UserEmbeddings[0]
+        UE = lu.out_features
+        I = Ic if item_ids is None else item_ids.numel()
+        U = user_rows.numel()
+        user_rows = user_rows.contiguous()
+        block_bytes = self.CATALOGUE_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+        rows_per_block = max(1, block_bytes // max(1, I * (4 * UE + 4 + 8)))
+        with torch.no_grad():
+            cache = self._refresh()
+            if use_table and table is None and torch.cuda.is_current_stream_capturing() and cache.get("cross_table") is None:
+                use_table = False
+            items = torch.arange(Ic, dtype=torch.int64, device=item_features.device) if item_ids is None else item_ids.contiguous()
+            if use_table:
+                ST = self.logit_table(item_features, cache)
+                rated_emb, _, proj = self.precompute_catalog(item_features, cache)
+                bias = lu.bias.detach()
+        pos, pos_n = None, -1
+        for u0 in range(0, U, rows_per_block):
+            u1 = min(U, u0 + rows_per_block)
+            nb = u1 - u0
+            with torch.no_grad():
+                if I == 0:
+                    scores = torch.empty((nb, 0), dtype=torch.float32, device=item_features.device)
+                elif use_table:
+                    if pos_n != nb:
+                        pos, pos_n = items.repeat(nb), nb
+                    user_emb = native.attn_cross(ST, ratings.rowptr, ratings.col, ratings.val, user_rows[u0:u1], proj, out_bias=bias,
+                                                 cand_ids=None if item_ids is None else items)
+                    # the fused scorer with an index on table A: cat(candidate_emb, user_emb) -> MLP (:219-222)
+                    scores = self._score(rated_emb, pos, user_emb, None, cache=cache).view(nb, I)
+                else:
+                    pairs = SparseRatings(ratings.rowptr, ratings.col, ratings.val, ratings.num_items,
+                                          pair_row=user_rows[u0:u1].repeat_interleave(I), pairs_per_row_hint=I)
+                    scores = self.forward(RowsOf(item_features, items.repeat(nb)), item_features, pairs).view(nb, I)
+            yield u0, u1, scores                  # outside the with: a suspended generator must not hold the grad mode
+
+    def catalogue_scores(self, item_features, ratings, user_rows, item_ids=None, table=None, block_bytes=None):
+        """(U, I) fp32 scores of the users ``user_rows`` (rows of ``ratings``) against the catalogue ``item_features`` (I_c, F) — all
+        of it, or the positions ``item_ids`` — where the catalogue is both the candidate list and the rated-item list: what the
+        reference computes one user per request (webapp/backend.py:78-121).  Eval only.  ratings: a SparseRatings whose rows are
+        users and whose columns are catalogue positions (``pair_row`` unused), e.g. a ``SparseDynamicProvider.device_state``.
+
+        table=True: the cross-product route.  The attention logits depend on (candidate, rated item) only, so they are ONE (I_c, I_c)
+        table per weight version and catalogue (``logit_table``; native.attn_logits) and a user's attention is a lookup plus a
+        softmax-weighted sum on the matrix cores (native.attn_cross); the MLP tail is the fused scorer ``forward`` ends with.
+        table=False: the same blocks as (user, item) pairs through ``forward`` (the grouped kernels).  table=None: the table where
+        the cross kernel takes ``user_emb`` and 4 * I_c^2 <= ``cross_table_max_bytes``, else the pair route.  The two routes
+        agree to fp32 summation order."""
+        blocks = [s for _, _, s in self.catalogue_score_blocks(item_features, ratings, user_rows, item_ids, table, block_bytes)]
+        if not blocks:
+            I = item_features.shape[0] if item_ids is None else item_ids.numel()
+            return torch.empty((0, I), dtype=torch.float32, device=item_features.device)
+        return blocks[0] if len(blocks) == 1 else torch.cat(blocks)
+
     # ------------------------------------------------------------------------------------------ torch training path
     def _forward_train_hip(self, candidate_items, rated_items, user_matrix, return_attention_weights, pair_split=None):
         """attention_ncf.py:136-224 with autograd recording, on the HIP blocks: the Linear layers (LinearFn), the attention with its

@@ -2,7 +2,8 @@
 Each user's held-out items are ranked against the WHOLE catalogue with the training items excluded, exactly (no cap on the rank),
 and HR@K / Recall@K / NDCG@K / MRR / AUC are computed from those ranks.
 
-``rank_of_items``      the exact rank of every held-out item of every listed user (BasicNCF / MF / GraphNCF), through the fused rank
+``rank_of_items``      the exact rank of every held-out item of every listed user (BasicNCF / MF / GraphNCF; AttentionNCF with
+                       ``profiles=``, always score-then-rank), through the fused rank
                        kernels (``native.dot_rank`` for a dot-product readout, ``native.mlp_rank`` for an MLP readout: no score
                        matrix) or block by block through the model's scoring path and ``native.rank_rows``.  Stays on the device.
 ``ranking_metrics``    HR@K, Recall@K, NDCG@K, MRR and AUC from those ranks, in float64 on the ranks' device; one host read.
@@ -69,7 +70,7 @@ def _scored_ranks(model, r, users, seen, targets, block_bytes):
 
 def rank_of_items(model, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, torch.Tensor], item_ids: Optional[torch.Tensor] = None,
                   exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, *, graph=None, fused: Optional[bool] = None,
-                  max_targets: Optional[int] = None, block_bytes: int = BLOCK_BYTES):
+                  max_targets: Optional[int] = None, block_bytes: int = BLOCK_BYTES, profiles=None):
     """The exact rank of each user's held-out items against the whole ranked list, for a BasicNCF / MF / GraphNCF model.
 
     user_ids, item_ids, exclude, graph: as in ``top_k_items`` (int64 positions on the GPU; columns of the ranked list; a GraphNCF
@@ -84,17 +85,22 @@ def rank_of_items(model, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, to
     scoring, a folded first layer, an MLP shape without a fused instance, width > 256) and ``fused=False`` score the users block by
     block through the model (score blocks under ``block_bytes``) and rank with ``native.rank_rows``.  All routes give the same
     integers.
+    profiles: ``(item_features, ratings)`` for an AttentionNCF, as in ``top_k_items``: ``fused`` is then the route of
+    ``AttentionNCF.catalogue_scores`` (``table=``), its score blocks are ranked with ``native.rank_rows`` (there is no fused rank
+    kernel for this model), and ``max_targets`` is not needed: nothing is read back.
     max_targets: the largest number of targets of one user.  ``None`` reads it from ``targets`` — the one host read of this
     function; a caller in a loop passes it in, and then nothing synchronises with the host (a user with more targets than stated
     sets the sticky flag ``native.check_rank_overflow`` reads and has only its first ``max_targets`` ranked).  Users with more than
     ``native.RANK_MAX_TARGETS`` targets are split off and ranked through ``native.rank_rows``; building that row subset reads its
     size on the host."""
-    r = _resolve_ranked(model, user_ids, item_ids, exclude, graph)
+    r = _resolve_ranked(model, user_ids, item_ids, exclude, graph, profiles, fused)
     users, seen, B, dev = r.users, r.seen, r.B, r.users.device
     targets = _csr(targets, B, "targets")
     trow, tcol = targets
     if B == 0:
         return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    if r.profiles is not None:
+        return _scored_ranks(model, r, users, seen, targets, block_bytes)
     if max_targets is None:
         max_targets = int((trow[1:] - trow[:-1]).max().item())          # the one host read
     max_targets = int(max_targets)
@@ -197,7 +203,7 @@ def ranking_metrics(rank: torch.Tensor, targets_rowptr: torch.Tensor, ranked: to
 
 def eval_full_ranking(model, user_ids: torch.Tensor, targets, exclude=None, cutoffs: Sequence[int] = (5, 10, 20), **route) -> dict:
     """``ranking_metrics`` of ``rank_of_items(model, user_ids, targets, exclude=exclude, **route)`` (route: item_ids, graph, fused,
-    max_targets, block_bytes).  The metrics, the out-of-range flag and the target overflow flag come back in one host read; a set
+    max_targets, block_bytes, profiles).  The metrics, the out-of-range flag and the target overflow flag come back in one host read; a set
     flag raises (IndexError / OverflowError) as ``native.check_oob`` / ``native.check_rank_overflow`` do."""
     cutoffs = [int(K) for K in cutoffs]
     rank, ranked = rank_of_items(model, user_ids, targets, exclude=exclude, **route)

@@ -1,10 +1,11 @@
 """Top-K recommendation on the device: the library function behind the reference's web backend (webapp/backend.py:78-121).
 
-``top_k_items``        BasicNCF / MF (index providers) and GraphNCF: every listed user against every item (or a subset), scored
+``top_k_items``        BasicNCF / MF (index providers), GraphNCF and AttentionNCF (``profiles=``): every listed user against every item (or a subset), scored
                        block by block through the model's HIP scoring path and ranked by ncf_topk_rows — or scored and ranked in
                        one pass (no score matrix) by ncf_dot_topk for a dot-product readout and by ncf_mlp_topk for an MLP
                        readout.  Results stay on the device.
 ``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
+``rated_exclusion``    the same for an AttentionNCF's users: the items each listed user rated.
 ``recommend_for_user`` AttentionNCF: one user given as a Series of ratings against a catalogue, with the reference's arguments,
                        threshold rule and DataFrame columns (imdbID, score, because, attention).  Only k scores, k ids and the k
                        winners' attention rows cross to the host.
@@ -54,6 +55,8 @@ class _RankedList(NamedTuple):
     seen: Optional[tuple]        # the exclusion CSR (rowptr (B + 1) int64, col int32), or None
     B: int
     I: int
+    profiles: Optional[tuple] = None   # (item_features, ratings) of an AttentionNCF; None for every other model
+    table: Optional[bool] = None       # AttentionNCF: catalogue_scores' route (fused=None / True / False)
 
 
 def _csr(pair, B, what):
@@ -65,9 +68,47 @@ def _csr(pair, B, what):
     return rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous()
 
 
-def _resolve_ranked(model, user_ids, item_ids, exclude, graph) -> _RankedList:
+def _attention_model(model) -> bool:
+    from .neural_collaborative_filtering.models.attention_ncf import AttentionNCF
+    return isinstance(model, AttentionNCF)
+
+
+def _resolve_attention(model, user_ids, item_ids, exclude, profiles, fused) -> _RankedList:
+    """_resolve_ranked for an AttentionNCF: ``profiles = (item_features (I_c, F), ratings)``, users = rows of ``ratings``.  Every
+    refusal that needs no device comes before the first that does."""
+    if not (isinstance(profiles, (tuple, list)) and len(profiles) == 2 and torch.is_tensor(profiles[0]) and profiles[0].dim() == 2
+            and all(hasattr(profiles[1], a) for a in ("rowptr", "col", "val", "num_items"))):
+        raise ValueError("profiles = (item_features (I_c, F) tensor, ratings SparseRatings over the catalogue's positions)")
+    item_features, ratings = profiles
+    if not isinstance(ratings, SparseRatings):       # a provider's device state: every user's rated set as one CSR
+        ratings = SparseRatings(ratings.rowptr, ratings.col, ratings.val, ratings.num_items)
+    if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
+        raise ValueError("user_ids must be a 1-D int64 tensor of user positions")
+    if item_ids is not None and (item_ids.dtype != torch.int64 or item_ids.dim() != 1):
+        raise ValueError("item_ids must be a 1-D int64 tensor of item positions")
+    if ratings.num_items != item_features.shape[0]:
+        raise ValueError(f"ratings has {ratings.num_items} columns, the catalogue {item_features.shape[0]} rows")
+    n_items = item_features.shape[0]
+    model.cross_route(n_items, fused)               # fused=True outside the table route's limits: ValueError
+    require_gpu(user_ids, item_ids, item_features, ratings.rowptr)
+    dev = user_ids.device
+    items = torch.arange(n_items, dtype=torch.int64, device=dev) if item_ids is None else item_ids.contiguous()
+    B = user_ids.numel()
+    seen = None if exclude is None else _csr(exclude, B, "exclude")
+    return _RankedList(None, user_ids.contiguous(), items, item_ids is None, n_items, seen, B, items.numel(), (item_features, ratings), fused)
+
+
+def _resolve_ranked(model, user_ids, item_ids, exclude, graph, profiles=None, fused=None) -> _RankedList:
     """The checks top_k_items and rank_of_items make on the arguments they share, and the ranked list those arguments name."""
     _eval_only(model)
+    if _attention_model(model):
+        if profiles is None:
+            raise ValueError("an AttentionNCF ranks items for users given by their ratings: pass profiles=(item_features, ratings)")
+        if graph is not None:
+            raise ValueError(f"graph= is only taken by a GraphNCF, not by {type(model).__name__}")
+        return _resolve_attention(model, user_ids, item_ids, exclude, profiles, fused)
+    if profiles is not None:
+        raise ValueError(f"profiles= is only taken by an AttentionNCF, not by {type(model).__name__}")
     require_gpu(user_ids)
     dev = user_ids.device
     if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
@@ -97,6 +138,9 @@ def _resolve_ranked(model, user_ids, item_ids, exclude, graph) -> _RankedList:
 def _score_blocks(model, r: _RankedList, users, block_bytes):
     """Yields ``(b0, b1, scores (b1 - b0, I))``: the users scored against the ranked list through the model, in blocks of rows
     whose (user, item) score block stays under ``block_bytes``."""
+    if r.profiles is not None:           # AttentionNCF: the model blocks its own user_emb rows (4 * UE bytes per pair)
+        yield from model.catalogue_score_blocks(r.profiles[0], r.profiles[1], users, None if r.all_items else r.items, r.table, block_bytes)
+        return
     score = (lambda u, i: model(r.graph, u, i)) if r.graph is not None else model
     rows_per_block = max(1, int(block_bytes) // max(1, r.I * _PAIR_BYTES))
     for b0 in range(0, users.numel(), rows_per_block):
@@ -108,7 +152,7 @@ def _score_blocks(model, r: _RankedList, users, block_bytes):
 
 def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
                 exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES, *, graph=None,
-                fused: Optional[bool] = None):
+                fused: Optional[bool] = None, profiles=None):
     """The ``k`` best items of every user in ``user_ids`` for a BasicNCF / MF / GraphNCF model (int64 position inputs).
 
     user_ids: (B,) int64 user positions on the GPU — for a GraphNCF node positions as in ``GraphNCF.forward`` (users come after
@@ -124,10 +168,18 @@ def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.
     routes give the same bits.  Where a fused kernel's limits do not hold it falls back to score-then-select: k <= 128 for both;
     width <= 256 for the dot kernel; for the MLP kernel fp32 scoring, no folded first layer and an MLP shape with an
     ``ncf_score_fused`` instance.
+    profiles: ``(item_features (I_c, F), ratings)`` for an AttentionNCF — required for that model and refused for any other.  The
+    catalogue is both the candidate list and the rated-item list; ``ratings`` is a SparseRatings whose rows are users and whose
+    columns are catalogue positions (``SparseDynamicProvider.device_state``), ``user_ids`` are rows of it, ``item_ids`` / ``exclude``
+    keep their meaning (``rated_exclusion`` builds the users' rated items as ``exclude``).  ``fused`` then picks the route of
+    ``AttentionNCF.catalogue_scores``: ``None`` / ``True`` / ``False`` = its ``table=``; the score blocks are ranked by
+    ``native.topk_rows`` on either route (there is no fused score-and-select kernel for this model).
     Returns ``(scores (B, k) fp32, item_positions (B, k) int64, counts (B,) int32)`` on the device, each row in descending score
     order (ties: lower column first; NaN last); slots past ``counts`` hold position -1 and score -inf.  Score-then-select scores
     the users in blocks of rows whose (user, item) score block stays under ``block_bytes``; nothing synchronises with the host."""
-    r = _resolve_ranked(model, user_ids, item_ids, exclude, graph)
+    r = _resolve_ranked(model, user_ids, item_ids, exclude, graph, profiles, fused)
+    if r.profiles is not None:
+        fused = False                     # no fused score-and-select kernel for this model: catalogue_scores, then ncf_topk_rows
     if fused and not _dot_readout(model):
         raise ValueError(f"fused=True needs a dot-product readout; {type(model).__name__} here scores through an MLP")
     if fused and getattr(model, "scoring_dtype", torch.float32) != torch.float32:
@@ -226,6 +278,24 @@ def seen_items(graph, user_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tenso
     row = torch.repeat_interleave(torch.arange(user_ids.numel(), device=dev), cnt)
     pos = lo[row] + torch.arange(row.numel(), device=dev) - rowptr[row]
     return rowptr, s_dst[pos].to(torch.int32)
+
+
+def rated_exclusion(ratings: SparseRatings, user_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exclusion CSR ``(rowptr (B + 1) int64, col int32)`` of each listed user's rated items — the counterpart of ``seen_items``
+    for an AttentionNCF's ``profiles=`` (the web backend's ``ignore_seen=True``), in the column space of ``top_k_items``' default item
+    list (catalogue positions).  user_ids: (B,) int64 rows of ``ratings`` on the GPU.  Built on the device with torch ops; a row
+    lists its items in the order of ``ratings`` (a masked entry, outside the catalogue, excludes nothing)."""
+    require_gpu(user_ids, ratings.rowptr, ratings.col)
+    if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
+        raise ValueError("user_ids must be a 1-D int64 tensor of rows of ratings")
+    dev = user_ids.device
+    lo = ratings.rowptr[user_ids]
+    cnt = ratings.rowptr[user_ids + 1] - lo
+    rowptr = torch.zeros(user_ids.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(cnt, 0, out=rowptr[1:])
+    row = torch.repeat_interleave(torch.arange(user_ids.numel(), device=dev), cnt)
+    pos = lo[row] + torch.arange(row.numel(), device=dev) - rowptr[row]
+    return rowptr, ratings.col[pos].to(torch.int32)
 
 
 # ---------------------------------------------------------------------------------------- AttentionNCF: one user, one catalogue

@@ -467,6 +467,41 @@ int ncf_attn_tail(const float* dev_cand_emb, int64_t ldcand, int EA,
                   const float* dev_W1, const float* dev_b1, int N1, const float* dev_W2, const float* dev_b2, int N2,
                   const float* dev_w3, float b3, int weights_packed, float* dev_out, int64_t B, ncf_stream_t stream);
 
+/* Cross-product form of K3 for MANY users against ONE ranked list (full-catalogue top-K and ranks; the reference scores one user
+ * per request, webapp/backend.py:78-121, through models/attention_ncf.py:154-216).  The attention logit of a (candidate, rated item)
+ * pair never depends on the user, so the logits of a catalogue are one table per weight version:
+ *
+ * ncf_attn_logits   dev_st[e * ldst + i] = logit of candidate i < I_c against rated item e < I_r (fp32, ldst >= I_c; padding columns
+ *     are not written).  Modes and operand conventions exactly as ncf_attn_forward: dev_pc (I_c, A) carries the bias b0, dev_pr
+ *     (I_r, A); NCF_ATT_MLP b1 + sum_a w1[a] relu(pc + pr); NCF_ATT_MLP_SCALED the same on the 2^-64 / 2^64 scaled operands with relu
+ *     as the [0, 1] clamp; NCF_ATT_COS the dot of the already normalised rows; NCF_ATT_LINEAR (A = 1) pc + pr.  TRANSPOSED on
+ *     purpose: for a fixed rated item, 64 consecutive candidates are one 256-byte load.  Every logit is one fmaf chain over
+ *     a = 0 .. A-1 in that order (+ b1 last): the table is bitwise independent of the tiling and of I_c / I_r.  No alignment needed.
+ *
+ * ncf_attn_cross    dev_out[(u * I + j) * ldout + f] = bias[f] + sum_e softmax_e(ST[col_e, cand_j]) val_e feat[col_e, f]
+ *     for the listed users u < U and the columns j < I of the ranked list: the user_emb of pair (u, j), the quantity
+ *     ncf_attn_forward writes for that pair.  The users' rated sets are a CSR of n_rows rows (dev_rowptr int64, dev_col int32 = rows
+ *     of dev_st and of dev_feat, dev_val); dev_user_rows (U,) int64 = the CSR row of each listed user (repeats, any order);
+ *     dev_cand_ids (I,) int64 = the columns of dev_st that are ranked, or NULL for 0 .. I-1 (then I <= I_c); dev_feat (I_r, Fdim)
+ *     the projected rows rated_items @ Wu^T, dev_out_bias (Fdim) or NULL.  An entry with col outside [0, I_r) is masked; an empty or
+ *     fully masked row (and a row whose logits are all -inf: softmax denominator 0) gives exactly the bias bits; a dev_user_rows or
+ *     dev_cand_ids value out of range sets *dev_oob_flag (sticky, may be NULL) and that pair's row is written as the bias.
+ *     One workgroup per (user, 128 candidates): the exact row maximum first, then exp / sum / aggregation per tile of entries
+ *     with the aggregation on v_mfma_f32_32x32x2_f32; no atomics, one fixed summation order: bitwise repeatable.
+ *     Shapes: ncf_attn_cross_supported(Fdim) = 1 for Fdim % 32 == 0, 32 <= Fdim <= 256, else NCF_EUNSUPPORTED (as the call then
+ *     returns; nothing is launched).  ncf_attn_cross_plan names what a call would launch, host only: *nb = Fdim / 32 (the kernel
+ *     instance attn_cross_kernel<nb, entry_tile>), *entry_tile = entries per staged tile (64 for nb <= 4, else 32), *lds_bytes,
+ *     *grid_x = U * ceil(I / 128); any output pointer may be NULL; status as ncf_attn_cross's for the shape. */
+int ncf_attn_logits(int mode, const float* dev_pc, int64_t ldpc, int64_t I_c, const float* dev_pr, int64_t ldpr, int64_t I_r, int A,
+                    const float* dev_w1, float b1, float* dev_st, int64_t ldst, ncf_stream_t stream);
+int ncf_attn_cross_supported(int Fdim);
+int ncf_attn_cross_plan(int Fdim, int64_t U, int64_t I, int* nb, int* entry_tile, int64_t* lds_bytes, int64_t* grid_x);
+int ncf_attn_cross(const float* dev_st, int64_t ldst, int64_t I_r, int64_t I_c,
+                   const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t n_rows,
+                   const int64_t* dev_user_rows, int64_t U, const int64_t* dev_cand_ids, int64_t I,
+                   const float* dev_feat, int64_t ldfeat, int Fdim, const float* dev_out_bias,
+                   float* dev_out, int64_t ldout, int32_t* dev_oob_flag, ncf_stream_t stream);
+
 /* Dense user_matrix -> CSR with shared rows, on the stream (no size is read by the host).  The reference passes AttentionNCF.forward a
  * dense (B, I) user_matrix in which a user's row is repeated for each of their samples (datasets/dynamic_datasets.py:24-40,
  * content_providers/dynamic_profiles_provider.py:55-71; one row for every candidate in webapp/backend.py:78-121) and keeps the
