@@ -1,5 +1,7 @@
 """Dev tool (GPU box): interleaved in-process A/B of the bf16 fused kernel (cfg-5 shape: E = 128, MLP 256-256-128-1,
-B = 65536) built with different -D flags."""
+B = 65536) built with different -D flags.  NCF_BF16_KERNEL=ws|stream|ws8 forces the kernel in every variant (default: the
+library's own choice, ws8 at this shape); the stamps of a -DNCF_BF16_STAMP=1 variant are decoded for ws and stream
+(tools/stamp_ws8.py decodes the 8-wave kernel's)."""
 import ctypes
 import os
 import subprocess
@@ -24,6 +26,7 @@ def build_variant(i, flags):
 
 def main():
     variants = sys.argv[1:] or [""]
+    kernel = os.environ.get("NCF_BF16_KERNEL", "auto")
     dev = torch.device("cuda:0")
     U, I, E, Bsz = int(os.environ.get("AB_U", 4_000_000)), int(os.environ.get("AB_I", 1_000_000)), 128, int(os.environ.get("AB_B", 65536))
     g = torch.Generator(device=dev).manual_seed(1)
@@ -39,9 +42,10 @@ def main():
     libs = []
     for i, fl in enumerate(variants):
         lib = ctypes.CDLL(build_variant(i, fl))
-        for name in ("ncf_mlp_packed_bytes", "ncf_mlp_pack", "ncf_score_fused"):
+        for name in ("ncf_mlp_packed_bytes", "ncf_mlp_pack", "ncf_score_fused", "ncf_set_option"):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = native.SIGNATURES[name]
+        assert lib.ncf_set_option(b"bf16_kernel", native.OPTION_VALUES["bf16_kernel"][kernel]) == 0
         nbytes = lib.ncf_mlp_packed_bytes(1, 3, d)
         blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         W = (ctypes.c_void_p * 3)(*[w.data_ptr() for w in ws])
@@ -77,9 +81,11 @@ def main():
             torch.cuda.synchronize()
             times[vi].append(e0.elapsed_time(e1) * 1e3 / reps)
     for vi, fl in enumerate(variants):
-        if "NCF_BF16_STAMP=1" in fl:
+        if "NCF_BF16_STAMP=1" in fl and kernel not in ("ws", "stream"):
+            print("    stamps not read: the buffer below is laid out for NCF_BF16_KERNEL=ws or stream")
+        elif "NCF_BF16_STAMP=1" in fl:
             lib, blob = libs[vi]
-            ws = "NCF_BF16_WS=0" not in fl
+            ws = kernel != "stream"
             ntiles = 256 * 8 if ws else Bsz // 32
             dbg = torch.zeros(ntiles * 8 + 256, dtype=torch.int64, device=dev)
             lib.ncf_dev_set_bf16_debug_buffer.argtypes = [ctypes.c_void_p]

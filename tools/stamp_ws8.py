@@ -40,7 +40,7 @@ def main():
     a, b = d[:, :4], d[:, 4:]
     per = a[:, :, 1:, 0] - a[:, :, :-1, 0]
     print(f"phase period: median {per.median().item():.0f} cycles, mean {per.mean().item():.0f}  (each stamp costs the wave ~150-200 cycles)")
-    for nm, x, i0, i1 in (("A stream (32 or 64 MFMAs + pack)", a, 0, 1), ("A locate + row DMAs", a, 1, 4), ("A vmcnt wait", a, 4, 2), ("A barrier wait", a, 2, 3),
+    for nm, x, i0, i1 in (("A stream (64 MFMAs + pack)", a, 0, 1), ("A barrier wait", a, 1, 3),
                           ("B head + k-steps 0..5 (locate, ids DMA, row DMAs at 1 and 4)", b, 0, 4), ("B k-steps 6..15", b, 4, 1),
                           ("B vmcnt wait", b, 1, 2), ("B barrier wait", b, 2, 3)):
         v = x[..., i1] - x[..., i0]
