@@ -57,6 +57,8 @@ SIGNATURES = {
                                       _c_i64, _c_p, _c_int, _c_p, ctypes.c_uint32, ctypes.c_float, _c_p]),
     "ncf_degree_accumulate": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
     "ncf_edge_coef": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
+    "ncf_edge_keep": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, ctypes.c_float, ctypes.c_uint32, _c_p,
+                               _c_p, _c_p, _c_p]),
     "ncf_scale_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, ctypes.c_float, _c_p, _c_i64, _c_p]),
     "ncf_attn_forward": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, ctypes.c_float, _c_p, _c_p, _c_p,
                                   _c_i64, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p]),
@@ -666,6 +668,43 @@ def edge_coef(src: torch.Tensor, dst: torch.Tensor, attr: Optional[torch.Tensor]
     coef = torch.empty(src.numel(), dtype=torch.float32, device=src.device)
     _check(lib.ncf_edge_coef(_ptr(src), _ptr(dst), _ptr(attr), _ptr(deg), src.numel(), deg.numel(), _ptr(coef), _stream(src)))
     return coef
+
+
+def edge_keep(segptr: torch.Tensor, row_of: Optional[torch.Tensor], N: int, col: torch.Tensor, attr: Optional[torch.Tensor],
+              pair_key: Optional[torch.Tensor] = None, targets_sorted: Optional[torch.Tensor] = None, slot: Optional[torch.Tensor] = None,
+              p: float = 0.0, seed: int = 0, node_keep: Optional[torch.Tensor] = None):
+    """The edges one training step keeps (ncf_edge_keep, "THE KEEP RULE" of include/ncf_abi.h) over the level-0 segments of a CSR by
+    destination: returns (w (E,) float32 = the entry's weight where kept, 0 where removed; deg (N,) int32 = kept entries per row).
+    ``targets_sorted``: ascending user * N + item keys of the batch (None / empty: no target masking); ``slot`` / ``p`` / ``seed``:
+    message dropout; ``node_keep``: (N,) uint8 mask of node dropout (None: every node kept)."""
+    lib = load_library()
+    _dev(col, "col")
+    E = col.numel()
+    if segptr.dtype != torch.int64 or col.dtype != torch.int32 or not segptr.is_contiguous() or not col.is_contiguous():
+        raise TypeError("segptr must be contiguous int64 and col contiguous int32")
+    if row_of is not None and row_of.dtype != torch.int32:
+        raise TypeError("row_of must be int32")
+    n_seg = segptr.numel() - 1
+    if row_of is not None and row_of.numel() != n_seg:
+        raise ValueError("row_of must hold one row per segment")
+    if row_of is None and n_seg != N:
+        raise ValueError("without row_of the segments are the N rows")
+    n_targets = 0 if targets_sorted is None else targets_sorted.numel()
+    for t, dt, what in ((attr, torch.float32, "attr"), (slot, torch.int32, "slot"), (pair_key, torch.int64, "pair_key")):
+        if t is not None and (t.dtype != dt or t.numel() != E or not t.is_contiguous()):
+            raise TypeError(f"{what} must be contiguous {dt}, one element per CSR entry")
+    if n_targets and (targets_sorted.dtype != torch.int64 or not targets_sorted.is_contiguous()):
+        raise TypeError("targets_sorted must be contiguous int64")
+    if node_keep is not None and (node_keep.dtype != torch.uint8 or node_keep.numel() != N or not node_keep.is_contiguous()):
+        raise TypeError("node_keep must be contiguous uint8, one byte per node")
+    w = torch.empty(E, dtype=torch.float32, device=col.device)
+    deg = torch.empty(N, dtype=torch.int32, device=col.device)
+    if E == 0:                                # an edgeless graph: nothing to keep, and empty tensors carry null pointers
+        return w, deg.zero_()
+    _check(lib.ncf_edge_keep(_ptr(segptr), _ptr(row_of), n_seg, N, _ptr(col), _ptr(attr), _ptr(pair_key),
+                             _ptr(targets_sorted) if n_targets else None, n_targets, _ptr(slot), float(p), int(seed) & 0xFFFFFFFF,
+                             _ptr(node_keep), _ptr(w), _ptr(deg), _stream(col)))
+    return w, deg
 
 
 def scale_rows(x: torch.Tensor, divisor: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:

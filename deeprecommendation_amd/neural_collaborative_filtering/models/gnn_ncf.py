@@ -12,8 +12,10 @@ Scoring (eval, no-grad) runs on the HIP kernels:
   * readout = fused gather(item) ‖ gather(user) -> MLP (gnn_ncf.py:354-362) or gather-dot (:365).
 Node numbering follows the reference: items first, user node id = num_items + rank (graph_providers.py:79-80).
 
-Training (module.training / autograd recording) keeps to differentiable torch ops, including the reference's
-train-only edge masking, node dropout and message dropout (gnn_ncf.py:246-296,314-333,369-378).
+Training (module.training / autograd recording) of LightGCN layers on CUDA tensors runs on the HIP autograd blocks; the
+reference's train-only edge masking, node dropout and message dropout (gnn_ncf.py:246-296,314-333,369-378) only choose which
+edges take part in a step, so they become per-entry weights of the unchanged CSR (ncf_edge_keep).  CPU tensors, LightGAT and
+``train_with_torch_ops`` keep to differentiable torch ops.
 LightGATConv (a SURVEY §8(f) "next" row) scores on the HIP path too: edge softmax kernel + the same SpMM.
 """
 from typing import Optional
@@ -164,21 +166,26 @@ class PreparedGraph:
         return self._transposed
 
     def train_state(self):
-        """Per-graph tensors of the training step, built on first use: destination and source of every CSR entry and its
-        (user, item) key for the target-edge masking (gnn_ncf.py:314-320, 369-378)."""
+        """Per-graph tensors of the training step, built on first use: destination and source of every CSR entry, its
+        (user, item) key for the target-edge masking (gnn_ncf.py:314-320, 369-378) and its message-dropout slot (:246-279; the
+        keep rule of include/ncf_abi.h): edge j of either list has slot j when the lists are symmetric (same length, both
+        attributes present: one mask bit removes both directions), else edge j of item2user has slot E1 + j."""
         if self._train is None:
             u2i, i2u = self._edges
             order = torch.argsort(torch.cat([u2i[1], i2u[1]]), stable=True)     # the CSR's own order (see __init__)
-            pair_key = torch.cat([u2i[0] * self.N + u2i[1], i2u[1] * self.N + i2u[0]])[order]
+            pair_key = torch.cat([u2i[0] * self.N + u2i[1], i2u[1] * self.N + i2u[0]])[order].contiguous()
             dst_of = torch.repeat_interleave(torch.arange(self.N, device=self.col.device), self.counts)
-            self._train = (dst_of, self.col.long(), pair_key)
+            E1, E2 = u2i.shape[1], i2u.shape[1]
+            symmetric = E1 == E2 and self.attr is not None
+            slot = torch.cat([torch.arange(E1, device=self.col.device), torch.arange(E2, device=self.col.device) + (0 if symmetric else E1)])
+            self._train = (dst_of, self.col.long(), pair_key, slot[order].to(torch.int32).contiguous())
         return self._train
 
     def masked_coef(self, user_ids, item_ids):
         """Coefficients of one training batch with the batch's target edges removed in both directions (gnn_ncf.py:314-320):
         the degrees are those of the REMAINING edges (the reference recomputes them from the masked edge lists, :47-50), a
         removed edge gets coefficient 0 — the CSR itself stays as it is."""
-        dst_of, src, pair_key = self.train_state()
+        dst_of, src, pair_key, _ = self.train_state()
         masked = torch.isin(pair_key, user_ids.long() * self.N + item_ids.long())
         deg = (self.counts - torch.bincount(dst_of[masked], minlength=self.N)).to(torch.float32)
         dis = deg.pow(-0.5)
@@ -186,6 +193,21 @@ class PreparedGraph:
         norm = dis[src] * dis[dst_of]
         coef = norm if self.attr is None else self.attr * norm
         return torch.where(masked, torch.zeros_like(coef), coef).contiguous()
+
+    def batch_coef(self, user_ids, item_ids, mask_targets=True, node_keep=None, message=None):
+        """Coefficients of one training batch under the reference's three train-only edge removals (gnn_ncf.py:246-296, 314-320):
+        the batch's target edges (``mask_targets``), node dropout (``node_keep``: (N,) uint8, see GraphNCF._draw_node_keep) and
+        message dropout (``message`` = (p, seed)), applied by ncf_edge_keep in one pass over the CSR, which also counts the
+        degrees of the remaining edges; ncf_edge_coef then normalises the kept weights.  A removed edge and every edge of a row
+        left without edges get coefficient 0 — the CSR itself stays as it is.  Nothing here needs a value on the host."""
+        dst_of, src, pair_key, slot = self.train_state()
+        targets = None
+        if mask_targets:
+            targets = torch.sort(user_ids.long() * self.N + item_ids.long()).values.contiguous()   # duplicates stay: no size on the host
+        p, seed = message if message is not None else (0.0, 0)
+        w, deg = native.edge_keep(self.segptr, self.row_of, self.N, self.col, self.attr, pair_key, targets,
+                                  slot if p > 0 else None, p, seed, node_keep)
+        return native.edge_coef(src, dst_of, w, deg.to(torch.float32))
 
 
 class _ConvBase(nn.Module):
@@ -426,11 +448,39 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
         return ei[:, keep], (attr[keep] if attr is not None else None)
 
     def _hip_training_possible(self, graph, userIds) -> bool:
-        """The training step runs on the HIP autograd blocks for LightGCN layers on CUDA tensors; node / message dropout (edge
-        sets redrawn per batch on the host, gnn_ncf.py:246-296) and LightGAT keep to the torch ops, as do hetero graphs whose
-        sources are not split items / users (two stacked hoisted tables)."""
-        return (userIds.is_cuda and not getattr(self, "train_with_torch_ops", False) and self.convType == 'LightGCN'
-                and not (self.training and ((self.node_dropout or 0.0) > 0.0 or (self.message_dropout or 0.0) > 0.0)))
+        """The training step runs on the HIP autograd blocks for LightGCN layers on CUDA tensors, node / message dropout
+        included (edge sets redrawn per call on the device, gnn_ncf.py:246-296 -> PreparedGraph.batch_coef); LightGAT keeps to
+        the torch ops, as do hetero graphs whose sources are not split items / users (two stacked hoisted tables)."""
+        return userIds.is_cuda and not getattr(self, "train_with_torch_ops", False) and self.convType == 'LightGCN'
+
+    @staticmethod
+    def _draw_node_keep(N, user_ids, item_ids, p, node_seed):
+        """Node dropout of gnn_ncf.py:281-296 as a byte mask (N,) on the ids' device, by the keep rule of include/ncf_abi.h:
+        every batch node is kept, and of the other nodes the K = int((1.0 - p) * (N - nb)) smallest by (key(n), n),
+        key(n) = lowbias32(n * 0x9E3779B1 ^ node_seed) in uint32 arithmetic (carried in int64, masked to 32 bits; products are
+        taken in 16-bit halves so that no intermediate leaves int64).  One sort over N; nb and K stay on the device."""
+        dev = user_ids.device
+        M = 0xFFFFFFFF
+
+        def mul32(x, c):
+            return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & M
+
+        n = torch.arange(N, dtype=torch.int64, device=dev)
+        x = mul32(n, 0x9E3779B1) ^ (int(node_seed) & M)
+        x = x ^ (x >> 16)
+        x = mul32(x, 0x7feb352d)
+        x = x ^ (x >> 15)
+        x = mul32(x, 0x846ca68b)
+        key = x ^ (x >> 16)
+        ids = torch.cat((item_ids.long(), user_ids.long()))
+        valid = (ids >= 0) & (ids < N)                 # an id out of range marks no node here: the step's row gather reports it
+        in_batch = torch.zeros(N, dtype=torch.int32, device=dev).index_put_((ids.clamp(0, N - 1),), valid.to(torch.int32), accumulate=True) > 0
+        nb = in_batch.sum()
+        K = ((1.0 - float(p)) * (N - nb).to(torch.float64)).floor().to(torch.int64)     # int() of the reference: the product is >= 0
+        composite = torch.where(in_batch, torch.full_like(key, torch.iinfo(torch.int64).max), (key << 31) | n)   # batch nodes sort last
+        rank = torch.empty_like(n)
+        rank[torch.sort(composite).indices] = n
+        return (in_batch | (rank < K)).to(torch.uint8).contiguous()
 
     def _forward_train_hip(self, graph, userIds, itemIds, mask_targets):
         """gnn_ncf.py:298-367 with autograd recording, on the HIP blocks: per-node hoisted Linear (LinearFn), aggregation
@@ -453,10 +503,20 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
 
         x = torch.vstack([feats(graph.item_features, self.item_embeddings[0]), feats(graph.user_features, self.user_embeddings[0])])
         userIds, itemIds = userIds.long().contiguous(), itemIds.long().contiguous()
-        coef = prep.masked_coef(userIds, itemIds) if (self.training and mask_targets) else prep.coef
         conv = self.gnn_convs[0]
         p = float((conv.W if not conv.hetero else conv.user2item_W)[1].p) if self.training else 0.0
         seed0 = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0     # host generator: no device sync
+        p_node = float(self.node_dropout or 0.0) if self.training else 0.0
+        p_msg = float(self.message_dropout or 0.0) if self.training else 0.0
+        if p_node > 0.0 or p_msg > 0.0:
+            # one edge set per call, shared by all layers (gnn_ncf.py:322-333); seeds drawn after seed0: seed0, node_seed, seed
+            node_keep = None
+            if p_node > 0.0:
+                node_keep = self._draw_node_keep(prep.N, userIds, itemIds, p_node, int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+            message = (p_msg, int(torch.randint(0, 2 ** 31 - 1, (1,)).item())) if p_msg > 0.0 else None
+            coef = prep.batch_coef(userIds, itemIds, mask_targets, node_keep, message)
+        else:
+            coef = prep.masked_coef(userIds, itemIds) if (self.training and mask_targets) else prep.coef
         hs = [x]
         for layer in range(len(self.gnn_convs)):
             if not conv.hetero:

@@ -276,6 +276,44 @@ int ncf_degree_accumulate(const int64_t* dev_dst, int64_t E, int64_t N, float* d
  * (gnn_ncf.py:49-50,54,58,66 and the product order of :91 / :93). */
 int ncf_edge_coef(const int64_t* dev_src, const int64_t* dev_dst, const float* dev_attr,
                   const float* dev_deg, int64_t E, int64_t N, float* dev_coef, ncf_stream_t stream);
+
+/* Which edges one GraphNCF training step keeps (gnn_ncf.py:246-296, 314-320): the batch's target edges, node dropout and message
+ * dropout only choose the edges that take part in a step.  The CSR never changes: a removed edge is an edge of weight 0, and the
+ * degrees are those of the remaining edges.  One pass over the level-0 segments of the CSR by destination (dev_segptr / dev_row_of
+ * of ncf_spmm_csr, one wave per segment; dev_row_of == NULL: segment s is row s).  For entry e with source dev_col[e] and
+ * destination = its segment's row:
+ *     kept      = dev_pair_key[e] is not among dev_targets_sorted[0 .. n_targets)              (n_targets = 0: no target masking)
+ *                 AND dev_node_keep[src] & dev_node_keep[dst]                                   (dev_node_keep = NULL: no node dropout)
+ *                 AND the message rule below on dev_slot[e]                                     (thr = 0: dev_slot may be NULL)
+ *     w_out[e]  = kept ? (dev_attr ? dev_attr[e] : 1.f) : 0.f
+ *     deg_out[row] = number of kept entries of the row       (cleared by this call; each segment adds its count with one integer
+ *                    atomic add — integer sums do not depend on arrival order, so the result is bitwise reproducible)
+ * dev_targets_sorted: the batch's user * N + item keys in ascending order, duplicates allowed (a per-lane binary search).
+ * dev_pair_key[e]: the same key of entry e's edge, whichever direction it runs.  A source outside [0, N) counts as not kept when
+ * dev_node_keep is given.  w_out then goes into ncf_edge_coef as attr with deg_out (as floats) as deg: a row left with no edge
+ * has dis = 0 there, so all its coefficients are 0.
+ *
+ * THE KEEP RULE (part of this ABI; restated in numpy by tests/edge_keep_ref.py, which the kernel is held to bit for bit).
+ *   Message dropout (gnn_ncf.py:246-279: an edge is kept with probability 1 - p, nothing is rescaled).  In uint32 arithmetic:
+ *       thr = (uint32)(p * 65536.f + 0.5f)   evaluated in fp32, clamped to 65535          (as in THE MASK above)
+ *       h   = lowbias32((uint32)slot * 0x9E3779B1 ^ (uint32)seed)                          (lowbias32: under ncf_sample_negatives)
+ *       kept iff (h >> 16) >= thr
+ *     slot of edge j of user2item_edge_index is j.  slot of edge j of item2user_edge_index is also j when both lists have the
+ *     same length and both edge attributes are present (the reference's "symmetrical" branch :254-264: one mask bit removes both
+ *     directions), else E1 + j with E1 the length of user2item_edge_index (independent masks, :266-277).  The condition is
+ *     evaluated on the graph's own lists, not on the lists after target masking.
+ *   Node dropout (gnn_ncf.py:281-296: subgraph over the kept nodes).  Every node of the batch is kept; of the other nodes exactly
+ *     K = int((1.0 - p) * (N - nb)) (float64) are kept, nb = number of distinct batch nodes: the K smallest by (key(n), n) with
+ *       key(n) = lowbias32((uint32)n * 0x9E3779B1 ^ (uint32)node_seed).
+ *     The caller builds the byte mask dev_node_keep (N) from this rule; an edge survives iff both its ends are kept.
+ * p outside [0, 1] or not finite, negative sizes, a null required pointer (dev_slot with thr > 0 included): NCF_EINVAL, and
+ * nothing is launched. */
+int ncf_edge_keep(const int64_t* dev_segptr, const int32_t* dev_row_of, int64_t n_seg, int64_t N,
+                  const int32_t* dev_col, const float* dev_attr,
+                  const int64_t* dev_pair_key, const int64_t* dev_targets_sorted, int64_t n_targets,
+                  const int32_t* dev_slot, float p, uint32_t seed,
+                  const uint8_t* dev_node_keep,
+                  float* dev_w_out, int32_t* dev_deg_out, ncf_stream_t stream);
 /* LightGAT edge attention over a CSR-by-destination graph (models/gnn_ncf.py:151-177; PyG softmax(src, index) =
  * exp(src - max_group) / (sum_group + 1e-16)):
  *   dev_out[e] = (attr ? attr[e] : 1) * softmax over the edges of e's destination row of s[col[.]]
