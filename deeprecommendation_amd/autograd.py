@@ -9,6 +9,12 @@ layers; loss, dropout masks and the optimizer stay torch ops (the reference's tr
   SpmmFn         : LightGCN propagation y = A z (ncf_spmm_csr on the CSR by destination); backward dz = A^T dy = the SAME
                    kernel on the CSR by source (gnn_ncf.py:74-94 through autograd in the reference); optional per-edge
                    message dropout regenerated from a hash in both directions (ncf_spmm_csr_dropout)
+  GatherPairOrderedFn : GatherConcatFn on one shared table with an ORDERED backward (stable sort of the ids + the segmented SpMM
+                   instead of float atomics): the LightGAT step's readout, so a seeded run repeats itself bit for bit (table
+                   widths that are a multiple of 4; others keep the atomics)
+  GatSpmmFn      : LightGAT aggregation over the edges a step keeps: ncf_gat_edge_softmax + the SpmmFn kernels; backward dz as
+                   SpmmFn, ds through ncf_gat_edge_grad (per-edge dot product, softmax backward per destination) and
+                   ncf_gat_source_reduce (ordered sum per source over the transposed CSR)
   AttnFn         : grouped item-item attention (ncf_attn_forward_grouped) with its backward (ncf_attn_backward_grouped)
 """
 import torch
@@ -155,6 +161,84 @@ class SpmmFn(torch.autograd.Function):
         drop = None if ctx.dropout is None or ctx.dropout[0] <= 0 else (ctx.dropout[0], ctx.dropout[1], eid)
         dZ = csr_t.spmm(dY.contiguous(), coef=coef[eid.long()], dropout=drop)   # same mask: entry e of A^T carries edge id eid[e]
         return dZ, None, None, None
+
+
+class GatherPairOrderedFn(torch.autograd.Function):
+    """cat(table[idxA], table[idxB]) — GatherConcatFn with both halves read from ONE table — whose backward adds the 2 B gradient
+    rows of each table row in a fixed order: the ids are sorted (stable), and the sorted positions are the entries of a CSR by
+    table row that the segmented SpMM sums without atomics (ncf_scatter_add_rows adds with float atomics, so its last bits depend
+    on arrival order).  Ids outside the table get no gradient (the forward gather reports them).  The SpMM takes rows of at most 256
+    floats, so wider tables (concat readouts) go through it in column blocks of 256.  A width that is no multiple of 4 cannot
+    use the SpMM's 16-byte lanes and keeps the scatter kernel: such a step is NOT repeatable to the last bit."""
+
+    @staticmethod
+    def forward(ctx, table, idxA, idxB):
+        ctx.save_for_backward(idxA, idxB)
+        ctx.shape = tuple(table.shape)
+        t = table.contiguous()
+        return native.gather_concat(t, idxA, t, idxB)
+
+    @staticmethod
+    def backward(ctx, dX):
+        idxA, idxB = ctx.saved_tensors
+        rows, e = ctx.shape
+        dX = dX.contiguous()
+        if e % 4:
+            d = torch.zeros((rows, e), dtype=torch.float32, device=dX.device)
+            native.scatter_add_rows(dX[:, :e], idxA, d)
+            native.scatter_add_rows(dX[:, e:], idxB, d)
+            return d, None, None
+        src = torch.cat((dX[:, :e], dX[:, e:]), dim=0)                # row p < B: the idxA half of pair p; row B + p: its idxB half
+        idx = torch.cat((idxA, idxB))
+        idx = torch.where((idx >= 0) & (idx < rows), idx, torch.full_like(idx, rows))       # bad ids: a spare row that is dropped
+        rowptr = torch.zeros(rows + 2, dtype=torch.int64, device=dX.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(idx, minlength=rows + 1), 0)
+        order = torch.argsort(idx, stable=True).to(torch.int32)
+        d = torch.empty((rows + 1, e), dtype=torch.float32, device=dX.device)
+        for c0 in range(0, e, 256):
+            c1 = min(c0 + 256, e)
+            native.spmm_csr(rowptr, None, order, None, src[:, c0:c1], rows + 1, y=d[:, c0:c1])
+        return d[:rows], None, None
+
+
+class GatSpmmFn(torch.autograd.Function):
+    """y (N, D) = sum over the KEPT edges into each destination of attr_e * alpha_e * [dropout mask / (1 - p)] * z[src_e], alpha the
+    per-destination softmax of the source scores s[src_e] over the kept edges  —  one LightGAT aggregation (gnn_ncf.py:151-177).
+    ``z`` (N, D) is the hoisted per-node Linear, ``s`` (N, 1) the source half of AttNet applied per node; ``prep`` the PreparedGraph;
+    ``keep`` the per-entry 1 / 0 indicator of the step's edge set (native.edge_keep with attr = None) or None; ``dropout`` = (p, seed)
+    or None.  ``att_zero_params``: AttNet's weight(s) and bias(es), taken only to hand them a gradient that is exactly zero — the
+    destination half of the score and the bias are constant inside a softmax group and cancel (the source half of the weight gets
+    its real gradient through ``s``), so an optimizer sees a gradient for every parameter, as on the torch path."""
+
+    @staticmethod
+    def forward(ctx, z, s, prep, keep, dropout, *att_zero_params):
+        z, sv = z.contiguous(), s.contiguous().view(-1)
+        seg = prep.softmax_segments()
+        seg_first = None if seg is None else seg[2]
+        alpha, coef = native.gat_edge_softmax(prep.segptr, prep.row_of, seg_first, prep.N, prep.col, prep.attr, keep, sv,
+                                              workspace=prep.gat_workspace())
+        ctx.prep, ctx.dropout, ctx.seg_first, ctx.s_shape = prep, dropout, seg_first, tuple(s.shape)
+        ctx.save_for_backward(z, alpha, coef, *att_zero_params)
+        drop = None if dropout is None or dropout[0] <= 0 else (dropout[0], dropout[1], None)
+        return prep.csr.spmm(z, coef=coef, dropout=drop)
+
+    @staticmethod
+    def backward(ctx, dY):
+        z, alpha, coef, *zero_params = ctx.saved_tensors
+        prep = ctx.prep
+        dY = dY.contiguous()
+        csr_t, eid = prep.transposed()
+        on = ctx.dropout is not None and ctx.dropout[0] > 0
+        dZ = ds = None
+        if ctx.needs_input_grad[0]:
+            dZ = csr_t.spmm(dY, coef=coef[eid.long()], dropout=(ctx.dropout[0], ctx.dropout[1], eid) if on else None)
+        if ctx.needs_input_grad[1]:
+            p, seed = ctx.dropout if on else (0.0, 0)
+            dlogit = native.gat_edge_grad(prep.segptr, prep.row_of, ctx.seg_first, prep.N, prep.col, prep.attr, alpha, dY, z, p, seed,
+                                          workspace=prep.gat_workspace())
+            ds = native.gat_source_reduce(csr_t, eid, dlogit).view(ctx.s_shape)
+        zeros = tuple(torch.zeros_like(q) if ctx.needs_input_grad[5 + k] else None for k, q in enumerate(zero_params))
+        return (dZ, ds, None, None, None) + zeros
 
 
 class AttnFn(torch.autograd.Function):

@@ -105,6 +105,12 @@ SIGNATURES = {
     "ncf_edge_softmax_csr": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_edge_softmax_segmented_workspace_bytes": (_c_size, [_c_i64, _c_i64]),
     "ncf_edge_softmax_segmented": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_size, _c_p]),
+    "ncf_gat_edge_softmax_workspace_bytes": (_c_size, [_c_i64, _c_i64]),
+    "ncf_gat_edge_softmax": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_size, _c_p]),
+    "ncf_gat_edge_grad_workspace_bytes": (_c_size, [_c_i64, _c_i64]),
+    "ncf_gat_edge_grad": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int,
+                                   ctypes.c_float, ctypes.c_uint32, _c_p, _c_p, _c_size, _c_p]),
+    "ncf_gat_source_reduce": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
     "ncf_score_fused_partial_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_p]),
     "ncf_score_fused_partial_in_lds": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_p]),
     "ncf_layer1_partial": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
@@ -1320,6 +1326,113 @@ def edge_softmax_csr(rowptr: torch.Tensor, col: torch.Tensor, attr: Optional[tor
                                               _ptr(out), _ptr(ws), nbytes, _stream(s)))
         return out
     _check(lib.ncf_edge_softmax_csr(_ptr(rowptr), _ptr(col), _ptr(attr), _ptr(s), rowptr.numel() - 1, s.numel(), _ptr(out), _stream(s)))
+    return out
+
+
+def _gat_segments(fn, segptr, row_of, seg_first, n_rows, col, per_entry):
+    """The refusals the three LightGAT wrappers share: level-0 segments of a CSR by destination and its per-entry arrays."""
+    if segptr.dtype != torch.int64 or col.dtype != torch.int32 or not segptr.is_contiguous() or not col.is_contiguous():
+        raise TypeError(f"{fn}: segptr must be contiguous int64 and col contiguous int32")
+    n_seg = segptr.numel() - 1
+    if row_of is not None:
+        if row_of.dtype != torch.int32 or row_of.numel() != n_seg or not row_of.is_contiguous():
+            raise TypeError(f"{fn}: row_of must be contiguous int32, one row per segment")
+        if seg_first is None or seg_first.dtype != torch.int64 or seg_first.numel() != n_rows + 1 or not seg_first.is_contiguous():
+            raise TypeError(f"{fn}: split rows need seg_first, contiguous int64 with n_rows + 1 entries")
+    elif n_seg != n_rows:
+        raise ValueError(f"{fn}: without row_of the segments are the rows")
+    E = col.numel()
+    for t, what in per_entry:
+        if t is not None and (t.dtype != torch.float32 or t.numel() != E or not t.is_contiguous()):
+            raise TypeError(f"{fn}: {what} must be contiguous float32, one element per CSR entry")
+    return n_seg
+
+
+def _gat_ws(workspace, nbytes, device):
+    """The caller's workspace when it is large enough (contiguous uint8 on ``device``), else a fresh one."""
+    if workspace is not None and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == device \
+            and workspace.numel() >= max(nbytes, 4):
+        return workspace
+    return torch.empty(max(nbytes, 4), dtype=torch.uint8, device=device)
+
+
+def gat_edge_softmax(segptr: torch.Tensor, row_of: Optional[torch.Tensor], seg_first: Optional[torch.Tensor], n_rows: int, col: torch.Tensor,
+                     attr: Optional[torch.Tensor], keep: Optional[torch.Tensor], s: torch.Tensor, workspace: Optional[torch.Tensor] = None):
+    """LightGAT's per-destination softmax over the KEPT entries (ncf_gat_edge_softmax): returns (alpha (E,), coef (E,) = attr * alpha;
+    the same tensor when ``attr`` is None).  ``segptr`` / ``row_of`` / ``seg_first``: the level-0 segments of the prepared CSR
+    (PreparedGraph.softmax_segments(); row_of None: segments are rows).  ``keep``: (E,) float32, 1 = kept, 0 = removed (the w of
+    edge_keep called with attr = None); None: every entry kept, and coef is edge_softmax_csr's bit for bit.  ``workspace``: a
+    contiguous uint8 buffer kept by the caller (PreparedGraph.gat_workspace(): one per graph); None or too small: one is allocated."""
+    lib = load_library()
+    _dev(s, "s")
+    n_seg = _gat_segments("gat_edge_softmax", segptr, row_of, seg_first, n_rows, col, ((attr, "attr"), (keep, "keep")))
+    if s.dtype != torch.float32 or not s.is_contiguous():
+        raise TypeError("gat_edge_softmax: s must be contiguous float32")
+    E = col.numel()
+    alpha = torch.empty(E, dtype=torch.float32, device=s.device)
+    coef = alpha if attr is None else torch.empty(E, dtype=torch.float32, device=s.device)
+    if E == 0:                                # an edgeless graph: empty tensors carry null pointers
+        return alpha, coef
+    nbytes = lib.ncf_gat_edge_softmax_workspace_bytes(n_seg, n_rows) if row_of is not None else 0
+    ws = _gat_ws(workspace, nbytes, s.device)
+    _check(lib.ncf_gat_edge_softmax(_ptr(segptr), _ptr(row_of), n_seg, _ptr(seg_first), n_rows, _ptr(col), _ptr(attr), _ptr(keep), _ptr(s),
+                                    s.numel(), _ptr(alpha), _ptr(coef) if attr is not None else None, _ptr(ws), nbytes, _stream(s)))
+    return alpha, coef
+
+
+def gat_edge_grad(segptr: torch.Tensor, row_of: Optional[torch.Tensor], seg_first: Optional[torch.Tensor], n_rows: int, col: torch.Tensor,
+                  attr: Optional[torch.Tensor], alpha: torch.Tensor, dY: torch.Tensor, z: torch.Tensor, p: float = 0.0, seed: int = 0,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dlogit (E,) of LightGAT's edge softmax (ncf_gat_edge_grad): alpha_e (g_e - S_r) with g_e = attr_e <dY[row_e], drop_e(z[col_e])>,
+    the forward's message dropout (p, seed) regenerated per (CSR position, feature)."""
+    lib = load_library()
+    _dev(z, "z")
+    _dev(dY, "dY")
+    if alpha is None:
+        raise TypeError("gat_edge_grad: alpha is required")
+    n_seg = _gat_segments("gat_edge_grad", segptr, row_of, seg_first, n_rows, col, ((attr, "attr"), (alpha, "alpha")))
+    Nz, D, ldz = _rows2d(z, "z")
+    Ny, Dy, ldy = _rows2d(dY, "dY")
+    if Dy != D or Ny != n_rows or z.dtype != torch.float32 or dY.dtype != torch.float32:
+        raise TypeError("gat_edge_grad: dY must be (n_rows, D) and z (Nz, D), both float32")
+    E = col.numel()
+    dlogit = torch.empty(E, dtype=torch.float32, device=z.device)
+    if E == 0:
+        return dlogit
+    nbytes = lib.ncf_gat_edge_grad_workspace_bytes(n_seg, n_rows)
+    ws = _gat_ws(workspace, nbytes, z.device)
+    _check(lib.ncf_gat_edge_grad(_ptr(segptr), _ptr(row_of), n_seg, _ptr(seg_first), n_rows, _ptr(col), _ptr(attr), _ptr(alpha), _ptr(dY), ldy,
+                                 _ptr(z), Nz, ldz, D, float(p), int(seed) & 0xFFFFFFFF, _ptr(dlogit), _ptr(ws), nbytes, _stream(z)))
+    return dlogit
+
+
+def gat_source_reduce(csr_t: "SegmentedCSR", eid: torch.Tensor, dlogit: torch.Tensor) -> torch.Tensor:
+    """ds (n_rows,) = the sum of dlogit[eid[k]] over each row of the CSR by source ``csr_t`` (PreparedGraph.transposed()), level by
+    level over csr_t's segment tree like SegmentedCSR.spmm: ncf_gat_source_reduce on the entries, then on the partial sums of split
+    rows.  The partial buffers are cached on ``csr_t``.  Empty rows give 0."""
+    lib = load_library()
+    _dev(dlogit, "dlogit")
+    E = eid.numel()
+    if eid.dtype != torch.int32 or not eid.is_contiguous() or E != csr_t.col.numel():
+        raise TypeError("gat_source_reduce: eid must be contiguous int32, one id per entry of the transposed CSR")
+    if dlogit.dtype != torch.float32 or not dlogit.is_contiguous() or dlogit.numel() != E:
+        raise TypeError("gat_source_reduce: dlogit must be contiguous float32, one element per CSR entry")
+    n = csr_t.n_rows
+    out = torch.empty(n, dtype=torch.float32, device=dlogit.device)
+    if E == 0:
+        return out.zero_()
+    levels = csr_t.levels
+    bufs = csr_t._partials.get("gat_reduce")
+    if bufs is None:
+        bufs = [torch.empty(lv[0].numel() - 1, dtype=torch.float32, device=dlogit.device) for lv in levels[:-1]]
+        csr_t._partials["gat_reduce"] = bufs
+    idx, val = eid, dlogit
+    for li, (segptr, row_of, edge_ids) in enumerate(levels):
+        if li > 0:
+            idx, val = edge_ids, bufs[li - 1]
+        last = li == len(levels) - 1
+        _check(lib.ncf_gat_source_reduce(_ptr(segptr), _ptr(row_of), segptr.numel() - 1, _ptr(idx), _ptr(val), val.numel(), _ptr(out), n,
+                                         None if last else _ptr(bufs[li]), _stream(dlogit)))
     return out
 
 

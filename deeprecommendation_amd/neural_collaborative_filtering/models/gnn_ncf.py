@@ -12,10 +12,13 @@ Scoring (eval, no-grad) runs on the HIP kernels:
   * readout = fused gather(item) ‖ gather(user) -> MLP (gnn_ncf.py:354-362) or gather-dot (:365).
 Node numbering follows the reference: items first, user node id = num_items + rank (graph_providers.py:79-80).
 
-Training (module.training / autograd recording) of LightGCN layers on CUDA tensors runs on the HIP autograd blocks; the
-reference's train-only edge masking, node dropout and message dropout (gnn_ncf.py:246-296,314-333,369-378) only choose which
-edges take part in a step, so they become per-entry weights of the unchanged CSR (ncf_edge_keep).  CPU tensors, LightGAT and
-``train_with_torch_ops`` keep to differentiable torch ops.
+Training (module.training / autograd recording) of LightGCN and LightGAT layers on CUDA tensors runs on the HIP autograd blocks;
+the reference's train-only edge masking, node dropout and message dropout (gnn_ncf.py:246-296,314-333,369-378) only choose which
+edges take part in a step, so they become per-entry weights of the unchanged CSR (ncf_edge_keep).  A LightGAT step takes the 1 / 0
+keep indicator into its per-destination softmax (ncf_gat_edge_softmax: a removed edge leaves its group) and gets the gradient of
+the attention scores from ncf_gat_edge_grad + ncf_gat_source_reduce (autograd.GatSpmmFn); neither the E x 2D concat nor the E x D
+messages of the torch path are formed.  CPU tensors, ``train_with_torch_ops``, hetero graphs whose sources are not split items /
+users and LightGAT on destinations that mix edge types keep to differentiable torch ops.
 LightGATConv (a SURVEY §8(f) "next" row) scores on the HIP path too: edge softmax kernel + the same SpMM.
 """
 from typing import Optional
@@ -208,6 +211,25 @@ class PreparedGraph:
         w, deg = native.edge_keep(self.segptr, self.row_of, self.N, self.col, self.attr, pair_key, targets,
                                   slot if p > 0 else None, p, seed, node_keep)
         return native.edge_coef(src, dst_of, w, deg.to(torch.float32))
+
+    def gat_workspace(self):
+        """One uint8 buffer per graph for the LightGAT training kernels (ncf_gat_edge_softmax needs 2 floats per segment and per row,
+        ncf_gat_edge_grad one of each; the calls of a step run one after another on one stream, so they share it)."""
+        if getattr(self, "_gat_ws", None) is None:
+            n_seg = self.segptr.numel() - 1
+            self._gat_ws = torch.empty(max(4 * (2 * n_seg + 2 * self.N), 4), dtype=torch.uint8, device=self.col.device)
+        return self._gat_ws
+
+    def batch_keep(self, user_ids, item_ids, mask_targets=True, node_keep=None, message=None):
+        """The same edge set as ``batch_coef`` as a per-entry indicator for LightGAT: (E,) float32, exactly 1 where the entry is kept
+        and 0 where it is removed (ncf_edge_keep with attr = None).  The edge weight goes to the softmax separately, so a kept edge
+        whose weight happens to be 0 still counts in its destination's group, as in the reference."""
+        _, _, pair_key, slot = self.train_state()
+        targets = None
+        if mask_targets:
+            targets = torch.sort(user_ids.long() * self.N + item_ids.long()).values.contiguous()
+        p, seed = message if message is not None else (0.0, 0)
+        return native.edge_keep(self.segptr, self.row_of, self.N, self.col, None, pair_key, targets, slot if p > 0 else None, p, seed, node_keep)[0]
 
 
 class _ConvBase(nn.Module):
@@ -448,10 +470,11 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
         return ei[:, keep], (attr[keep] if attr is not None else None)
 
     def _hip_training_possible(self, graph, userIds) -> bool:
-        """The training step runs on the HIP autograd blocks for LightGCN layers on CUDA tensors, node / message dropout
-        included (edge sets redrawn per call on the device, gnn_ncf.py:246-296 -> PreparedGraph.batch_coef); LightGAT keeps to
-        the torch ops, as do hetero graphs whose sources are not split items / users (two stacked hoisted tables)."""
-        return userIds.is_cuda and not getattr(self, "train_with_torch_ops", False) and self.convType == 'LightGCN'
+        """The training step runs on the HIP autograd blocks for LightGCN and LightGAT layers on CUDA tensors, node / message
+        dropout included (edge sets redrawn per call on the device, gnn_ncf.py:246-296 -> PreparedGraph.batch_coef / batch_keep);
+        hetero graphs whose sources are not split items / users (two stacked hoisted tables; for LightGAT also softmax groups
+        that would mix edge types) keep to the torch ops: _forward_train_hip returns None for them."""
+        return userIds.is_cuda and not getattr(self, "train_with_torch_ops", False) and self.convType in ('LightGCN', 'LightGAT')
 
     @staticmethod
     def _draw_node_keep(N, user_ids, item_ids, p, node_seed):
@@ -485,14 +508,15 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
     def _forward_train_hip(self, graph, userIds, itemIds, mask_targets):
         """gnn_ncf.py:298-367 with autograd recording, on the HIP blocks: per-node hoisted Linear (LinearFn), aggregation
         (SpmmFn, with the per-edge message dropout of gnn_ncf.py:22-31 regenerated inside the kernel), row gather + MLP."""
-        from ...autograd import GatherConcatFn, LinearFn, SpmmFn, mlp_train
+        from ...autograd import GatSpmmFn, LinearFn, SpmmFn
         dev = userIds.device
         graph = graph.to(dev)
         pk = ("prep", self.hetero)
         if pk not in graph._prepared:
             graph._prepared[pk] = PreparedGraph(graph, self.hetero)
         prep = graph._prepared[pk]
-        if prep.z_rows != prep.N:
+        gat = self.convType == 'LightGAT'
+        if prep.z_rows != prep.N or (gat and not prep.type_pure):
             return None                                    # stacked hoisted tables: torch path
         I = graph.num_items
 
@@ -508,15 +532,22 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
         seed0 = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0     # host generator: no device sync
         p_node = float(self.node_dropout or 0.0) if self.training else 0.0
         p_msg = float(self.message_dropout or 0.0) if self.training else 0.0
+        coef = keep = None
         if p_node > 0.0 or p_msg > 0.0:
             # one edge set per call, shared by all layers (gnn_ncf.py:322-333); seeds drawn after seed0: seed0, node_seed, seed
             node_keep = None
             if p_node > 0.0:
                 node_keep = self._draw_node_keep(prep.N, userIds, itemIds, p_node, int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
             message = (p_msg, int(torch.randint(0, 2 ** 31 - 1, (1,)).item())) if p_msg > 0.0 else None
-            coef = prep.batch_coef(userIds, itemIds, mask_targets, node_keep, message)
+            if gat:
+                keep = prep.batch_keep(userIds, itemIds, mask_targets, node_keep, message)
+            else:
+                coef = prep.batch_coef(userIds, itemIds, mask_targets, node_keep, message)
+        elif gat:
+            keep = prep.batch_keep(userIds, itemIds, True, None, None) if (self.training and mask_targets) else None
         else:
             coef = prep.masked_coef(userIds, itemIds) if (self.training and mask_targets) else prep.coef
+        D = x.shape[1]
         hs = [x]
         for layer in range(len(self.gnn_convs)):
             if not conv.hetero:
@@ -524,12 +555,36 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
             else:                                          # rows [0, I) are item sources (item2user_W), the rest user sources
                 z = torch.cat((LinearFn.apply(x[:I], conv.item2user_W[0].weight, conv.item2user_W[0].bias, False),
                                LinearFn.apply(x[I:], conv.user2item_W[0].weight, conv.user2item_W[0].bias, False)), dim=0)
-            x = SpmmFn.apply(z, prep, coef, (p, seed0 + 7919 * layer) if p > 0 else None)
+            drop = (p, seed0 + 7919 * layer) if p > 0 else None
+            if not gat:
+                x = SpmmFn.apply(z, prep, coef, drop)
+            elif not conv.hetero:                          # s[n] = w_j . x[n]: the source half of AttNet (LightGATConv's docstring)
+                att = conv.AttNet[0]
+                s = LinearFn.apply(x, att.weight[:, :D], None, False)
+                x = GatSpmmFn.apply(z, s, prep, keep, drop, att.weight, att.bias)
+            else:
+                ai, au = conv.item2user_AttNet[0], conv.user2item_AttNet[0]
+                s = torch.cat((LinearFn.apply(x[:I], ai.weight[:, :D], None, False), LinearFn.apply(x[I:], au.weight[:, :D], None, False)), dim=0)
+                x = GatSpmmFn.apply(z, s, prep, keep, drop, ai.weight, ai.bias, au.weight, au.bias)
             hs.append(x)
         combined = torch.cat(hs, dim=1) if self.concat else torch.mean(torch.stack(hs, dim=0), dim=0)
-        if self.MLP is not None:
-            return mlp_train(self.MLP, GatherConcatFn.apply(combined, itemIds, combined, userIds))   # cat(item, user): :361
-        item_emb, user_emb = combined[itemIds], combined[userIds]
+        return self._readout(combined, itemIds, userIds, ordered=gat)
+
+    def _readout(self, combined, itemIds, userIds, ordered):
+        """gnn_ncf.py:354-365 on the HIP blocks: cat(item, user) rows -> MLP, or their dot product.  ``ordered`` (the LightGAT step):
+        the row gradients of the gather are summed in a fixed order (GatherPairOrderedFn), so that every gradient of that step is
+        and a seeded run repeats itself; the LightGCN step keeps the readout it had (scatter kernel / torch indexing)."""
+        from ...autograd import GatherConcatFn, GatherPairOrderedFn, mlp_train
+        if ordered:
+            pair = GatherPairOrderedFn.apply(combined, itemIds, userIds)
+            if self.MLP is not None:
+                return mlp_train(self.MLP, pair)
+            W = combined.shape[1]
+            item_emb, user_emb = pair[:, :W], pair[:, W:]
+        else:
+            if self.MLP is not None:
+                return mlp_train(self.MLP, GatherConcatFn.apply(combined, itemIds, combined, userIds))   # cat(item, user): :361
+            item_emb, user_emb = combined[itemIds], combined[userIds]
         return torch.bmm(user_emb.unsqueeze(1), item_emb.unsqueeze(2)).view(-1, 1)
 
     def _forward_train(self, graph, userIds, itemIds, device, mask_targets):

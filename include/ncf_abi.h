@@ -330,7 +330,52 @@ int ncf_edge_softmax_segmented(const int64_t* dev_segptr, const int32_t* dev_row
                                int64_t n_rows, const int32_t* dev_col, const float* dev_attr, const float* dev_s, int64_t n_src,
                                float* dev_out, void* dev_workspace, size_t workspace_bytes, ncf_stream_t stream);
 
-/* out[n, :] = in[n, :] / divisor  (the division of torch.mean over the L+1 stacked layers, gnn_ncf.py:351). */
+/* LightGAT TRAINING STEP (models/gnn_ncf.py:151-177 with autograd recording).  z = W(x) is hoisted per node as for LightGCN and
+ * s[n] = w_j . x[n] is the source half of AttNet (the destination half and the bias are constant in a softmax group and cancel).
+ * For destination row r with KEPT entries e (kept = dev_keep[e] != 0 and dev_col[e] in range; dev_keep = NULL: all kept):
+ *     alpha_e = exp(s[col_e] - M_r) / (sum_kept exp(s[col_.] - M_r) + 1e-16)      M_r = max over the kept entries of the row
+ *     coef_e  = (attr ? attr_e : 1) * alpha_e
+ *     y[r]    = sum_e coef_e * drop_e(z[col_e])                                    ncf_spmm_csr_dropout (THE MASK, e = CSR position)
+ * and backward for a given dY:
+ *     dZ[n]    = sum_{e: col_e = n} coef_e * drop_e(dY[row_e])                     ncf_spmm_csr_dropout on the CSR by source
+ *     g_e      = (attr ? attr_e : 1) * < dY[row_e], drop_e(z[col_e]) >
+ *     S_r      = sum_{e in r} alpha_e * g_e
+ *     dlogit_e = alpha_e * (g_e - S_r)              exact also with the 1e-16: d alpha_e / d t_k = delta alpha_e - alpha_e alpha_k
+ *     ds[n]    = sum_{e: col_e = n} dlogit_e
+ * A removed entry and an entry whose col is out of range are not in their group: alpha = coef = dlogit = 0.  A row with no kept
+ * entry produces 0 everywhere; nothing is NaN or inf for finite inputs.
+ * All three entries walk the level-0 segments of the prepared CSR (dev_segptr / dev_row_of of ncf_spmm_csr, dev_seg_first[r] =
+ * first segment of row r, n_rows + 1 entries; dev_row_of == NULL: segment s is row s, n_seg == n_rows, dev_seg_first unused).
+ * Loops are bounded by the segment ends only.  No float atomics, a fixed summation order: every output is bitwise repeatable.
+ * A null required pointer, a negative size, D % 4 != 0, p outside [0, 1) or not finite: NCF_EINVAL; D > 256: NCF_EUNSUPPORTED; a
+ * short workspace: NCF_EWORKSPACE — and nothing is launched.
+ *
+ * ncf_gat_edge_softmax: dev_alpha_out[E], and dev_coef_out[E] when dev_attr is given.  The three passes and the operation order of
+ * ncf_edge_softmax_csr (dev_row_of == NULL) / ncf_edge_softmax_segmented: with dev_keep == NULL, alpha * attr is their dev_out
+ * bit for bit.  dev_keep is the dev_w_out of ncf_edge_keep called with dev_attr = NULL (exactly 1 / 0), so a kept edge whose
+ * weight is 0 still counts in its group.  The workspace is needed only with dev_row_of. */
+size_t ncf_gat_edge_softmax_workspace_bytes(int64_t n_seg, int64_t n_rows);
+int ncf_gat_edge_softmax(const int64_t* dev_segptr, const int32_t* dev_row_of, int64_t n_seg, const int64_t* dev_seg_first,
+                         int64_t n_rows, const int32_t* dev_col, const float* dev_attr, const float* dev_keep, const float* dev_s,
+                         int64_t n_src, float* dev_alpha_out, float* dev_coef_out, void* dev_workspace, size_t workspace_bytes,
+                         ncf_stream_t stream);
+/* ncf_gat_edge_grad: dev_dlogit_out[E] from dY (n_rows, D), z (Nz, D) (hoisted, before dropout), alpha of ncf_gat_edge_softmax and
+ * the forward's (p, seed).  One wave per segment in the lane layout of ncf_spmm_csr (D % 4 == 0, D <= 256, rows 16-byte aligned);
+ * rows split over segments get S_r in a per-row pass over the segment sums.  An entry with alpha == 0 reads no z row. */
+size_t ncf_gat_edge_grad_workspace_bytes(int64_t n_seg, int64_t n_rows);
+int ncf_gat_edge_grad(const int64_t* dev_segptr, const int32_t* dev_row_of, int64_t n_seg, const int64_t* dev_seg_first, int64_t n_rows,
+                      const int32_t* dev_col, const float* dev_attr, const float* dev_alpha, const float* dev_dY, int64_t ldy,
+                      const float* dev_z, int64_t Nz, int64_t ldz, int D, float p, uint32_t seed, float* dev_dlogit_out,
+                      void* dev_workspace, size_t workspace_bytes, ncf_stream_t stream);
+/* ncf_gat_source_reduce: ONE LEVEL of ds[n] = sum_k dev_val[dev_idx[k]] over row n of the CSR by source (dev_idx = the transpose's
+ * edge ids; NULL: k itself; ids outside [0, n_val) are skipped).  The segment walk of ncf_spmm_csr on scalars: a segment that is
+ * the first and the last of its row writes dev_out[row] (0 for an empty row), any other writes its sum to dev_partial[segment]
+ * (when given); the caller re-applies the entry to the partial sums level by level, as for ncf_spmm_csr's split rows. */
+int ncf_gat_source_reduce(const int64_t* dev_segptr, const int32_t* dev_row_of, int64_t n_seg, const int32_t* dev_idx,
+                          const float* dev_val, int64_t n_val, float* dev_out, int64_t n_rows, float* dev_partial,
+                          ncf_stream_t stream);
+
+/* out[n, :] = in[n, :] / divisor (the division of torch.mean over the L+1 stacked layers, gnn_ncf.py:351). */
 int ncf_scale_rows(const float* dev_in, int64_t ldin, int64_t N, int D, float divisor,
                    float* dev_out, int64_t ldout, ncf_stream_t stream);
 
