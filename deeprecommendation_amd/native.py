@@ -102,6 +102,9 @@ SIGNATURES = {
     "ncf_attn_cross_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p]),
     "ncf_attn_cross": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_int,
                                 _c_p, _c_p, _c_i64, _c_p, _c_p]),
+    "ncf_attn_explain_max_reasons": (_c_int, []),
+    "ncf_attn_explain": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_int,
+                                  _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "ncf_edge_softmax_csr": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_edge_softmax_segmented_workspace_bytes": (_c_size, [_c_i64, _c_i64]),
     "ncf_edge_softmax_segmented": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_size, _c_p]),
@@ -1275,6 +1278,53 @@ def attn_cross(ST: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, val: t
                               _ptr(cand_ids), I, _ptr(feat), ldf, Fdim, _ptr(out_bias), _ptr(out), ldo, _ptr(_oob_flag(ST.device)),
                               _stream(ST)))
     return out
+
+
+ATTN_EXPLAIN_MAX_REASONS = 64   # include/ncf_abi.h ncf_attn_explain_max_reasons
+
+
+def attn_explain(ST: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, user_rows: torch.Tensor,
+                 items: torch.Tensor, thr: torch.Tensor, max_reasons: int, out=None):
+    """The reasons of (user, winner) pairs from the logit table (ncf_attn_explain): ``(col (U, k, E) int32, w (U, k, E) fp32,
+    val (U, k, E) fp32, cnt (U, k) int32)`` with E = ``max_reasons`` — per pair the entries of the user's row whose attention weight
+    towards table column ``items[u, s]`` exceeds ``thr[u]``, in descending weight (ties: the entry stored earlier), ``cnt`` uncapped,
+    slots past ``min(cnt, E)`` as ``(-1, 0, 0)``.  ``ST / rowptr / col / val / user_rows`` as ``attn_cross`` takes them; ``items``
+    (U, k) int64, -1 = an empty slot; ``thr`` (U,) fp32.  ``out``: the four tensors preallocated (contiguous).  An out-of-range user
+    row or item raises at the next check_oob().  Every shape and dtype check comes before the first device use; one launch on the
+    current stream; nothing synchronises."""
+    E = int(max_reasons)
+    if not 1 <= E <= ATTN_EXPLAIN_MAX_REASONS:
+        raise ValueError(f"max_reasons = {max_reasons} is outside 1 .. {ATTN_EXPLAIN_MAX_REASONS}")
+    Ir, Ic, ldst = _rows2d(ST, "ST")
+    if ST.dtype != torch.float32:
+        raise TypeError("ST must be fp32")
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float32:
+        raise TypeError("CSR must be (int64 rowptr, int32 col, fp32 val)")
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1 or val.shape != col.shape:
+        raise ValueError("CSR must be 1-D (rowptr (rows + 1,), col (nnz,), val (nnz,))")
+    user_rows = _idx(user_rows)
+    U = user_rows.numel()
+    if items.dtype != torch.int64 or items.dim() != 2 or items.shape[0] != U or not items.is_contiguous():
+        raise ValueError(f"items must be a contiguous ({U}, k) int64 tensor")
+    if thr.dtype != torch.float32 or thr.dim() != 1 or thr.numel() != U or not thr.is_contiguous():
+        raise ValueError(f"thr must be a contiguous ({U},) fp32 tensor")
+    k = items.shape[1]
+    shapes = ((U, k, E), (U, k, E), (U, k, E), (U, k))
+    dtypes = (torch.int32, torch.float32, torch.float32, torch.int32)
+    if out is not None:
+        if len(out) != 4 or any(tuple(o.shape) != s or o.dtype != d or not o.is_contiguous() for o, s, d in zip(out, shapes, dtypes)):
+            raise ValueError(f"out must be contiguous (col {shapes[0]} int32, w fp32, val fp32, cnt {shapes[3]} int32)")
+    named = [(ST, "ST"), (rowptr, "rowptr"), (col, "col"), (val, "val"), (user_rows, "user_rows"), (items, "items"), (thr, "thr")]
+    for t, what in named + [(o, "out") for o in out or ()]:
+        _dev(t, what)
+    lib = load_library()
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=ST.device) for s, d in zip(shapes, dtypes))
+    rc, rw, rv, cnt = out
+    _check(lib.ncf_attn_explain(_ptr(ST), ldst, Ir, Ic, _ptr(rowptr), _ptr(col), _ptr(val), rowptr.numel() - 1, _ptr(user_rows), U,
+                                _ptr(items), k, _ptr(thr), E, _ptr(rc), _ptr(rw), _ptr(rv), _ptr(cnt), _ptr(_oob_flag(ST.device)),
+                                _stream(ST)))
+    return rc, rw, rv, cnt
 
 
 def l2_normalize_rows(x: torch.Tensor) -> torch.Tensor:

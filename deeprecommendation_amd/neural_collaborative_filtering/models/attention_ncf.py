@@ -482,6 +482,40 @@ class AttentionNCF(_ScoringMixin, NCF):
             return torch.empty((0, I), dtype=torch.float32, device=item_features.device)
         return blocks[0] if len(blocks) == 1 else torch.cat(blocks)
 
+    def explain(self, item_features, ratings, user_rows, items, thr, max_reasons):
+        """The reasons behind recommendations, for many users at once: ``(positions (U, k, E) int32, weights (U, k, E) fp32, ratings
+        (U, k, E) fp32, counts (U, k) int32)`` with E = ``max_reasons`` — per (user, slot) the rated items of user ``user_rows[u]``
+        whose attention weight towards catalogue position ``items[u, s]`` exceeds ``thr[u]``, in descending weight, ``counts``
+        uncapped, unused slots ``(-1, 0, 0)`` (native.attn_explain; the reference thresholds one user's dense weight rows on the host,
+        webapp/backend.py:105-121).  Eval only.  ``ratings`` as in ``catalogue_scores``; ``items`` (U, k) int64 catalogue positions
+        with -1 for an empty slot; ``thr`` (U,) fp32.  Reads ``logit_table(item_features)`` only — any ``user_emb`` width — so the
+        table must fit ``cross_table_max_bytes``.  Nothing synchronises with the host."""
+        if self.training:
+            raise RuntimeError("explanations are computed in eval mode: call model.eval() first")
+        if not isinstance(ratings, SparseRatings):
+            raise TypeError("ratings must be a SparseRatings whose rows are users and whose columns are catalogue positions")
+        if item_features.dim() != 2 or ratings.num_items != item_features.shape[0]:
+            raise ValueError(f"ratings has {ratings.num_items} columns, the catalogue {tuple(item_features.shape)} rows")
+        if user_rows.dtype != torch.int64 or user_rows.dim() != 1:
+            raise ValueError("user_rows must be a 1-D int64 tensor of rows of ratings")
+        U = user_rows.numel()
+        if items.dtype != torch.int64 or items.dim() != 2 or items.shape[0] != U:
+            raise ValueError(f"items must be a ({U}, k) int64 tensor of catalogue positions (-1: an empty slot)")
+        if thr.dtype != torch.float32 or thr.dim() != 1 or thr.numel() != U:
+            raise ValueError(f"thr must be a ({U},) fp32 tensor: one threshold per listed user")
+        if not 1 <= int(max_reasons) <= native.ATTN_EXPLAIN_MAX_REASONS:
+            raise ValueError(f"max_reasons = {max_reasons} is outside 1 .. {native.ATTN_EXPLAIN_MAX_REASONS}")
+        Ic = item_features.shape[0]
+        nbytes = 4 * Ic * Ic
+        if nbytes > self.cross_table_max_bytes:
+            raise ValueError(f"the logit table of {Ic} items takes {nbytes} bytes, above AttentionNCF.cross_table_max_bytes = "
+                             f"{self.cross_table_max_bytes}")
+        require_gpu(item_features, ratings.rowptr, ratings.col, ratings.val, user_rows, items, thr)
+        with torch.no_grad():
+            ST = self.logit_table(item_features)       # raises inside a stream capture when no table has been built
+            return native.attn_explain(ST, ratings.rowptr, ratings.col, ratings.val, user_rows.contiguous(), items.contiguous(),
+                                       thr.contiguous(), int(max_reasons))
+
     # ------------------------------------------------------------------------------------------ torch training path
     def _forward_train_hip(self, candidate_items, rated_items, user_matrix, return_attention_weights, pair_split=None):
         """attention_ncf.py:136-224 with autograd recording, on the HIP blocks: the Linear layers (LinearFn), the attention with its

@@ -6,6 +6,8 @@
                        readout.  Results stay on the device.
 ``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
 ``rated_exclusion``    the same for an AttentionNCF's users: the items each listed user rated.
+``explain_items``      AttentionNCF: the reasons behind winners of many users at once (which rated items carry the attention), from the
+                       shared logit table; the batch counterpart of recommend_for_user's ``because`` / ``attention`` columns.
 ``recommend_for_user`` AttentionNCF: one user given as a Series of ratings against a catalogue, with the reference's arguments,
                        threshold rule and DataFrame columns (imdbID, score, because, attention).  Only k scores, k ids and the k
                        winners' attention rows cross to the host.
@@ -296,6 +298,59 @@ def rated_exclusion(ratings: SparseRatings, user_ids: torch.Tensor) -> Tuple[tor
     row = torch.repeat_interleave(torch.arange(user_ids.numel(), device=dev), cnt)
     pos = lo[row] + torch.arange(row.numel(), device=dev) - rowptr[row]
     return rowptr, ratings.col[pos].to(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------- AttentionNCF: why these items
+class Explanations(NamedTuple):
+    """What explain_items returns, all on the device; E = max_reasons."""
+    positions: torch.Tensor      # (B, k, E) int64 catalogue positions of the rated items that explain a winner; -1 in unused slots
+    weights: torch.Tensor        # (B, k, E) fp32 attention weights, descending; 0 in unused slots
+    ratings: torch.Tensor        # (B, k, E) fp32 the rating stored for that rated item; 0 in unused slots
+    counts: torch.Tensor         # (B, k) int32 rated items above the threshold (not capped at E)
+    threshold: torch.Tensor      # (B,) fp32 the threshold of each listed user
+
+
+def explain_items(model, user_ids: torch.Tensor, item_positions: torch.Tensor, profiles, max_reasons: int = 8,
+                  explain_factor: float = 1.5, explain_constant: float = 0.025) -> Explanations:
+    """Why an AttentionNCF recommends ``item_positions[b, s]`` to user ``user_ids[b]``: per (user, slot) the rated items whose
+    attention weight exceeds ``explain_factor / n_rated + explain_constant`` — the reference's ``because`` and ``attention`` columns
+    (webapp/backend.py:105-121) for many users at once, read from the shared logit table (``AttentionNCF.explain``,
+    native.attn_explain) without a dense (B * k, I_c) weight matrix.
+
+    user_ids: (B,) int64 rows of ``profiles``' ratings on the GPU.  item_positions: (B, k) int64 catalogue positions, typically
+    ``top_k_items(...)[1]``; -1 (a slot past that call's ``counts``) gives an empty explanation.  profiles: ``(item_features
+    (I_c, F), ratings)`` with the meaning it has in ``top_k_items``.  max_reasons: E, 1 .. 64 reasons kept per winner.
+    The threshold of user u is ``explain_factor / max(n_u, 1) + explain_constant`` in fp32 on the device, n_u = the number of
+    STORED entries of the user's row.  The reference's ``n_rated`` also counts a rating whose centred value is exactly 0
+    (backend.py:88-92); the CSR does not store those, so for such a user this threshold is slightly higher than the reference's.
+    Returns ``Explanations(positions (B, k, E) int64, weights, ratings, counts (B, k) int32, threshold (B,) fp32)`` on the device:
+    per winner the qualifying rated items in descending weight (ties: the lower catalogue position for a provider-built row),
+    ``counts`` not capped at E, unused slots ``(-1, 0, 0)``.  Needs the logit table (4 * I_c^2 bytes <=
+    ``AttentionNCF.cross_table_max_bytes``), not a ``user_emb`` width the cross kernel takes.  Nothing synchronises with the host."""
+    _eval_only(model)
+    if not _attention_model(model):
+        raise ValueError(f"explanations come from attention weights: explain_items takes an AttentionNCF, not {type(model).__name__}")
+    if profiles is None:
+        raise ValueError("an AttentionNCF explains items for users given by their ratings: pass profiles=(item_features, ratings)")
+    if not torch.is_tensor(item_positions) or item_positions.dtype != torch.int64 or item_positions.dim() != 2:
+        raise ValueError("item_positions must be a (B, k) int64 tensor of catalogue positions")
+    if not 1 <= int(max_reasons) <= native.ATTN_EXPLAIN_MAX_REASONS:
+        raise ValueError(f"max_reasons = {max_reasons} is outside 1 .. {native.ATTN_EXPLAIN_MAX_REASONS}")
+    if torch.is_tensor(user_ids) and user_ids.dim() == 1 and item_positions.shape[0] != user_ids.numel():
+        raise ValueError(f"item_positions has {item_positions.shape[0]} rows for {user_ids.numel()} users")
+    r = _resolve_attention(model, user_ids, None, None, profiles, None)
+    item_features, ratings = r.profiles
+    require_gpu(item_positions, ratings.col, ratings.val)
+    with torch.no_grad():
+        n_rows = ratings.rowptr.numel() - 1
+        if n_rows > 0:
+            rows = r.users.clamp(0, n_rows - 1)          # an out-of-range user is refused by the kernel (check_oob), not here
+            n = ratings.rowptr[rows + 1] - ratings.rowptr[rows]
+        else:
+            n = torch.zeros_like(r.users)
+        thr = (float(explain_factor) / n.clamp_min(1).to(torch.float32) + float(explain_constant)).contiguous()
+        pos, w, val, cnt = model.explain(item_features, ratings, r.users, item_positions.contiguous(), thr, int(max_reasons))
+        return Explanations(pos.to(torch.int64), w, val, cnt, thr)
 
 
 # ---------------------------------------------------------------------------------------- AttentionNCF: one user, one catalogue

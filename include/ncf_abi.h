@@ -585,6 +585,34 @@ int ncf_attn_cross(const float* dev_st, int64_t ldst, int64_t I_r, int64_t I_c,
                    const float* dev_feat, int64_t ldfeat, int Fdim, const float* dev_out_bias,
                    float* dev_out, int64_t ldout, int32_t* dev_oob_flag, ncf_stream_t stream);
 
+/* Explanations from the logit table (csrc/attn_explain.hip): for U listed users x k winners each, the rated items whose attention
+ * weight exceeds the user's threshold — the `because` / `attention` columns of webapp/backend.py:105-121 — without a dense
+ * (U * k, I_c) weight matrix.  dev_st / ldst / I_r / I_c and the CSR (dev_rowptr, dev_col, dev_val, n_rows) exactly as
+ * ncf_attn_cross reads them; dev_user_rows (U,) int64; dev_items (U, k) int64 columns of dev_st, -1 = an empty slot (what a top-K
+ * result holds past its count); dev_thr (U,) fp32, one threshold per LISTED user (the kernel does not own the threshold rule);
+ * max_reasons = E, 1 <= E <= ncf_attn_explain_max_reasons() = 64.  Outputs, contiguous: dev_reason_col (U, k, E) int32,
+ * dev_reason_w (U, k, E) fp32, dev_reason_val (U, k, E) fp32 (the rating stored for that entry), dev_reason_cnt (U, k) int32.
+ * For the pair (u, s) with candidate c = items[u, s]:
+ *   - the valid entries of the user's row are those with 0 <= col_e < I_r; their weights are w_e = exp(ST[col_e, c] - m) / l with m
+ *     the exact maximum (taken before any exponential) and l the sum in one fixed order; w_e is a function of the entry's logit, m
+ *     and l alone, so equal logits give bit-equal weights;
+ *   - an entry qualifies when w_e > thr[u], compared in fp32 on the value that is written; a NaN weight never qualifies;
+ *   - reason_cnt = the number of qualifying entries, NOT capped at E;
+ *   - the first min(cnt, E) slots hold the qualifying entries in descending weight, ties to the entry stored earlier in the row
+ *     (for rows with ascending columns: the lower catalogue position); every remaining slot is written as (-1, 0, 0);
+ *   - an empty slot (-1), an empty or fully masked row and an all -inf column give cnt = 0; so does a user row or a candidate out
+ *     of range (other than -1), which also sets *dev_oob_flag (sticky, may be NULL).
+ * One wave per pair, four pairs per workgroup; no atomics, every order fixed: two calls on the same inputs give the same bits.
+ * Refusals, before anything is launched (ncf_last_error set): NCF_EUNSUPPORTED for E outside 1 .. 64 (and for more than 2^31 - 1
+ * workgroups), NCF_EINVAL for negative sizes, ldst < I_c or a NULL buffer (dev_col / dev_val may be NULL for a CSR without
+ * entries, dev_st for a table without cells); U == 0 or k == 0 is an empty call. */
+int ncf_attn_explain_max_reasons(void);
+int ncf_attn_explain(const float* dev_st, int64_t ldst, int64_t I_r, int64_t I_c,
+                     const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t n_rows,
+                     const int64_t* dev_user_rows, int64_t U, const int64_t* dev_items, int64_t k, const float* dev_thr,
+                     int max_reasons, int32_t* dev_reason_col, float* dev_reason_w, float* dev_reason_val,
+                     int32_t* dev_reason_cnt, int32_t* dev_oob_flag, ncf_stream_t stream);
+
 /* Dense user_matrix -> CSR with shared rows, on the stream (no size is read by the host).  The reference passes AttentionNCF.forward a
  * dense (B, I) user_matrix in which a user's row is repeated for each of their samples (datasets/dynamic_datasets.py:24-40,
  * content_providers/dynamic_profiles_provider.py:55-71; one row for every candidate in webapp/backend.py:78-121) and keeps the
