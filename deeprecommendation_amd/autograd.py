@@ -245,14 +245,22 @@ class AttnFn(torch.autograd.Function):
     """user_emb (B, UE) = bias + sum_e softmax_e(score(b, e)) * val_e * proj[col_e, :]  —  attention_ncf.py:176-216 for one CSR row
     of rated entries per pair, forward (ncf_attn_forward / _dropout) and backward (ncf_attn_backward) on the HIP kernels.
     ``b1`` (AttentionNet's output bias) is taken only to hand it its gradient, which is exactly zero: a shift of every score
-    cancels in the softmax.  ``dropout`` = (p, seed) or None: AttentionNet's hidden dropout, regenerated in both kernels."""
+    cancels in the softmax.  ``dropout`` = (p, seed) or None: AttentionNet's hidden dropout, regenerated in both kernels.
+    ``msg_dropout`` = (p, seed) or None: the message dropout over the logits (ncf_attn_forward_train / _backward_train).  With it the
+    value of ``b1`` does reach the kernel: the reference's ``attOut == 0`` test is made on the score with its bias, so an entry whose
+    hidden units are all inactive is kept with score b1, not dropped.  That is one 4-byte host read per step, on this path only:
+    a blocking read (the step waits for the queued work before it), and one that cannot be made inside a stream capture — a step with
+    message dropout on the device cannot be captured into a HIP graph.  11-argument callers leave ``msg_dropout`` at None."""
 
     @staticmethod
-    def forward(ctx, pc, pr, w1, b1, proj, bias, rowptr, col, val, mode, dropout):
+    def forward(ctx, pc, pr, w1, b1, proj, bias, rowptr, col, val, mode, dropout, msg_dropout=None):
         pc, pr, proj = pc.contiguous(), pr.contiguous(), proj.contiguous()
         w1c = None if w1 is None else w1.contiguous()
-        out, wts = native.attn_forward(mode, pc, pr, w1c, 0.0, rowptr, col, val, proj, out_bias=bias, dropout=dropout)
-        ctx.mode, ctx.dropout = mode, dropout
+        msg_on = msg_dropout is not None and msg_dropout[0] > 0
+        b1v = float(b1.detach().reshape(-1)[0].item()) if msg_on and b1 is not None else 0.0
+        out, wts = native.attn_forward(mode, pc, pr, w1c, b1v, rowptr, col, val, proj, out_bias=bias, dropout=dropout,
+                                       **({"msg_dropout": msg_dropout} if msg_on else {}))
+        ctx.mode, ctx.dropout, ctx.msg_dropout = mode, dropout, (msg_dropout if msg_on else None)
         ctx.has = (w1 is not None, b1 is not None, bias is not None)
         ctx.save_for_backward(pc, pr, w1c, proj, rowptr, col, val, wts)
         ctx.mark_non_differentiable(wts)
@@ -261,11 +269,13 @@ class AttnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _dwts):
         pc, pr, w1c, proj, rowptr, col, val, wts = ctx.saved_tensors
-        d_pc, d_pr, d_w1, d_proj = native.attn_backward(ctx.mode, pc, pr, w1c, rowptr, col, val, proj, wts, dout, dropout=ctx.dropout)
+        d_pc, d_pr, d_w1, d_proj = native.attn_backward(ctx.mode, pc, pr, w1c, rowptr, col, val, proj, wts, dout, dropout=ctx.dropout,
+                                                        **({"msg_dropout": ctx.msg_dropout} if ctx.msg_dropout else {}))
         has_w1, has_b1, has_bias = ctx.has
         d_b1 = torch.zeros(1, dtype=torch.float32, device=dout.device) if has_b1 else None
         d_bias = native.colsum(dout.contiguous()) if has_bias else None
-        return d_pc, d_pr, (d_w1 if has_w1 else None), d_b1, d_proj, d_bias, None, None, None, None, None
+        # one gradient slot per forward argument; autograd drops a trailing None when the caller passed 11
+        return d_pc, d_pr, (d_w1 if has_w1 else None), d_b1, d_proj, d_bias, None, None, None, None, None, None
 
 
 class LinearFn(torch.autograd.Function):

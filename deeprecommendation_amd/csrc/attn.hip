@@ -42,15 +42,26 @@ __device__ __forceinline__ f32x4 att_mask4(uint32_t entry, int chunk, const AttD
                  (h1 & 0xFFFFU) >= d.thr ? d.scale : 0.f, (h1 >> 16) >= d.thr ? d.scale : 0.f};
 }
 
+// Training-time message dropout (attention_ncf.py:184-189: F.dropout over the (pair, rated entry) logits, then
+// `attOut[attOut == 0] = -inf`).  Entry e keeps iff element (e, feature 0) of THE MASK under the message seed does; a kept raw score
+// is multiplied by the scale, and a score that is then exactly zero — dropped, or kept and zero — leaves the softmax.
+__device__ __forceinline__ float att_msg_score(float raw, uint32_t entry, const AttDrop& m) {
+    const bool keep = (att_mix32(entry * 0x9E3779B1U ^ m.seed) & 0xFFFFU) >= m.thr;
+    const float s = keep ? raw * m.scale : 0.f;
+    return s == 0.f ? -INFINITY : s;
+}
+
 // MODE 0: MLP (relu + w1 dot), 1: linear (A == 1, pc + pr), 2: cosine (dot of normalised rows)
-template <int MODE, bool DROP = false>
+// MSG: message dropout on the stored score (MODE 0 and 2; the lane that stores wts[e] applies it)
+template <int MODE, bool DROP = false, bool MSG = false>
 __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ pc, int64_t ldpc, const float* __restrict__ pr,
                                                    int64_t ldpr, int A, const float* __restrict__ w1, float b1,
                                                    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                    const float* __restrict__ val, int64_t B, int64_t I,
                                                    const float* __restrict__ feat, int64_t ldfeat, int Fdim,
                                                    const float* __restrict__ out_bias, float* __restrict__ out,
-                                                   int64_t ldout, float* __restrict__ wts, AttDrop drop = AttDrop{}) {
+                                                   int64_t ldout, float* __restrict__ wts, AttDrop drop = AttDrop{},
+                                                   AttDrop msg = AttDrop{}) {
     const int lane = threadIdx.x & 63;
     // XCD-aware block order: hardware deals blocks round-robin over the 8 XCDs (b and b+8 share one), so logical block
     // L = (b % 8) * ceil(n/8) + b / 8 (bijective form) puts CONSECUTIVE pair groups on the same XCD.  Batches are
@@ -123,7 +134,11 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ pc,
                         part = fmaf(pcv[3], r[u][3], part);
                     }
                     for (int off = 1; off < LPA; off <<= 1) part += __shfl_xor(part, off);
-                    if (e < end && c == 0) wts[e] = ok[u] ? part + (MODE == 0 ? b1 : 0.f) : -INFINITY;
+                    if (e < end && c == 0) {
+                        float sc = ok[u] ? part + (MODE == 0 ? b1 : 0.f) : -INFINITY;
+                        if (MSG) sc = att_msg_score(sc, (uint32_t)e, msg);
+                        wts[e] = sc;
+                    }
                 }
             }
         } else {
@@ -139,6 +154,9 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ pc,
                     }
                     s = acc + (MODE == 0 ? b1 : 0.f);
                 }
+                // MSG here is the same rule for completeness only: ncf_attn_forward_train refuses every shape that is not `vec`
+                // (attn_train_shape), so no call reaches this line with MSG and no test runs it
+                if (MSG) s = att_msg_score(s, (uint32_t)e, msg);
                 wts[e] = s;
             }
         }
@@ -233,7 +251,9 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ pc,
 //   cosine: d pc[b,:] += ds_e pr[i_e,:],  d pr[i_e,:] += ds_e pc[b,:]
 // A % 4 == 0, Fdim % 4 == 0, both <= 256.  `ds` (nnz floats) is scratch.  Atomic adds make d pr / d feat order-dependent in the
 // last bits, like ncf_scatter_add_rows.
-template <int MODE, bool DROP>
+// MSG (message dropout in the forward): the logit was msg_scale * raw score for a kept entry, so the gradient that reaches the raw
+// score is msg_scale * ds_e; an entry the forward dropped has p_e = 0 and every term of it is already 0 — no mask is regenerated.
+template <int MODE, bool DROP, bool MSG = false>
 __global__ __launch_bounds__(256) void attn_backward_kernel(const float* __restrict__ pc, int64_t ldpc, const float* __restrict__ pr,
                                                             int64_t ldpr, int A, const float* __restrict__ w1,
                                                             const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -242,7 +262,7 @@ __global__ __launch_bounds__(256) void attn_backward_kernel(const float* __restr
                                                             const float* __restrict__ wts, const float* __restrict__ dout, int64_t lddout,
                                                             float* __restrict__ d_pc, int64_t ldd_pc, float* __restrict__ d_pr, int64_t ldd_pr,
                                                             float* __restrict__ d_w1_part, float* __restrict__ d_feat, int64_t ldd_feat,
-                                                            float* __restrict__ ds, AttDrop drop) {
+                                                            float* __restrict__ ds, AttDrop drop, float msg_scale = 1.f) {
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (b >= B) return;  // wave-uniform
@@ -281,7 +301,9 @@ __global__ __launch_bounds__(256) void attn_backward_kernel(const float* __restr
         __builtin_amdgcn_wave_barrier();
         for (int64_t e = beg + lane; e < end; e += 64) {
             const int64_t i = col[e];
-            ds[e] = (i >= 0 && i < I) ? wts[e] * (ds[e] - tsum) : 0.f;
+            float dse = (i >= 0 && i < I) ? wts[e] * (ds[e] - tsum) : 0.f;
+            if (MSG) dse *= msg_scale;
+            ds[e] = dse;
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
@@ -1054,7 +1076,7 @@ extern "C" int ncf_l2_normalize_rows(const float* x, int64_t ldx, int64_t R, int
 static int attn_forward_impl(const char* who, int mode, const float* pc, int64_t ldpc, const float* pr, int64_t ldpr, int A,
                              const float* w1, float b1, const int64_t* rowptr, const int32_t* col, const float* val,
                              int64_t B, int64_t I, const float* feat, int64_t ldfeat, int Fdim, const float* out_bias,
-                             float* out, int64_t ldout, float* wts, const AttDrop* drop, ncf_stream_t stream) {
+                             float* out, int64_t ldout, float* wts, const AttDrop* drop, const AttDrop* msg, ncf_stream_t stream) {
     if (mode < 0 || mode > 3) return fail(NCF_EINVAL, "%s: bad mode %d", who, mode);
     if (mode == NCF_ATT_MLP_SCALED) mode = NCF_ATT_MLP;   // w' relu(p' + q') with exact power-of-two scales IS w relu(p + q): same kernel
     if (B < 0 || I < 0 || A <= 0 || Fdim <= 0) return fail(NCF_EINVAL, "%s: bad sizes", who);
@@ -1070,12 +1092,18 @@ static int attn_forward_impl(const char* who, int mode, const float* pc, int64_t
         return fail(NCF_EUNSUPPORTED, "%s: hidden-layer dropout needs the MLP mode with A %% 4 == 0, A <= 256", who);
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((B + 3) / 4);
-#define LAUNCH(M) hipLaunchKernelGGL((attn_kernel<M, false>), dim3(blocks), dim3(256), 0, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, B, I, feat, ldfeat, Fdim, out_bias, out, ldout, wts, AttDrop{})
-    if (drop) hipLaunchKernelGGL((attn_kernel<0, true>), dim3(blocks), dim3(256), 0, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, B, I, feat, ldfeat, Fdim, out_bias, out, ldout, wts, *drop);
+#define LAUNCH(M) hipLaunchKernelGGL((attn_kernel<M, false>), dim3(blocks), dim3(256), 0, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, B, I, feat, ldfeat, Fdim, out_bias, out, ldout, wts, AttDrop{}, AttDrop{})
+#define LAUNCHM(M, D) hipLaunchKernelGGL((attn_kernel<M, D, true>), dim3(blocks), dim3(256), 0, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, B, I, feat, ldfeat, Fdim, out_bias, out, ldout, wts, drop ? *drop : AttDrop{}, *msg)
+    if (msg) {   // ncf_attn_forward_train with thr_m > 0: MLP or cosine (the caller has refused the rest)
+        if (mode == 0 && drop) LAUNCHM(0, true);
+        else if (mode == 0) LAUNCHM(0, false);
+        else LAUNCHM(2, false);
+    } else if (drop) hipLaunchKernelGGL((attn_kernel<0, true>), dim3(blocks), dim3(256), 0, s, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, B, I, feat, ldfeat, Fdim, out_bias, out, ldout, wts, *drop, AttDrop{});
     else if (mode == 0) LAUNCH(0);
     else if (mode == 1) LAUNCH(1);
     else LAUNCH(2);
 #undef LAUNCH
+#undef LAUNCHM
     return check_launch(who);
 }
 
@@ -1092,7 +1120,7 @@ extern "C" int ncf_attn_forward(int mode, const float* pc, int64_t ldpc, const f
                                 int64_t B, int64_t I, const float* feat, int64_t ldfeat, int Fdim, const float* out_bias,
                                 float* out, int64_t ldout, float* wts, ncf_stream_t stream) {
     return attn_forward_impl("ncf_attn_forward", mode, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, B, I, feat, ldfeat, Fdim, out_bias,
-                             out, ldout, wts, nullptr, stream);
+                             out, ldout, wts, nullptr, nullptr, stream);
 }
 
 extern "C" int ncf_attn_forward_dropout(int mode, const float* pc, int64_t ldpc, const float* pr, int64_t ldpr, int A,
@@ -1103,7 +1131,70 @@ extern "C" int ncf_attn_forward_dropout(int mode, const float* pc, int64_t ldpc,
     AttDrop d;
     const bool on = att_drop_args(p, seed, d);
     return attn_forward_impl("ncf_attn_forward_dropout", mode, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, B, I, feat, ldfeat, Fdim,
-                             out_bias, out, ldout, wts, on ? &d : nullptr, stream);
+                             out_bias, out, ldout, wts, on ? &d : nullptr, nullptr, stream);
+}
+
+// The shapes the training pair takes: ncf_attn_backward's own NCF_EUNSUPPORTED conditions, applied to the forward's operands too.
+static bool attn_train_shape(int mode, int A, int Fdim, int64_t ldpc, int64_t ldpr, int64_t ldfeat) {
+    return (mode == NCF_ATT_MLP || mode == NCF_ATT_MLP_SCALED || mode == NCF_ATT_COS) && A > 0 && Fdim > 0 && A % 4 == 0 && Fdim % 4 == 0 &&
+           A <= 256 && Fdim <= 256 && ldpc % 4 == 0 && ldpr % 4 == 0 && ldfeat % 4 == 0;
+}
+
+extern "C" int ncf_attn_forward_train(int mode, const float* pc, int64_t ldpc, const float* pr, int64_t ldpr, int A,
+                                      const float* w1, float b1, const int64_t* rowptr, const int32_t* col, const float* val,
+                                      int64_t B, int64_t I, const float* feat, int64_t ldfeat, int Fdim, const float* out_bias,
+                                      float* out, int64_t ldout, float* wts, uint32_t seed, float p, uint32_t msg_seed, float msg_p,
+                                      ncf_stream_t stream) {
+    if (!(p >= 0.f && p < 1.f)) return fail(NCF_EINVAL, "ncf_attn_forward_train: p = %g is not in [0, 1)", (double)p);
+    if (!(msg_p >= 0.f && msg_p < 1.f)) return fail(NCF_EINVAL, "ncf_attn_forward_train: msg_p = %g is not in [0, 1)", (double)msg_p);
+    if (mode < 0 || mode > 3) return fail(NCF_EINVAL, "ncf_attn_forward_train: bad mode %d", mode);
+    if (A <= 0 || Fdim <= 0) return fail(NCF_EINVAL, "ncf_attn_forward_train: bad sizes");
+    if (!attn_train_shape(mode, A, Fdim, ldpc, ldpr, ldfeat) || ldout % 4)
+        return fail(NCF_EUNSUPPORTED, "ncf_attn_forward_train: MLP and cosine only; needs A, Fdim and the leading dimensions %% 4 == 0, A, Fdim <= 256");
+    AttDrop d, m;
+    const bool on = att_drop_args(p, seed, d), msg_on = att_drop_args(msg_p, msg_seed, m);
+    return attn_forward_impl("ncf_attn_forward_train", mode, pc, ldpc, pr, ldpr, A, w1, b1, rowptr, col, val, B, I, feat, ldfeat, Fdim,
+                             out_bias, out, ldout, wts, on ? &d : nullptr, msg_on ? &m : nullptr, stream);
+}
+
+// `msg_scale` = nullptr: ncf_attn_backward (today's instantiations); else the message-dropout scale of a forward with thr_m > 0
+static int attn_backward_impl(const char* who, int mode, const float* pc, int64_t ldpc, const float* pr, int64_t ldpr, int A, const float* w1,
+                              const int64_t* rowptr, const int32_t* col, const float* val, int64_t B, int64_t I,
+                              const float* feat, int64_t ldfeat, int Fdim, const float* wts, const float* dout, int64_t lddout,
+                              float* d_pc, int64_t ldd_pc, float* d_pr, int64_t ldd_pr, float* d_w1_part, float* d_feat,
+                              int64_t ldd_feat, float* ds, uint32_t seed, float p, const float* msg_scale, ncf_stream_t stream) {
+    if (mode == NCF_ATT_MLP_SCALED) mode = NCF_ATT_MLP;
+    if (mode != NCF_ATT_MLP && mode != NCF_ATT_COS) return fail(NCF_EUNSUPPORTED, "%s: mode %d (MLP and cosine only)", who, mode);
+    if (B < 0 || I < 0 || A <= 0 || Fdim <= 0) return fail(NCF_EINVAL, "%s: bad sizes", who);
+    if (B == 0) return NCF_OK;
+    if (!pc || !pr || !rowptr || !feat || !wts || !dout || !d_pc || !d_pr || !d_feat || !ds || (mode == NCF_ATT_MLP && (!w1 || !d_w1_part)))
+        return fail(NCF_EINVAL, "%s: null pointer", who);
+    if (A % 4 || Fdim % 4 || A > 256 || Fdim > 256 || ldpc % 4 || ldpr % 4 || ldfeat % 4 || lddout % 4 || ldd_pc % 4)
+        return fail(NCF_EUNSUPPORTED, "%s: needs A, Fdim and the leading dimensions %% 4 == 0, A, Fdim <= 256", who);
+    if (ldpc < A || ldpr < A || ldfeat < Fdim || lddout < Fdim || ldd_pc < A || ldd_pr < A || ldd_feat < Fdim)
+        return fail(NCF_EINVAL, "%s: leading dimension smaller than row", who);
+    if (!aligned16(pc) || !aligned16(pr) || (w1 && !aligned16(w1)) || !aligned16(feat) || !aligned16(dout) || !aligned16(d_pc) ||
+        (d_w1_part && !aligned16(d_w1_part)))
+        return fail(NCF_EINVAL, "%s: operands must be 16-byte aligned", who);
+    if (!(p >= 0.f && p < 1.f)) return fail(NCF_EINVAL, "%s: p = %g is not in [0, 1)", who, (double)p);
+    AttDrop d;
+    const bool on = att_drop_args(p, seed, d) && mode == NCF_ATT_MLP;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((B + 3) / 4);
+#define LAUNCHB(M, D) hipLaunchKernelGGL((attn_backward_kernel<M, D>), dim3(blocks), dim3(256), 0, s, pc, ldpc, pr, ldpr, A, w1, rowptr, col, val, B, I, \
+                                         feat, ldfeat, Fdim, wts, dout, lddout, d_pc, ldd_pc, d_pr, ldd_pr, d_w1_part, d_feat, ldd_feat, ds, d, 1.f)
+#define LAUNCHBM(M, D) hipLaunchKernelGGL((attn_backward_kernel<M, D, true>), dim3(blocks), dim3(256), 0, s, pc, ldpc, pr, ldpr, A, w1, rowptr, col, val, B, I, \
+                                          feat, ldfeat, Fdim, wts, dout, lddout, d_pc, ldd_pc, d_pr, ldd_pr, d_w1_part, d_feat, ldd_feat, ds, d, *msg_scale)
+    if (msg_scale) {
+        if (mode == NCF_ATT_MLP && on) LAUNCHBM(0, true);
+        else if (mode == NCF_ATT_MLP) LAUNCHBM(0, false);
+        else LAUNCHBM(2, false);
+    } else if (mode == NCF_ATT_MLP && on) LAUNCHB(0, true);
+    else if (mode == NCF_ATT_MLP) LAUNCHB(0, false);
+    else LAUNCHB(2, false);
+#undef LAUNCHB
+#undef LAUNCHBM
+    return check_launch(who);
 }
 
 extern "C" int ncf_attn_backward(int mode, const float* pc, int64_t ldpc, const float* pr, int64_t ldpr, int A, const float* w1,
@@ -1111,31 +1202,20 @@ extern "C" int ncf_attn_backward(int mode, const float* pc, int64_t ldpc, const 
                                  const float* feat, int64_t ldfeat, int Fdim, const float* wts, const float* dout, int64_t lddout,
                                  float* d_pc, int64_t ldd_pc, float* d_pr, int64_t ldd_pr, float* d_w1_part, float* d_feat,
                                  int64_t ldd_feat, float* ds, uint32_t seed, float p, ncf_stream_t stream) {
-    if (mode == NCF_ATT_MLP_SCALED) mode = NCF_ATT_MLP;
-    if (mode != NCF_ATT_MLP && mode != NCF_ATT_COS) return fail(NCF_EUNSUPPORTED, "ncf_attn_backward: mode %d (MLP and cosine only)", mode);
-    if (B < 0 || I < 0 || A <= 0 || Fdim <= 0) return fail(NCF_EINVAL, "ncf_attn_backward: bad sizes");
-    if (B == 0) return NCF_OK;
-    if (!pc || !pr || !rowptr || !feat || !wts || !dout || !d_pc || !d_pr || !d_feat || !ds || (mode == NCF_ATT_MLP && (!w1 || !d_w1_part)))
-        return fail(NCF_EINVAL, "ncf_attn_backward: null pointer");
-    if (A % 4 || Fdim % 4 || A > 256 || Fdim > 256 || ldpc % 4 || ldpr % 4 || ldfeat % 4 || lddout % 4 || ldd_pc % 4)
-        return fail(NCF_EUNSUPPORTED, "ncf_attn_backward: needs A, Fdim and the leading dimensions %% 4 == 0, A, Fdim <= 256");
-    if (ldpc < A || ldpr < A || ldfeat < Fdim || lddout < Fdim || ldd_pc < A || ldd_pr < A || ldd_feat < Fdim)
-        return fail(NCF_EINVAL, "ncf_attn_backward: leading dimension smaller than row");
-    if (!aligned16(pc) || !aligned16(pr) || (w1 && !aligned16(w1)) || !aligned16(feat) || !aligned16(dout) || !aligned16(d_pc) ||
-        (d_w1_part && !aligned16(d_w1_part)))
-        return fail(NCF_EINVAL, "ncf_attn_backward: operands must be 16-byte aligned");
-    if (!(p >= 0.f && p < 1.f)) return fail(NCF_EINVAL, "ncf_attn_backward: p = %g is not in [0, 1)", (double)p);
-    AttDrop d;
-    const bool on = att_drop_args(p, seed, d) && mode == NCF_ATT_MLP;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)((B + 3) / 4);
-#define LAUNCHB(M, D) hipLaunchKernelGGL((attn_backward_kernel<M, D>), dim3(blocks), dim3(256), 0, s, pc, ldpc, pr, ldpr, A, w1, rowptr, col, val, B, I, \
-                                         feat, ldfeat, Fdim, wts, dout, lddout, d_pc, ldd_pc, d_pr, ldd_pr, d_w1_part, d_feat, ldd_feat, ds, d)
-    if (mode == NCF_ATT_MLP && on) LAUNCHB(0, true);
-    else if (mode == NCF_ATT_MLP) LAUNCHB(0, false);
-    else LAUNCHB(2, false);
-#undef LAUNCHB
-    return check_launch("ncf_attn_backward");
+    return attn_backward_impl("ncf_attn_backward", mode, pc, ldpc, pr, ldpr, A, w1, rowptr, col, val, B, I, feat, ldfeat, Fdim, wts, dout, lddout,
+                              d_pc, ldd_pc, d_pr, ldd_pr, d_w1_part, d_feat, ldd_feat, ds, seed, p, nullptr, stream);
+}
+
+extern "C" int ncf_attn_backward_train(int mode, const float* pc, int64_t ldpc, const float* pr, int64_t ldpr, int A, const float* w1,
+                                       const int64_t* rowptr, const int32_t* col, const float* val, int64_t B, int64_t I,
+                                       const float* feat, int64_t ldfeat, int Fdim, const float* wts, const float* dout, int64_t lddout,
+                                       float* d_pc, int64_t ldd_pc, float* d_pr, int64_t ldd_pr, float* d_w1_part, float* d_feat,
+                                       int64_t ldd_feat, float* ds, uint32_t seed, float p, float msg_p, ncf_stream_t stream) {
+    if (!(msg_p >= 0.f && msg_p < 1.f)) return fail(NCF_EINVAL, "ncf_attn_backward_train: msg_p = %g is not in [0, 1)", (double)msg_p);
+    AttDrop m;
+    const bool msg_on = att_drop_args(msg_p, 0u, m);
+    return attn_backward_impl("ncf_attn_backward_train", mode, pc, ldpc, pr, ldpr, A, w1, rowptr, col, val, B, I, feat, ldfeat, Fdim, wts, dout,
+                              lddout, d_pc, ldd_pc, d_pr, ldd_pr, d_w1_part, d_feat, ldd_feat, ds, seed, p, msg_on ? &m.scale : nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -168,6 +168,11 @@ class AttentionNCF(_ScoringMixin, NCF):
     # a dense (B, I) user_matrix is converted to shared-row CSR on the stream (no host read; the grouped kernels are used whatever the
     # sharing turns out to be).  False: round 2's conversion — two host reads, exact choice between the grouped and the per-pair kernel.
     dense_user_matrix_on_stream = True
+    # True: a training step with message_dropout > 0 runs on the HIP attention kernels (ncf_attn_forward_train / _backward_train: the
+    # entry mask is regenerated from a counter hash, not drawn from torch's Philox stream, so a seeded run draws other masks of the
+    # same law).  False: that step takes the torch ops of _forward_train, as before.  A class attribute, not a kwarg: checkpoints
+    # (get_model_parameters) stay the reference's.
+    message_dropout_on_device = False
 
     def __init__(self, item_dim, item_emb=128, user_emb=128, att_dense=None, mlp_dense_layers=None,
                  use_cos_sim_instead=False, dropout_rate=0.2, message_dropout=None):
@@ -520,7 +525,7 @@ class AttentionNCF(_ScoringMixin, NCF):
     def _forward_train_hip(self, candidate_items, rated_items, user_matrix, return_attention_weights, pair_split=None):
         """attention_ncf.py:136-224 with autograd recording, on the HIP blocks: the Linear layers (LinearFn), the attention with its
         softmax and weighted sum (AttnFn: forward and backward kernels; AttentionNet's hidden dropout regenerated from a hash in
-        both), the MLP (mlp_train).  The train-only target masking (:195-205, a candidate must not attend to itself) is decided
+        both; with message_dropout_on_device the message dropout over the logits too), the MLP (mlp_train).  The train-only target masking (:195-205, a candidate must not attend to itself) is decided
         per rated ENTRY with the reference's own test (isclose of the two embedding rows) and applied by dropping the entry."""
         from ...autograd import AttnFn, LinearFn, mlp_train
         li, lu = self.ItemEmbeddings[0], self.UserEmbeddings[0]
@@ -547,6 +552,7 @@ class AttentionNCF(_ScoringMixin, NCF):
             same = torch.isclose(cand_emb.detach()[b_of], rated_emb.detach()[col.long()], atol=1e-5).all(dim=1)
             col = torch.where(same, torch.full_like(col, -1), col)        # a dropped entry: score -inf, weight 0 (:192-205)
         dropout = None
+        hidden_seed, msg_seed = self._draw_attention_seeds()
         if self.use_cos_sim_instead:
             mode, w1, b1 = native.ATT_COS, None, None
             pc, pr = F.normalize(cand_emb, p=2, dim=1), F.normalize(rated_emb, p=2, dim=1)
@@ -556,19 +562,36 @@ class AttentionNCF(_ScoringMixin, NCF):
             pc = LinearFn.apply(cand_emb, l0.weight[:, :IE], l0.bias, False)      # AttentionNet.0 split at the cat boundary (:176)
             pr = LinearFn.apply(rated_emb, l0.weight[:, IE:], None, False)
             mode, w1, b1 = native.ATT_MLP, l1.weight.view(-1), l1.bias
-            drop = self.AttentionNet[2]
-            if self.training and isinstance(drop, nn.Dropout) and drop.p > 0:
-                dropout = (float(drop.p), int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))    # host generator: no device sync
+            if hidden_seed is not None:
+                dropout = (float(self.AttentionNet[2].p), hidden_seed)
         proj = LinearFn.apply(rated, lu.weight, None, False)        # UserEmbeddings is linear over the weighted sum (:212-216)
-        user_emb, wts = AttnFn.apply(pc, pr, w1, b1, proj, lu.bias, rowptr, col, val, mode, dropout)
+        msg_dropout = None if msg_seed is None else (float(self.message_dropout), msg_seed)
+        user_emb, wts = AttnFn.apply(pc, pr, w1, b1, proj, lu.bias, rowptr, col, val, mode, dropout, msg_dropout)
         out = self._train_mlp(torch.cat((cand_emb, user_emb), dim=1), True, pair_split)
         if return_attention_weights:
             dense = SparseRatings(rowptr, ratings.col, val, ratings.num_items).to_dense(wts.detach())
             return out, dense
         return out
 
+    def _message_dropout_active(self):
+        return bool(self.training and self.message_dropout)
+
+    def _draw_attention_seeds(self):
+        """(hidden seed or None, message seed or None) of one step on the HIP blocks, from the host generator (no device sync).  The
+        hidden seed is drawn first and only when AttentionNet's hidden dropout is active; the message seed after it and only when
+        the message dropout runs on the device — so a run without message_dropout_on_device consumes the generator as before."""
+        hidden = msg = None
+        if not self.use_cos_sim_instead and self.att_dense:
+            drop = self.AttentionNet[2]
+            if self.training and isinstance(drop, nn.Dropout) and drop.p > 0:
+                hidden = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        if self._message_dropout_active() and self.message_dropout_on_device:
+            msg = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        return hidden, msg
+
     def _forward_train(self, candidate_items, rated_items, user_matrix, return_attention_weights, pair_split=None):
-        hip = (candidate_items.is_cuda and not getattr(self, "train_with_torch_ops", False) and not (self.training and self.message_dropout)
+        hip = (candidate_items.is_cuda and not getattr(self, "train_with_torch_ops", False)
+               and (self.message_dropout_on_device or not self._message_dropout_active())
                and (self.use_cos_sim_instead or self.att_dense) and native.attn_backward_supported(
                    native.ATT_COS if self.use_cos_sim_instead else native.ATT_MLP,
                    self.ItemEmbeddings[0].out_features if self.use_cos_sim_instead else int(self.att_dense), self.UserEmbeddings[0].out_features))

@@ -455,6 +455,41 @@ int ncf_attn_backward(int mode,
                       float* dev_d_feat, int64_t ldd_feat, float* dev_scratch,
                       uint32_t seed, float p, ncf_stream_t stream);
 
+/* The training pair with AttentionNCF's MESSAGE dropout (attention_ncf.py:184-189: F.dropout over the (pair, rated entry) logits, then
+ * `attOut[attOut == 0] = -inf` before the softmax).  Arguments as ncf_attn_forward_dropout / ncf_attn_backward, then the message
+ * dropout's own.  With thr_m, p' and the fp32 scale_m computed from msg_p exactly as thr, p' and the scale under THE MASK:
+ *   forward   raw_e  = the score of ncf_attn_forward_dropout (b1 and the hidden mask under `seed` included; the dot product for cosine)
+ *             keep_e = element (entry e, feature 0) of THE MASK under msg_seed: lowbias32(e * 0x9E3779B1 ^ msg_seed) & 0xFFFF >= thr_m,
+ *                      e = the entry's position in the per-pair CSR of the call, as for the hidden mask
+ *             s_e    = keep_e ? raw_e * scale_m : 0      (one fp32 product)
+ *             s_e == 0 (either sign) becomes -inf: a dropped entry leaves the softmax, and so does a KEPT entry whose score is exactly
+ *             zero — the reference's test cannot tell the two apart.  Softmax and aggregation are ncf_attn_forward's; a row whose
+ *             entries are all dropped has zero weights and dev_out_feat = bias.
+ *   backward  a dropped entry has weight 0, so its ds_e, its share of d feat and its score gradient are 0 already; for a kept entry the
+ *             logit is scale_m * raw_e, so the only change is ds_e = scale_m * w_e (dpv_e - t).  No mask is regenerated and no message
+ *             seed is taken.  d b1 stays exactly 0: scale_m * b1 is one shift over the kept entries, which cancels in the softmax.
+ * thr_m = 0 (msg_p < 2^-17) runs the instantiations of ncf_attn_forward[_dropout] / ncf_attn_backward bit for bit; the zero rule is NOT
+ * applied there (a message_dropout of 0 never applied it on this path).  msg_seed should differ from seed: with equal seeds the
+ * entry's keep bit is hidden unit 0's.  NCF_ATT_MLP, NCF_ATT_MLP_SCALED and NCF_ATT_COS (hidden p must quantise to 0 for cosine);
+ * NCF_ATT_LINEAR, or A, Fdim or a leading dimension outside ncf_attn_backward's conditions (multiples of 4, A, Fdim <= 256), is
+ * NCF_EUNSUPPORTED and launches nothing, whatever msg_p.  p or msg_p outside [0, 1) or NaN: NCF_EINVAL. */
+int ncf_attn_forward_train(int mode,
+                           const float* dev_pc, int64_t ldpc, const float* dev_pr, int64_t ldpr, int A,
+                           const float* dev_w1, float b1,
+                           const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val,
+                           int64_t B, int64_t I,
+                           const float* dev_feat, int64_t ldfeat, int Fdim, const float* dev_out_bias,
+                           float* dev_out_feat, int64_t ldout, float* dev_weights,
+                           uint32_t seed, float p, uint32_t msg_seed, float msg_p, ncf_stream_t stream);
+int ncf_attn_backward_train(int mode,
+                            const float* dev_pc, int64_t ldpc, const float* dev_pr, int64_t ldpr, int A, const float* dev_w1,
+                            const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t B, int64_t I,
+                            const float* dev_feat, int64_t ldfeat, int Fdim,
+                            const float* dev_weights, const float* dev_dout, int64_t lddout,
+                            float* dev_d_pc, int64_t ldd_pc, float* dev_d_pr, int64_t ldd_pr, float* dev_d_w1_part,
+                            float* dev_d_feat, int64_t ldd_feat, float* dev_scratch,
+                            uint32_t seed, float p, float msg_p, ncf_stream_t stream);
+
 /* The same computation for batches in which several pairs share one rated set (evaluation batches grouped by user;
  * serving one user against the whole catalogue, reference webapp/backend.py:78-121), LDS-tiled: the CSR has one row
  * per USER (n_rows rows), the B pairs are listed user by user —

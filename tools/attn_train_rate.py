@@ -1,8 +1,8 @@
-"""Dev tool (GPU box): the measurements of DESIGN §4.24 — an AttentionNCF training epoch on device-built batches against the
+"""Dev tool (GPU box): the measurements of DESIGN §4.24 and §4.29 — an AttentionNCF training epoch on device-built batches against the
 DataLoader loop, at the cfg 3 shape (100 k-item catalogue of 2094 features, batches of 4096 pairs from 64
 users with 256 rated items each, item_emb = user_emb = 64, att_dense = 128, MLP [256, 128]).
 
-    python tools/attn_train_rate.py [--scale S] [--rounds N] [part ...]        parts: epoch, split, forms (default: all)
+    python tools/attn_train_rate.py [--scale S] [--rounds N] [part ...]        parts: epoch, split, forms (default: these three), msgdrop
 
   epoch   train_model, both dynamic datasets, resident=False and resident=True alternating in one process, N rounds of 2 epochs
           each after one untimed round; the SECOND epoch of a call is the figure (host clock, device synchronised at both ends;
@@ -10,11 +10,19 @@ users with 256 rated items each, item_emb = user_emb = 64, att_dense = 128, MLP 
   split   the resident step in parts (HIP events, back to back, FusedAdam): batch assembly (gathers; + sample_negatives for
           pairs), native.pair_rows alone at the step's shape, forward + loss + backward, the optimiser
   forms   the pair-wise step as one forward of 2B pairs against two forwards of B
+  msgdrop the resident step (HIP events, FusedAdam) of three models with equal weights, alternating in one process, N rounds:
+          (a) message_dropout = 0.2 with AttentionNCF.message_dropout_on_device (ncf_attn_forward_train / _backward_train),
+          (b) the same model without the opt-in: the torch ops of _forward_train (a dense (B, I) score matrix and an isclose over
+              B x I x IE elements: point-wise only, and only where that can fit the free device memory; where the isclose still
+              runs out of memory the model warns and the step goes on WITHOUT the target mask, as the reference does — counted),
+          (c) message_dropout = None on the HIP blocks
 
 --scale S divides the catalogue and the batch by S (a rehearsal of the host side; figures at S > 1 measure overheads).
 A training file is 8 batches; it is laid out so that, unshuffled, a batch holds 64 users, as cfg 3's batches do.
 """
 import argparse
+import contextlib
+import io
 import os
 import sys
 import tempfile
@@ -77,10 +85,10 @@ def workload(scale):
     return prov, point, ranking, point.iloc[:64].reset_index(drop=True), (I, B, nnz, Fdim, IE, UE, A)
 
 
-def new_model(dims):
+def new_model(dims, message_dropout=None):
     I, B, nnz, Fdim, IE, UE, A = dims
     torch.manual_seed(7)
-    return AttentionNCF(item_dim=Fdim, item_emb=IE, user_emb=UE, att_dense=A, mlp_dense_layers=[256, 128])
+    return AttentionNCF(item_dim=Fdim, item_emb=IE, user_emb=UE, att_dense=A, mlp_dense_layers=[256, 128], message_dropout=message_dropout)
 
 
 def part_epoch(dev, w, rounds):
@@ -212,6 +220,46 @@ def part_forms(dev, w):
     native.check_pair_rows(dev)
 
 
+def part_msgdrop(dev, w, rounds):
+    dims = w[4]
+    I, B, IE = dims[0], dims[1], dims[4]
+    pds, rds, point_batch, pair_batch, pairs = _resident_makers(dev, w)
+    for name, ds, make in (("point-wise", pds, point_batch), ("pair-wise", rds, pair_batch)):
+        variants = {"a: HIP, message dropout 0.2": (0.2, True), "b: torch ops, message dropout 0.2": (0.2, False), "c: HIP, no message dropout": (None, False)}
+        # (b) compares every candidate row with every rated row: a - b, |a - b| (fp32) and the comparison's result over B x I x IE
+        need = (2 * 4 + 1) * B * I * IE + 3 * 4 * B * I
+        free = torch.cuda.mem_get_info(dev)[0]
+        if name == "pair-wise" or need > 0.8 * free:
+            print(f"{name}: (b) is not measured: its target mask alone needs {need * (2 if name == 'pair-wise' else 1) / 2 ** 30:.0f} GiB "
+                  f"({free / 2 ** 30:.0f} GiB free)", flush=True)
+            del variants["b: torch ops, message dropout 0.2"]
+        steps = {}
+        for tag, (p, on_device) in variants.items():
+            m = new_model(dims, p).to(dev).train()
+            m.message_dropout_on_device = on_device
+            opt = FusedAdam(m.parameters(), lr=1e-3)
+
+            def step(m=m, opt=opt):
+                opt.zero_grad()
+                a, b = type(ds).do_forward(m, make(), dev)
+                ds.calculate_loss(a, b).backward()
+                opt.step()
+
+            steps[tag] = step
+        runs, said = {}, io.StringIO()
+        for _ in range(rounds):
+            for tag, fn in steps.items():
+                with contextlib.redirect_stderr(said):
+                    runs.setdefault(tag, []).append(events_us(fn, 4 if tag.startswith("b") else 10, settle=1 if tag.startswith("b") else 3))
+        unmasked = said.getvalue().count("Could not calculate training mask")
+        if unmasked:
+            print(f"{name}: {unmasked} of {5 * rounds} steps of (b) could not build the target mask and ran without it", flush=True)
+        print(f"{name} resident step, message dropout: " + "; ".join(
+            f"({tag}) {min(v) / 1e3:.2f} ms (all rounds: {', '.join(f'{t / 1e3:.2f}' for t in v)})" for tag, v in runs.items()), flush=True)
+    pairs.check()
+    native.check_pair_rows(dev)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=int, default=1)
@@ -224,7 +272,8 @@ def main():
         raise SystemExit("no GPU: nothing is measured without one")
     dev = torch.device("cuda:0")
     for p in args.parts:
-        {"epoch": lambda: part_epoch(dev, w, args.rounds), "split": lambda: part_split(dev, w), "forms": lambda: part_forms(dev, w)}[p]()
+        {"epoch": lambda: part_epoch(dev, w, args.rounds), "split": lambda: part_split(dev, w), "forms": lambda: part_forms(dev, w),
+         "msgdrop": lambda: part_msgdrop(dev, w, args.rounds)}[p]()
 
 
 if __name__ == "__main__":
