@@ -652,6 +652,8 @@ def test_attn_candidates_both_weight_forms(gpu, B, K, N1, N2, users):
     the pairs by rated set in one launch): both against an fp64 product, bit-identical to each other where the packed form is one
     launch (B > 2048; below that its K range is cut over workgroups), grouping = ncf_group_pairs_rows'.
     Ragged K (2094 = 65 * 32 + 14; 31 < one step), B not a multiple of the 16-row tile, both widths of ItemEmbeddings."""
+    # "bit-identical where the packed form is one launch": on float data the split-K form can only be held to the bar.  On the
+    # exact-integer cases of tests/test_gpu_serve_forms.py every form — split-K included — must equal the exact product bit for bit.
     from deeprecommendation_amd import native
     g = torch.Generator().manual_seed(B + K)
     x = ((torch.rand(B, K, generator=g) < 0.1).float() + torch.rand(B, K, generator=g) * 0.1).to(gpu)
