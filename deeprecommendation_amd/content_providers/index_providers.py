@@ -122,6 +122,45 @@ class OneHotProvider(IndexProvider):
         return self._onehot(_positions(self.all_user_ids, userID), self.get_num_users())
 
 
+class ContentIndexProvider(IndexProvider):
+    """The content form's counterpart of the reference's FixedProfilesProvider: a user is a fixed profile row, an item its feature
+    row (``item_dim = user_dim = F``).  It hands out POSITIONS exactly as IndexProvider does (same ``device_lookup``), so the fixed
+    datasets take their resident paths, and carries the two tables the positions name: ``user_profiles`` (U, F) in sorted user id
+    order and ``item_features`` (I, F) in sorted item id order.  ``content(device)`` is what ``BasicNCF.set_content`` takes."""
+
+    def __init__(self, user_ids, item_ids, user_profiles, item_features):
+        super().__init__(user_ids, item_ids)
+        self.user_profiles = torch.as_tensor(user_profiles, dtype=torch.float32)
+        self.item_features = torch.as_tensor(item_features, dtype=torch.float32)
+        if self.user_profiles.dim() != 2 or self.user_profiles.shape[0] != len(self.all_user_ids):
+            raise ValueError(f"user_profiles must be ({len(self.all_user_ids)}, F): one row per distinct user id, in sorted id order")
+        if self.item_features.dim() != 2 or self.item_features.shape[0] != len(self.all_item_ids):
+            raise ValueError(f"item_features must be ({len(self.all_item_ids)}, F): one row per distinct item id, in sorted id order")
+        if self.user_profiles.shape[1] != self.item_features.shape[1]:
+            raise ValueError("a user profile is a weighted mean of item feature rows: both tables have the same width")
+
+    @classmethod
+    def from_dynamic(cls, provider: "SparseDynamicProvider", device):
+        """From a SparseDynamicProvider: its feature table, and its users' profiles built on ``device`` (``user_profiles``),
+        reordered from the provider's user order to sorted id order."""
+        uid = np.asarray(list(provider.user_pos.keys()))
+        upos = np.asarray(list(provider.user_pos.values()), dtype=np.int64)
+        order = torch.from_numpy(upos[np.argsort(uid, kind="stable")])
+        profiles = provider.user_profiles(device)
+        return cls(uid, provider.item_ids, profiles[order.to(profiles.device)], provider.features)
+
+    def get_item_feature_dim(self):
+        return self.item_features.shape[1]
+
+    def content(self, device):
+        """``(user_profiles, item_features)`` as contiguous fp32 tensors on ``device`` (cached per device)."""
+        cache = self.__dict__.setdefault("_device_content", {})
+        key = str(device)
+        if key not in cache:
+            cache[key] = (self.user_profiles.to(device).contiguous(), self.item_features.to(device).contiguous())
+        return cache[key]
+
+
 class IndexGraphProvider(GraphContentProvider):
     """Vectorised counterpart of GraphProvider + create_graph (graph_providers.py:10-118) with one-hot node features
     (OneHotGraphProvider): items are nodes 0..I-1 in sorted id order, user node id = I + rank (:79-80); edge
@@ -235,6 +274,32 @@ class SparseDynamicProvider(DynamicContentProvider):
                 cache[key] = _DynamicDeviceState(self, device)
             except ValueError:
                 cache[key] = None
+        return cache[key]
+
+    def profile_csr(self):
+        """The raw ratings as the profile kernel reads them (host arrays): ``rowptr`` (U + 1) int64, ``col`` int32 catalogue
+        positions, ``rating`` fp32 and ``avg`` (U,) float64 = (mean + 2.5) / 2.  EVERY rating is kept, in the provider's order (by
+        item id) — unlike ``device_state``'s CSR, which stores the centred value in fp32 and drops the entries that are zero."""
+        n_users = len(self.user_rated_items)
+        counts = np.fromiter((len(x) for x in self.user_rated_items), dtype=np.int64, count=n_users)
+        rowptr = np.zeros(n_users + 1, dtype=np.int64)
+        np.cumsum(counts, out=rowptr[1:])
+        rated = np.concatenate(self.user_rated_items) if rowptr[-1] else np.zeros(0, self.item_ids.dtype)
+        col = (_positions(self.item_ids, rated) if len(rated) else np.zeros(0, np.int64)).astype(np.int32)
+        rating = (np.concatenate(self.user_ratings) if rowptr[-1] else np.zeros(0)).astype(np.float32)
+        return rowptr, col, rating, (self.user_mean + 2.5) / 2
+
+    def user_profiles(self, device):
+        """The fixed profile of every user, (U, F) fp32 on ``device`` in the provider's user order (cached per device): the mean
+        over the user's rated items of ``(rating - (mean + 2.5) / 2) * item_features`` in float64 — the reference's
+        create_user_embedding — by native.user_profiles.  A user without ratings gets a zero row."""
+        from .. import native
+        cache = self.__dict__.setdefault("_device_profiles", {})
+        key = str(device)
+        if key not in cache:
+            rowptr, col, rating, avg = self.profile_csr()
+            cache[key] = native.user_profiles(*(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (rowptr, col, rating, avg)),
+                                              self.features.to(device).contiguous())
         return cache[key]
 
     def collate_interacted_items(self, batch, for_ranking: bool, ignore_ratings=False):

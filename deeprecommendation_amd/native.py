@@ -138,6 +138,7 @@ SIGNATURES = {
     "ncf_relu_backward_out": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, ctypes.c_float, _c_p]),
     "ncf_scatter_add_rows": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_l2_normalize_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p]),
+    "ncf_user_profiles": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p, _c_p]),
     "ncf_gather_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_int, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
     "ncf_scatter_add_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
@@ -1356,6 +1357,36 @@ def l2_normalize_rows(x: torch.Tensor) -> torch.Tensor:
     R, E, ld = _rows2d(x, "x")
     out = torch.empty((R, E), dtype=torch.float32, device=x.device)
     _check(lib.ncf_l2_normalize_rows(_ptr(x), ld, R, E, _ptr(out), out.stride(0), _stream(x)))
+    return out
+
+
+def user_profiles(rowptr: torch.Tensor, col: torch.Tensor, rating: torch.Tensor, avg: torch.Tensor, features: torch.Tensor,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fixed user profiles (ncf_user_profiles, the contract in include/ncf_abi.h): out[u] = the float64 mean over user u's ratings, in
+    order, of (rating - avg[u]) * features[col], rounded to fp32; an empty row gives zeros.  ``rowptr`` (U + 1,) int64, ``col`` int32 and
+    ``rating`` fp32 of one entry per rating, ``avg`` (U,) float64, ``features`` (I, F) fp32 rows (a column slice is fine).  A column
+    outside [0, I) sets the sticky out-of-range flag (check_oob) and adds nothing.  Shapes, dtypes and layout are checked before the
+    device is."""
+    for t, what, dt in ((rowptr, "rowptr", torch.int64), (col, "col", torch.int32), (rating, "rating", torch.float32),
+                        (avg, "avg", torch.float64)):
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"user_profiles: {what} must be a contiguous 1-D {dt} tensor")
+    if features.dtype != torch.float32 or (out is not None and out.dtype != torch.float32):
+        raise ValueError("user_profiles: features and out must be float32")
+    I, F, ldf = _rows2d(features, "features")
+    U = avg.numel()
+    if rowptr.numel() != U + 1 or col.numel() != rating.numel():
+        raise ValueError(f"user_profiles: rowptr has {rowptr.numel()} entries for {U} users, col {col.numel()} for {rating.numel()} ratings")
+    if out is not None and (out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (U, F)):
+        raise ValueError(f"user_profiles: out must be ({U}, {F}) with unit inner stride")
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (rating, "rating"), (avg, "avg"), (features, "features"), (out, "out")):
+        if t is not None:
+            _dev(t, what)
+    lib = load_library()
+    if out is None:
+        out = torch.empty((U, F), dtype=torch.float32, device=features.device)
+    _check(lib.ncf_user_profiles(_ptr(rowptr), _ptr(col), _ptr(rating), col.numel(), _ptr(avg), U, _ptr(features), I, ldf, F, _ptr(out),
+                                 out.stride(0), _ptr(_oob_flag(features.device)), _stream(features)))
     return out
 
 

@@ -5,6 +5,8 @@ forward(X_user, X_item) dispatches on the input:
     basic_ncf.py:38-39 with src/util.py:5-10), gathered and scored by ONE fused HIP kernel (ncf_score_fused);
   * float (B, dim) rows   -> dense path: the two Linears as HIP GEMMs, then the same fused MLP kernel on the
     (B, E) activations (identity gather).
+With content attached (``set_content``: the reference's FixedProfilesProvider form, item_dim = user_dim = F) int64 positions name
+rows of the content tables and the table path runs on T = content·W^T + b, built once per weight version.
 Both run only on CUDA(HIP) tensors in eval / no-grad mode; a training step uses the differentiable torch ops.
 """
 import torch
@@ -24,6 +26,7 @@ class _ScoringMixin:
     partial_first_layer = None      # None = automatic (see _partial), True = whenever supported, False = never
     partial_max_bytes = None        # cap on the partial table; None = min(4 GiB, free device memory / 4) at build time
     PARTIAL_MIN_ROUNDS = 1          # automatic mode: batches of at least this many rounds of 4 x CUs 32-pair tiles
+    _content = None                 # BasicNCF.set_content: (user_profiles (U, user_dim), item_features (I, item_dim)); None = one-hot form
 
     def set_partial_first_layer(self, enabled=None, max_bytes=None):
         """Partial first layer (frozen weights, bit-identical): layer 1's accumulators after the user table's k-groups are
@@ -67,8 +70,15 @@ class _ScoringMixin:
         cache = self._refresh() if cache is None else cache
         if name not in cache:
             with torch.no_grad():
-                # row i = W[:, i] + b : exactly what Linear(onehot(i)) computes (one fp32 rounding)
-                cache[name] = (lin.weight.detach().t().contiguous() + lin.bias.detach()).to(self.scoring_dtype).contiguous()
+                if self._content is not None:
+                    # content form (BasicNCF.set_content): row i = content[i] . W^T + b, the Linear of the float-row forward over
+                    # every content row, once per weight version
+                    content = self._content[0 if name == "user" else 1]
+                    emb = native.linear(content, self._dense_weight(name, lin, cache), lin.bias.detach())
+                else:
+                    # row i = W[:, i] + b : exactly what Linear(onehot(i)) computes (one fp32 rounding)
+                    emb = lin.weight.detach().t().contiguous() + lin.bias.detach()
+                cache[name] = emb.to(self.scoring_dtype).contiguous()
         return cache[name]
 
     def _dense_weight(self, name: str, lin: nn.Linear, cache=None) -> torch.Tensor:
@@ -194,6 +204,39 @@ class BasicNCF(_ScoringMixin, NCF):
     def get_model_parameters(self) -> dict:
         return self.kwargs
 
+    def set_content(self, user_profiles=None, item_features=None):
+        """Content form (the reference's FixedProfilesProvider: a user is a fixed profile row, an item its feature row): attach
+        the two fp32 device tables, ``user_profiles`` (U, user_dim) and ``item_features`` (I, item_dim).  int64 arguments of
+        ``forward`` are then ROWS of these tables: in eval mode the embedding tables are ``content . W^T + b``, built once per
+        weight version and per ``set_content``, and every table kernel (fused, partial, folded, bf16, top-K, ranks) runs on them
+        as it does for a one-hot model; a training step gathers the content rows and runs the Linear of the float-row forward.
+        ``set_content(None, None)`` detaches them.  Float-row forwards are not affected.  Neither table is copied or saved."""
+        if user_profiles is None and item_features is None:
+            self._content = None
+            self._native_ver = None
+            return self
+        for t, what, width in ((user_profiles, "user_profiles", self.kwargs["user_dim"]), (item_features, "item_features", self.kwargs["item_dim"])):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2:
+                raise ValueError(f"{what} must be a 2-D float32 tensor")
+            if t.shape[1] != width:
+                raise ValueError(f"{what} has {t.shape[1]} columns, the model's embedding takes {width}")
+            if not t.is_contiguous():
+                raise ValueError(f"{what} must be row-contiguous")
+            if not t.is_cuda:
+                raise ValueError(f"{what} must live on the GPU (got {t.device})")
+        self._content = (user_profiles, item_features)
+        self._native_ver = None
+        return self
+
+    @property
+    def num_users(self) -> int:
+        """Rows a user position may name: the content table's with content attached, the one-hot width otherwise."""
+        return self._content[0].shape[0] if self._content is not None else self.user_embeddings[0].in_features
+
+    @property
+    def num_items(self) -> int:
+        return self._content[1].shape[0] if self._content is not None else self.item_embeddings[0].in_features
+
     def forward(self, X_user, X_item):
         indexed = X_user.dtype == torch.int64 and X_user.dim() == 1
         if not use_native(self):
@@ -214,6 +257,11 @@ class BasicNCF(_ScoringMixin, NCF):
         if X_user.is_cuda and not getattr(self, "train_with_torch_ops", False):
             from ...autograd import GatherColumnsConcatFn, GatherColumnsFn, LinearFn, mlp_train
             ue, ie = self.user_embeddings[0], self.item_embeddings[0]
+            if indexed and self._content is not None:
+                # content form: the batch's (B, F) content rows, gathered by position, then the float-row step below on them
+                X_user = native.gather_concat(self._content[0], X_user.contiguous())
+                X_item = native.gather_concat(self._content[1], X_item.contiguous())
+                indexed = False
             if indexed:
                 # The parameters live in nn.Linear layout [E, U] (checkpoint compatibility), so a training step gathers
                 # COLUMNS of W (materialising T = W^T + b every step for the row-gather kernel costs two full-table
@@ -230,6 +278,8 @@ class BasicNCF(_ScoringMixin, NCF):
                 x = torch.cat((LinearFn.apply(X_user.float(), ue.weight, ue.bias, False),
                                LinearFn.apply(X_item.float(), ie.weight, ie.bias, False)), dim=1)
             return mlp_train(self.MLP, x)
+        if indexed and self._content is not None:
+            X_user, X_item, indexed = self._content[0][X_user], self._content[1][X_item], False
         if indexed:
             ue, ie = self.user_embeddings[0], self.item_embeddings[0]
             user_emb = ue.weight.t()[X_user] + ue.bias

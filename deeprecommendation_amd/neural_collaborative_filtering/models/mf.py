@@ -20,6 +20,14 @@ class MF(_ScoringMixin, NCF):
     def get_model_parameters(self) -> dict:
         return self.kwargs
 
+    @property
+    def num_users(self) -> int:
+        return self.user_embeddings[0].in_features
+
+    @property
+    def num_items(self) -> int:
+        return self.item_embeddings[0].in_features
+
     def forward(self, X_user, X_item):
         indexed = X_user.dtype == torch.int64 and X_user.dim() == 1
         if not use_native(self):

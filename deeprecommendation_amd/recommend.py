@@ -4,6 +4,9 @@
                        block by block through the model's HIP scoring path and ranked by ncf_topk_rows — or scored and ranked in
                        one pass (no score matrix) by ncf_dot_topk for a dot-product readout and by ncf_mlp_topk for an MLP
                        readout.  Results stay on the device.
+                       A BasicNCF with content attached (``set_content``) ranks the rows of its item table like a one-hot model.
+``content_cosine_top_k`` / ``content_cosine_ranks``
+                       the reference's content-based baseline: cosine of a user's fixed profile and an item's feature row.
 ``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
 ``rated_exclusion``    the same for an AttentionNCF's users: the items each listed user rated.
 ``explain_items``      AttentionNCF: the reasons behind winners of many users at once (which rated items carry the attention), from the
@@ -124,7 +127,7 @@ def _resolve_ranked(model, user_ids, item_ids, exclude, graph, profiles=None, fu
         graph = graph.to(dev)
         n_items = graph.num_items
     else:
-        n_items = model.item_embeddings[0].in_features
+        n_items = model.num_items       # a BasicNCF with content attached: the rows of its item table, not the feature width
     if item_ids is None:
         items = torch.arange(n_items, dtype=torch.int64, device=dev)
     else:
@@ -298,6 +301,71 @@ def rated_exclusion(ratings: SparseRatings, user_ids: torch.Tensor) -> Tuple[tor
     row = torch.repeat_interleave(torch.arange(user_ids.numel(), device=dev), cnt)
     pos = lo[row] + torch.arange(row.numel(), device=dev) - rowptr[row]
     return rowptr, ratings.col[pos].to(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------- content-based baseline
+def _cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes):
+    """Yields ``(b0, b1, cosines (b1 - b0, I))`` of the listed users' profiles against the ranked list's feature rows: both sides
+    L2-normalised by rows (ncf_l2_normalize_rows: a zero row stays zero), then one Linear launch per block of users."""
+    for t, what in ((user_profiles, "user_profiles"), (item_features, "item_features")):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError(f"{what} must be a 2-D float32 tensor")
+    if user_profiles.shape[1] != item_features.shape[1]:
+        raise ValueError(f"user_profiles has {user_profiles.shape[1]} columns, item_features {item_features.shape[1]}")
+    for t, what in ((user_ids, "user_ids"), (item_ids, "item_ids")):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1):
+            raise ValueError(f"{what} must be a 1-D int64 tensor of positions")
+    require_gpu(user_profiles, item_features, user_ids, item_ids)
+    with torch.no_grad():
+        items = native.l2_normalize_rows(item_features if item_ids is None else native.gather_concat(item_features, item_ids.contiguous()))
+    rows_per_block = max(1, int(block_bytes) // max(1, items.shape[0] * 4))
+    users = user_ids.contiguous()
+    for b0 in range(0, users.numel(), rows_per_block):
+        b1 = min(users.numel(), b0 + rows_per_block)
+        with torch.no_grad():
+            prof = native.l2_normalize_rows(native.gather_concat(user_profiles, users[b0:b1]))
+            scores = native.linear(prof, items, None)
+        yield b0, b1, scores                  # outside the with: a suspended generator must not hold the grad mode
+
+
+def content_cosine_top_k(user_profiles: torch.Tensor, item_features: torch.Tensor, user_ids: torch.Tensor, k: int,
+                         item_ids: Optional[torch.Tensor] = None, exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                         block_bytes: int = BLOCK_BYTES):
+    """The reference's content-based baseline (contentbased_baseline.py) on the device: the ``k`` items whose feature rows have the
+    largest cosine with each listed user's fixed profile.  user_profiles (U, F) / item_features (I, F): fp32 device tables
+    (``SparseDynamicProvider.user_profiles``, ``ContentIndexProvider.content``); user_ids, item_ids, exclude, block_bytes and the
+    returned ``(scores (B, k), item_positions (B, k) int64, counts (B,) int32)`` as in ``top_k_items``.  A user whose profile is all
+    zeros (no ratings) scores 0 against every item, as the reference leaves it, and so gets the first ``k`` columns."""
+    if not 1 <= int(k) <= native.TOPK_MAX_K:
+        raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
+    seen = None if exclude is None else _csr(exclude, user_ids.numel(), "exclude")
+    outs = [native.topk_rows(scores, int(k), None if seen is None else (seen[0][b0:b1 + 1], seen[1]))
+            for b0, b1, scores in _cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes)]
+    if not outs:
+        dev = user_profiles.device
+        return (torch.empty((0, int(k)), dtype=torch.float32, device=dev), torch.empty((0, int(k)), dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev))
+    s, idx, cnt = (torch.cat([o[j] for o in outs]) if len(outs) != 1 else outs[0][j] for j in range(3))
+    pos = idx.to(torch.int64)
+    if item_ids is not None:
+        pos = torch.where(pos >= 0, item_ids[pos.clamp_min(0)], pos)
+    return s, pos, cnt
+
+
+def content_cosine_ranks(user_profiles: torch.Tensor, item_features: torch.Tensor, user_ids: torch.Tensor,
+                         targets: Tuple[torch.Tensor, torch.Tensor], item_ids: Optional[torch.Tensor] = None,
+                         exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES):
+    """The ranks twin of ``content_cosine_top_k``: ``(rank (n_targets,) int32, ranked (B,) int32)`` of each listed user's held-out
+    items under the baseline's cosines, with the meaning ``rank_of_items`` gives them (``ranking_metrics`` takes them as they are)."""
+    B = user_ids.numel()
+    trow, tcol = _csr(targets, B, "targets")
+    seen = None if exclude is None else _csr(exclude, B, "exclude")
+    rank = torch.empty(tcol.numel(), dtype=torch.int32, device=tcol.device)
+    ranked = [native.rank_rows(scores, (trow[b0:b1 + 1], tcol), None if seen is None else (seen[0][b0:b1 + 1], seen[1]), rank=rank)[1]
+              for b0, b1, scores in _cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes)]
+    if not ranked:
+        return rank, torch.empty(0, dtype=torch.int32, device=tcol.device)
+    return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])
 
 
 # ---------------------------------------------------------------------------------------- AttentionNCF: why these items

@@ -738,6 +738,30 @@ int ncf_l2_normalize_rows(const float* dev_x, int64_t ldx, int64_t R, int E, flo
                           ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fixed user profiles (csrc/user_profiles.hip) — the users of the content form of BasicNCF (FixedProfilesProvider: item_dim =
+ * user_dim = F, an item is its feature row) and of the content-based baseline.
+ * Replaces: create_user_embedding of create_dataset.ipynb, a Python loop over the users.
+ * The ratings are one CSR with a row per user: dev_rowptr (U + 1, int64), the rated items' positions dev_col (int32; every rating
+ * kept, ascending within a row as the reference sorts them) and dev_rating (fp32), nnz entries each; dev_avg (U, float64) is the
+ * caller's (mean rating + 2.5) / 2 per user; dev_features (I, F) fp32 rows of ldf floats; dev_out (U, F) fp32 rows of ldout floats.
+ * THE CONTRACT, per user u (n_u = rowptr[u + 1] - rowptr[u] entries) and column f:
+ *       acc = 0.0 (double)
+ *       for e in row u, in order:
+ *           acc = acc + ((double)rating[e] - avg[u]) * (double)features[col[e], f]      (product rounded, THEN sum rounded: no FMA)
+ *       out[u, f] = (float)(acc / (double)n_u)
+ *   — numpy's ((r - avg).reshape(-1, 1) * feat[col]).mean(axis=0) in float64, rounded to fp32, bit for bit.  A row is never split:
+ *   no atomics, no reduction across lanes; the same inputs give the same bits.
+ * An empty row writes zeros.  A column outside [0, I) sets the sticky *dev_oob_flag (when non-NULL) and that entry adds nothing
+ * (n_u still counts it); a row pointer outside [0, nnz] or a decreasing pair sets the flag too and the row is treated as empty.
+ * 16-byte accesses when F, ldf and ldout are multiples of 4 and both tables are 16-byte aligned, single floats otherwise (any F >= 1).
+ * U == 0 launches nothing.  NCF_EINVAL, before any launch, for a negative U / I / nnz, F <= 0, ldf < F, ldout < F, a NULL
+ * rowptr / avg / out with U > 0, a NULL col / rating with nnz > 0 or a NULL feature table with nnz > 0 and I > 0.
+ * ------------------------------------------------------------------------------------------------ */
+int ncf_user_profiles(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_rating, int64_t nnz, const double* dev_avg,
+                      int64_t U, const float* dev_features, int64_t I, int64_t ldf, int F, float* dev_out, int64_t ldout,
+                      int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Backward (training step).  The reference trains through torch autograd (train.py:95-110); these
  * are the gradient kernels of K1 / K2.  fp32.
  *   dX = dY . W            : ncf_mlp_forward(n_layers = 1) with the transposed weight (no dedicated entry)
