@@ -111,6 +111,9 @@ SIGNATURES = {
     "ncf_attn_explain_max_reasons": (_c_int, []),
     "ncf_attn_explain": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_int,
                                   _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "ncf_attn_stats_workspace_bytes": (_c_size, [_c_i64]),
+    "ncf_attn_stats": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64,
+                                _c_p, _c_p, _c_size, _c_p]),
     "ncf_edge_softmax_csr": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_edge_softmax_segmented_workspace_bytes": (_c_size, [_c_i64, _c_i64]),
     "ncf_edge_softmax_segmented": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_size, _c_p]),
@@ -1349,6 +1352,52 @@ def attn_explain(ST: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, val:
                                 _ptr(items), k, _ptr(thr), E, _ptr(rc), _ptr(rw), _ptr(rv), _ptr(cnt), _ptr(_oob_flag(ST.device)),
                                 _stream(ST)))
     return rc, rw, rv, cnt
+
+
+ATTN_STATS_SLAB = 512   # csrc/attn_stats.hip kStSlab: rated columns owned by one wave of the accumulation kernel
+
+
+def attn_stats(ST: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, user_rows: torch.Tensor, cands: torch.Tensor,
+               sum: torch.Tensor, count: torch.Tensor):
+    """Item-item attention statistics of S samples from the logit table (ncf_attn_stats, the contract in include/ncf_abi.h), added
+    IN PLACE to ``sum`` (I_c, I_r) float64 and ``count`` (I_c, I_r) int64 (row strides allowed): for sample s and every valid entry e
+    of row ``user_rows[s]``, ``sum[cands[s], col_e] +=`` the fp32 attention weight of col_e towards ``cands[s]`` and ``count[...] += 1``.
+    ``ST / rowptr / col`` as ``attn_explain`` takes them; ``user_rows`` and ``cands`` (S,) int64.  The additions into a cell happen
+    in ascending sample index from the value already there: equal inputs give equal bits, and a file fed in consecutive pieces gives
+    the bits of one call.  Valid columns within a row must be distinct.  The per-candidate sample lists are built here on the
+    device (a stable sort of the candidates, ``searchsorted`` for the bucket offsets: neither reads a size on the host).  An
+    out-of-range user row or candidate adds nothing and raises at the next check_oob().  Every shape and dtype check comes before the
+    first device use; nothing synchronises.  Returns ``(sum, count)``."""
+    Ir, Ic, ldst = _rows2d(ST, "ST")
+    if ST.dtype != torch.float32:
+        raise TypeError("ST must be fp32")
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32:
+        raise TypeError("CSR must be (int64 rowptr, int32 col)")
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1 or not rowptr.is_contiguous() or not col.is_contiguous():
+        raise ValueError("CSR must be contiguous 1-D (rowptr (rows + 1,), col (nnz,))")
+    user_rows, cands = _idx(user_rows), _idx(cands)
+    S = user_rows.numel()
+    if cands.numel() != S:
+        raise ValueError(f"cands has {cands.numel()} entries for {S} user rows")
+    if sum.dtype != torch.float64 or count.dtype != torch.int64:
+        raise TypeError("sum must be float64 and count int64")
+    for t, what in ((sum, "sum"), (count, "count")):
+        if tuple(_rows2d(t, what)[:2]) != (Ic, Ir):
+            raise ValueError(f"{what} must be ({Ic}, {Ir}): one row per candidate, one column per rated item")
+    for t, what in ((ST, "ST"), (rowptr, "rowptr"), (col, "col"), (user_rows, "user_rows"), (cands, "cands"), (sum, "sum"), (count, "count")):
+        _dev(t, what)
+    lib = load_library()
+    if S == 0:
+        return sum, count
+    key = torch.where((cands >= 0) & (cands < Ic), cands, torch.full_like(cands, Ic))      # out of range: after every bucket
+    skey, order = torch.sort(key, stable=True)                                              # within a bucket: ascending sample index
+    cand_rowptr = torch.searchsorted(skey, torch.arange(Ic + 1, dtype=torch.int64, device=ST.device))
+    nbytes = int(lib.ncf_attn_stats_workspace_bytes(S))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ST.device)
+    _check(lib.ncf_attn_stats(_ptr(ST), ldst, Ir, Ic, _ptr(rowptr), _ptr(col), rowptr.numel() - 1, _ptr(user_rows), _ptr(cands), S,
+                              _ptr(order), _ptr(cand_rowptr), _ptr(sum), sum.stride(0), _ptr(count), count.stride(0),
+                              _ptr(_oob_flag(ST.device)), _ptr(ws), nbytes, _stream(ST)))
+    return sum, count
 
 
 def l2_normalize_rows(x: torch.Tensor) -> torch.Tensor:

@@ -156,10 +156,51 @@ def _resident_batches(res, batch_size, device):
         consumed[b].record(main)
 
 
+ATT_STATS_CHUNK = 1 << 20   # samples per native.attn_stats call of eval_model(att_stats=True)
+
+
+def _att_stats_source(model, test_dataset, device):
+    """What eval_model(att_stats=True) reads, or ValueError: the provider's device state and the file's id columns."""
+    from .datasets.dynamic_datasets import DynamicPointwiseDataset
+    from .models.attention_ncf import AttentionNCF
+    if not isinstance(model, AttentionNCF):
+        raise ValueError(f"att_stats=True collects attention weights: it takes an AttentionNCF, not {type(model).__name__}")
+    if not isinstance(test_dataset, DynamicPointwiseDataset):
+        raise ValueError(f"att_stats=True needs a DynamicPointwiseDataset, not {type(test_dataset).__name__}")
+    if torch.device(device).type != "cuda":
+        raise ValueError(f"att_stats=True is computed on a CUDA device, not on {device}")
+    dp = test_dataset.dynamic_provider
+    ints = np.issubdtype(test_dataset._u.dtype, np.integer) and np.issubdtype(test_dataset._i.dtype, np.integer)
+    state = dp.device_state(torch.device(device)) if ints and hasattr(dp, "device_state") and getattr(dp, "sparse", False) else None
+    if state is None:
+        raise ValueError("att_stats=True needs integer user and item ids and a sparse provider with a device state")
+    return state
+
+
+def _att_stats(model, test_dataset, state, device):
+    """The attention statistics of the whole sample file (recommend.attention_statistics), fed in chunks of ATT_STATS_CHUNK samples
+    in file order: rows of the whole user base's CSR and catalogue positions through the state's lookups.  No host read."""
+    from ..recommend import AttentionStats, attention_statistics
+    from .models.attention_ncf import SparseRatings
+    profiles = (state.features, SparseRatings(state.rowptr, state.col, state.val, state.num_items))
+    n = state.num_items
+    out = AttentionStats(torch.zeros((n, n), dtype=torch.float64, device=device), torch.zeros((n, n), dtype=torch.int64, device=device))
+    users, items = torch.as_tensor(test_dataset._u, dtype=torch.int64), torch.as_tensor(test_dataset._i, dtype=torch.int64)
+    for s in range(0, users.numel(), ATT_STATS_CHUNK):
+        rows, pos = state.train_positions(users[s:s + ATT_STATS_CHUNK].to(device), items[s:s + ATT_STATS_CHUNK].to(device))
+        out = attention_statistics(model, rows.contiguous(), pos.contiguous(), profiles, out=out)
+    return out
+
+
 def eval_model(model, test_dataset: PointwiseDataset, batch_size, ranking=False, device=None, verbose=False, resident=None,
-               cutoffs=(5, 10, 20)):
-    """eval.py:78-182 (metrics only).  Returns a dict: predictions, mse, rmse, ndcg@k / adj_ndcg@k for k in ``cutoffs``
-    (the reference reports 5, 10, 20).
+               cutoffs=(5, 10, 20), att_stats=False):
+    """eval.py:78-182 (metrics, and on request the attention statistics; no plots).  Returns a dict: predictions, mse, rmse,
+    ndcg@k / adj_ndcg@k for k in ``cutoffs`` (the reference reports 5, 10, 20).
+
+    ``att_stats=True`` adds the key ``"att_stats"``: the ``AttentionStats`` (sum float64, count int64, both (n_items, n_items) on
+    the device) the reference accumulates over the test file for its attention heat-map (eval.py:101-108, 137-143), from the logit
+    table (recommend.attention_statistics).  It takes an AttentionNCF, a DynamicPointwiseDataset with integer ids over a sparse
+    provider and a CUDA device; any other combination raises ValueError.  Without it the result is what it was.
 
     ``resident`` (None = when possible): datasets whose inputs are index ids (`Dataset.resident_inputs`) are evaluated
     without the DataLoader — same batches, same ``do_forward`` plug-in call, same per-batch loss sums accumulated in
@@ -168,6 +209,7 @@ def eval_model(model, test_dataset: PointwiseDataset, batch_size, ranking=False,
     assert isinstance(test_dataset, PointwiseDataset), 'Should only be testing on pointwise datasets.'
     cap_host_threads()
     device = device or next(model.parameters()).device
+    stats_state = _att_stats_source(model, test_dataset, device) if att_stats else None     # refusals before any work
     model.to(device)
     on_gpu = torch.device(device).type == "cuda"
     host = test_dataset.resident_inputs(torch.device(device), batch_size) if (resident is not False and on_gpu) else None
@@ -196,6 +238,7 @@ def eval_model(model, test_dataset: PointwiseDataset, batch_size, ranking=False,
                 if not ranking:
                     total += test_dataset.calculate_loss(out, y.to(device)).item()
                 fitted.append(out.detach().cpu().numpy())
+    stats = _att_stats(model, test_dataset, stats_state, torch.device(device)) if att_stats else None
     if on_gpu:
         from .. import native
         native.check_oob(torch.device(device))  # an out-of-range id anywhere in the run raises IndexError here
@@ -214,6 +257,8 @@ def eval_model(model, test_dataset: PointwiseDataset, batch_size, ranking=False,
         frame = test_dataset.samples.assign(prediction=pred)
     for k in cutoffs:
         res[f"ndcg@{k}"], res[f"adj_ndcg@{k}"] = ranked[k] if ranked is not None else eval_ranking(frame, cutoff=k)
+    if att_stats:
+        res["att_stats"] = stats
     if verbose:
-        print({k: v for k, v in res.items() if k != "predictions"})
+        print({k: v for k, v in res.items() if k not in ("predictions", "att_stats")})
     return res

@@ -521,6 +521,44 @@ class AttentionNCF(_ScoringMixin, NCF):
             return native.attn_explain(ST, ratings.rowptr, ratings.col, ratings.val, user_rows.contiguous(), items.contiguous(),
                                        thr.contiguous(), int(max_reasons))
 
+    def attention_stats(self, item_features, ratings, user_rows, cands, out=None):
+        """The item-item attention statistics of a sample file: ``(sum (I_c, I_c) float64, count (I_c, I_c) int64)`` where, for every
+        sample (user ``user_rows[s]``, candidate ``cands[s]``) and every rated item j of that user, ``sum[cand, j]`` collects the
+        attention weight of j towards the candidate and ``count[cand, j]`` the number of such samples — the tables the reference's
+        evaluation keeps for its attention heat-map (eval.py:101-108, 137-143), without a dense (samples, I_c) weight matrix
+        (native.attn_stats).  Eval only.  ``ratings`` as in ``catalogue_scores`` (a row lists a catalogue position once);
+        ``user_rows`` and ``cands`` (S,) int64.  ``out``: ``(sum, count)`` of an earlier call to continue — the additions into a cell
+        happen in sample order from the value already there, so a file fed in consecutive pieces gives the bits of one call; zeroed
+        tables are allocated without it.  Reads ``logit_table(item_features)`` only, so the table must fit ``cross_table_max_bytes``.
+        Nothing synchronises with the host."""
+        if self.training:
+            raise RuntimeError("attention statistics are computed in eval mode: call model.eval() first")
+        if not isinstance(ratings, SparseRatings):
+            raise TypeError("ratings must be a SparseRatings whose rows are users and whose columns are catalogue positions")
+        if item_features.dim() != 2 or ratings.num_items != item_features.shape[0]:
+            raise ValueError(f"ratings has {ratings.num_items} columns, the catalogue {tuple(item_features.shape)} rows")
+        if user_rows.dtype != torch.int64 or user_rows.dim() != 1:
+            raise ValueError("user_rows must be a 1-D int64 tensor of rows of ratings")
+        S = user_rows.numel()
+        if not torch.is_tensor(cands) or cands.dtype != torch.int64 or cands.dim() != 1 or cands.numel() != S:
+            raise ValueError(f"cands must be a ({S},) int64 tensor of catalogue positions: one candidate per sample")
+        Ic = item_features.shape[0]
+        if out is not None:
+            if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(o) and tuple(o.shape) == (Ic, Ic) for o in out)
+                    and out[0].dtype == torch.float64 and out[1].dtype == torch.int64):
+                raise ValueError(f"out must be (sum ({Ic}, {Ic}) float64, count ({Ic}, {Ic}) int64)")
+        nbytes = 4 * Ic * Ic
+        if nbytes > self.cross_table_max_bytes:
+            raise ValueError(f"the logit table of {Ic} items takes {nbytes} bytes, above AttentionNCF.cross_table_max_bytes = "
+                             f"{self.cross_table_max_bytes}")
+        require_gpu(item_features, ratings.rowptr, ratings.col, user_rows, cands, *(out or ()))
+        with torch.no_grad():
+            ST = self.logit_table(item_features)       # raises inside a stream capture when no table has been built
+            if out is None:
+                out = (torch.zeros((Ic, Ic), dtype=torch.float64, device=ST.device), torch.zeros((Ic, Ic), dtype=torch.int64, device=ST.device))
+            return native.attn_stats(ST, ratings.rowptr.contiguous(), ratings.col.contiguous(), user_rows.contiguous(), cands.contiguous(),
+                                     out[0], out[1])
+
     # ------------------------------------------------------------------------------------------ torch training path
     def _forward_train_hip(self, candidate_items, rated_items, user_matrix, return_attention_weights, pair_split=None):
         """attention_ncf.py:136-224 with autograd recording, on the HIP blocks: the Linear layers (LinearFn), the attention with its

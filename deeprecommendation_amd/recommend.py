@@ -421,6 +421,58 @@ def explain_items(model, user_ids: torch.Tensor, item_positions: torch.Tensor, p
         return Explanations(pos.to(torch.int64), w, val, cnt, thr)
 
 
+# ---------------------------------------------------------------------------------------- AttentionNCF: item-item attention statistics
+class AttentionStats(NamedTuple):
+    """What attention_statistics returns, on the device: row = candidate position, column = rated position."""
+    sum: torch.Tensor            # (I_c, I_c) float64 attention weight collected by (candidate, rated item) over the samples
+    count: torch.Tensor          # (I_c, I_c) int64 samples in which that rated item stood in the candidate's softmax
+
+
+def attention_statistics(model, user_ids: torch.Tensor, item_positions: torch.Tensor, profiles, out: Optional[AttentionStats] = None) -> AttentionStats:
+    """The item-item attention statistics of a sample file under an AttentionNCF — the tables the reference's ``eval_model`` keeps
+    for its attention heat-map (eval.py:101-108, 137-143): for every sample (user ``user_ids[s]``, candidate ``item_positions[s]``) and
+    every rated item j of that user, ``sum[candidate, j] +=`` the attention weight of j towards the candidate and
+    ``count[candidate, j] += 1``.  Read from the shared logit table (``AttentionNCF.attention_stats``, native.attn_stats) without a
+    dense (S, I_c) weight matrix.
+
+    user_ids, item_positions: (S,) int64 on the GPU — rows of ``profiles``' ratings and catalogue positions.  profiles:
+    ``(item_features (I_c, F), ratings)`` with the meaning it has in ``explain_items``; a row of ``ratings`` lists a catalogue
+    position once.  out: the ``AttentionStats`` of an earlier call, continued in place (a file fed in consecutive pieces gives the bits
+    of one call; equal inputs give equal bits: every cell is summed in sample order, no atomics).  ``count`` is structural: every
+    stored rating counts (the reference's ``user_matrix != 0``), also one whose weight underflowed to 0.  Needs the logit table
+    (4 * I_c^2 bytes <= ``AttentionNCF.cross_table_max_bytes``).  An out-of-range user or position adds nothing and raises at the
+    next ``native.check_oob``.  Nothing synchronises with the host."""
+    _eval_only(model)
+    if not _attention_model(model):
+        raise ValueError(f"attention statistics come from attention weights: attention_statistics takes an AttentionNCF, not {type(model).__name__}")
+    if profiles is None:
+        raise ValueError("an AttentionNCF collects attention statistics for users given by their ratings: pass profiles=(item_features, ratings)")
+    if not torch.is_tensor(item_positions) or item_positions.dtype != torch.int64 or item_positions.dim() != 1:
+        raise ValueError("item_positions must be a (S,) int64 tensor of catalogue positions")
+    if torch.is_tensor(user_ids) and user_ids.dim() == 1 and item_positions.numel() != user_ids.numel():
+        raise ValueError(f"item_positions has {item_positions.numel()} entries for {user_ids.numel()} users")
+    if out is not None and not (isinstance(out, tuple) and len(out) == 2):
+        raise ValueError("out must be the AttentionStats of an earlier call")
+    r = _resolve_attention(model, user_ids, None, None, profiles, None)
+    item_features, ratings = r.profiles
+    require_gpu(item_positions, ratings.col)
+    return AttentionStats(*model.attention_stats(item_features, ratings, r.users, item_positions, None if out is None else tuple(out)))
+
+
+def attention_stat_ratios(stats, positions):
+    """The sub-tables the reference's heat-map shows (plots.py:172-181): ``(sum, count, ratio)`` as float64 / int64 / float64 numpy
+    arrays of shape (n, n) for the n listed catalogue ``positions``, rows and columns in the listed order.  ``ratio`` is the
+    reference's formula AS WRITTEN, ``sum / np.max(count, 1)``: the vector of per-row maxima broadcasts over the LAST axis, so cell
+    (i, j) is divided by the maximum of row j, not of row i.  A zero maximum gives what numpy gives (inf, or nan for 0 / 0)."""
+    pos = np.asarray(positions.cpu() if torch.is_tensor(positions) else positions, dtype=np.int64).reshape(-1)
+    to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    s = to_np(stats[0])[pos, :][:, pos]
+    c = to_np(stats[1])[pos, :][:, pos]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = s / (np.max(c, 1) if pos.size else np.zeros(0, dtype=c.dtype))
+    return s, c, ratio
+
+
 # ---------------------------------------------------------------------------------------- AttentionNCF: one user, one catalogue
 _catalogue_cache = {}
 

@@ -648,6 +648,40 @@ int ncf_attn_explain(const float* dev_st, int64_t ldst, int64_t I_r, int64_t I_c
                      int max_reasons, int32_t* dev_reason_col, float* dev_reason_w, float* dev_reason_val,
                      int32_t* dev_reason_cnt, int32_t* dev_oob_flag, ncf_stream_t stream);
 
+/* Item-item attention statistics of a sample file from the logit table (csrc/attn_stats.hip): the two (n_items, n_items) tables the
+ * reference's eval_model accumulates on the host from dense (batch, catalogue) weight matrices (eval.py:101-108, 137-143).
+ * dev_st / ldst / I_r / I_c and the CSR (dev_rowptr int64, dev_col int32, n_rows) exactly as ncf_attn_explain reads them (the
+ * ratings' values are not needed); S samples (dev_user_rows[s], dev_cands[s]), both int64; dev_order (S,) int64 and dev_cand_rowptr
+ * (I_c + 1,) int64 together list the samples of each candidate c, order[cand_rowptr[c] .. cand_rowptr[c + 1]), in ascending sample
+ * index (a stable sort of dev_cands and the bucket offsets).  dev_sum (I_c, ldsum) float64 and dev_count (I_c, ldcount) int64 are
+ * UPDATED IN PLACE; dev_workspace: ncf_attn_stats_workspace_bytes(S) = 8 * S bytes, 8-byte aligned.
+ * For a valid entry e (0 <= col_e < I_r) of sample s's row, with c = cands[s]:
+ *     w = exp(ST[col_e, c] - m_s) / l_s      sum[c, col_e] += (double)w      count[c, col_e] += 1
+ * m_s the exact maximum over the row's valid entries and l_s the sum in ncf_attn_explain's order (per lane in entry order, then the
+ * xor butterfly): the fp32 weight is the one ncf_attn_explain reports.  w = 0 when the row has no finite logit or l_s is 0 or NaN
+ * (the reference's NaN -> 0); count is structural: a valid stored entry always counts.  A user row or candidate out of range
+ * contributes nothing and sets *dev_oob_flag (sticky, may be NULL).
+ * Order contract: no floating-point atomics and no fixed-point substitute — each cell is owned by one wave, which adds the fp32
+ * weights as float64 in the order the list gives (ascending sample index), starting from the value already in the table.  So two
+ * calls on the same inputs give the same bits, and a file accumulated in two calls (first half, then second half) gives the bits
+ * of one call on the whole file.  A sample that dev_order lists under a candidate other than its own is skipped, and nothing
+ * outside [0, S) is read whatever the two arrays hold.
+ * Precondition: the valid columns within one user row are distinct (provider-built rows are).  A repeated column cannot fault; the
+ * value of its cell is unspecified.
+ * Two launches: one wave per sample for (m_s, l_s); then one wave per (candidate, slab of 512 rated columns) with the slab's
+ * accumulators in LDS.  A candidate's chain of samples is serial: the run time is bounded below by the most sampled candidate.
+ * Refusals, before anything is launched (ncf_last_error set): NCF_EINVAL for negative sizes, a NULL buffer (dev_col may be NULL for
+ * a CSR without entries; dev_st / dev_sum / dev_count for tables without cells), a pointer not aligned to its element, ldst < I_c,
+ * ldsum < I_r or ldcount < I_r; NCF_EUNSUPPORTED for I_r > 2^31 - 1, I_c * ceil(I_r / 512) > 2^31 - 1 or S > 4 * (2^31 - 1);
+ * NCF_EWORKSPACE for a short workspace.  S == 0 is an empty call (NCF_OK before any pointer is looked at). */
+size_t ncf_attn_stats_workspace_bytes(int64_t S);
+int ncf_attn_stats(const float* dev_st, int64_t ldst, int64_t I_r, int64_t I_c,
+                   const int64_t* dev_rowptr, const int32_t* dev_col, int64_t n_rows,
+                   const int64_t* dev_user_rows, const int64_t* dev_cands, int64_t S,
+                   const int64_t* dev_order, const int64_t* dev_cand_rowptr,
+                   double* dev_sum, int64_t ldsum, int64_t* dev_count, int64_t ldcount, int32_t* dev_oob_flag,
+                   void* dev_workspace, size_t workspace_bytes, ncf_stream_t stream);
+
 /* Dense user_matrix -> CSR with shared rows, on the stream (no size is read by the host).  The reference passes AttentionNCF.forward a
  * dense (B, I) user_matrix in which a user's row is repeated for each of their samples (datasets/dynamic_datasets.py:24-40,
  * content_providers/dynamic_profiles_provider.py:55-71; one row for every candidate in webapp/backend.py:78-121) and keeps the
