@@ -1,8 +1,9 @@
-"""MI355X (gfx950) path of the NCF models.  The recommendation and ranking-evaluation functions are re-exported here, imported on
-first use."""
+"""MI355X (gfx950) path of the NCF models.  The recommendation and ranking-evaluation functions and the baselines are re-exported
+here, imported on first use."""
 _RECOMMEND = ("top_k_items", "recommend_for_user", "seen_items", "rated_exclusion", "explain_items", "content_cosine_top_k",
               "content_cosine_ranks", "attention_statistics", "attention_stat_ratios", "AttentionStats")
 _RANKING_EVAL = ("rank_of_items", "ranking_metrics", "eval_full_ranking", "held_out_items")
+_BASELINES = ("KernelMF",)
 
 
 def __getattr__(name):
@@ -12,4 +13,7 @@ def __getattr__(name):
     if name in _RANKING_EVAL:
         from . import ranking_eval
         return getattr(ranking_eval, name)
+    if name in _BASELINES:
+        from . import baselines
+        return getattr(baselines, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

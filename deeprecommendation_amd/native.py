@@ -142,6 +142,10 @@ SIGNATURES = {
     "ncf_scatter_add_rows": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_l2_normalize_rows": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p]),
     "ncf_user_profiles": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p, _c_p]),
+    "ncf_kmf_epoch": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_int,
+                               ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_p, _c_p, _c_p]),
+    "ncf_kmf_fold_users": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64,
+                                    ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_p, _c_p, _c_p]),
     "ncf_gather_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_int, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
     "ncf_scatter_add_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
@@ -1437,6 +1441,133 @@ def user_profiles(rowptr: torch.Tensor, col: torch.Tensor, rating: torch.Tensor,
     _check(lib.ncf_user_profiles(_ptr(rowptr), _ptr(col), _ptr(rating), col.numel(), _ptr(avg), U, _ptr(features), I, ldf, F, _ptr(out),
                                  out.stride(0), _ptr(_oob_flag(features.device)), _stream(features)))
     return out
+
+
+KMF_MAX_FACTORS, KMF_MAX_BLOCKS = 256, 1024       # csrc/kmf.hip
+KMF_FLAG_ID, KMF_FLAG_BLOCK, KMF_FLAG_PTR = 1, 2, 4
+_kmf_flags = {}
+
+
+def kmf_flag(device) -> torch.Tensor:
+    """The sticky int32 flag word of the KernelMF kernels on ``device`` (bits KMF_FLAG_*)."""
+    f = _kmf_flags.get(device)
+    if f is None:
+        f = torch.zeros(1, dtype=torch.int32, device=device)
+        _kmf_flags[device] = f
+    return f
+
+
+def check_kmf(device, flag: Optional[torch.Tensor] = None):
+    """Synchronising check of the KernelMF flag word: raises, and clears it, when a kernel met an id outside its table, a sample
+    filed in the wrong block or a broken block / row pointer (each such sample or block was skipped)."""
+    f = kmf_flag(device) if flag is None else flag
+    bits = int(f.item())
+    if bits:
+        f.zero_()
+        what = [w for b, w in ((KMF_FLAG_ID, "an id outside its table"), (KMF_FLAG_BLOCK, "a sample filed in the wrong block"),
+                               (KMF_FLAG_PTR, "a block / row pointer outside the samples")) if bits & b]
+        raise IndexError("KernelMF: " + ", ".join(what) + f" (flag {bits})")
+
+
+def _kmf_tables(who, PU, QI, F):
+    for t, what in ((PU, "PU"), (QI, "QI")):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"{who}: {what} must be a 2-D float32 tensor with unit inner stride")
+    F = int(F)
+    if F < 1 or PU.shape[1] < F + 1 or QI.shape[1] < F + 1:
+        raise ValueError(f"{who}: rows of {PU.shape[1]} / {QI.shape[1]} floats cannot hold F = {F} factors and the bias")
+    return F
+
+
+def _kmf_vec(who, t, what, dt, n=None):
+    if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous 1-D {dt} tensor")
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{who}: {what} has {t.numel()} entries, expected {n}")
+
+
+def _kmf_out(who, t, what, dt, n):
+    if t is not None and (not torch.is_tensor(t) or t.dtype != dt or not t.is_contiguous() or t.numel() != n):
+        raise ValueError(f"{who}: {what} must be a contiguous {dt} tensor of {n} entries")
+
+
+def kmf_epoch(PU: torch.Tensor, QI: torch.Tensor, F: int, user: torch.Tensor, item: torch.Tensor, rating: torch.Tensor,
+              block_ptr: torch.Tensor, user_block: torch.Tensor, item_block: torch.Tensor, mu: float, lr: float, reg: float,
+              n_epochs: int = 1, sse: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``n_epochs`` epochs of stratified SGD over a prepared plan, in place on the KernelMF tables (ncf_kmf_epoch, THE CONTRACT in
+    include/ncf_abi.h).  ``PU`` (U, >= F + 1) and ``QI`` (I, >= F + 1) fp32 rows: F factors, then the bias.  ``user`` / ``item`` int32
+    and ``rating`` fp32 are the samples in stratum-major block order, ``block_ptr`` (W * W + 1,) int64, ``user_block`` (U,) and
+    ``item_block`` (I,) int32.  Returns the (n_epochs, W) float64 partial sums of squared errors (``sse`` when given: ADDED to).  What
+    the kernel refuses sets ``flag`` (default: the device's word, check_kmf).  Shapes, dtypes and layout are checked before the device
+    is."""
+    who = "kmf_epoch"
+    F = _kmf_tables(who, PU, QI, F)
+    U, I = PU.shape[0], QI.shape[0]
+    _kmf_vec(who, user, "user", torch.int32)
+    n = user.numel()
+    _kmf_vec(who, item, "item", torch.int32, n)
+    _kmf_vec(who, rating, "rating", torch.float32, n)
+    _kmf_vec(who, block_ptr, "block_ptr", torch.int64)
+    W = int(round((block_ptr.numel() - 1) ** 0.5)) if block_ptr.numel() > 1 else 0
+    if W < 1 or W * W + 1 != block_ptr.numel() or W > KMF_MAX_BLOCKS:
+        raise ValueError(f"{who}: block_ptr has {block_ptr.numel()} entries, not W * W + 1 for a W in 1 .. {KMF_MAX_BLOCKS}")
+    _kmf_vec(who, user_block, "user_block", torch.int32, U)
+    _kmf_vec(who, item_block, "item_block", torch.int32, I)
+    n_epochs = int(n_epochs)
+    if n_epochs < 0:
+        raise ValueError(f"{who}: n_epochs = {n_epochs}")
+    _kmf_out(who, sse, "sse", torch.float64, n_epochs * W)
+    _kmf_out(who, flag, "flag", torch.int32, 1)
+    for t, what in ((PU, "PU"), (QI, "QI"), (user, "user"), (item, "item"), (rating, "rating"), (block_ptr, "block_ptr"),
+                    (user_block, "user_block"), (item_block, "item_block"), (sse, "sse"), (flag, "flag")):
+        if t is not None:
+            _dev(t, what)
+    lib = load_library()
+    if sse is None:
+        sse = torch.zeros((n_epochs, W), dtype=torch.float64, device=PU.device)
+    if flag is None:
+        flag = kmf_flag(PU.device)
+    if n and n_epochs and U and I:
+        _check(lib.ncf_kmf_epoch(_ptr(PU), PU.stride(0), U, _ptr(QI), QI.stride(0), I, F, _ptr(user), _ptr(item), _ptr(rating), n,
+                                 _ptr(block_ptr), _ptr(user_block), _ptr(item_block), W, float(mu), float(lr), float(reg), n_epochs,
+                                 _ptr(sse), _ptr(flag), _stream(PU)))
+    return sse
+
+
+def kmf_fold_users(PU: torch.Tensor, QI: torch.Tensor, F: int, users: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor,
+                   rating: torch.Tensor, mu: float, lr: float, reg: float, n_epochs: int = 1, sse: Optional[torch.Tensor] = None,
+                   flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fold-in of users against the fixed item table (ncf_kmf_fold_users): ``n_epochs`` passes of the contract's user-side update
+    over row k of the CSR (``rowptr`` (n_users + 1,) int64, ``col`` int32 item positions, ``rating`` fp32) for user ``users[k]`` (int32,
+    no user twice), in place on ``PU``; ``QI`` is only read.  Returns the (n_epochs, n_users) float64 sums of squared errors (``sse``
+    when given: overwritten).  Checked before the device is, as kmf_epoch."""
+    who = "kmf_fold_users"
+    F = _kmf_tables(who, PU, QI, F)
+    U, I = PU.shape[0], QI.shape[0]
+    _kmf_vec(who, users, "users", torch.int32)
+    nu = users.numel()
+    _kmf_vec(who, rowptr, "rowptr", torch.int64, nu + 1)
+    _kmf_vec(who, col, "col", torch.int32)
+    nnz = col.numel()
+    _kmf_vec(who, rating, "rating", torch.float32, nnz)
+    n_epochs = int(n_epochs)
+    if n_epochs < 0:
+        raise ValueError(f"{who}: n_epochs = {n_epochs}")
+    _kmf_out(who, sse, "sse", torch.float64, n_epochs * nu)
+    _kmf_out(who, flag, "flag", torch.int32, 1)
+    for t, what in ((PU, "PU"), (QI, "QI"), (users, "users"), (rowptr, "rowptr"), (col, "col"), (rating, "rating"), (sse, "sse"),
+                    (flag, "flag")):
+        if t is not None:
+            _dev(t, what)
+    lib = load_library()
+    if sse is None:
+        sse = torch.zeros((n_epochs, nu), dtype=torch.float64, device=PU.device)
+    if flag is None:
+        flag = kmf_flag(PU.device)
+    if nu and n_epochs:
+        _check(lib.ncf_kmf_fold_users(_ptr(PU), PU.stride(0), U, _ptr(QI), QI.stride(0), I, F, _ptr(users), nu, _ptr(rowptr), _ptr(col),
+                                      _ptr(rating), nnz, float(mu), float(lr), float(reg), n_epochs, _ptr(sse), _ptr(flag), _stream(PU)))
+    return sse
 
 
 def folded_supported(N1: int, N2: int) -> bool:

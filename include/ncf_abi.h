@@ -796,6 +796,60 @@ int ncf_user_profiles(const int64_t* dev_rowptr, const int32_t* dev_col, const f
                       int32_t* dev_oob_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * KernelMF (csrc/kmf.hip) — the collaborative-filtering baseline of the reference's evaluation: biased matrix factorisation
+ *       r^ = mu + b_u + b_i + p_u . q_i
+ * fitted by per-sample SGD, the linear kernel of the matrix_factorization package (cf_baseline.py).  Replaces: that package's
+ * fitting loop (numba on the host), which nothing on the device can run.
+ * Tables: dev_PU (U, ldu) and dev_QI (I, ldq) fp32; columns 0 .. F-1 of a row are the factors, column F is the row's bias (b_u in the
+ * user's row, b_i in the item's), 1 <= F <= 256, ld >= F + 1.  Columns beyond F are never written.  16-byte accesses when both
+ * leading dimensions are multiples of 4 and both tables are 16-byte aligned, single floats otherwise.
+ * Stratified SGD (DSGD): users and items are dealt to W blocks each (dev_user_block (U,), dev_item_block (I,), int32); stratum s is
+ * the blocks (a, (a + s) mod W), a = 0 .. W-1, which share no user row and no item row.  The samples dev_user / dev_item (int32) and
+ * dev_rating (fp32), n of each, are stored stratum-major: block s * W + a holds the samples whose user block is a and whose item
+ * block is (a + s) mod W, at dev_block_ptr[s * W + a] .. dev_block_ptr[s * W + a + 1] (int64, W * W + 1 entries).  1 <= W <= 1024.
+ * One call enqueues n_epochs * W launches; launch (e, s) is W workgroups of one wave, wave a walks block (s, a) in stored order.  A
+ * launch boundary is the only hand-off between strata; within a launch a wave reads and writes the rows of its own block only.
+ * THE CONTRACT, per sample (u, i, r) of a block, in stored order, all in fp32 with every product and sum rounded on its own (no FMA):
+ *       column c (0 <= c < F) belongs to lane (c / 4) mod 64
+ *       part_l = +0.0f;  for the lane's columns in ascending order:  part_l = part_l + p[c] * q[c]
+ *       dot    = balanced tree over lanes 0..63 in lane order: adjacent pairs first, then pairs of pairs, ... (6 levels)
+ *       pred   = ((mu + bi) + bu) + dot
+ *       err    = pred - r
+ *       bu'    = bu - lr * (err + reg * bu)
+ *       bi'    = bi - lr * (err + reg * bi)
+ *       for every c:  p'[c] = p[c] - lr * (err * q[c] + reg * p[c])
+ *                     q'[c] = q[c] - lr * (err * p[c] + reg * q[c])      (both from the OLD p[c], q[c])
+ *   — the update of the package's linear kernel; the fitting loop does not clip.  The blocks of a stratum touch disjoint rows, so
+ *   the result is the one of ANY sequential order of them: the same inputs give the same bits.
+ * The kernel checks its own inputs, never dereferences an unchecked id, and a flagged case writes nothing for that sample:
+ *       bit 0 of the sticky *dev_flag: an id outside [0, U) / [0, I) — the sample is skipped
+ *       bit 1: user_block[u] != a or item_block[i] != (a + s) mod W — the sample is skipped
+ *       bit 2: a block_ptr pair that decreases or lies outside [0, n] — the block is treated as empty
+ * Loss: wave a keeps sse = sum of (double)err * (double)err over its block, added sequentially from 0.0, and after the block lane 0
+ * does dev_sse[e * W + a] = dev_sse[e * W + a] + sse (a plain read-modify-write: launch order makes it the only writer).  dev_sse
+ * (n_epochs * W doubles, zeroed by the caller) and dev_flag may be NULL.
+ * n == 0 or n_epochs == 0 launches nothing.  NCF_EINVAL, before any launch, for a negative U / I / n / n_epochs, F <= 0,
+ * ld < F + 1, W outside 1 .. 1024, a NULL table or plan array, NULL samples with n > 0, a non-finite lr or reg; NCF_EUNSUPPORTED
+ * for F > 256.
+ * ------------------------------------------------------------------------------------------------ */
+int ncf_kmf_epoch(float* dev_PU, int64_t ldu, int64_t U, float* dev_QI, int64_t ldq, int64_t I, int F,
+                  const int32_t* dev_user, const int32_t* dev_item, const float* dev_rating, int64_t n,
+                  const int64_t* dev_block_ptr, const int32_t* dev_user_block, const int32_t* dev_item_block, int W,
+                  float mu, float lr, float reg, int n_epochs, double* dev_sse, int32_t* dev_flag, ncf_stream_t stream);
+/* Fold-in (the package's update_users): fits the rows of dev_PU of the users dev_users[k] (int32, n_users of them, no user twice)
+ * against a FIXED dev_QI, n_epochs passes over the user's ratings, which are row k of a CSR: dev_rowptr (n_users + 1, int64),
+ * dev_col (item positions, int32) and dev_rating (fp32), nnz entries each.  One wave per user, one launch; per sample THE CONTRACT of
+ * ncf_kmf_epoch without the q' and bi' lines.  dev_QI is never written and users not listed keep their rows.  Flags: bit 0 for a user
+ * or an item outside its table (the user's whole row, or that sample, is skipped), bit 2 for a row pointer pair that decreases or
+ * lies outside [0, nnz] (the row is treated as empty).  dev_sse[e * n_users + k], when non-NULL, is SET to the user's sum of
+ * (double)err * (double)err of pass e.  n_users == 0 or n_epochs == 0 launches nothing; the refusals are ncf_kmf_epoch's, with
+ * n_users / nnz for n, and NULL pointers refused only where their arrays are non-empty. */
+int ncf_kmf_fold_users(float* dev_PU, int64_t ldu, int64_t U, const float* dev_QI, int64_t ldq, int64_t I, int F,
+                       const int32_t* dev_users, int64_t n_users, const int64_t* dev_rowptr, const int32_t* dev_col,
+                       const float* dev_rating, int64_t nnz, float mu, float lr, float reg, int n_epochs, double* dev_sse,
+                       int32_t* dev_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Backward (training step).  The reference trains through torch autograd (train.py:95-110); these
  * are the gradient kernels of K1 / K2.  fp32.
  *   dX = dY . W            : ncf_mlp_forward(n_layers = 1) with the transposed weight (no dedicated entry)

@@ -1,0 +1,86 @@
+"""The collaborative-filtering baseline of the reference's evaluation (its cf_baseline.py) on the device.
+
+    python tools/cf_baseline.py TRAIN VAL TEST [--factors 64 128 256] [--lrs 0.001 0.0005] [--regs 0.01 0.005]
+                                               [--epochs 64 80 100 128] [--blocks N] [--seed 0]
+
+TRAIN / VAL / TEST are the sample files (CSV with userId, movieId, rating columns; ``.csv`` may be left off).  Grid search of
+KernelMF over factors x lr x reg; the epoch counts of the grid are stops of ONE fit per (factors, lr, reg) — a fit is deterministic
+and its first k epochs are the k-epoch fit (KernelMF.fit, at_epochs).  Every grid point prints its validation MSE on clipped
+predictions; the best one is then scored on TEST: MSE, NDCG@10 and min-max adjusted NDCG@10 (eval_ranking).  An id of VAL / TEST
+that TRAIN does not hold predicts the global mean plus the known side's bias, as the package does."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import pandas as pd
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from deeprecommendation_amd import KernelMF  # noqa: E402
+from deeprecommendation_amd.neural_collaborative_filtering.eval import eval_ranking  # noqa: E402
+
+
+def read_samples(path):
+    path = path if os.path.exists(path) else path + ".csv"
+    return pd.read_csv(path, usecols=["userId", "movieId", "rating"])
+
+
+def positions(frames, column):
+    """One id -> position map over the three files (positions of ids TRAIN lacks get zero rows in the fit)."""
+    ids = pd.unique(pd.concat([f[column] for f in frames]))
+    lookup = pd.Series(np.arange(len(ids), dtype=np.int64), index=ids)
+    return len(ids), [lookup.loc[f[column]].to_numpy() for f in frames]
+
+
+def mse(pred, rating):
+    d = pred.double().cpu().numpy() - rating.astype(np.float64)
+    return float(np.mean(d * d))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("train"), ap.add_argument("val"), ap.add_argument("test")
+    ap.add_argument("--factors", type=int, nargs="+", default=[64, 128, 256])
+    ap.add_argument("--lrs", type=float, nargs="+", default=[0.001, 0.0005])
+    ap.add_argument("--regs", type=float, nargs="+", default=[0.01, 0.005])
+    ap.add_argument("--epochs", type=int, nargs="+", default=[64, 80, 100, 128])
+    ap.add_argument("--blocks", type=int, default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    frames = [read_samples(p) for p in (args.train, args.val, args.test)]
+    n_users, upos = positions(frames, "userId")
+    n_items, ipos = positions(frames, "movieId")
+    u, i = [torch.from_numpy(a).to(dev) for a in upos], [torch.from_numpy(a).to(dev) for a in ipos]
+    ratings = [f["rating"].to_numpy(dtype=np.float32) for f in frames]
+    train_r = torch.from_numpy(ratings[0]).to(dev)
+    stops = sorted(set(args.epochs))
+    best = {"val_mse": float("inf")}
+
+    def on_stop(model, epoch):
+        val_mse = mse(model.predict(u[1], i[1]), ratings[1])
+        print(f"factors={model.n_factors} lr={model.lr} reg={model.reg} epochs={epoch}: val MSE {val_mse:.4f}, "
+              f"train RMSE {model.train_rmse_[-1]:.4f}", flush=True)
+        if val_mse < best["val_mse"]:
+            best.update(val_mse=val_mse, epoch=epoch, test_pred=model.predict(u[2], i[2]), factors=model.n_factors, lr=model.lr, reg=model.reg,
+                        blocks=model.n_blocks_)
+
+    for factors in args.factors:
+        for lr in args.lrs:
+            for reg in args.regs:
+                model = KernelMF(n_factors=factors, n_epochs=stops[-1], lr=lr, reg=reg, n_blocks=args.blocks)
+                model.fit(u[0], i[0], train_r, n_users, n_items, generator=torch.Generator().manual_seed(args.seed), epoch_callback=on_stop,
+                          at_epochs=stops)
+    test_mse = mse(best["test_pred"], ratings[2])
+    print(f"best by val MSE: factors={best['factors']} lr={best['lr']} reg={best['reg']} epochs={best['epoch']} blocks={best['blocks']}")
+    print(f"test MSE {test_mse:.4f} (val MSE {best['val_mse']:.4f})")
+    frame = pd.DataFrame({"userId": frames[2]["userId"].to_numpy(), "movieId": frames[2]["movieId"].to_numpy(), "rating": ratings[2],
+                          "prediction": best["test_pred"].cpu().numpy()})
+    ndcg, adj = eval_ranking(frame, cutoff=10)
+    print(f"test NDCG@10 {ndcg:.4f}, adjusted NDCG@10 {adj:.4f}")
+
+
+if __name__ == "__main__":
+    main()
