@@ -146,6 +146,9 @@ SIGNATURES = {
                                ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_p, _c_p, _c_p]),
     "ncf_kmf_fold_users": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_p, _c_p, _c_p]),
+    "ncf_mmr_supported": (_c_int, [_c_int, _c_int, _c_int]),
+    "ncf_mmr_rerank": (_c_int, [_c_p, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, ctypes.c_float, _c_int, _c_p, _c_p,
+                                _c_p, _c_p, _c_p]),
     "ncf_gather_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_int, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
     "ncf_scatter_add_cols": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
     "ncf_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
@@ -1568,6 +1571,57 @@ def kmf_fold_users(PU: torch.Tensor, QI: torch.Tensor, F: int, users: torch.Tens
         _check(lib.ncf_kmf_fold_users(_ptr(PU), PU.stride(0), U, _ptr(QI), QI.stride(0), I, F, _ptr(users), nu, _ptr(rowptr), _ptr(col),
                                       _ptr(rating), nnz, float(mu), float(lr), float(reg), n_epochs, _ptr(sse), _ptr(flag), _stream(PU)))
     return sse
+
+
+MMR_MAX_N, MMR_MAX_D, MMR_MAX_K = 256, 256, 128       # csrc/mmr.hip
+
+
+def mmr_supported(N: int, D: int, K: int) -> bool:
+    """Whether ncf_mmr_rerank takes a pool of ``N`` slots, vectors of ``D`` columns and ``K`` picks (host only)."""
+    return bool(load_library().ncf_mmr_supported(int(N), int(D), int(K)))
+
+
+def mmr_rerank(vectors: torch.Tensor, scores: torch.Tensor, positions: torch.Tensor, counts: Optional[torch.Tensor], k: int,
+               lam: float = 0.5, normalize: bool = True):
+    """Greedy MMR re-ranking of one candidate pool per user (ncf_mmr_rerank, THE CONTRACT in include/ncf_abi.h).  ``vectors``
+    (n_items, D) fp32 rows (a column slice is fine), ``scores`` (B, N) fp32 and ``positions`` (B, N) int64 contiguous pools, ``counts``
+    (B,) int32 slots in use per pool or None for N.  Returns ``(slot (B, k) int32, value (B, k) fp32, count (B,) int32)``: the pool
+    slot picked at each step and its value when picked, -1 / -inf past ``count``.  A position >= n_items or < -1 is never picked and
+    sets the sticky out-of-range flag (check_oob).  Shapes, dtypes and the kernel's limits are checked before the device is; one
+    launch on the current stream, nothing synchronises."""
+    who = "mmr_rerank"
+    if not torch.is_tensor(vectors) or vectors.dtype != torch.float32 or vectors.dim() != 2 or vectors.stride(1) != 1:
+        raise ValueError(f"{who}: vectors must be a 2-D float32 tensor with unit inner stride")
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():
+        raise ValueError(f"{who}: scores must be a contiguous (B, N) float32 tensor")
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or not positions.is_contiguous():
+        raise ValueError(f"{who}: positions must be a contiguous (B, N) int64 tensor")
+    if positions.shape != scores.shape:
+        raise ValueError(f"{who}: scores is {tuple(scores.shape)}, positions {tuple(positions.shape)}")
+    B, N = scores.shape
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or not counts.is_contiguous()
+                               or counts.numel() != B):
+        raise ValueError(f"{who}: counts must be a contiguous ({B},) int32 tensor")
+    n_items, D = vectors.shape
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"{who}: k = {k!r} is not an int")
+    if not (1 <= N <= MMR_MAX_N and 4 <= D <= MMR_MAX_D and D % 4 == 0 and 1 <= k <= min(N, MMR_MAX_K)):
+        raise ValueError(f"{who}: pool width N = {N}, vector width D = {D}, k = {k} is outside 1 <= N <= {MMR_MAX_N}, 4 <= D <= {MMR_MAX_D} "
+                         f"with D % 4 == 0, 1 <= k <= min(N, {MMR_MAX_K})")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"{who}: lam = {lam} is outside [0, 1]")
+    for t, what in ((vectors, "vectors"), (scores, "scores"), (positions, "positions"), (counts, "counts")):
+        if t is not None:
+            _dev(t, what)
+    lib = load_library()
+    dev = scores.device
+    slot = torch.empty((B, k), dtype=torch.int32, device=dev)
+    value = torch.empty((B, k), dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    _check(lib.ncf_mmr_rerank(_ptr(vectors), n_items, D, vectors.stride(0), _ptr(scores), _ptr(positions), _ptr(counts), B, N, k, lam,
+                              1 if normalize else 0, _ptr(slot), _ptr(value), _ptr(count), _ptr(_oob_flag(dev)), _stream(scores)))
+    return slot, value, count
 
 
 def folded_supported(N1: int, N2: int) -> bool:

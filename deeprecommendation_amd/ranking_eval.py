@@ -9,6 +9,9 @@ and HR@K / Recall@K / NDCG@K / MRR / AUC are computed from those ranks.
 ``ranking_metrics``    HR@K, Recall@K, NDCG@K, MRR and AUC from those ranks, in float64 on the ranks' device; one host read.
 ``eval_full_ranking``  the two composed.
 ``held_out_items``     the users and the de-duplicated target CSR of a test DataFrame.
+``intra_list_diversity`` / ``catalogue_coverage``
+                       beyond accuracy: how unlike each other the items of a recommendation list are, and how much of the catalogue
+                       the lists of all users reach — what ``diversify_top_k`` trades relevance for.  Torch ops, on the lists' device.
 
 The rank of a target is the number of non-excluded columns that come before it in ``top_k_items``' order (descending score, equal
 scores to the lower column, NaN last): the slot it would hold in an unbounded ``top_k_items`` result.  ``eval_ranking`` in
@@ -236,3 +239,46 @@ def held_out_items(samples, user_positions, item_positions, device=None):
     if device is not None:
         out = out[0].to(device), (out[1][0].to(device), out[1][1].to(device))
     return out
+
+
+# ---------------------------------------------------------------------------------------- beyond accuracy: diversity and coverage
+def _lists(positions, counts, who):
+    if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2:
+        raise ValueError(f"{who}: positions must be a (B, k) int64 tensor of item positions")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dim() != 1 or counts.numel() != positions.shape[0]
+                               or counts.dtype not in (torch.int32, torch.int64)):
+        raise ValueError(f"{who}: counts must be a ({positions.shape[0]},) int32 tensor")
+    used = positions >= 0
+    if counts is not None:
+        used = used & (torch.arange(positions.shape[1], device=positions.device)[None, :] < counts[:, None])
+    return used
+
+
+def intra_list_diversity(positions: torch.Tensor, counts: Optional[torch.Tensor], item_vectors: torch.Tensor) -> torch.Tensor:
+    """Intra-list diversity of recommendation lists: per list the mean over its unordered pairs of items of ``1 - sim``, ``sim`` the
+    dot product of the two items' rows of ``item_vectors`` (unit rows: one minus the cosine).  positions (B, k) int64 and counts (B,)
+    int32 (or None) as ``top_k_items`` / ``diversify_top_k`` return them: slots past ``counts`` and slots holding -1 are not part of
+    a list.  Returns (B,) fp32 on the lists' device, NaN for a list of fewer than two items; summed in float64.  No host sync."""
+    used = _lists(positions, counts, "intra_list_diversity")
+    if not torch.is_tensor(item_vectors) or item_vectors.dim() != 2 or not item_vectors.is_floating_point():
+        raise ValueError("intra_list_diversity: item_vectors must be a (n_items, D) floating-point tensor")
+    with torch.no_grad():
+        rows = item_vectors[positions.clamp_min(0)].to(torch.float64)                      # (B, k, D)
+        gram = torch.bmm(rows, rows.transpose(1, 2))
+        pair = (used[:, :, None] & used[:, None, :]).triu(diagonal=1)
+        total = ((1.0 - gram) * pair).sum(dim=(1, 2))
+        return (total / pair.sum(dim=(1, 2)).to(torch.float64)).to(torch.float32)          # 0 / 0: NaN under two items
+
+
+def catalogue_coverage(positions: torch.Tensor, counts: Optional[torch.Tensor], n_items: int) -> torch.Tensor:
+    """Catalogue coverage of recommendation lists: the number of distinct item positions in all lists together, divided by
+    ``n_items``.  positions / counts as in ``intra_list_diversity``; a position outside ``[0, n_items)`` counts for nothing.  Returns a
+    float64 scalar on the lists' device.  No host sync."""
+    used = _lists(positions, counts, "catalogue_coverage")
+    if isinstance(n_items, bool) or not isinstance(n_items, (int, np.integer)) or n_items < 1:
+        raise ValueError(f"catalogue_coverage: n_items = {n_items!r} is not a positive int")
+    with torch.no_grad():
+        used = used & (positions < n_items)
+        hit = torch.zeros(int(n_items) + 1, dtype=torch.int64, device=positions.device)
+        hit[torch.where(used, positions, torch.full_like(positions, int(n_items))).reshape(-1)] = 1    # slot n_items: the unused
+        return hit[:int(n_items)].sum().to(torch.float64) / float(n_items)

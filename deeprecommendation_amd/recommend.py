@@ -7,6 +7,8 @@
                        A BasicNCF with content attached (``set_content``) ranks the rows of its item table like a one-hot model.
 ``content_cosine_top_k`` / ``content_cosine_ranks``
                        the reference's content-based baseline: cosine of a user's fixed profile and an item's feature row.
+``diversify_top_k``    greedy MMR re-ranking of the pools those two return (native.mmr_rerank, one launch): relevance traded against the
+                       similarity to what is already in the list.  ``item_vectors`` gives a model's own item space for it.
 ``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
 ``rated_exclusion``    the same for an AttentionNCF's users: the items each listed user rated.
 ``explain_items``      AttentionNCF: the reasons behind winners of many users at once (which rated items carry the attention), from the
@@ -366,6 +368,93 @@ def content_cosine_ranks(user_profiles: torch.Tensor, item_features: torch.Tenso
     if not ranked:
         return rank, torch.empty(0, dtype=torch.int32, device=tcol.device)
     return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])
+
+
+# ---------------------------------------------------------------------------------------- diversified top-K
+def item_vectors(model, *, graph=None, item_features=None) -> torch.Tensor:
+    """The L2-normalised item rows (native.l2_normalize_rows) of the model's own embedding space, one row per item position, as
+    ``diversify_top_k`` and ``intra_list_diversity`` take them.  BasicNCF / MF: the item table the ranking routes build (content
+    attached: the item Linear over the content rows).  GraphNCF: the first ``graph.num_items`` rows of ``propagate_all(graph)``.
+    AttentionNCF: ItemEmbeddings over the catalogue ``item_features`` — the candidate-side item embedding.  A width over
+    ``native.MMR_MAX_D`` is refused (raw content features narrower than that may be passed to ``diversify_top_k`` directly)."""
+    _eval_only(model)
+    too_wide = "item vectors of {} columns are wider than the {} diversify_top_k takes"
+    if _attention_model(model):
+        if graph is not None:
+            raise ValueError(f"graph= is only taken by a GraphNCF, not by {type(model).__name__}")
+        if not torch.is_tensor(item_features) or item_features.dim() != 2:
+            raise ValueError("an AttentionNCF embeds a catalogue: pass item_features=(I_c, F) tensor")
+        if model.ItemEmbeddings[0].out_features > native.MMR_MAX_D:           # known before any GPU work
+            raise ValueError(too_wide.format(model.ItemEmbeddings[0].out_features, native.MMR_MAX_D))
+    else:
+        if item_features is not None:
+            raise ValueError(f"item_features= is only taken by an AttentionNCF, not by {type(model).__name__}")
+        if _graph_model(model) and graph is None:
+            raise ValueError("a GraphNCF embeds its items on a graph: pass graph=")
+        if not _graph_model(model) and graph is not None:
+            raise ValueError(f"graph= is only taken by a GraphNCF, not by {type(model).__name__}")
+    with torch.no_grad():
+        if _attention_model(model):
+            require_gpu(item_features)
+            rows = model.precompute_catalog(item_features)[0]
+        elif graph is not None:
+            graph = graph.to(_model_device(model))
+            rows = model.propagate_all(graph)[:graph.num_items]
+        else:
+            rows = model._table("item", model.item_embeddings[0])
+        if rows.shape[1] > native.MMR_MAX_D:
+            raise ValueError(too_wide.format(rows.shape[1], native.MMR_MAX_D))
+        return native.l2_normalize_rows(rows.float())
+
+
+def diversify_top_k(scores: torch.Tensor, positions: torch.Tensor, counts: Optional[torch.Tensor], item_vectors: torch.Tensor, k: int,
+                    lam: float = 0.5, normalize: Optional[str] = "minmax"):
+    """Greedy Maximal Marginal Relevance over the candidate pools ``top_k_items`` / ``content_cosine_top_k`` return: from each user's
+    pool of N = ``scores.shape[1]`` candidates, ``k`` are picked one after the other, each the candidate with the largest
+    ``lam * relevance - (1 - lam) * (largest similarity to a candidate already picked)`` (ncf_mmr_rerank, THE CONTRACT in
+    include/ncf_abi.h; one launch for all users).
+
+    scores (B, N) fp32, positions (B, N) int64, counts (B,) int32 or None (every slot in use): a pool per user, on the GPU; it need not
+    be sorted, and a slot with position -1 or a non-finite score is never picked.  item_vectors (n_items, D) fp32: row p is the
+    vector of item position p, the similarity of two items is the dot product of their rows — pass ``item_vectors(model)`` (unit rows:
+    cosines) or raw content features.  lam in [0, 1]: 1 is pure relevance, 0 pure diversity after the first pick.  normalize:
+    ``"minmax"`` rescales each pool's scores to [0, 1] over its live slots, so that ``lam`` means the same for every model's score
+    range; ``None`` takes the scores as they are.  Limits: N <= 256, D <= 256 and a multiple of 4, k <= min(N, 128).
+    Returns ``(scores (B, k) fp32, positions (B, k) int64, counts (B,) int32, mmr (B, k) fp32)`` on the device: the picks in picking
+    order with the model scores they had in the pool, and the MMR value each had when picked; slots past ``counts`` hold score -inf,
+    position -1 and value -inf.  Every refusal comes before any GPU work; nothing synchronises with the host (a position outside
+    ``item_vectors`` is skipped and raises at the next ``native.check_oob``)."""
+    if normalize not in (None, "minmax"):
+        raise ValueError(f"normalize = {normalize!r} is neither 'minmax' nor None")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"k = {k!r} is not an int")
+    if not isinstance(lam, (int, float)) or isinstance(lam, bool) or not 0.0 <= float(lam) <= 1.0:
+        raise ValueError(f"lam = {lam!r} is outside [0, 1]")
+    for t, what, dt, dim in ((scores, "scores", torch.float32, 2), (positions, "positions", torch.int64, 2),
+                             (item_vectors, "item_vectors", torch.float32, 2)) + (() if counts is None else ((counts, "counts", torch.int32, 1),)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != dim:
+            raise ValueError(f"{what} must be a {dim}-D {dt} tensor")
+    if positions.shape != scores.shape or (counts is not None and counts.numel() != scores.shape[0]):
+        raise ValueError(f"scores is {tuple(scores.shape)}, positions {tuple(positions.shape)}" +
+                         ("" if counts is None else f", counts {tuple(counts.shape)}"))
+    N, D = scores.shape[1], item_vectors.shape[1]
+    if not 1 <= N <= native.MMR_MAX_N:
+        raise ValueError(f"a pool of N = {N} candidates is outside 1 .. {native.MMR_MAX_N}")
+    if not 4 <= D <= native.MMR_MAX_D or D % 4:
+        raise ValueError(f"item vectors of D = {D} columns: D must be a multiple of 4 in 4 .. {native.MMR_MAX_D}")
+    if not 1 <= int(k) <= min(N, native.MMR_MAX_K):
+        raise ValueError(f"k = {k} is outside 1 .. min(N = {N}, {native.MMR_MAX_K})")
+    require_gpu(scores, positions, counts, item_vectors)
+    with torch.no_grad():
+        scores, positions = scores.contiguous(), positions.contiguous()
+        vectors = item_vectors if item_vectors.stride(1) == 1 else item_vectors.contiguous()
+        slot, value, count = native.mmr_rerank(vectors, scores, positions, None if counts is None else counts.contiguous(), int(k),
+                                               float(lam), normalize == "minmax")
+        picked = slot >= 0
+        at = slot.clamp_min(0).to(torch.int64)
+        out_s = torch.where(picked, scores.gather(1, at), torch.full_like(value, float("-inf")))
+        out_p = torch.where(picked, positions.gather(1, at), torch.full_like(at, -1))
+    return out_s, out_p, count, value
 
 
 # ---------------------------------------------------------------------------------------- AttentionNCF: why these items

@@ -850,6 +850,47 @@ int ncf_kmf_fold_users(float* dev_PU, int64_t ldu, int64_t U, const float* dev_Q
                        int32_t* dev_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Diversified top-K (csrc/mmr.hip) — greedy Maximal Marginal Relevance (MMR) re-ranking of one candidate pool per user, the pools
+ * being what ncf_topk_rows / ncf_dot_topk / ncf_mlp_topk return.  Replaces: nothing in the reference, which stops at the relevance
+ * list; a torch composition needs a (B, N, N) Gram tensor and K rounds of masked arg-max launches.
+ * dev_vec: item vectors (n_items, D) fp32, rows of ldv floats (the similarity is their plain dot product: pass L2-normalised rows
+ * for cosines).  dev_score (B, N) fp32 and dev_pos (B, N) int64, contiguous: the pools, slot j of user b at b * N + j; dev_count
+ * (B,) int32 slots in use per pool, NULL = N.  Outputs, contiguous: dev_out_slot (B, K) int32, dev_out_value (B, K) fp32,
+ * dev_out_count (B,) int32.
+ * THE CONTRACT, per user b, independent of every other user:
+ *       n = min(count[b], N), N when dev_count is NULL; a negative count is 0
+ *       slot j < n is LIVE iff 0 <= pos[j] < n_items and score[j] is finite.  The pool is NOT assumed sorted.
+ *       a position >= n_items or < -1 in a slot j < n also sets the sticky *dev_oob_flag (when non-NULL); -1, the padding of the
+ *       top-K kernels, sets nothing.  Every position is checked before it is used as an address; a dead slot's row is never read.
+ *   relevance:   normalize = 0:  rel_j = score_j
+ *                normalize = 1:  rel_j = (score_j - lo) / (hi - lo), lo / hi = the minimum / maximum score over the live slots; two
+ *                                subtractions and one division, each one IEEE fp32 operation; rel_j = 0 for all j when hi == lo
+ *   similarity:  sim(j, p) = sum over d of vec[pos_j, d] * vec[pos_p, d] in fp32, every product and every sum rounded on its own
+ *                (no FMA), summed SEQUENTIALLY in ascending d:
+ *       acc = +0.0f;  for d = 0 .. D-1:  acc = acc + vec[pos_j, d] * vec[pos_p, d]
+ *   step 0 picks the live slot with the largest rel_j; its value is rel_j.
+ *   step t >= 1 picks, among the live slots not picked yet, the largest value
+ *       v_j = (lambda * rel_j) - ((1 - lambda) * m_j)           (three operations, each rounded; 1 - lambda once, in fp32)
+ *       m_j = the largest sim(j, p) over the slots p picked so far:  m_j starts at -inf, and after each pick  if sim > m_j: m_j = sim
+ *   comparator:  a beats b iff  a > b,  or a == b and a's slot is lower,  or b is NaN and a is not,  or both are NaN and a's slot is
+ *                lower — ncf_topk_rows' order: ties to the lower column, NaN last.
+ *   outputs:     out_count[b] = min(K, number of live slots); for t < out_count[b]: out_slot[b, t] = the slot picked at step t and
+ *                out_value[b, t] = its value when picked; past that slot -1 and value -inf.
+ *   No atomics, one thread per slot: the same inputs give the same bits.
+ * ncf_mmr_supported (host only) answers 1 for 1 <= N <= 256, 4 <= D <= 256 with D % 4 == 0, 1 <= K <= min(N, 128), else 0; outside
+ * that envelope ncf_mmr_rerank returns NCF_EUNSUPPORTED.  NCF_EINVAL, before any launch, for a negative B / n_items / N / D / K, a
+ * lambda outside [0, 1] or NaN, normalize not 0 or 1, ldv < D, and (with B > 0) a NULL dev_score / dev_pos / output, or a NULL
+ * dev_vec with n_items > 0.  B == 0 launches nothing and looks at no pointer.
+ * The pool's rows are gathered once into LDS (stride D + 1 words) as far as 160 KiB hold them beside the per-slot state; slots past
+ * that (N = 256 with D > 156 only) read their rows from global memory at every step, in the same summation order.  16-byte global
+ * reads when ldv is a multiple of 4 and dev_vec is 16-byte aligned, single floats otherwise.
+ * ------------------------------------------------------------------------------------------------ */
+int ncf_mmr_supported(int N, int D, int K);
+int ncf_mmr_rerank(const float* dev_vec, int64_t n_items, int D, int64_t ldv, const float* dev_score, const int64_t* dev_pos,
+                   const int32_t* dev_count, int64_t B, int N, int K, float lambda, int normalize, int32_t* dev_out_slot,
+                   float* dev_out_value, int32_t* dev_out_count, int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Backward (training step).  The reference trains through torch autograd (train.py:95-110); these
  * are the gradient kernels of K1 / K2.  fp32.
  *   dX = dY . W            : ncf_mlp_forward(n_layers = 1) with the transposed weight (no dedicated entry)
