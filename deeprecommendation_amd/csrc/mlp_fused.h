@@ -1,5 +1,6 @@
-// Shared pieces of the fp32 fused MLP scorers (mlp_fused.hip: ncf_score_fused; mlp_topk.hip: ncf_mlp_topk): the packed-blob
-// layout written by ncf_mlp_pack and the list of compiled (K0, N1, N2) instances.  Internal: not part of the ABI.
+// Shared pieces of the fp32 fused MLP scorers (mlp_fused.hip: ncf_score_fused, ncf_score_folded; mlp_partial.hip:
+// ncf_score_fused_partial; mlp_topk.hip: ncf_mlp_topk, ncf_mlp_rank): the packed-blob layout written by ncf_mlp_pack, the list of
+// compiled (K0, N1, N2) instances and the device stages every kernel of the family runs.  Internal: not part of the ABI.
 #pragma once
 #include "ncf_common.h"
 
@@ -33,26 +34,64 @@ static BlobLayout blob_layout(const int* dims, int n_layers) {
     X(128, 256, 128) X(128, 256, 0) X(128, 128, 0) X(128, 128, 64) \
     X(256, 256, 128) X(256, 256, 0) X(256, 128, 0)
 
-// The part of the one-wave-per-tile fp32 scorers after layer 1 (score_fused_f32_kernel in mlp_fused.hip and
-// score_fused_partial_f32_kernel in mlp_partial.hip), in ONE place: both kernels return the same bits because both run this.
+// blob -> the pointers the kernels take (Wp2 / b2 NULL without a second hidden layer)
+struct BlobPtrs {
+    const float *Wp1, *b1, *Wp2, *b2, *wl, *bl;
+};
+static BlobPtrs blob_ptrs(const void* packed, const int* dims, int n_layers) {
+    const BlobLayout L = blob_layout(dims, n_layers);
+    const float* P = (const float*)packed;
+    const bool l2 = n_layers == 3;
+    return {P + L.wp1, P + L.b1, l2 ? P + L.wp2 : nullptr, l2 ? P + L.b2 : nullptr, P + L.wl, P + L.bl};
+}
+
+// The stages the fp32 MLP scorers share (mlp_fused.hip, mlp_partial.hip, mlp_topk.hip), in ONE place: the kernels return the same
+// bits for the same pair because they run this code.
 // Lane (m, h) of a 32-pair tile: the accumulator rows are neurons, register r of tile nt holds neuron 32nt + (r&3) + 8(r>>2) + 4h.
 __device__ __forceinline__ f32x4 fused_ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
-// Layer 2: acc2 = b2 + W2 . relu(acc1); acc1's registers are the B operands.  Per k-step, MFMAs nt-major and the next step's
-// weight fragment of tile nt issued right behind tile nt's MFMAs.  PAIR / ABLATE: mlp_fused.hip's NCF_PAIR / NCF_ABLATE_LOADS.
-template <int N1, int N2, bool PAIR = false, bool ABLATE = false>
+// Tile nt of a bias, P row or prefix state (neuron order) into an accumulator, and back: four 16-byte chunks at
+// src + 32nt + 8g + 4h (h = 0 where src already points at the lane half's chunk).
+__device__ __forceinline__ void fused_load_tile(f32x16& acc, const float* src, int nt, int h) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 v = fused_ldg4(src + 32 * nt + 8 * g + 4 * h);
+        acc[4 * g + 0] = v[0]; acc[4 * g + 1] = v[1];
+        acc[4 * g + 2] = v[2]; acc[4 * g + 3] = v[3];
+    }
+}
+__device__ __forceinline__ void fused_store_tile(float* dst, const f32x16& acc, int nt, int h) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<f32x4*>(dst + 32 * nt + 8 * g + 4 * h) =
+            f32x4{acc[4 * g + 0], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+}
+
+// Pair prologue: this lane's row of `tab` for position p (id idx[p], p itself with idx NULL), offset to the lane half's chunk.
+// Returns whether the id is in range.  An out-of-range id reads row 0, which fused_zmul's factor zeroes at USE; the caller raises
+// the flag under its own condition.  The flag is the return value and the factor a function of its own on purpose: with a bool&
+// or with the factor formed in here, score_fused_f32_kernel no longer compiles to the instructions it had.  The folded and the
+// partial kernel (both ids are read before either is checked), mlp_topk_kernel and mlp_prefix_kernel (their register counts move)
+// keep their own prologue.
+__device__ __forceinline__ bool fused_row(int64_t p, const int64_t* idx, const float* tab, int64_t rows, int64_t ld, int h,
+                                          const float*& row) {
+    const int64_t i = idx ? idx[p] : p;
+    const bool ok = (i >= 0) & (i < rows);
+    row = tab + (ok ? i : 0) * ld + 4 * h;
+    return ok;
+}
+__device__ __forceinline__ float fused_zmul(bool ok) { return ok ? 1.f : 0.f; }
+
+// Layer 2: acc2 = b2 + W2 . relu(acc1); acc1's registers are the B operands.  Per k-step, MFMAs nt-major (4 dependent MFMAs per
+// accumulator: the dependent latency of 32x32x2 equals its issue interval) and the next step's weight fragment of tile nt issued
+// right behind tile nt's MFMAs.
+template <int N1, int N2>
 __device__ __forceinline__ void fused_layer2(const f32x16 (&acc1)[N1 / 32], f32x16 (&acc2)[N2 / 32], const float* b2,
                                              const float* Wp2, int lane) {
     constexpr int NT2 = N2 / 32, Q2 = N1 / 8;
     const int h = lane >> 5;
 #pragma unroll
-    for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bb = fused_ldg4(b2 + 32 * nt + 8 * g + 4 * h);
-            acc2[nt][4 * g + 0] = bb[0]; acc2[nt][4 * g + 1] = bb[1];
-            acc2[nt][4 * g + 2] = bb[2]; acc2[nt][4 * g + 3] = bb[3];
-        }
+    for (int nt = 0; nt < NT2; ++nt) fused_load_tile(acc2[nt], b2, nt, h);
     const f32x4* wp = reinterpret_cast<const f32x4*>(Wp2) + lane;
     f32x4 w[2][NT2];
 #pragma unroll
@@ -64,51 +103,25 @@ __device__ __forceinline__ void fused_layer2(const f32x16 (&acc1)[N1 / 32], f32x
         f32x4 hv;
 #pragma unroll
         for (int j = 0; j < 4; ++j) hv[j] = fmaxf(acc1[kb][4 * g + j], 0.f);  // ReLU (util.py:15)
-        if (PAIR && NT2 % 2 == 0) {
 #pragma unroll
-            for (int nt = 0; nt < NT2; nt += 2) {
+        for (int nt = 0; nt < NT2; ++nt) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
-                    acc2[nt + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt + 1][j], hv[j], acc2[nt + 1], 0, 0, 0);
-                }
-                if (q + 1 < Q2) {
-                    w[nxt][nt] = ABLATE ? w[cur][nt] : wp[((q + 1) * NT2 + nt) * 64];
-                    w[nxt][nt + 1] = ABLATE ? w[cur][nt + 1] : wp[((q + 1) * NT2 + nt + 1) * 64];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int nt = 0; nt < NT2; ++nt) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
-                if (q + 1 < Q2) w[nxt][nt] = ABLATE ? w[cur][nt] : wp[((q + 1) * NT2 + nt) * 64];
-            }
+            for (int j = 0; j < 4; ++j)
+                acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
+            if (q + 1 < Q2) w[nxt][nt] = wp[((q + 1) * NT2 + nt) * 64];
         }
-        if (!ABLATE) {
-            if (PAIR && NT2 % 2 == 0) {
 #pragma unroll
-                for (int nt = 0; nt < NT2; nt += 2) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-                }
-            } else {
-#pragma unroll
-                for (int nt = 0; nt < NT2; ++nt) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-            }
+        for (int nt = 0; nt < NT2; ++nt) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMA
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
         }
         __builtin_amdgcn_sched_barrier(0);
     }
 }
 
-// The 1-wide last layer: bl + sum_n wl[n] * relu(acc[n]), per lane half over nt, g, j, then half 0 + half 1.  Every lane
-// returns its pair's score.
+// The 1-wide last layer without its bias: sum_n wl[n] * relu(acc[n]), per lane half over nt, g, j, then half 0 + half 1.
 template <int NT>
-__device__ __forceinline__ float fused_last_layer(const f32x16 (&acc)[NT], const float* wl, const float* bl, int lane) {
+__device__ __forceinline__ float fused_last_sum(const f32x16 (&acc)[NT], const float* wl, int lane) {
     const int h = lane >> 5;
     float partial = 0.f;
 #pragma unroll
@@ -119,8 +132,13 @@ __device__ __forceinline__ float fused_last_layer(const f32x16 (&acc)[NT], const
 #pragma unroll
             for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc[nt][4 * g + j], 0.f), partial);
         }
-    partial += __shfl_xor(partial, 32);  // the two lane halves hold complementary neuron rows
-    return partial + bl[0];
+    return partial + __shfl_xor(partial, 32);  // the two lane halves hold complementary neuron rows
+}
+
+// ... and with it: every lane returns its pair's score.
+template <int NT>
+__device__ __forceinline__ float fused_last_layer(const f32x16 (&acc)[NT], const float* wl, const float* bl, int lane) {
+    return fused_last_sum(acc, wl, lane) + bl[0];
 }
 
 }  // namespace ncf

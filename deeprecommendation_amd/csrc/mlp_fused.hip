@@ -19,31 +19,14 @@
 #ifndef NCF_X_DEPTH
 #define NCF_X_DEPTH 4       // measured (interleaved A/B, cfg 2): 2 -> 72.4 us, 3 -> 70.0 us, 4 -> 69.5 us
 #endif
-#ifndef NCF_PAIR
-#define NCF_PAIR 0          // 1: MFMAs alternate between two accumulator tiles; measured no gain (70.2 vs 69.7 us): dependent 32x32x2 MFMAs issue back to back at full rate
-#endif
-#ifndef NCF_ABLATE_LOADS
-#define NCF_ABLATE_LOADS 0  // diagnostic: skip the in-loop weight / row loads (wrong results, pure MFMA stream timing)
-#endif
 #ifndef NCF_WG_WAVES
 #define NCF_WG_WAVES 4      // waves per workgroup (4 or 8)
 #endif
 #ifndef NCF_MIN_WAVES
 #define NCF_MIN_WAVES 2     // launch_bounds second argument: waves per SIMD the register budget must allow
 #endif
-#ifndef NCF_STAGGER
-#define NCF_STAGGER 0       // s_sleep units (64 clk) the second half of the workgroup's waves start late by
-#endif
-
-#ifndef NCF_STAMP
-#define NCF_STAMP 0         // diagnostic builds only (tools/ab_fused.py): per-wave s_memtime / s_memrealtime stamps
-#endif
 
 namespace ncf {
-
-#if NCF_STAMP
-static unsigned long long* g_dbg = nullptr;  // dev builds only; never present in the shipped library
-#endif
 
 struct FusedArgs {
     const float* tabA; int64_t rowsA; int64_t ldA;
@@ -54,65 +37,32 @@ struct FusedArgs {
     const float* Wp2; const float* b2;
     const float* wl; const float* bl;   // last (1-wide) layer: weights [Nlast], bias [1]
     float* out; int32_t* oob;
-#if NCF_STAMP
-    unsigned long long* dbg;
-#endif
 };
-
-__device__ __forceinline__ f32x4 ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 template <int K0, int N1, int N2>
 __global__ __launch_bounds__(NCF_WG_WAVES * 64, NCF_MIN_WAVES) void score_fused_f32_kernel(FusedArgs a) {
     constexpr int NT1 = N1 / 32, Q1 = K0 / 8;
-    constexpr int NT2 = N2 / 32, Q2 = N1 / 8;
     const int lane = threadIdx.x & 63;
     const int m = lane & 31, h = lane >> 5;
     const int64_t tile = (int64_t)blockIdx.x * NCF_WG_WAVES + (threadIdx.x >> 6);
     if (tile * 32 >= a.B) return;  // whole wave exits together
-#if NCF_STAMP
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    if (NCF_STAGGER > 0 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= NCF_WG_WAVES * 32) __builtin_amdgcn_s_sleep(NCF_STAGGER);
     const int64_t p = tile * 32 + m;
     const int64_t pc = p < a.B ? p : a.B - 1;
 
-    // ---- gather setup: row pointers of this lane's pair ----
-    const int64_t ia = a.idxA ? a.idxA[pc] : pc;
-    const bool okA = (ia >= 0) & (ia < a.rowsA);
-    const float* rowA = a.tabA + (okA ? ia : 0) * a.ldA + 4 * h;
+    // ---- gather setup: row pointers of this lane's pair; out-of-range rows read as zeros ----
+    const float *rowA, *rowB;
+    const bool okA = fused_row(pc, a.idxA, a.tabA, a.rowsA, a.ldA, h, rowA);
     const int qa = a.EA / 8;  // groups served by table A
-    const float* rowB = rowA;
+    rowB = rowA;
     bool okB = true;
-    if (qa < Q1) {
-        const int64_t ib = a.idxB ? a.idxB[pc] : pc;
-        okB = (ib >= 0) & (ib < a.rowsB);
-        rowB = a.tabB + (okB ? ib : 0) * a.ldB + 4 * h;
-    }
+    if (qa < Q1) okB = fused_row(pc, a.idxB, a.tabB, a.rowsB, a.ldB, h, rowB);
     if (!(okA & okB) && a.oob) *a.oob = 1;
-    const float zA = okA ? 1.f : 0.f, zB = okB ? 1.f : 0.f;  // out-of-range rows read as zeros
-    // Touch every 128-byte line of this pair's two rows NOW (one dword each, lane half h takes lines h, h+2, ...):
-    // the HBM misses of all lines overlap each other and the bias / first-weight loads, instead of surfacing one
-    // by one at every 4th k-step of layer 1 (each step only prefetches one step ahead).
-#ifndef NCF_TOUCH
-#define NCF_TOUCH 0   // measured: touching all lines at kernel start is SLOWER (81 vs 75 us): 2048 waves issue the whole
-#endif                // batch's 34 MB of HBM misses at once and every wave's first weight wait queues behind them
-    if (NCF_TOUCH) {
-        float touch = 0.f;
-        for (int l = h; l * 32 < a.EA; l += 2) touch += rowA[l * 32 - 4 * h];
-        for (int l = h; l * 32 < K0 - a.EA; l += 2) touch += rowB[l * 32 - 4 * h];
-        asm volatile("" ::"v"(touch));
-    }
+    const float zA = fused_zmul(okA), zB = fused_zmul(okB);
 
     // ---- layer 1: acc1 = b1 (broadcast over pairs) + W1 . X^T ----
     f32x16 acc1[NT1];
 #pragma unroll
-    for (int nt = 0; nt < NT1; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bb = ldg4(a.b1 + 32 * nt + 8 * g + 4 * h);
-            acc1[nt][4 * g + 0] = bb[0]; acc1[nt][4 * g + 1] = bb[1];
-            acc1[nt][4 * g + 2] = bb[2]; acc1[nt][4 * g + 3] = bb[3];
-        }
+    for (int nt = 0; nt < NT1; ++nt) fused_load_tile(acc1[nt], a.b1, nt, h);
     {
         const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wp1) + lane;  // + (q*NT1 + nt)*64
         // XD = depth of the gathered-row prefetch ring: chunk q + XD - 1 is requested while step q computes.  The
@@ -126,7 +76,7 @@ __global__ __launch_bounds__(NCF_WG_WAVES * 64, NCF_MIN_WAVES) void score_fused_
         for (int nt = 0; nt < NT1; ++nt) w[0][nt] = wp[nt * 64];
 #pragma unroll
         for (int t = 0; t < XD - 1; ++t)
-            if (t < Q1) x[t] = ldg4(xsrc(t));
+            if (t < Q1) x[t] = fused_ldg4(xsrc(t));
 #pragma unroll
         for (int q = 0; q < Q1; ++q) {
             // One scheduling region per k-step.  MFMAs run nt-major (4 dependent MFMAs per accumulator: the 64-cycle
@@ -136,74 +86,34 @@ __global__ __launch_bounds__(NCF_WG_WAVES * 64, NCF_MIN_WAVES) void score_fused_
             // compiler's counted vmcnt waits only for the tile it is about to use.
             const int cur = q & 1, nxt = cur ^ 1;
             const f32x4 xb = x[q % XD] * (q < qa ? zA : zB);  // zero an out-of-range row at USE time
-            if (NCF_PAIR && NT1 % 2 == 0) {
 #pragma unroll
-                for (int nt = 0; nt < NT1; nt += 2) {
+            for (int nt = 0; nt < NT1; ++nt) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], xb[j], acc1[nt], 0, 0, 0);
-                        acc1[nt + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt + 1][j], xb[j], acc1[nt + 1], 0, 0, 0);
-                    }
-                    if (q + 1 < Q1) {
-                        w[nxt][nt] = NCF_ABLATE_LOADS ? w[cur][nt] : wp[((q + 1) * NT1 + nt) * 64];
-                        w[nxt][nt + 1] = NCF_ABLATE_LOADS ? w[cur][nt + 1] : wp[((q + 1) * NT1 + nt + 1) * 64];
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int nt = 0; nt < NT1; ++nt) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], xb[j], acc1[nt], 0, 0, 0);
-                    if (q + 1 < Q1) w[nxt][nt] = NCF_ABLATE_LOADS ? w[cur][nt] : wp[((q + 1) * NT1 + nt) * 64];
-                }
+                for (int j = 0; j < 4; ++j)
+                    acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], xb[j], acc1[nt], 0, 0, 0);
+                if (q + 1 < Q1) w[nxt][nt] = wp[((q + 1) * NT1 + nt) * 64];
             }
-            if (q + XD - 1 < Q1) x[(q + XD - 1) % XD] = NCF_ABLATE_LOADS ? x[q % XD] : ldg4(xsrc(q + XD - 1));
-            if (!NCF_ABLATE_LOADS) {
-                if (NCF_PAIR && NT1 % 2 == 0) {
+            if (q + XD - 1 < Q1) x[(q + XD - 1) % XD] = fused_ldg4(xsrc(q + XD - 1));
 #pragma unroll
-                    for (int nt = 0; nt < NT1; nt += 2) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);  // 8 MFMA (two tiles alternating)
-                        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);  // 2 VMEM reads
-                    }
-                } else {
-#pragma unroll
-                    for (int nt = 0; nt < NT1; ++nt) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
-                    }
-                }
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            for (int nt = 0; nt < NT1; ++nt) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMA
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
             }
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
 
-#if NCF_STAMP
-    const unsigned long long st_rL1 = __builtin_amdgcn_s_memrealtime();
-#endif
     float score;
     if constexpr (N2 > 0) {
         // ---- layer 2 (acc1's registers are the B operands) and the 1-wide layer: mlp_fused.h ----
         f32x16 acc2[N2 / 32];
-        fused_layer2<N1, N2, NCF_PAIR != 0, NCF_ABLATE_LOADS != 0>(acc1, acc2, a.b2, a.Wp2, lane);
-#if NCF_STAMP
-        if (a.dbg && lane == 0) a.dbg[tile * 4 + 0] = __builtin_amdgcn_s_memrealtime();  // end of layer 2
-#endif
+        fused_layer2<N1, N2>(acc1, acc2, a.b2, a.Wp2, lane);
         score = fused_last_layer(acc2, a.wl, a.bl, lane);
     } else {
         score = fused_last_layer(acc1, a.wl, a.bl, lane);
     }
     if (h == 0 && p < a.B) a.out[p] = score;
-#if NCF_STAMP
-    if (a.dbg && lane == 0) {
-        const unsigned long long st_t1 = __builtin_amdgcn_s_memtime(), st_r1 = __builtin_amdgcn_s_memrealtime();
-        (void)st_t0; (void)st_t1;
-        a.dbg[tile * 4 + 1] = st_rL1;          // end of layer 1 (100 MHz ticks)
-        a.dbg[tile * 4 + 2] = st_r0;           // wave start
-        a.dbg[tile * 4 + 3] = st_r1;           // wave end
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -225,28 +135,24 @@ __global__ __launch_bounds__(256) void score_fused_small_f32_kernel(FusedArgs a)
     const int64_t p = (int64_t)blockIdx.x * 32 + m;
     const int64_t pc = p < a.B ? p : a.B - 1;
 
-    const int64_t ia = a.idxA ? a.idxA[pc] : pc;
-    const bool okA = (ia >= 0) & (ia < a.rowsA);
-    const float* rowA = a.tabA + (okA ? ia : 0) * a.ldA + 4 * h;
+    const float *rowA, *rowB;
+    const bool okA = fused_row(pc, a.idxA, a.tabA, a.rowsA, a.ldA, h, rowA);
     const int qa = a.EA / 8;
-    const float* rowB = rowA;
+    rowB = rowA;
     bool okB = true;
-    if (qa < Q1) {
-        const int64_t ib = a.idxB ? a.idxB[pc] : pc;
-        okB = (ib >= 0) & (ib < a.rowsB);
-        rowB = a.tabB + (okB ? ib : 0) * a.ldB + 4 * h;
-    }
+    if (qa < Q1) okB = fused_row(pc, a.idxB, a.tabB, a.rowsB, a.ldB, h, rowB);
     if (!(okA & okB) && a.oob && wave == 0 && p < a.B) *a.oob = 1;
-    const float zA = okA ? 1.f : 0.f, zB = okB ? 1.f : 0.f;
+    const float zA = fused_zmul(okA), zB = fused_zmul(okB);
     auto xsrc = [&](int q) { return q < qa ? rowA + 8 * q : rowB + 8 * (q - qa); };
 
-    // ---- layer 1: this wave's tiles nt = wave*T1 + t ----
+    // ---- layer 1: this wave's tiles nt = wave*T1 + t (fused_load_tile written out: through the helper the N1 = 128 instances,
+    // one tile per wave, compile to another register allocation) ----
     f32x16 acc1[T1];
 #pragma unroll
     for (int t = 0; t < T1; ++t)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const f32x4 bb = ldg4(a.b1 + 32 * (wave * T1 + t) + 8 * g + 4 * h);
+            const f32x4 bb = fused_ldg4(a.b1 + 32 * (wave * T1 + t) + 8 * g + 4 * h);
             acc1[t][4 * g + 0] = bb[0]; acc1[t][4 * g + 1] = bb[1];
             acc1[t][4 * g + 2] = bb[2]; acc1[t][4 * g + 3] = bb[3];
         }
@@ -262,14 +168,14 @@ __global__ __launch_bounds__(256) void score_fused_small_f32_kernel(FusedArgs a)
             }
 #pragma unroll
         for (int s0 = 0; s0 < XD - 1; ++s0)
-            if (s0 < Q1) x[s0] = ldg4(xsrc(s0));
+            if (s0 < Q1) x[s0] = fused_ldg4(xsrc(s0));
 #pragma unroll
         for (int q = 0; q < Q1; ++q) {
             if (q + WD - 1 < Q1) {
 #pragma unroll
                 for (int t = 0; t < T1; ++t) w[(q + WD - 1) % WD][t] = wp[((q + WD - 1) * NT1 + wave * T1 + t) * 64];
             }
-            if (q + XD - 1 < Q1) x[(q + XD - 1) % XD] = ldg4(xsrc(q + XD - 1));
+            if (q + XD - 1 < Q1) x[(q + XD - 1) % XD] = fused_ldg4(xsrc(q + XD - 1));
             __builtin_amdgcn_sched_barrier(0);
             const f32x4 xb = x[q % XD] * (q < qa ? zA : zB);
 #pragma unroll
@@ -297,14 +203,10 @@ __global__ __launch_bounds__(256) void score_fused_small_f32_kernel(FusedArgs a)
         const bool l2_active = wave < NT2;      // wave-uniform
         if (l2_active) {
 #pragma unroll
-            for (int t = 0; t < T2; ++t)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int nt = wave + 4 * t;
-                    const f32x4 bb = ldg4(a.b2 + 32 * (nt < NT2 ? nt : 0) + 8 * g + 4 * h);
-                    acc2[t][4 * g + 0] = bb[0]; acc2[t][4 * g + 1] = bb[1];
-                    acc2[t][4 * g + 2] = bb[2]; acc2[t][4 * g + 3] = bb[3];
-                }
+            for (int t = 0; t < T2; ++t) {
+                const int nt = wave + 4 * t;
+                fused_load_tile(acc2[t], a.b2, nt < NT2 ? nt : 0, h);
+            }
             const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wp2) + lane;
             f32x4 w[WD][T2];
 #pragma unroll
@@ -359,7 +261,7 @@ __global__ __launch_bounds__(256) void score_fused_small_f32_kernel(FusedArgs a)
     for (int nt = 0; nt < NTL; ++nt)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const f32x4 ww = ldg4(a.wl + 32 * nt + 8 * g + 4 * h);
+            const f32x4 ww = fused_ldg4(a.wl + 32 * nt + 8 * g + 4 * h);
             const f32x4 v = (N2 > 0) ? h2s[8 * nt + 2 * g + h][m] : h1s[8 * nt + 2 * g + h][m];
 #pragma unroll
             for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], v[j], partial);
@@ -375,17 +277,7 @@ __global__ __launch_bounds__(256) void score_fused_small_f32_kernel(FusedArgs a)
 // E = 64, N1 = 256) and the kernel is  gather 2 x N1 floats -> add -> ReLU -> layer 2 (MFMA) -> 1-wide layer.
 // Lane (m, h) loads the 16-byte chunk (8kb + 2g + h) of pair m's two rows DIRECTLY in accumulator-row order
 // (neuron 32kb + 8g + 4h + j), i.e. straight into the B operand of layer 2's k-step 4kb + g.
-// Layer 2's packed weights (N1*N2 floats = 128 KB at 256x128) live in LDS for the whole workgroup (8 waves, 256
-// pairs): they are read with ds_read_b128 on lgkmcnt, so vmcnt tracks ONLY the HBM row gathers and those can be
-// prefetched several k-blocks ahead without the in-order vmcnt making every weight wait queue behind an HBM miss.
 // Bound: fp32 MFMA on layer 2 (2*N1*N2 + 2*N2 FLOP/pair = 65 792 at 256x128) vs HBM 2*N1*4 + 20 B/pair = 2068 B.
-#ifndef NCF_FOLD_PF
-#define NCF_FOLD_PF 2   // accumulator tiles (k-blocks of 32 neurons) of row data requested ahead; measured 2 -> 45.6 us, 3 -> 47.5, 5 -> 55.3, 8 (all up front) -> 69.3
-#endif
-#ifndef NCF_FOLD_ABLATE
-#define NCF_FOLD_ABLATE 0   // diagnostics: 1 = no row gathers in the loop (constant data), 2 = weights from registers only
-#endif
-
 struct FoldArgs {
     const float* PA; int64_t rowsA; int64_t ldA;
     const float* PB; int64_t rowsB; int64_t ldB;
@@ -395,109 +287,11 @@ struct FoldArgs {
     float* out; int32_t* oob;
 };
 
-template <int N1, int N2>
-__global__ __launch_bounds__(512, 2) void score_folded_f32_kernel(FoldArgs a) {
-    constexpr int NT1 = N1 / 32, NT2 = N2 / 32, Q2 = N1 / 8;
-    constexpr int PF = NCF_FOLD_PF < NT1 ? NCF_FOLD_PF : NT1;
-    constexpr int RING = PF + 1;
-    __shared__ __attribute__((aligned(16))) f32x4 wlds[Q2 * NT2 * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int m = lane & 31, h = lane >> 5;
-    const int64_t tile = (int64_t)blockIdx.x * 8 + wave;
-    const int64_t p = tile * 32 + m;
-    const int64_t pc = p < a.B ? p : a.B - 1;
-
-    const int64_t ia = a.idxA ? a.idxA[pc] : pc;
-    const int64_t ib = a.idxB ? a.idxB[pc] : pc;
-    const bool okA = (ia >= 0) & (ia < a.rowsA), okB = (ib >= 0) & (ib < a.rowsB);
-    if (!(okA & okB) && a.oob && p < a.B) *a.oob = 1;
-    const float* rowA = a.PA + (okA ? ia : 0) * a.ldA + 4 * h;
-    const float* rowB = a.PB + (okB ? ib : 0) * a.ldB + 4 * h;
-    const float zA = okA ? 1.f : 0.f, zB = okB ? 1.f : 0.f;
-
-    // row-data ring: tile kb = chunks g = 0..3 at row + 32kb + 8g
-    f32x4 pa[RING][4], pb[RING][4];
-#pragma unroll
-    for (int t = 0; t < PF; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            pa[t][g] = ldg4(rowA + 32 * t + 8 * g);
-            pb[t][g] = ldg4(rowB + 32 * t + 8 * g);
-        }
-    // layer-2 weights -> LDS once per workgroup
-    {
-        const f32x4* src = reinterpret_cast<const f32x4*>(a.Wp2);
-        for (int i = threadIdx.x; i < Q2 * NT2 * 64; i += 512) wlds[i] = src[i];
-    }
-    f32x16 acc2[NT2];
-#pragma unroll
-    for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bb = ldg4(a.b2 + 32 * nt + 8 * g + 4 * h);
-            acc2[nt][4 * g + 0] = bb[0]; acc2[nt][4 * g + 1] = bb[1];
-            acc2[nt][4 * g + 2] = bb[2]; acc2[nt][4 * g + 3] = bb[3];
-        }
-    __syncthreads();
-
-    const f32x4* wq = wlds + lane;  // + (q*NT2 + nt)*64
-    f32x4 w[2][NT2];
-#pragma unroll
-    for (int nt = 0; nt < NT2; ++nt) w[0][nt] = wq[nt * 64];
-#pragma unroll
-    for (int kb = 0; kb < NT1; ++kb) {
-        if (kb + PF < NT1 && NCF_FOLD_ABLATE != 1) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                pa[(kb + PF) % RING][g] = ldg4(rowA + 32 * (kb + PF) + 8 * g);
-                pb[(kb + PF) % RING][g] = ldg4(rowB + 32 * (kb + PF) + 8 * g);
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int q = 4 * kb + g, cur = q & 1, nxt = cur ^ 1;
-            const f32x4 s4 = pa[kb % RING][g] * zA + pb[kb % RING][g] * zB;  // bias b1 is folded into PA
-            f32x4 hv;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) hv[j] = fmaxf(s4[j], 0.f);
-#pragma unroll
-            for (int nt = 0; nt < NT2; ++nt) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
-                if (q + 1 < Q2) w[nxt][nt] = (NCF_FOLD_ABLATE == 2) ? w[cur][nt] : wq[((q + 1) * NT2 + nt) * 64];
-            }
-            if (NCF_FOLD_ABLATE != 2) {
-#pragma unroll
-                for (int nt = 0; nt < NT2; ++nt) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // 1 DS read
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    float partial = 0.f;
-#pragma unroll
-    for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 ww = ldg4(a.wl + 32 * nt + 8 * g + 4 * h);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc2[nt][4 * g + j], 0.f), partial);
-        }
-    partial += __shfl_xor(partial, 32);
-    if (h == 0 && p < a.B) a.out[p] = partial + a.bl[0];
-}
-
-#ifndef NCF_FOLD_DIRECT
-#define NCF_FOLD_DIRECT 1   // 1: weights streamed per wave from L2 like the fused kernel (no LDS, no barrier); 0: LDS-resident W2
-#endif
 #ifndef NCF_FOLD_XD
-#define NCF_FOLD_XD 4       // k-steps of row data requested ahead in the direct variant
+#define NCF_FOLD_XD 4       // k-steps of row data requested ahead
 #endif
 
-// Direct variant: exactly the fused kernel's layer-2 step (next step's weights interleaved behind the MFMAs), with the
+// Exactly the fused kernel's layer-2 step (next step's weights streamed per wave from L2, interleaved behind the MFMAs), with the
 // B operand taken from a ring of gathered pre-activation chunks instead of layer-1 accumulators.  One wave = 32 pairs,
 // 256-thread workgroups, two per CU, no LDS and no barrier.  The two row loads of k-step q + XD are issued after the
 // step's weight loads so the in-order vmcnt wait for the next step's weights never queues behind an HBM miss.
@@ -511,6 +305,7 @@ __global__ __launch_bounds__(256, 2) void score_folded_direct_kernel(FoldArgs a)
     if (tile * 32 >= a.B) return;
     const int64_t p = tile * 32 + m;
     const int64_t pc = p < a.B ? p : a.B - 1;
+    // the prologue is not fused_row's: both ids are read before either is checked
     const int64_t ia = a.idxA ? a.idxA[pc] : pc;
     const int64_t ib = a.idxB ? a.idxB[pc] : pc;
     const bool okA = (ia >= 0) & (ia < a.rowsA), okB = (ib >= 0) & (ib < a.rowsB);
@@ -521,13 +316,7 @@ __global__ __launch_bounds__(256, 2) void score_folded_direct_kernel(FoldArgs a)
 
     f32x16 acc2[NT2];
 #pragma unroll
-    for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bb = ldg4(a.b2 + 32 * nt + 8 * g + 4 * h);
-            acc2[nt][4 * g + 0] = bb[0]; acc2[nt][4 * g + 1] = bb[1];
-            acc2[nt][4 * g + 2] = bb[2]; acc2[nt][4 * g + 3] = bb[3];
-        }
+    for (int nt = 0; nt < NT2; ++nt) fused_load_tile(acc2[nt], a.b2, nt, h);
     const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wp2) + lane;
     f32x4 w[2][NT2];
     f32x4 xa[XD], xb[XD];
@@ -535,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void score_folded_direct_kernel(FoldArgs a)
     for (int nt = 0; nt < NT2; ++nt) w[0][nt] = wp[nt * 64];
 #pragma unroll
     for (int t = 0; t < XD - 1; ++t)
-        if (t < Q2) { xa[t] = ldg4(rowA + 8 * t); xb[t] = ldg4(rowB + 8 * t); }
+        if (t < Q2) { xa[t] = fused_ldg4(rowA + 8 * t); xb[t] = fused_ldg4(rowB + 8 * t); }
 #pragma unroll
     for (int q = 0; q < Q2; ++q) {
         const int cur = q & 1, nxt = cur ^ 1;
@@ -551,8 +340,8 @@ __global__ __launch_bounds__(256, 2) void score_folded_direct_kernel(FoldArgs a)
             if (q + 1 < Q2) w[nxt][nt] = wp[((q + 1) * NT2 + nt) * 64];
         }
         if (q + XD - 1 < Q2) {
-            xa[(q + XD - 1) % XD] = ldg4(rowA + 8 * (q + XD - 1));
-            xb[(q + XD - 1) % XD] = ldg4(rowB + 8 * (q + XD - 1));
+            xa[(q + XD - 1) % XD] = fused_ldg4(rowA + 8 * (q + XD - 1));
+            xb[(q + XD - 1) % XD] = fused_ldg4(rowB + 8 * (q + XD - 1));
         }
 #pragma unroll
         for (int nt = 0; nt < NT2; ++nt) {
@@ -562,26 +351,14 @@ __global__ __launch_bounds__(256, 2) void score_folded_direct_kernel(FoldArgs a)
         __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
-    float partial = 0.f;
-#pragma unroll
-    for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 ww = ldg4(a.wl + 32 * nt + 8 * g + 4 * h);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc2[nt][4 * g + j], 0.f), partial);
-        }
-    partial += __shfl_xor(partial, 32);
-    if (h == 0 && p < a.B) a.out[p] = partial + a.bl[0];
+    const float score = fused_last_layer(acc2, a.wl, a.bl, lane);
+    if (h == 0 && p < a.B) a.out[p] = score;
 }
 
 template <int N1, int N2>
 static void launch_folded(const FoldArgs& a, hipStream_t s) {
     const int64_t tiles = (a.B + 31) / 32;
-    if (NCF_FOLD_DIRECT)
-        hipLaunchKernelGGL((score_folded_direct_kernel<N1, N2>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((score_folded_f32_kernel<N1, N2>), dim3((unsigned)((tiles + 7) / 8)), dim3(512), 0, s, a);
+    hipLaunchKernelGGL((score_folded_direct_kernel<N1, N2>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
 }
 
 static bool folded_dispatch(int N1, int N2, const FoldArgs* a, hipStream_t s) {
@@ -615,12 +392,9 @@ typedef void (*fused_fn)(FusedArgs);
 #define NCF_SMALL_TILES 768   // below this many 32-pair tiles the 4-waves-per-tile kernel is used (measured crossover)
 #endif
 
-#ifndef NCF_HYBRID
-#define NCF_HYBRID 1          // ragged last round of the one-wave-per-tile kernel goes to the 4-waves-per-tile kernel
-#endif
 #ifndef NCF_HYBRID_MAX_PERMILLE
-#define NCF_HYBRID_MAX_PERMILLE 850   // ... when it fills less than this share of a round (above: one more full round is cheaper)
-#endif
+#define NCF_HYBRID_MAX_PERMILLE 850   // a ragged last round of the one-wave-per-tile kernel goes to the 4-waves-per-tile kernel when it
+#endif                                // fills less than this share of a round (above: one more full round is cheaper; 0: never split)
 
 static int fused_num_cus() { return num_cus(); }  // per-device cache in abi.hip
 
@@ -645,7 +419,7 @@ static void launch_inst(const FusedArgs& a, hipStream_t s) {
         const int64_t round = 4 * (int64_t)fused_num_cus();
         const int64_t full = tiles / round, rem = tiles % round;
         const bool ids_ok = a.idxA && (a.EA == K0 || a.idxB);
-        if (NCF_HYBRID && ids_ok && rem > 0 && rem * 1000 < round * NCF_HYBRID_MAX_PERMILLE) {
+        if (ids_ok && rem > 0 && rem * 1000 < round * NCF_HYBRID_MAX_PERMILLE) {
             const int64_t split = full * round * 32;   // pairs handled by the full rounds
             FusedArgs tail = a;
             tail.idxA = a.idxA + split;
@@ -745,26 +519,16 @@ extern "C" int ncf_score_fused(int dtype, const void* tabA, int64_t rowsA, int64
     if (ldA < EA || (EB > 0 && ldB < EB) || ldA % 4 || (EB > 0 && ldB % 4) || !aligned16(tabA) || (EB > 0 && !aligned16(tabB)) || !aligned16(packed))
         return fail(NCF_EINVAL, "ncf_score_fused: tables must be 16-byte aligned with ld %% 4 == 0");
     if (B == 0) return NCF_OK;
-    const BlobLayout L = blob_layout(dims, n_layers);
-    const float* P = (const float*)packed;
+    const BlobPtrs w = blob_ptrs(packed, dims, n_layers);
     FusedArgs a;
     a.tabA = (const float*)tabA; a.rowsA = rowsA; a.ldA = ldA;
     a.tabB = (const float*)(EB ? tabB : tabA); a.rowsB = EB ? rowsB : rowsA; a.ldB = EB ? ldB : ldA;
     a.idxA = idxA; a.idxB = idxB; a.B = B; a.EA = EA;
-    a.Wp1 = P + L.wp1; a.b1 = P + L.b1;
-    a.Wp2 = n_layers == 3 ? P + L.wp2 : nullptr; a.b2 = n_layers == 3 ? P + L.b2 : nullptr;
-    a.wl = P + L.wl; a.bl = P + L.bl;
+    a.Wp1 = w.Wp1; a.b1 = w.b1; a.Wp2 = w.Wp2; a.b2 = w.b2; a.wl = w.wl; a.bl = w.bl;
     a.out = out; a.oob = oob;
-#if NCF_STAMP
-    a.dbg = g_dbg;
-#endif
     fused_dispatch(dims[0], dims[1], n_layers == 3 ? dims[2] : 0, &a, (hipStream_t)stream);
     return check_launch("ncf_score_fused");
 }
-
-#if NCF_STAMP
-extern "C" void ncf_dev_set_debug_buffer(void* p) { ncf::g_dbg = (unsigned long long*)p; }
-#endif
 
 extern "C" int ncf_score_folded_supported(int dtype, int N1, int N2) {
     return (dtype == NCF_F32 && folded_dispatch(N1, N2, nullptr, nullptr)) ? 1 : 0;
@@ -780,13 +544,12 @@ extern "C" int ncf_score_folded(int dtype, const void* PA, int64_t rowsA, int64_
     if (ldA < N1 || ldB < N1 || ldA % 4 || ldB % 4 || !aligned16(PA) || !aligned16(PB) || !aligned16(packed_tail))
         return fail(NCF_EINVAL, "ncf_score_folded: tables must be 16-byte aligned with ld %% 4 == 0 and ld >= N1");
     const int dims[3] = {N1, N2, 1};
-    const BlobLayout L = blob_layout(dims, 2);  // the tail MLP [N1 -> N2 -> 1] packed by ncf_mlp_pack
-    const float* P = (const float*)packed_tail;
+    const BlobPtrs w = blob_ptrs(packed_tail, dims, 2);  // the tail MLP [N1 -> N2 -> 1] packed by ncf_mlp_pack: its layer 1 is W2
     FoldArgs a;
     a.PA = (const float*)PA; a.rowsA = rowsA; a.ldA = ldA;
     a.PB = (const float*)PB; a.rowsB = rowsB; a.ldB = ldB;
     a.idxA = idxA; a.idxB = idxB; a.B = B;
-    a.Wp2 = P + L.wp1; a.b2 = P + L.b1; a.wl = P + L.wl; a.bl = P + L.bl;
+    a.Wp2 = w.Wp1; a.b2 = w.b1; a.wl = w.wl; a.bl = w.bl;
     a.out = out; a.oob = oob;
     folded_dispatch(N1, N2, &a, (hipStream_t)stream);
     return check_launch("ncf_score_folded");

@@ -25,9 +25,6 @@
 #ifndef NCF_PART_LDS_PF
 #define NCF_PART_LDS_PF 2   // P tiles requested ahead in the LDS form (the only loads on its vector-memory queue); swept 1 .. 8
 #endif
-#ifndef NCF_PART_ABLATE
-#define NCF_PART_ABLATE 0   // diagnostic, wrong results, timing only: bit 0 = every pair reads P row rowsA (one L2-resident row),
-#endif                      // bit 1 = the layer-1 weight fragment is never reloaded
 #ifndef NCF_PART_HYBRID_MAX_PERMILLE
 #define NCF_PART_HYBRID_MAX_PERMILLE 500  // a batch, or a ragged last round, of at most this share of a round goes to ncf_score_fused
 #endif
@@ -35,7 +32,9 @@
 namespace ncf {
 
 // ---------------------------------------------------------------------------------------------------------------
-// Build: one wave = 32 rows of A, each in a pair's place of the fused kernel's layer 1, groups q < QA only.
+// Build: one wave = 32 rows of A, each in a pair's place of the fused kernel's layer 1, groups q < QA only.  The prefix pass of
+// ncf_mlp_topk (mlp_prefix_kernel, mlp_topk.hip) is the same computation without the look-ahead: this loop, which asks for the next
+// group's fragments and row chunk ahead of a group's MFMAs, measured 2.5 % slower there at 1 M rows, so both stay.
 struct PartialBuildArgs {
     const float* tabA; int64_t rowsA; int64_t ldA; int QA;
     const float* Wp1; const float* b1;
@@ -53,17 +52,11 @@ __global__ __launch_bounds__(256) void layer1_partial_kernel(PartialBuildArgs a)
     const int64_t r = tile * 32 + m;
     const bool ok = r < a.rowsA;    // row rowsA (and the lanes past it): the fused kernel's out-of-range id = row 0 times 0
     const float* rowA = a.tabA + (ok ? r : 0) * a.ldA + 4 * h;
-    const float zA = ok ? 1.f : 0.f;
+    const float zA = fused_zmul(ok);
 
     f32x16 acc[NT1];
 #pragma unroll
-    for (int nt = 0; nt < NT1; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bb = fused_ldg4(a.b1 + 32 * nt + 8 * g + 4 * h);
-            acc[nt][4 * g + 0] = bb[0]; acc[nt][4 * g + 1] = bb[1];
-            acc[nt][4 * g + 2] = bb[2]; acc[nt][4 * g + 3] = bb[3];
-        }
+    for (int nt = 0; nt < NT1; ++nt) fused_load_tile(acc[nt], a.b1, nt, h);
     const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wp1) + lane;  // + (q*NT1 + nt)*64
     f32x4 w[NT1], x;
 #pragma unroll
@@ -87,16 +80,8 @@ __global__ __launch_bounds__(256) void layer1_partial_kernel(PartialBuildArgs a)
         x = xn;
     }
     if (r >= rows) return;
-    float* dst = a.P + r * a.ldP + 4 * h;
 #pragma unroll
-    for (int nt = 0; nt < NT1; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 v;
-            v[0] = acc[nt][4 * g + 0]; v[1] = acc[nt][4 * g + 1];
-            v[2] = acc[nt][4 * g + 2]; v[3] = acc[nt][4 * g + 3];
-            *reinterpret_cast<f32x4*>(dst + 32 * nt + 8 * g) = v;
-        }
+    for (int nt = 0; nt < NT1; ++nt) fused_store_tile(a.P + r * a.ldP, acc[nt], nt, h);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -132,7 +117,6 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
     constexpr int PF0 = LDS ? NCF_PART_LDS_PF : NCF_PART_PF;
     constexpr int PF = PF0 < 1 ? 1 : (PF0 < NT1 ? PF0 : NT1);
     constexpr int FILL = LDS ? S / 4 : 1;                            // fragments each of the 4 waves copies into the image
-    constexpr bool ABL_P = (NCF_PART_ABLATE & 1) != 0, ABL_W = (NCF_PART_ABLATE & 2) != 0;
     __shared__ __attribute__((aligned(16))) f32x4 wlds[LDS ? S * 64 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = lane & 31, h = lane >> 5;
@@ -153,19 +137,13 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
     }
     const bool okA = (ia >= 0) & (ia < a.rowsA), okB = (ib >= 0) & (ib < a.rowsB);
     if (!(okA & okB) && a.oob && live) *a.oob = 1;
-    const float* prow = a.P + ((okA && !ABL_P) ? ia : a.rowsA) * a.ldP + 4 * h;
+    // Not fused_row's prologue: both ids are read ahead of the fill loads, and a bad A id reads the sentinel row, not row 0.
+    const float* prow = a.P + (okA ? ia : a.rowsA) * a.ldP + 4 * h;
     const float* rowB = a.tabB + (okB ? ib : 0) * a.ldB + 4 * h;
     const float zB = okB ? 1.f : 0.f;
 
     f32x16 acc1[NT1];
-    auto load_p = [&](int nt) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = fused_ldg4(prow + 32 * nt + 8 * g);
-            acc1[nt][4 * g + 0] = v[0]; acc1[nt][4 * g + 1] = v[1];
-            acc1[nt][4 * g + 2] = v[2]; acc1[nt][4 * g + 3] = v[3];
-        }
-    };
+    auto load_p = [&](int nt) { fused_load_tile(acc1[nt], prow, nt, 0); };  // prow carries the lane half's 4h already
     f32x4 w[WD], x[QB];
     // Issue order = first-use order: the in-order vmcnt wait for a fragment never waits for a younger load.
     load_p(0);
@@ -197,18 +175,16 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
             for (int j = 0; j < 4; ++j)
                 acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[s % WD][j], xb[j], acc1[nt], 0, 0, 0);
             if constexpr (LDS) {  // the fragment of step s + 2 into the quad step s has just read: a full step of cover
-                if (s + 2 < S && !ABL_W) w[s % 2] = wq[(s + 2) * 64];
+                if (s + 2 < S) w[s % 2] = wq[(s + 2) * 64];
             } else {
-                if (s + WD - 1 < S) w[(s + WD - 1) % WD] = ABL_W ? w[s % WD] : wfrag(s + WD - 1);
+                if (s + WD - 1 < S) w[(s + WD - 1) % WD] = wfrag(s + WD - 1);
             }
         }
         if (nt + PF < NT1) load_p(nt + PF);
-        if (!ABL_W) {
 #pragma unroll
-            for (int t = 0; t < QB; ++t) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                 // 4 MFMA
-                __builtin_amdgcn_sched_group_barrier(LDS ? 0x100 : 0x020, 1, 0);  // 1 DS / VMEM read (a later fragment)
-            }
+        for (int t = 0; t < QB; ++t) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                 // 4 MFMA
+            __builtin_amdgcn_sched_group_barrier(LDS ? 0x100 : 0x020, 1, 0);  // 1 DS / VMEM read (a later fragment)
         }
         __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);      // the P tile
         __builtin_amdgcn_sched_barrier(0);
@@ -274,10 +250,10 @@ extern "C" int ncf_layer1_partial(int dtype, const void* tabA, int64_t rowsA, in
     if (rowsA < 1 || !tabA || !packed || !P) return fail(NCF_EINVAL, "ncf_layer1_partial: bad argument");
     if (ldA < EA || ldA % 4 || ldP < N1 || ldP % 4 || !aligned16(tabA) || !aligned16(P) || !aligned16(packed))
         return fail(NCF_EINVAL, "ncf_layer1_partial: tables must be 16-byte aligned with ld %% 4 == 0");
-    const BlobLayout L = blob_layout(dims, n_layers);
+    const BlobPtrs w = blob_ptrs(packed, dims, n_layers);
     PartialBuildArgs a;
     a.tabA = (const float*)tabA; a.rowsA = rowsA; a.ldA = ldA; a.QA = EA / 8;
-    a.Wp1 = (const float*)packed + L.wp1; a.b1 = (const float*)packed + L.b1;
+    a.Wp1 = w.Wp1; a.b1 = w.b1;
     a.P = (float*)P; a.ldP = ldP;
     const int64_t tiles = (rowsA + 1 + 31) / 32;
     const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
@@ -314,15 +290,12 @@ extern "C" int ncf_score_fused_partial(int dtype, const void* P, int64_t ldP, co
     int64_t head = B;
     if (rem > 0 && rem * 1000 <= round * NCF_PART_HYBRID_MAX_PERMILLE && (full == 0 || (idxA && idxB))) head = full * round * 32;
     if (head == 0) return plain(0, B);
-    const BlobLayout L = blob_layout(dims, n_layers);
-    const float* pk = (const float*)packed;
+    const BlobPtrs w = blob_ptrs(packed, dims, n_layers);
     PartialArgs a;
     a.P = (const float*)P; a.rowsA = rowsA; a.ldP = ldP;
     a.tabB = (const float*)tabB; a.rowsB = rowsB; a.ldB = ldB;
     a.idxA = idxA; a.idxB = idxB; a.B = head; a.QA = EA / 8;
-    a.Wp1 = pk + L.wp1;
-    a.Wp2 = n_layers == 3 ? pk + L.wp2 : nullptr; a.b2 = n_layers == 3 ? pk + L.b2 : nullptr;
-    a.wl = pk + L.wl; a.bl = pk + L.bl;
+    a.Wp1 = w.Wp1; a.Wp2 = w.Wp2; a.b2 = w.b2; a.wl = w.wl; a.bl = w.bl;
     a.out = out; a.oob = oob;
     partial_dispatch(EB / 8, N1, n_layers == 3 ? dims[2] : 0, &a, s);
     const int rc = check_launch("ncf_score_fused_partial");

@@ -11,10 +11,10 @@
 //   main kernel   one wave = one user x a range of ranked columns, 32 columns (one MFMA tile) at a time.  Layer 1's accumulator
 //                 starts from the prefix state (user-first: the user's state, broadcast over the columns and loaded like b1;
 //                 item-first: each column's own state), the remaining Q1 - EA/8 k-steps take the second part's rows (item rows
-//                 per column, or the user row broadcast), then layer 2 and the 1-wide layer run as in the fused kernel, with its
-//                 weight prefetch schedule, bias + ReLU and the final partial + shfl_xor(partial, 32) + bl.  The same instructions
-//                 run on the same operands in the same order, so every score has the fused scorer's bits; the first part's FLOP
-//                 (2 EA N1 per pair) is paid once per row instead of once per pair.
+//                 per column, or the user row broadcast), then layer 2 and the 1-wide layer are the fused kernel's own code
+//                 (fused_layer2, fused_last_sum: mlp_fused.h).  The same operations run on the same operands in the same order,
+//                 so every score has the fused scorer's bits; the first part's FLOP (2 EA N1 per pair) is paid once per row
+//                 instead of once per pair.
 // Selection: per wave, the user's candidate keys (map(score) << 32 | ~column, the topk.hip order) live in LDS behind a running k-th
 // key threshold; excluded columns are skipped through an LDS bitmap of the range.  A buffer that cannot take another 32 keys is
 // re-selected down to k (wave_reselect).  Each (user, range) writes its k best keys in the layout topk_tile_kernel's merge levels
@@ -39,11 +39,10 @@ constexpr int kMtCap = 256;                      // candidate keys per wave (= w
 constexpr int kMtMaxK = 128;                     // fused limit on k (a re-select must free >= 32 + some slots)
 constexpr int64_t kMtTargetWaves = 2048;         // range shrinks (8192 -> 32 columns) until the grid has this many waves
 
-__device__ __forceinline__ f32x4 mt_ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
 // State of layer 1 after the first part's k-steps for n first-part rows tab[idx[p]] (tab[p] with idx NULL):
 // state[p][n] = (b1 + W1[:, :EA] . row)[n], accumulated in score_fused_f32_kernel's order.  Out-of-range ids read row 0 scaled
-// by zero (as the fused kernel does) and set the flag.
+// by zero (as the fused kernel does) and set the flag.  (layer1_partial_kernel, mlp_partial.hip, is this computation with a
+// look-ahead; see there why both exist.)
 template <int K0, int N1>
 __global__ __launch_bounds__(256) void mlp_prefix_kernel(const float* __restrict__ tab, int64_t rows, int64_t ld,
                                                          const int64_t* __restrict__ idx, int64_t n, int EA,
@@ -63,17 +62,11 @@ __global__ __launch_bounds__(256) void mlp_prefix_kernel(const float* __restrict
     const float z = ok ? 1.f : 0.f;
     f32x16 acc[NT1];
 #pragma unroll
-    for (int nt = 0; nt < NT1; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bb = mt_ldg4(b1 + 32 * nt + 8 * g + 4 * h);
-            acc[nt][4 * g + 0] = bb[0]; acc[nt][4 * g + 1] = bb[1];
-            acc[nt][4 * g + 2] = bb[2]; acc[nt][4 * g + 3] = bb[3];
-        }
+    for (int nt = 0; nt < NT1; ++nt) fused_load_tile(acc[nt], b1, nt, h);
     const f32x4* wp = reinterpret_cast<const f32x4*>(Wp1) + lane;
     const int qa = EA / 8;
     for (int q = 0; q < qa; ++q) {
-        const f32x4 xb = mt_ldg4(row + 8 * q) * z;
+        const f32x4 xb = fused_ldg4(row + 8 * q) * z;
 #pragma unroll
         for (int nt = 0; nt < NT1; ++nt) {
             const f32x4 w = wp[(q * NT1 + nt) * 64];
@@ -82,13 +75,8 @@ __global__ __launch_bounds__(256) void mlp_prefix_kernel(const float* __restrict
         }
     }
     if (p >= n) return;
-    float* dst = state + p * N1 + 4 * h;
 #pragma unroll
-    for (int nt = 0; nt < NT1; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<f32x4*>(dst + 32 * nt + 8 * g) =
-                f32x4{acc[nt][4 * g + 0], acc[nt][4 * g + 1], acc[nt][4 * g + 2], acc[nt][4 * g + 3]};
+    for (int nt = 0; nt < NT1; ++nt) fused_store_tile(state + p * N1, acc[nt], nt, h);
 }
 
 struct MtArgs {
@@ -134,7 +122,7 @@ template <> struct MtSinkShared<kMtSinkTopk> { typedef MtWaveShared type; };
 template <int K0, int N1, int N2, int SINK, class Args>
 __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(Args a) {
     constexpr int NT1 = N1 / 32, Q1 = K0 / 8;
-    constexpr int NT2 = N2 / 32, Q2 = N1 / 8;
+    constexpr int NT2 = N2 / 32;
     typedef typename MtSinkShared<SINK>::type Shared;
     __shared__ Shared shw[kMtWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -226,13 +214,7 @@ __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(Args a) {
         // ---- layer 1: acc1 = prefix state + the second part's k-steps (score_fused_f32_kernel's steps qa .. Q1 - 1) ----
         f32x16 acc1[NT1];
 #pragma unroll
-        for (int nt = 0; nt < NT1; ++nt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 bb = mt_ldg4(srow + 32 * nt + 8 * g + 4 * h);
-                acc1[nt][4 * g + 0] = bb[0]; acc1[nt][4 * g + 1] = bb[1];
-                acc1[nt][4 * g + 2] = bb[2]; acc1[nt][4 * g + 3] = bb[3];
-            }
+        for (int nt = 0; nt < NT1; ++nt) fused_load_tile(acc1[nt], srow, nt, h);
         {
             // Qr is a runtime count, so the steps run in a loop of step pairs with two weight buffers (a fully unrolled loop with
             // per-step guards keeps both versions of every ring register live and spills).  As in the fused kernel, the next
@@ -254,13 +236,13 @@ __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(Args a) {
             f32x4 x0, x1, x2, x3;
 #pragma unroll
             for (int nt = 0; nt < NT1; ++nt) wA[nt] = wp[nt * 64];
-            x0 = mt_ldg4(xrow);
-            x1 = mt_ldg4(xrow + 8 * min(1, Qr - 1));
+            x0 = fused_ldg4(xrow);
+            x1 = fused_ldg4(xrow + 8 * min(1, Qr - 1));
             int s = 0;
             for (; s + 1 < Qr; s += 2) {
                 mfma_step(wA, wB, s + 1, x0);
-                x2 = mt_ldg4(xrow + 8 * min(s + 2, Qr - 1));
-                x3 = mt_ldg4(xrow + 8 * min(s + 3, Qr - 1));
+                x2 = fused_ldg4(xrow + 8 * min(s + 2, Qr - 1));
+                x3 = fused_ldg4(xrow + 8 * min(s + 3, Qr - 1));
 #pragma unroll
                 for (int nt = 0; nt < NT1; ++nt) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMA
@@ -288,64 +270,15 @@ __global__ __launch_bounds__(kMtThreads, 2) void mlp_topk_kernel(Args a) {
             }
         }
 
-        float partial = 0.f;
+        // ---- layer 2 and the 1-wide layer: the fused kernel's code (mlp_fused.h); bl[0] was read before the tile loop ----
+        float score;
         if constexpr (N2 > 0) {
-            // ---- layer 2: acc2 = b2 + W2 . relu(acc1) ----
             f32x16 acc2[NT2];
-#pragma unroll
-            for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 bb = mt_ldg4(b2 + 32 * nt + 8 * g + 4 * h);
-                    acc2[nt][4 * g + 0] = bb[0]; acc2[nt][4 * g + 1] = bb[1];
-                    acc2[nt][4 * g + 2] = bb[2]; acc2[nt][4 * g + 3] = bb[3];
-                }
-            const f32x4* wp = reinterpret_cast<const f32x4*>(Wp2) + lane;
-            f32x4 w[2][NT2];
-#pragma unroll
-            for (int nt = 0; nt < NT2; ++nt) w[0][nt] = wp[nt * 64];
-#pragma unroll
-            for (int q = 0; q < Q2; ++q) {
-                const int cur = q & 1, nxt = cur ^ 1;
-                const int kb = q >> 2, g = q & 3;
-                f32x4 hv;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) hv[j] = fmaxf(acc1[kb][4 * g + j], 0.f);
-#pragma unroll
-                for (int nt = 0; nt < NT2; ++nt) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
-                    if (q + 1 < Q2) w[nxt][nt] = wp[((q + 1) * NT2 + nt) * 64];
-                }
-#pragma unroll
-                for (int nt = 0; nt < NT2; ++nt) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // ---- last layer (1 wide): bl + sum_n wl[n] * relu(acc2[n]) ----
-#pragma unroll
-            for (int nt = 0; nt < NT2; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 ww = mt_ldg4(wl + 32 * nt + 8 * g + 4 * h);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc2[nt][4 * g + j], 0.f), partial);
-                }
+            fused_layer2<N1, N2>(acc1, acc2, b2, Wp2, lane);
+            score = fused_last_sum(acc2, wl, lane) + bl0;
         } else {
-#pragma unroll
-            for (int nt = 0; nt < NT1; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 ww = mt_ldg4(wl + 32 * nt + 8 * g + 4 * h);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) partial = fmaf(ww[j], fmaxf(acc1[nt][4 * g + j], 0.f), partial);
-                }
+            score = fused_last_sum(acc1, wl, lane) + bl0;
         }
-        partial += __shfl_xor(partial, 32);              // the two lane halves hold complementary neuron rows
-        const float score = partial + bl0;
 
         // ---- select: lanes of half 0 hold columns cb + m ----
         const unsigned long long key = ((unsigned long long)topk_map(score) << 32) | (0xFFFFFFFFu - (uint32_t)c);
@@ -471,14 +404,13 @@ static void mlp_prefix_pass(MtArgs& a, const void* tabA, int64_t rowsA, int64_t 
                             const int* dims, const void* packed, const int64_t* seen_rowptr, const int32_t* seen_col, float* state,
                             int32_t* oob, hipStream_t s) {
     const int K0 = dims[0], N1 = dims[1], N2 = n_layers == 3 ? dims[2] : 0;
-    const BlobLayout L = blob_layout(dims, n_layers);
-    const float* P = (const float*)packed;
+    const BlobPtrs w = blob_ptrs(packed, dims, n_layers);
     const int64_t npre = user_first ? rows : cols;
     const unsigned pblocks = (unsigned)(((npre + 31) / 32 + 3) / 4);
 #define X(k0, n1, n2) \
     if (K0 == k0 && N1 == n1 && N2 == n2) \
         hipLaunchKernelGGL((mlp_prefix_kernel<k0, n1>), dim3(pblocks), dim3(256), 0, s, (const float*)tabA, rowsA, ldA, \
-                           user_first ? user_ids : item_ids, npre, EA, P + L.wp1, P + L.b1, state, oob);
+                           user_first ? user_ids : item_ids, npre, EA, w.Wp1, w.b1, state, oob);
     NCF_FUSED_INSTANCES(X)
 #undef X
     a.tabB = (const float*)tabB; a.rowsB = rowsB; a.ldB = ldB;
@@ -486,9 +418,7 @@ static void mlp_prefix_pass(MtArgs& a, const void* tabA, int64_t rowsA, int64_t 
     a.user_first = user_first ? 1 : 0;
     a.cols = cols; a.EA = EA;
     a.state = state;
-    a.Wp1 = P + L.wp1;
-    a.Wp2 = n_layers == 3 ? P + L.wp2 : nullptr; a.b2 = n_layers == 3 ? P + L.b2 : nullptr;
-    a.wl = P + L.wl; a.bl = P + L.bl;
+    a.Wp1 = w.Wp1; a.Wp2 = w.Wp2; a.b2 = w.b2; a.wl = w.wl; a.bl = w.bl;
     a.seen_rowptr = seen_rowptr; a.seen_col = seen_col;
     a.oob = oob;
 }

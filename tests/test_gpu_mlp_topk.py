@@ -221,6 +221,10 @@ def test_mlp_topk_bad_ids_set_the_flag(gpu):
         native.mlp_topk(tA, None, tB, None, packed, 5, user_first=user_first)
         torch.cuda.synchronize()
         native.check_oob(gpu)                                   # good ids leave it clear
+        # without the reference's score_fused call: only the prefix pass reads the first part's ids, so the flag is its own
+        native.mlp_topk(tA, bad_u if user_first else bad_i, tB, None, packed, 2, user_first=user_first)
+        with pytest.raises(IndexError):
+            native.check_oob(gpu)
 
 
 def test_mlp_topk_refusals_launch_nothing(gpu):

@@ -1,6 +1,6 @@
 """Dev tool (GPU box): interleaved in-process A/B of ncf_score_fused built with different -D flags.
 
-    python tools/ab_fused.py "" "-DNCF_TOUCH=0" "-DNCF_X_DEPTH=4" ...
+    python tools/ab_fused.py "" "-DNCF_X_DEPTH=3" "-DNCF_WG_WAVES=8" ...
 
 Each argument is a flag string; one .so per variant is compiled into gpurun_out/ab/ and timed over interleaved
 rounds on the cfg-2 workload (rule: perf deltas only from interleaved rounds in ONE process on ONE device).
@@ -85,24 +85,6 @@ def main():
             torch.cuda.synchronize()
             times[vi].append(e0.elapsed_time(e1) * 1e3 / reps)
     for vi, fl in enumerate(variants):
-        if "NCF_STAMP=1" in fl:
-            lib, blob = libs[vi]
-            ntiles = Bsz // 32
-            dbg = torch.zeros(ntiles * 4, dtype=torch.int64, device=dev)
-            lib.ncf_dev_set_debug_buffer.argtypes = [ctypes.c_void_p]
-            lib.ncf_dev_set_debug_buffer(dbg.data_ptr())
-            for k in range(20):
-                run(lib, blob, k)
-            torch.cuda.synchronize()
-            dd = dbg.view(ntiles, 4).cpu().double() / 100.0   # us
-            t0 = dd[:, 2].min()
-            for nme, col in (("wave start", dd[:, 2]), ("end of layer 1", dd[:, 1]), ("end of layer 2", dd[:, 0]), ("wave end", dd[:, 3])):
-                c = col - t0
-                print(f"    {nme:16s}: median {c.median().item():6.2f} us  min {c.min().item():6.2f}  max {c.max().item():6.2f}")
-            d1 = dd[:, 1] - dd[:, 2]
-            d2 = dd[:, 0] - dd[:, 1]
-            print(f"    per wave: start->L1 end median {d1.median().item():.2f} (min {d1.min().item():.2f} max {d1.max().item():.2f}); "
-                  f"L2 median {d2.median().item():.2f} (min {d2.min().item():.2f} max {d2.max().item():.2f}); tail {(dd[:,3]-dd[:,0]).median().item():.2f}")
         t = sorted(times[vi])
         med = t[len(t) // 2]
         print(f"variant {vi} [{fl or 'default'}]: median {med:.2f} us  min {t[0]:.2f} us  -> {131328*Bsz/med/1e6:.1f} TFLOP/s")

@@ -2,13 +2,12 @@
 (1 M users x 100 k items, E = 64, MLP 128-256-128-1), back to back, plus the build time of the partial table P.
 
     python tools/ab_partial.py [--batches 16384,32768,40000,65536,262144] [--reps 50] [--rounds 8] [--emb 64] [--hidden 256,128]
-                               [--variants lds0=deeprecommendation_amd/libncf_hip_lds0.so,...] [--unchecked abl1,...]
+                               [--variants lds0=deeprecommendation_amd/libncf_hip_lds0.so,...]
 
 Every batch size is checked bit for bit (partial == fused) before it is timed.  --variants adds one column per variant
 library (tools/ab_build.sh, e.g. `ab_build.sh lds0 mlp_partial.hip -DNCF_PART_LDS=0` for the streaming kernel everywhere): its
 ncf_score_fused_partial is timed interleaved with the loaded library's in this process, on the same P, and checked bit for
-bit first unless named in --unchecked (the NCF_PART_ABLATE builds compute wrong scores on purpose).  NCF_HIP_LIBRARY
-replaces the loaded library itself."""
+bit first.  NCF_HIP_LIBRARY replaces the loaded library itself."""
 import argparse
 import json
 import os
@@ -29,7 +28,6 @@ def main():
     ap.add_argument("--emb", type=int, default=64)
     ap.add_argument("--hidden", default="256,128")
     ap.add_argument("--variants", default="")
-    ap.add_argument("--unchecked", default="")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     U, I, E, H = 1_000_000, 100_000, args.emb, tuple(int(h) for h in args.hidden.split(","))
@@ -37,7 +35,6 @@ def main():
     for item in filter(None, args.variants.split(",")):
         name, path = item.split("=", 1)
         vlibs[name] = native.load_library(os.path.abspath(path))
-    unchecked = set(filter(None, args.unchecked.split(",")))
     g = torch.Generator(device=dev).manual_seed(1234)
     tu = torch.randn(U, E, device=dev, generator=g) * 0.05
     ti = torch.randn(I, E, device=dev, generator=g) * 0.05
@@ -82,7 +79,7 @@ def main():
         for k in range(8):
             variants["fused"](k)
             for name in variants:
-                if name == "fused" or name in unchecked:
+                if name == "fused":
                     continue
                 out = out_p if name == "partial" else out_v.fill_(float("nan"))
                 variants[name](k)
@@ -103,12 +100,12 @@ def main():
         spread = {n: (min(t), max(t)) for n, t in times.items()}
         result["batches"][Bsz] = {"fused_us": med["fused"], "partial_us": med["partial"], "speedup": med["fused"] / med["partial"],
                                   "fused_range": spread["fused"], "partial_range": spread["partial"],
-                                  "variants": {n: {"us": med[n], "range": spread[n], "checked": n not in unchecked} for n in vlibs}}
+                                  "variants": {n: {"us": med[n], "range": spread[n]} for n in vlibs}}
         print(f"B={Bsz:7d}: fused {med['fused']:8.2f} us [{spread['fused'][0]:.2f}, {spread['fused'][1]:.2f}]  "
               f"partial {med['partial']:8.2f} us [{spread['partial'][0]:.2f}, {spread['partial'][1]:.2f}]  "
               f"x{med['fused'] / med['partial']:.3f}  (bit-identical)"
               + "".join(f"\n           {n:>8s} {med[n]:8.2f} us [{spread[n][0]:.2f}, {spread[n][1]:.2f}]  partial is x{med[n] / med['partial']:.3f} of it"
-                        + ("  (unchecked)" if n in unchecked else "  (bit-identical)") for n in vlibs), flush=True)
+                        + "  (bit-identical)" for n in vlibs), flush=True)
     native.check_oob(dev)
     print(json.dumps(result))
 
