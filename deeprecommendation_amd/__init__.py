@@ -1,9 +1,10 @@
 """MI355X (gfx950) path of the NCF models.  The recommendation and ranking-evaluation functions and the baselines are re-exported
 here, imported on first use."""
 _RECOMMEND = ("top_k_items", "recommend_for_user", "seen_items", "rated_exclusion", "explain_items", "content_cosine_top_k",
-              "content_cosine_ranks", "attention_statistics", "attention_stat_ratios", "AttentionStats", "diversify_top_k", "item_vectors")
+              "content_cosine_ranks", "attention_statistics", "attention_stat_ratios", "AttentionStats", "diversify_top_k", "item_vectors",
+              "item_knn_top_k", "item_knn_ranks")
 _RANKING_EVAL = ("rank_of_items", "ranking_metrics", "eval_full_ranking", "held_out_items", "intra_list_diversity", "catalogue_coverage")
-_BASELINES = ("KernelMF",)
+_BASELINES = ("KernelMF", "ItemKNN")
 
 
 def __getattr__(name):

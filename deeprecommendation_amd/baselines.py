@@ -5,7 +5,11 @@
 
 fitted by per-sample SGD.  Here the fit runs on the device as stratified SGD (csrc/kmf.hip, THE CONTRACT in include/ncf_abi.h): the
 rating matrix is cut into W x W blocks, the W blocks of a stratum share no user and no item and run side by side, and a fit is a
-fixed function of its inputs, W included.  There is no host path."""
+fixed function of its inputs, W included.  There is no host path.
+
+``ItemKNN`` is the neighbourhood baseline such comparisons are also read against (Sarwar et al. 2001; Surprise KNNBasic, LensKit
+ItemItem): shrunk cosine similarities of the items over the rating matrix, each item's k nearest neighbours, scores from the
+neighbours a user rated (csrc/knn.hip, THE CONTRACT in include/ncf_abi.h).  Its neighbour table is also "more like this item"."""
 import math
 from typing import Optional, Sequence
 
@@ -218,3 +222,190 @@ class KernelMF:
         with torch.no_grad():
             out = self.as_mf()(user_pos.contiguous(), item_pos.contiguous()).view(-1)
         return out.clamp(self.min_rating, self.max_rating) if clip else out
+
+
+# ---------------------------------------------------------------------------------------- ItemKNN
+def _knn_ratings(who, ratings):
+    """A ratings CSR argument: a SparseRatings-like object (rowptr / col / val) or a (rowptr, col, val) tuple, as the kernels take it."""
+    if isinstance(ratings, (tuple, list)) and len(ratings) == 3:
+        rowptr, col, val = ratings
+    elif all(hasattr(ratings, a) for a in ("rowptr", "col", "val")):
+        if getattr(ratings, "pair_row", None) is not None:
+            raise ValueError(f"{who}: the ratings share rows through pair_row; pass the CSR with one row per user")
+        rowptr, col, val = ratings.rowptr, ratings.col, ratings.val
+    else:
+        raise ValueError(f"{who}: ratings must be a SparseRatings or a (rowptr, col, val) tuple")
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val")):
+        if not torch.is_tensor(t) or t.dim() != 1:
+            raise ValueError(f"{who}: {what} must be a 1-D tensor")
+    if rowptr.dtype not in (torch.int64, torch.int32) or col.dtype not in (torch.int64, torch.int32) or val.dtype != torch.float32:
+        raise ValueError(f"{who}: rowptr / col must be integer tensors and val float32")
+    if rowptr.numel() < 1 or col.numel() != val.numel():
+        raise ValueError(f"{who}: rowptr is empty or col and val differ in length")
+    return rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), val.contiguous()
+
+
+class ItemKNN:
+    """Item-item k-nearest-neighbours over the rating matrix (csrc/knn.hip, THE CONTRACT in include/ncf_abi.h): shrunk cosine
+    similarities ``s_ij = cos(i, j) * co / (co + shrink)`` of items co-rated by at least ``min_support`` users, the ``k`` largest
+    positive ones kept per item, and scores ``sum s_ij * v_uj`` over the neighbours a user rated, divided by ``sum s_ij`` with
+    ``weighted_average`` (``fill`` where no neighbour was rated).  ``fit`` / ``fit_dataset`` / ``fit_csr``; then ``neighbours``,
+    ``similar_items``, ``scores``, ``predict``; ``recommend.item_knn_top_k`` / ``item_knn_ranks`` rank with it.  A fit is a fixed
+    function of its inputs, bit for bit.  There is no host path."""
+
+    def __init__(self, k=50, shrink=0.0, min_support=1, weighted_average=True, fill=0.0):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= native.KNN_MAX_N:
+            raise ValueError(f"ItemKNN: k = {k!r} (an integer in 1 .. {native.KNN_MAX_N})")
+        if isinstance(min_support, bool) or not isinstance(min_support, (int, np.integer)) or min_support < 1:
+            raise ValueError(f"ItemKNN: min_support = {min_support!r} (an integer >= 1)")
+        for name, v in (("shrink", shrink), ("fill", fill)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"ItemKNN: {name} = {v!r} is not a finite number")
+        if shrink < 0:
+            raise ValueError(f"ItemKNN: shrink = {shrink} < 0")
+        if not isinstance(weighted_average, (bool, np.bool_)):
+            raise ValueError(f"ItemKNN: weighted_average = {weighted_average!r} is not a bool")
+        self.k, self.shrink, self.min_support = int(k), float(shrink), int(min_support)
+        self.weighted_average, self.fill = bool(weighted_average), float(fill)
+        self.nb_pos_ = self.nb_sim_ = self.nb_cnt_ = None      # (I, k) int32 / (I, k) fp32 / (I,) int32
+        self.item_sq_ = None                                   # (I,) fp32 squared norms
+        self.num_items_ = None
+
+    # ------------------------------------------------------------------ fit
+    @staticmethod
+    def build_transpose(rowptr, col, val, num_items):
+        """``(colptr (I + 1) int64, row int32, tval fp32)``: the CSR by item, torch ops on whatever device the CSR is on.  A stable
+        sort of the entries on their column keeps the users of a column in ascending order."""
+        counts = rowptr[1:] - rowptr[:-1]
+        users = torch.repeat_interleave(torch.arange(counts.numel(), device=col.device), counts)
+        c64 = col.to(torch.int64)
+        order = torch.argsort(c64, stable=True)
+        colptr = torch.zeros(num_items + 1, dtype=torch.int64, device=col.device)
+        inside = c64[(c64 >= 0) & (c64 < num_items)]           # an id outside the items is the kernels' to flag, not bincount's to index
+        colptr[1:] = torch.cumsum(torch.bincount(inside, minlength=num_items), 0)
+        keep = order[(c64[order] >= 0) & (c64[order] < num_items)]
+        return colptr, users[keep].to(torch.int32), val[keep].contiguous()
+
+    def fit_csr(self, rowptr, col, val, num_items, block_bytes: int = 256 << 20, col_tile: int = 0):
+        """Fits on a user CSR on the GPU: ``rowptr`` (U + 1) int64, ``col`` int32 item positions strictly ascending inside a row,
+        ``val`` fp32 (SparseRatings' arrays as they are).  The similarity rows are computed ``block_bytes`` at a time and the table
+        selected from each block by native.topk_rows; the table does not depend on the blocking.  Synchronises once, in check()."""
+        rowptr, col, val = _knn_ratings("ItemKNN.fit_csr", (rowptr, col, val))
+        I = int(num_items)
+        if I < 1 or rowptr.numel() < 2 or col.numel() == 0:
+            raise ValueError(f"ItemKNN: nothing to fit ({col.numel()} ratings, {rowptr.numel() - 1} users, {I} items)")
+        dev = rowptr.device
+        if dev.type != "cuda" or col.device != dev or val.device != dev:
+            raise RuntimeError(f"ItemKNN.fit_csr runs on the GPU: the CSR must live on one GPU (got {dev}, {col.device}, {val.device}); "
+                               "there is no CPU path")
+        colptr, row, tval = self.build_transpose(rowptr, col, val, I)
+        sq = native.knn_item_sq(colptr, tval)
+        N = self.k
+        pos = torch.empty((I, N), dtype=torch.int32, device=dev)
+        sim = torch.empty((I, N), dtype=torch.float32, device=dev)
+        cnt = torch.empty(I, dtype=torch.int32, device=dev)
+        rows = max(1, min(native.KNN_MAX_ROWS, int(block_bytes) // (4 * I)))
+        for i0 in range(0, I, rows):
+            i1 = min(I, i0 + rows)
+            block = native.knn_sim_rows(rowptr, col, val, colptr, row, tval, sq, (i0, i1), self.min_support, self.shrink, col_tile)
+            s, idx, _ = native.topk_rows(block, N)
+            live = (idx >= 0) & (s > 0)                          # a selected zero is no neighbour; the live slots are a prefix
+            pos[i0:i1] = torch.where(live, idx, torch.full_like(idx, -1))
+            sim[i0:i1] = torch.where(live, s, torch.zeros_like(s))
+            cnt[i0:i1] = live.sum(1).to(torch.int32)
+        self.nb_pos_, self.nb_sim_, self.nb_cnt_, self.item_sq_, self.num_items_ = pos, sim, cnt, sq, I
+        self.check()
+        return self
+
+    def fit(self, user_pos, item_pos, rating, num_users, num_items, **fit_args):
+        """Fits on int64 positions and fp32 ratings that live on the GPU (KernelMF.fit's arguments): the CSR is built on the device by
+        a stable sort on (user, item).  A (user, item) pair given twice raises in check()."""
+        n = user_pos.numel() if torch.is_tensor(user_pos) else None
+        for t, what in ((user_pos, "user_pos"), (item_pos, "item_pos")):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != n:
+                raise ValueError(f"ItemKNN: {what} must be a 1-D int64 tensor of {n} positions")
+        if not torch.is_tensor(rating) or rating.dtype != torch.float32 or rating.dim() != 1 or rating.numel() != n:
+            raise ValueError(f"ItemKNN: rating must be a 1-D float32 tensor of {n} entries")
+        num_users, num_items = int(num_users), int(num_items)
+        if n == 0 or num_users < 1 or num_items < 1:
+            raise ValueError(f"ItemKNN: nothing to fit ({n} ratings, {num_users} users, {num_items} items)")
+        dev = user_pos.device
+        if dev.type != "cuda" or item_pos.device != dev or rating.device != dev:
+            raise RuntimeError(f"ItemKNN.fit runs on the GPU: the samples must live on one GPU (got {dev}, {item_pos.device}, {rating.device}); "
+                               "there is no CPU path")
+        rowptr, col, val = self.build_csr(user_pos, item_pos, rating, num_users, num_items)
+        return self.fit_csr(rowptr, col, val, num_items, **fit_args)
+
+    @staticmethod
+    def build_csr(user_pos, item_pos, rating, num_users, num_items):
+        """``(rowptr (U + 1) int64, col int32, val fp32)`` of samples in any order: torch ops on the samples' device."""
+        order = torch.argsort(user_pos * num_items + item_pos, stable=True)
+        rowptr = torch.zeros(num_users + 1, dtype=torch.int64, device=user_pos.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(user_pos, minlength=num_users), 0)
+        return rowptr, item_pos[order].to(torch.int32), rating[order].contiguous()
+
+    def fit_dataset(self, dataset, device="cuda", **fit_args):
+        """fit on the positions and ratings of a FixedPointwiseDataset over an index provider (its ``resident_inputs()``)."""
+        dev = torch.device(device)
+        res = dataset.resident_inputs(dev)
+        if res is None:
+            raise ValueError("ItemKNN.fit_dataset: the dataset's provider hands out dense rows, not positions")
+        u, i = (t.to(dev) for t in res.tensors)
+        if res.on_chunk is not None:
+            u, i = res.on_chunk(u, i)
+        cp = dataset.content_provider
+        return self.fit(u.contiguous(), i.contiguous(), res.targets.to(dev), cp.get_num_users(), cp.get_num_items(), **fit_args)
+
+    def check(self):
+        """Synchronises.  Raises ValueError when a fit walked a row whose columns do not strictly ascend, and IndexError when a kernel
+        of this device met an id outside its range; each raises once and is then cleared."""
+        self._fitted()
+        dev = self.nb_pos_.device
+        native.check_knn(dev)
+        native.check_oob(dev)
+
+    def _fitted(self):
+        if self.nb_pos_ is None:
+            raise RuntimeError("ItemKNN: not fitted")
+
+    # ------------------------------------------------------------------ the table
+    @property
+    def neighbours(self):
+        """``(nb_sim (I, k) fp32, nb_pos (I, k) int64, nb_cnt (I,) int32)``: each item's neighbours by falling similarity, ties to the
+        lower position; past the count the similarity is 0 and the position -1."""
+        self._fitted()
+        return self.nb_sim_, self.nb_pos_.to(torch.int64), self.nb_cnt_
+
+    def similar_items(self, item_pos, k: Optional[int] = None):
+        """"More like this": ``(scores (n, k) fp32, item_positions (n, k) int64, counts (n,) int32)`` of the listed items' nearest
+        neighbours, in ``top_k_items``' form (past the count: score -inf, position -1).  ``k`` defaults to the table's width."""
+        self._fitted()
+        k = self.k if k is None else k
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= self.k:
+            raise ValueError(f"ItemKNN.similar_items: k = {k!r} (an integer in 1 .. {self.k})")
+        if not torch.is_tensor(item_pos) or item_pos.dtype != torch.int64 or item_pos.dim() != 1:
+            raise ValueError("ItemKNN.similar_items: item_pos must be a 1-D int64 tensor of positions")
+        pos = self.nb_pos_[item_pos, :k].to(torch.int64)
+        sim = self.nb_sim_[item_pos, :k]
+        return torch.where(pos >= 0, sim, torch.full_like(sim, float("-inf"))), pos, self.nb_cnt_[item_pos].clamp_max(k)
+
+    # ------------------------------------------------------------------ scoring
+    def scores(self, ratings, user_rows, item_range=None, stage_cap: int = 0):
+        """(B, i1 - i0) fp32 scores of the rows ``user_rows`` (int64) of ``ratings`` — a SparseRatings or a (rowptr, col, val) tuple
+        over the fitted items, not necessarily the fitted ratings, so new users work — against the items ``item_range`` = (i0, i1)
+        (default: all)."""
+        self._fitted()
+        rowptr, col, val = _knn_ratings("ItemKNN.scores", ratings)
+        return native.knn_scores(rowptr, col, val, user_rows.contiguous() if torch.is_tensor(user_rows) else user_rows, self.nb_pos_,
+                                 self.nb_sim_, self.nb_cnt_, item_range, self.weighted_average, self.fill, stage_cap)
+
+    def predict(self, ratings, user_rows, item_pos, clip=None):
+        """(n,) fp32 scores of the pairs (row ``user_rows[k]`` of ``ratings``, item ``item_pos[k]``), int64 both: ``scores``' values
+        bit for bit, clamped to ``clip`` = (lo, hi) when given."""
+        self._fitted()
+        rowptr, col, val = _knn_ratings("ItemKNN.predict", ratings)
+        if clip is not None and (len(clip) != 2 or not clip[0] < clip[1]):
+            raise ValueError(f"ItemKNN.predict: clip = {clip!r} (None or (lo, hi) with lo < hi)")
+        out = native.knn_predict(rowptr, col, val, user_rows, item_pos, self.nb_pos_, self.nb_sim_, self.nb_cnt_, self.weighted_average,
+                                 self.fill)
+        return out if clip is None else out.clamp(float(clip[0]), float(clip[1]))

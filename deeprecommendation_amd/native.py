@@ -7,6 +7,8 @@ There is NO fallback: if the shared library is missing or a tensor is not on a G
 from __future__ import annotations
 
 import ctypes
+import math
+import numbers
 import os
 from typing import Optional, Sequence
 
@@ -146,6 +148,13 @@ SIGNATURES = {
                                ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_p, _c_p, _c_p]),
     "ncf_kmf_fold_users": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_p, _c_p, _c_p]),
+    "ncf_knn_item_sq": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "ncf_knn_sim_rows": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int,
+                                  ctypes.c_float, _c_int, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    "ncf_knn_scores": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_i64, _c_i64, _c_int,
+                                ctypes.c_float, _c_int, _c_p, _c_i64, _c_p, _c_p]),
+    "ncf_knn_predict": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int,
+                                 ctypes.c_float, _c_p, _c_p, _c_p]),
     "ncf_mmr_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "ncf_mmr_rerank": (_c_int, [_c_p, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, ctypes.c_float, _c_int, _c_p, _c_p,
                                 _c_p, _c_p, _c_p]),
@@ -1571,6 +1580,190 @@ def kmf_fold_users(PU: torch.Tensor, QI: torch.Tensor, F: int, users: torch.Tens
         _check(lib.ncf_kmf_fold_users(_ptr(PU), PU.stride(0), U, _ptr(QI), QI.stride(0), I, F, _ptr(users), nu, _ptr(rowptr), _ptr(col),
                                       _ptr(rating), nnz, float(mu), float(lr), float(reg), n_epochs, _ptr(sse), _ptr(flag), _stream(PU)))
     return sse
+
+
+KNN_MAX_N, KNN_MAX_TILE, KNN_MAX_STAGE, KNN_MAX_ROWS = 256, 8192, 8192, 65535       # csrc/knn.hip
+_knn_flags = {}
+
+
+def knn_flag(device) -> torch.Tensor:
+    """The sticky int32 word of ncf_knn_sim_rows on ``device``: set by a row whose columns do not strictly ascend."""
+    f = _knn_flags.get(device)
+    if f is None:
+        f = torch.zeros(1, dtype=torch.int32, device=device)
+        _knn_flags[device] = f
+    return f
+
+
+def check_knn(device, flag: Optional[torch.Tensor] = None):
+    """Synchronising check of the ItemKNN flag word: raises, and clears it, when ncf_knn_sim_rows walked a row of the user CSR whose
+    columns do not strictly ascend (a duplicate rating or an unsorted row; the similarities of such a fit are unspecified)."""
+    f = knn_flag(device) if flag is None else flag
+    if int(f.item()):
+        f.zero_()
+        raise ValueError("ItemKNN: a row of the ratings CSR does not hold strictly ascending columns")
+
+
+def _knn_csr(who, ptr, idx, val, names, rows=None):
+    """Checks one CSR (pointers int64, ids int32, values fp32, contiguous 1-D); returns (rows, nnz)."""
+    _kmf_vec(who, ptr, names[0], torch.int64, None if rows is None else rows + 1)
+    if ptr.numel() < 1:
+        raise ValueError(f"{who}: {names[0]} is empty")
+    _kmf_vec(who, idx, names[1], torch.int32)
+    _kmf_vec(who, val, names[2], torch.float32, idx.numel())
+    return ptr.numel() - 1, idx.numel()
+
+
+def _knn_int(who, v, what, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+        raise ValueError(f"{who}: {what} = {v!r} (an integer in {lo} .. {hi})")
+    return int(v)
+
+
+def _knn_float(who, v, what, lo=None):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (lo is not None and v < lo):
+        raise ValueError(f"{who}: {what} = {v!r} is not a finite number" + ("" if lo is None else f" >= {lo}"))
+    return float(v)
+
+
+def _knn_range(who, item_range, I):
+    i0, i1 = (0, I) if item_range is None else (int(item_range[0]), int(item_range[1]))
+    if not 0 <= i0 <= i1 <= I:
+        raise ValueError(f"{who}: items [{i0}, {i1}) outside [0, {I})")
+    return i0, i1
+
+
+def _knn_table(who, nb_pos, nb_sim, nb_cnt):
+    if not torch.is_tensor(nb_pos) or nb_pos.dtype != torch.int32 or nb_pos.dim() != 2 or not nb_pos.is_contiguous():
+        raise ValueError(f"{who}: nb_pos must be a contiguous (I, N) int32 tensor")
+    I, N = nb_pos.shape
+    if not torch.is_tensor(nb_sim) or nb_sim.dtype != torch.float32 or tuple(nb_sim.shape) != (I, N) or not nb_sim.is_contiguous():
+        raise ValueError(f"{who}: nb_sim must be a contiguous ({I}, {N}) float32 tensor")
+    _kmf_vec(who, nb_cnt, "nb_cnt", torch.int32, I)
+    if not 1 <= N <= KNN_MAX_N:
+        raise ValueError(f"{who}: N = {N} neighbours per item is outside 1 .. {KNN_MAX_N}")
+    return I, N
+
+
+def knn_item_sq(colptr: torch.Tensor, tval: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(I,) fp32 squared norms of the item columns of a transposed ratings CSR (ncf_knn_item_sq, THE CONTRACT in include/ncf_abi.h):
+    ``colptr`` (I + 1,) int64, ``tval`` fp32.  Checked before the device is; one launch on the current stream."""
+    who = "knn_item_sq"
+    _kmf_vec(who, colptr, "colptr", torch.int64)
+    if colptr.numel() < 1:
+        raise ValueError(f"{who}: colptr is empty")
+    _kmf_vec(who, tval, "tval", torch.float32)
+    I = colptr.numel() - 1
+    _kmf_out(who, out, "out", torch.float32, I)
+    for t, what in ((colptr, "colptr"), (tval, "tval"), (out, "out")):
+        if t is not None:
+            _dev(t, what)
+    lib = load_library()
+    if out is None:
+        out = torch.empty(I, dtype=torch.float32, device=colptr.device)
+    _check(lib.ncf_knn_item_sq(_ptr(colptr), _ptr(tval), tval.numel(), I, _ptr(out), _ptr(_oob_flag(colptr.device)), _stream(colptr)))
+    return out
+
+
+def knn_sim_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, colptr: torch.Tensor, row: torch.Tensor, tval: torch.Tensor,
+                 sq: torch.Tensor, item_range=None, min_support: int = 1, shrink: float = 0.0, col_tile: int = 0,
+                 out: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The similarity rows of the items ``item_range`` = (i0, i1) (default: all) as a dense (i1 - i0, I) fp32 tensor
+    (ncf_knn_sim_rows, THE CONTRACT in include/ncf_abi.h).  ``rowptr`` / ``col`` / ``val``: the user CSR (int64 / int32 strictly
+    ascending in a row / fp32); ``colptr`` / ``row`` / ``tval``: its transpose; ``sq`` (I,) fp32 from knn_item_sq.  ``col_tile``: 0 =
+    choose, else a multiple of 64.  An id outside its range raises at the next check_oob(), a non-ascending row at check_knn()
+    (``flag``: another word than the device's).  Checked before the device is; one launch on the current stream."""
+    who = "knn_sim_rows"
+    U, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    I, nnzT = _knn_csr(who, colptr, row, tval, ("colptr", "row", "tval"))
+    _kmf_vec(who, sq, "sq", torch.float32, I)
+    i0, i1 = _knn_range(who, item_range, I)
+    if i1 - i0 > KNN_MAX_ROWS:
+        raise ValueError(f"{who}: {i1 - i0} items in one call (at most {KNN_MAX_ROWS})")
+    min_support = _knn_int(who, min_support, "min_support", 1, 2 ** 31 - 1)
+    shrink = _knn_float(who, shrink, "shrink", 0.0)
+    col_tile = _knn_int(who, col_tile, "col_tile", 0, KNN_MAX_TILE)
+    if col_tile % 64:
+        raise ValueError(f"{who}: col_tile = {col_tile} is not a multiple of 64")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (i1 - i0, I)
+                            or (I > 1 and out.stride(1) != 1)):
+        raise ValueError(f"{who}: out must be a ({i1 - i0}, {I}) float32 tensor with unit inner stride")
+    _kmf_out(who, flag, "flag", torch.int32, 1)
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (colptr, "colptr"), (row, "row"), (tval, "tval"), (sq, "sq"), (out, "out"),
+                    (flag, "flag")):
+        if t is not None:
+            _dev(t, what)
+    lib = load_library()
+    dev = rowptr.device
+    if out is None:
+        out = torch.empty((i1 - i0, I), dtype=torch.float32, device=dev)
+    if flag is None:
+        flag = knn_flag(dev)
+    if i1 > i0 and I:
+        _check(lib.ncf_knn_sim_rows(_ptr(rowptr), _ptr(col), _ptr(val), nnz, U, _ptr(colptr), _ptr(row), _ptr(tval), nnzT, I, _ptr(sq), i0, i1,
+                                    min_support, shrink, col_tile, _ptr(out), max(out.stride(0), I), _ptr(_oob_flag(dev)), _ptr(flag),
+                                    _stream(rowptr)))
+    return out
+
+
+def knn_scores(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, users: torch.Tensor, nb_pos: torch.Tensor, nb_sim: torch.Tensor,
+               nb_cnt: torch.Tensor, item_range=None, weighted_average: bool = True, fill: float = 0.0, stage_cap: int = 0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, i1 - i0) fp32 ItemKNN scores of the rows ``users`` (int64) of a ratings CSR against the items ``item_range`` (default: all)
+    of a neighbour table ``nb_pos`` (I, N) int32 / ``nb_sim`` (I, N) fp32 / ``nb_cnt`` (I,) int32 (ncf_knn_scores, THE CONTRACT in
+    include/ncf_abi.h).  The CSR need not be the fitted one.  ``stage_cap``: rows of at most that many entries are staged in LDS
+    (0 = the default); the bits do not depend on it.  A row outside the CSR scores as an empty one and raises at the next
+    check_oob().  Checked before the device is; one launch on the current stream."""
+    who = "knn_scores"
+    R, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    _kmf_vec(who, users, "users", torch.int64)
+    B = users.numel()
+    if B > KNN_MAX_ROWS:
+        raise ValueError(f"{who}: {B} users in one call (at most {KNN_MAX_ROWS})")
+    I, N = _knn_table(who, nb_pos, nb_sim, nb_cnt)
+    i0, i1 = _knn_range(who, item_range, I)
+    fill = _knn_float(who, fill, "fill")
+    stage_cap = _knn_int(who, stage_cap, "stage_cap", 0, KNN_MAX_STAGE)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (B, i1 - i0)
+                            or (i1 - i0 > 1 and out.stride(1) != 1)):
+        raise ValueError(f"{who}: out must be a ({B}, {i1 - i0}) float32 tensor with unit inner stride")
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (nb_pos, "nb_pos"), (nb_sim, "nb_sim"),
+                    (nb_cnt, "nb_cnt"), (out, "out")):
+        if t is not None:
+            _dev(t, what)
+    lib = load_library()
+    dev = rowptr.device
+    if out is None:
+        out = torch.empty((B, i1 - i0), dtype=torch.float32, device=dev)
+    if B and i1 > i0:
+        _check(lib.ncf_knn_scores(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(users), B, _ptr(nb_pos), _ptr(nb_sim), _ptr(nb_cnt), I, N,
+                                  i0, i1, 1 if weighted_average else 0, fill, stage_cap, _ptr(out), max(out.stride(0), i1 - i0),
+                                  _ptr(_oob_flag(dev)), _stream(rowptr)))
+    return out
+
+
+def knn_predict(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, users: torch.Tensor, items: torch.Tensor, nb_pos: torch.Tensor,
+                nb_sim: torch.Tensor, nb_cnt: torch.Tensor, weighted_average: bool = True, fill: float = 0.0) -> torch.Tensor:
+    """(n,) fp32 ItemKNN scores of the pairs (``users[k]`` row of the CSR, ``items[k]``), both int64 (ncf_knn_predict): knn_scores'
+    value of that user and item, bit for bit.  A row or an item outside its range scores as an empty row and raises at the next
+    check_oob().  Checked before the device is; one launch on the current stream."""
+    who = "knn_predict"
+    R, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    _kmf_vec(who, users, "users", torch.int64)
+    n = users.numel()
+    _kmf_vec(who, items, "items", torch.int64, n)
+    I, N = _knn_table(who, nb_pos, nb_sim, nb_cnt)
+    fill = _knn_float(who, fill, "fill")
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (items, "items"), (nb_pos, "nb_pos"),
+                    (nb_sim, "nb_sim"), (nb_cnt, "nb_cnt")):
+        _dev(t, what)
+    lib = load_library()
+    dev = rowptr.device
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    if n:
+        _check(lib.ncf_knn_predict(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(users), _ptr(items), n, _ptr(nb_pos), _ptr(nb_sim),
+                                   _ptr(nb_cnt), I, N, 1 if weighted_average else 0, fill, _ptr(out), _ptr(_oob_flag(dev)), _stream(rowptr)))
+    return out
 
 
 MMR_MAX_N, MMR_MAX_D, MMR_MAX_K = 256, 256, 128       # csrc/mmr.hip

@@ -7,6 +7,8 @@
                        A BasicNCF with content attached (``set_content``) ranks the rows of its item table like a one-hot model.
 ``content_cosine_top_k`` / ``content_cosine_ranks``
                        the reference's content-based baseline: cosine of a user's fixed profile and an item's feature row.
+``item_knn_top_k`` / ``item_knn_ranks``
+                       the neighbourhood baseline: a fitted ``baselines.ItemKNN`` scored over the catalogue (ncf_knn_scores) and ranked.
 ``diversify_top_k``    greedy MMR re-ranking of the pools those two return (native.mmr_rerank, one launch): relevance traded against the
                        similarity to what is already in the list.  ``item_vectors`` gives a model's own item space for it.
 ``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
@@ -365,6 +367,64 @@ def content_cosine_ranks(user_profiles: torch.Tensor, item_features: torch.Tenso
     rank = torch.empty(tcol.numel(), dtype=torch.int32, device=tcol.device)
     ranked = [native.rank_rows(scores, (trow[b0:b1 + 1], tcol), None if seen is None else (seen[0][b0:b1 + 1], seen[1]), rank=rank)[1]
               for b0, b1, scores in _cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes)]
+    if not ranked:
+        return rank, torch.empty(0, dtype=torch.int32, device=tcol.device)
+    return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])
+
+
+# ---------------------------------------------------------------------------------------- neighbourhood baseline
+def _knn_blocks(model, ratings, user_ids, item_ids, block_bytes):
+    """Yields ``(b0, b1, scores (b1 - b0, I))`` of the listed rows of ``ratings`` under a fitted ``baselines.ItemKNN``: one
+    ncf_knn_scores launch per block of users over the whole catalogue, the ranked list's columns gathered from it."""
+    for t, what in ((user_ids, "user_ids"), (item_ids, "item_ids")):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1):
+            raise ValueError(f"{what} must be a 1-D int64 tensor of positions")
+    model._fitted()
+    require_gpu(user_ids, item_ids)
+    rows_per_block = max(1, min(native.KNN_MAX_ROWS, int(block_bytes) // max(1, model.num_items_ * 4)))
+    users = user_ids.contiguous()
+    for b0 in range(0, users.numel(), rows_per_block):
+        b1 = min(users.numel(), b0 + rows_per_block)
+        scores = model.scores(ratings, users[b0:b1])
+        yield b0, b1, scores if item_ids is None else scores.index_select(1, item_ids)
+
+
+def item_knn_top_k(model, ratings, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
+                   exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES):
+    """The neighbourhood baseline's recommendations: the ``k`` items with the largest ItemKNN score for each listed user.  model: a
+    fitted ``baselines.ItemKNN``; ratings: the CSR the users' rows are read from (a SparseRatings or (rowptr, col, val); not
+    necessarily the fitted one); user_ids: (B,) int64 rows of it; item_ids, exclude, block_bytes and the returned ``(scores (B, k),
+    item_positions (B, k) int64, counts (B,) int32)`` as in ``top_k_items`` (``rated_exclusion(ratings, user_ids)`` leaves out what
+    a user rated)."""
+    model._fitted()
+    if not 1 <= int(k) <= native.TOPK_MAX_K:
+        raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
+    seen = None if exclude is None else _csr(exclude, user_ids.numel(), "exclude")
+    outs = [native.topk_rows(scores, int(k), None if seen is None else (seen[0][b0:b1 + 1], seen[1]))
+            for b0, b1, scores in _knn_blocks(model, ratings, user_ids, item_ids, block_bytes)]
+    if not outs:
+        dev = user_ids.device
+        return (torch.empty((0, int(k)), dtype=torch.float32, device=dev), torch.empty((0, int(k)), dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev))
+    s, idx, cnt = (torch.cat([o[j] for o in outs]) if len(outs) != 1 else outs[0][j] for j in range(3))
+    pos = idx.to(torch.int64)
+    if item_ids is not None:
+        pos = torch.where(pos >= 0, item_ids[pos.clamp_min(0)], pos)
+    return s, pos, cnt
+
+
+def item_knn_ranks(model, ratings, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, torch.Tensor],
+                   item_ids: Optional[torch.Tensor] = None, exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                   block_bytes: int = BLOCK_BYTES):
+    """The ranks twin of ``item_knn_top_k``: ``(rank (n_targets,) int32, ranked (B,) int32)`` of each listed user's held-out items
+    under the ItemKNN scores, with the meaning ``rank_of_items`` gives them (``ranking_metrics`` takes them as they are)."""
+    model._fitted()
+    B = user_ids.numel()
+    trow, tcol = _csr(targets, B, "targets")
+    seen = None if exclude is None else _csr(exclude, B, "exclude")
+    rank = torch.empty(tcol.numel(), dtype=torch.int32, device=tcol.device)
+    ranked = [native.rank_rows(scores, (trow[b0:b1 + 1], tcol), None if seen is None else (seen[0][b0:b1 + 1], seen[1]), rank=rank)[1]
+              for b0, b1, scores in _knn_blocks(model, ratings, user_ids, item_ids, block_bytes)]
     if not ranked:
         return rank, torch.empty(0, dtype=torch.int32, device=tcol.device)
     return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])

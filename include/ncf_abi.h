@@ -850,6 +850,67 @@ int ncf_kmf_fold_users(float* dev_PU, int64_t ldu, int64_t U, const float* dev_Q
                        int32_t* dev_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * ItemKNN (csrc/knn.hip) — neighbourhood collaborative filtering, the third baseline NCF models are read against (Sarwar et al.
+ * 2001; Surprise KNNBasic, LensKit ItemItem): shrunk cosine similarities of the items over the rating matrix, each item's N nearest
+ * neighbours, and scores from the neighbours a user rated.  Replaces: nothing in the reference; a torch composition needs the dense
+ * (U, I) matrix and its X^T X, whose summation order is not fixed.
+ * Ratings: a user CSR dev_rowptr (U + 1, int64), dev_col (int32 item positions, STRICTLY ASCENDING inside a row) and dev_val (fp32,
+ * finite, centred however the caller likes), nnz entries each; and its transpose dev_colptr (I + 1, int64), dev_row (int32 user
+ * positions, ascending inside a column) and dev_tval (fp32), nnzT entries each, built by a stable sort of the entries on col.
+ * THE CONTRACT, all in fp32, every product, sum, quotient and square root rounded on its own (no FMA; division and sqrtf are the
+ * correctly rounded IEEE operations, hipcc's default for fp32 — csrc/knn.hip is built without any fast-math flag):
+ *   squared norm of item i (ncf_knn_item_sq), over the entries e = 0, 1, ... of column i in stored order:
+ *       part_l = +0.0f;  for e = l, l + 64, l + 128, ... in that order:  part_l = part_l + tval[e] * tval[e]
+ *       sq[i]  = balanced tree over lanes 0..63 in lane order: adjacent pairs first, then pairs of pairs, ... (6 levels)
+ *   Gram row of item i:  dot[j] = +0.0f and co[j] = 0 for every j; then
+ *       for the users u of column i in ascending order, for every entry (j, v_uj) of row u:
+ *           dot[j] = dot[j] + v_ui * v_uj;   co[j] = co[j] + 1
+ *     (a user holds an item at most once, so the order inside a user is immaterial; the order across users is fixed)
+ *   similarity:  n = sqrtf(sq[i]) * sqrtf(sq[j])
+ *       s_ij = 0.0f  if j == i, or co[j] < min_support, or n == 0
+ *       s_ij = (dot[j] / n) * ((float)co[j] / ((float)co[j] + shrink))  otherwise, and 0.0f unless that is > 0
+ *   neighbour table: the N largest s_ij > 0 of item i, ties to the lower j (ncf_topk_rows' order): nb_pos (I, N) int32, -1 past the
+ *       count; nb_sim (I, N) fp32, 0 past the count; nb_cnt (I,) int32
+ *   score of (user row u, item i):  num = den = +0.0f; for t = 0 .. nb_cnt[i] - 1 in slot order, with j = nb_pos[i][t], s = nb_sim[i][t]:
+ *           if row u holds j with value v:  num = num + s * v;   den = den + s
+ *       weighted_average = 1:  num / den if den > 0, else fill;      weighted_average = 0:  num
+ *   No float atomics anywhere and one fixed order of every sum: the same inputs give the same bits.
+ * ncf_knn_item_sq: one wave per item.  ncf_knn_sim_rows writes the similarity rows of the items [i0, i1) into dev_out (i1 - i0, I)
+ * fp32, rows of ldo floats; ncf_topk_rows over those rows selects the table.  One workgroup of one wave per (item, tile of col_tile
+ * columns), the tile's dot / co in LDS, a workgroup barrier between two users of the walk; col_tile = 0 chooses (at most 2048),
+ * otherwise a multiple of 64 up to 8192.  Every id is checked before it is dereferenced: a user or an item outside [0, U) / [0, I)
+ * or a pointer pair that decreases or leaves its array sets the sticky *dev_oob_flag (when non-NULL) and that entry (row, column) adds
+ * nothing; a row of the user CSR whose columns do not strictly ascend sets the sticky *dev_order_flag (when non-NULL; the result of
+ * such a row is unspecified, no address leaves the arrays).
+ * ncf_knn_scores: the listed rows dev_users (B, int64) of ANY ratings CSR of R rows over the same items (not only the fitted one)
+ * against the items [i0, i1), into dev_out (B, i1 - i0) fp32 rows of ldo floats.  One workgroup per (user, 256 items), one lane per
+ * item, each neighbour looked up in the user's row by binary search; a row of at most stage_cap entries is staged in LDS first
+ * (stage_cap = 0: 2048; at most 8192), a longer one is searched in global memory, with the same bits.  A user row outside [0, R)
+ * scores as an empty row and sets *dev_oob_flag, as does a table slot outside [0, I) other than -1 (skipped).
+ * ncf_knn_predict: the same device function for n pairs (dev_users[k], dev_items[k]) (int64), one lane per pair, into dev_out (n,):
+ * predict(u, i) == scores[u, i] bit for bit.  A pair with a row or an item outside its range scores as an empty row and sets the flag.
+ * Refusals, before any launch, with the entry's name in ncf_last_error(): NCF_EINVAL for a negative size, an item range outside
+ * [0, I), N outside 1 .. 256, min_support < 1, a shrink or fill that is not finite, shrink < 0, weighted_average not 0 or 1, a
+ * col_tile that is not a multiple of 64 (or above 8192), a stage_cap outside 0 .. 8192, ldo below the row's width, and a NULL
+ * array that the sizes say is read or written; NCF_EUNSUPPORTED for more than 65535 items (sim_rows) or users (scores) in one call.
+ * A call with nothing to do (no item, no user, no pair) returns NCF_OK without a launch.
+ * ------------------------------------------------------------------------------------------------ */
+int ncf_knn_item_sq(const int64_t* dev_colptr, const float* dev_tval, int64_t nnzT, int64_t I, float* dev_sq, int32_t* dev_oob_flag,
+                    ncf_stream_t stream);
+int ncf_knn_sim_rows(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t nnz, int64_t U,
+                     const int64_t* dev_colptr, const int32_t* dev_row, const float* dev_tval, int64_t nnzT, int64_t I,
+                     const float* dev_sq, int64_t i0, int64_t i1, int min_support, float shrink, int col_tile, float* dev_out,
+                     int64_t ldo, int32_t* dev_oob_flag, int32_t* dev_order_flag, ncf_stream_t stream);
+int ncf_knn_scores(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t nnz, int64_t R,
+                   const int64_t* dev_users, int64_t B, const int32_t* dev_nb_pos, const float* dev_nb_sim, const int32_t* dev_nb_cnt,
+                   int64_t I, int N, int64_t i0, int64_t i1, int weighted_average, float fill, int stage_cap, float* dev_out,
+                   int64_t ldo, int32_t* dev_oob_flag, ncf_stream_t stream);
+int ncf_knn_predict(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t nnz, int64_t R,
+                    const int64_t* dev_users, const int64_t* dev_items, int64_t n, const int32_t* dev_nb_pos, const float* dev_nb_sim,
+                    const int32_t* dev_nb_cnt, int64_t I, int N, int weighted_average, float fill, float* dev_out,
+                    int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Diversified top-K (csrc/mmr.hip) — greedy Maximal Marginal Relevance (MMR) re-ranking of one candidate pool per user, the pools
  * being what ncf_topk_rows / ncf_dot_topk / ncf_mlp_topk return.  Replaces: nothing in the reference, which stops at the relevance
  * list; a torch composition needs a (B, N, N) Gram tensor and K rounds of masked arg-max launches.

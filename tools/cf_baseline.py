@@ -2,12 +2,17 @@
 
     python tools/cf_baseline.py TRAIN VAL TEST [--factors 64 128 256] [--lrs 0.001 0.0005] [--regs 0.01 0.005]
                                                [--epochs 64 80 100 128] [--blocks N] [--seed 0]
+                                               [--knn-k 50] [--knn-shrink 10] [--knn-support 1]
 
 TRAIN / VAL / TEST are the sample files (CSV with userId, movieId, rating columns; ``.csv`` may be left off).  Grid search of
 KernelMF over factors x lr x reg; the epoch counts of the grid are stops of ONE fit per (factors, lr, reg) — a fit is deterministic
 and its first k epochs are the k-epoch fit (KernelMF.fit, at_epochs).  Every grid point prints its validation MSE on clipped
 predictions; the best one is then scored on TEST: MSE, NDCG@10 and min-max adjusted NDCG@10 (eval_ranking).  An id of VAL / TEST
-that TRAIN does not hold predicts the global mean plus the known side's bias, as the package does."""
+that TRAIN does not hold predicts the global mean plus the known side's bias, as the package does.
+
+One more row of the table, between the best grid point and its test scores: the neighbourhood baseline ItemKNN (``--knn-k`` neighbours,
+0 leaves the row out) fitted on TRAIN's ratings centred on their mean (a pair rated twice keeps its last rating), predicting the mean
+plus the similarity-weighted average of the user's centred ratings of the item's neighbours, clipped like KernelMF's predictions."""
 import argparse
 import os
 import sys
@@ -18,7 +23,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from deeprecommendation_amd import KernelMF  # noqa: E402
+from deeprecommendation_amd import ItemKNN, KernelMF  # noqa: E402
 from deeprecommendation_amd.neural_collaborative_filtering.eval import eval_ranking  # noqa: E402
 
 
@@ -39,6 +44,22 @@ def mse(pred, rating):
     return float(np.mean(d * d))
 
 
+def item_knn_row(args, frames, upos, ipos, n_users, n_items, ratings, dev):
+    """The ItemKNN row: validation and test MSE, NDCG@10 and adjusted NDCG@10 on TEST."""
+    train = pd.DataFrame({"u": upos[0], "i": ipos[0], "r": ratings[0]}).drop_duplicates(["u", "i"], keep="last")
+    mu = float(train["r"].mean())
+    model = ItemKNN(k=args.knn_k, shrink=args.knn_shrink, min_support=args.knn_support, weighted_average=True, fill=0.0)
+    u, i = torch.from_numpy(train["u"].to_numpy()).to(dev), torch.from_numpy(train["i"].to_numpy()).to(dev)
+    csr = model.build_csr(u, i, torch.from_numpy((train["r"].to_numpy() - mu).astype(np.float32)).to(dev), n_users, n_items)
+    model.fit_csr(*csr, n_items)
+    pred = [(model.predict(csr, torch.from_numpy(upos[k]).to(dev), torch.from_numpy(ipos[k]).to(dev)) + mu).clamp(0.0, 5.0) for k in (1, 2)]
+    frame = pd.DataFrame({"userId": frames[2]["userId"].to_numpy(), "movieId": frames[2]["movieId"].to_numpy(), "rating": ratings[2],
+                          "prediction": pred[1].cpu().numpy()})
+    ndcg, adj = eval_ranking(frame, cutoff=10)
+    print(f"ItemKNN k={model.k} shrink={model.shrink} min_support={model.min_support}: val MSE {mse(pred[0], ratings[1]):.4f}, "
+          f"test MSE {mse(pred[1], ratings[2]):.4f}, test NDCG@10 {ndcg:.4f}, adjusted NDCG@10 {adj:.4f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("train"), ap.add_argument("val"), ap.add_argument("test")
@@ -48,6 +69,9 @@ def main():
     ap.add_argument("--epochs", type=int, nargs="+", default=[64, 80, 100, 128])
     ap.add_argument("--blocks", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--knn-k", type=int, default=50)
+    ap.add_argument("--knn-shrink", type=float, default=10.0)
+    ap.add_argument("--knn-support", type=int, default=1)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     frames = [read_samples(p) for p in (args.train, args.val, args.test)]
@@ -75,6 +99,8 @@ def main():
                           at_epochs=stops)
     test_mse = mse(best["test_pred"], ratings[2])
     print(f"best by val MSE: factors={best['factors']} lr={best['lr']} reg={best['reg']} epochs={best['epoch']} blocks={best['blocks']}")
+    if args.knn_k:
+        item_knn_row(args, frames, upos, ipos, n_users, n_items, ratings, dev)
     print(f"test MSE {test_mse:.4f} (val MSE {best['val_mse']:.4f})")
     frame = pd.DataFrame({"userId": frames[2]["userId"].to_numpy(), "movieId": frames[2]["movieId"].to_numpy(), "rating": ratings[2],
                           "prediction": best["test_pred"].cpu().numpy()})
