@@ -1288,17 +1288,6 @@ extern "C" int ncf_attn_forward_grouped(int mode, const float* pc, int64_t ldpc,
     const unsigned blocks = (unsigned)p.grid;
     const size_t lds = p.lds;
     // the dynamic-LDS limit of an instantiation is raised ONCE per device (to the 160 KiB a workgroup may declare)
-    auto raise_lds = [](const void* fn, std::atomic<unsigned long long>& done) -> bool {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (done.load(std::memory_order_relaxed) >> dev & 1ull) return true;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        done.fetch_or(1ull << dev, std::memory_order_relaxed);
-        return true;
-    };
     if (p.form == ATTG_SC) {
         // ---- scalar-operand form (default): tiles by LDS-DMA, aggregation on the matrix cores; 4 waves for up to 16 pairs per
         // workgroup, 8 waves for 17..32 (half the staged bytes per pair: the choice for batches that fill the chip either way) ----

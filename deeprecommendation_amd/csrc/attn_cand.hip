@@ -537,21 +537,10 @@ int cand_launch(bool packed, const float* x, int64_t B, int64_t ldx, int K, cons
     const size_t lds_grp = (size_t)group_small_lds_ints<true>(512) * sizeof(int);
     if (lds_red > lds) lds = lds_red;
     if (pair_row && lds_grp > lds) lds = lds_grp;
-    auto raise = [&](const void* fn, std::atomic<unsigned long long>& done) -> bool {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (done.load(std::memory_order_relaxed) >> dev & 1ull) return true;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        done.fetch_or(1ull << dev, std::memory_order_relaxed);
-        return true;
-    };
 #define NCF_CAND_LAUNCH(KERNEL)                                                                                                   \
     {                                                                                                                             \
         static std::atomic<unsigned long long> done{0};                                                                           \
-        if (!raise((const void*)KERNEL, done)) return fail(NCF_EUNSUPPORTED, "%s: cannot reserve %zu bytes of LDS", who, lds);     \
+        if (!raise_lds((const void*)KERNEL, done)) return fail(NCF_EUNSUPPORTED, "%s: cannot reserve %zu bytes of LDS", who, lds);     \
         hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(512), lds, s, a);                                                           \
     }
     if (packed && KS > 1) {                                        // few row tiles: K range over workgroups, then a short finishing launch
@@ -562,7 +551,7 @@ int cand_launch(bool packed, const float* x, int64_t B, int64_t ldx, int K, cons
 #define NCF_CAND_SPLITK(N)                                                                                                        \
     {                                                                                                                             \
         static std::atomic<unsigned long long> done{0};                                                                           \
-        if (!raise((const void*)cand_splitk_kernel<N>, done)) return fail(NCF_EUNSUPPORTED, "%s: cannot reserve %zu bytes of LDS", who, lds_a); \
+        if (!raise_lds((const void*)cand_splitk_kernel<N>, done)) return fail(NCF_EUNSUPPORTED, "%s: cannot reserve %zu bytes of LDS", who, lds_a); \
         hipLaunchKernelGGL(cand_splitk_kernel<N>, dim3(tiles, (unsigned)KS), dim3(512), lds_a, s, a, part, KS);                   \
         hipLaunchKernelGGL(cand_finish_kernel<N>, dim3(blocks), dim3(512), lds_b, s, a, (const float*)part, KS, (int)tiles);      \
     }

@@ -5,16 +5,13 @@
 //
 // One wave = one (user, slot) pair, four pairs per workgroup, no barrier (the waves of a workgroup share nothing).  Lane l owns the
 // entries beg + l, beg + l + 64, ... of the user's row in every pass:
-//   pass 1  s_e = ST[col_e, c] (-inf for a masked entry), kept in the wave's LDS strip for the first kExCache entries (a lane reads
-//           back only what it wrote; longer rows look the rest up again); m = the exact maximum (fmaxf, then the xor butterfly).
-//   pass 2  l = sum of exp_le0(s_e - m): per lane in entry order, then the xor butterfly 32, 16, .., 1 (commutative at every step:
-//           all lanes hold the same bits).
+//   passes 1-2  the column softmax of attn_table.h: the logits s_e = ST[col_e, c], their maximum m and the denominator l.
 //   pass 3  w_e = exp_le0(s_e - m) / l, a function of (s_e, m, l) alone; a valid entry with w_e > thr[u] counts, and its key
 //           (topk_map(w_e) << 32 | ~entry index: larger weight first, then the entry stored earlier) is appended to the wave's key
 //           buffer; past 192 keys the buffer is cut to the E best (wave_reselect) and the E-th key becomes a floor for later ones.
 //   final   at most E keys are left, one per lane; a lane's slot is the number of larger keys (the keys are distinct).
 // No atomics; every order is fixed: two calls on the same inputs give the same bits.
-#include "attn_util.h"
+#include "attn_table.h"
 #include "topk_common.h"
 
 namespace ncf {
@@ -22,7 +19,6 @@ namespace ncf {
 constexpr int kExMaxReasons = 64;      // one key per lane in the final ranking
 constexpr int kExWaves = 4;
 constexpr int kExBuf = 4 * kWave;      // wave_reselect's capacity
-constexpr int kExCache = 512;          // logits kept per wave between the passes (a multiple of 64)
 
 __global__ __launch_bounds__(kExWaves* kWave) void attn_explain_kernel(
     const float* __restrict__ st, int64_t ldst, int64_t Ir, int64_t Ic, const int64_t* __restrict__ rowptr,
@@ -30,7 +26,7 @@ __global__ __launch_bounds__(kExWaves* kWave) void attn_explain_kernel(
     const int64_t* __restrict__ items, int64_t pairs, int64_t k, const float* __restrict__ thr, int E, int32_t* __restrict__ rcol,
     float* __restrict__ rw, float* __restrict__ rval, int32_t* __restrict__ rcnt, int32_t* __restrict__ oob) {
     __shared__ unsigned long long bufs[kExWaves][kExBuf];
-    __shared__ float caches[kExWaves][kExCache];
+    __shared__ float caches[kExWaves][kTableCache];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t p = (int64_t)blockIdx.x * kExWaves + wave;
     if (p >= pairs) return;                                            // wave-uniform; the kernel has no barrier
@@ -41,39 +37,13 @@ __global__ __launch_bounds__(kExWaves* kWave) void attn_explain_kernel(
     const bool live = row_ok && cand_ok;
     const int64_t beg = live ? rowptr[row] : 0, end = live ? rowptr[row + 1] : 0;
     const float t = thr[u];
-    const float* __restrict__ stc = st + (cand_ok ? c : 0);
     unsigned long long* buf = bufs[wave];
-    float* cache = caches[wave];
 
-    // ---------------- pass 1: the logits and their exact maximum ----------------
-    float m = -INFINITY;
-    for (int64_t e0 = beg; e0 < end; e0 += kWave) {
-        const int64_t e = e0 + lane;
-        float s = -INFINITY;
-        if (e < end) {
-            const int cc = col[e];
-            if (cc >= 0 && cc < Ir) s = stc[(int64_t)cc * ldst];
-        }
-        if (e0 - beg < kExCache) cache[e0 - beg + lane] = s;
-        m = fmaxf(m, s);
-    }
-    m = wave_max(m);
+    // ---------------- passes 1-2: the logits, their exact maximum and the denominator ----------------
+    const TableColumn tc{st + (cand_ok ? c : 0), ldst, Ir, col, beg, end, caches[wave], lane};
+    const float m = tc.max();
     const bool any = m != -INFINITY;                                   // false: empty / fully masked row, all -inf column, dead pair
-
-    auto logit = [&](int64_t e0, int64_t e) -> float {                 // e < end; the branch is wave-uniform
-        if (e0 - beg < kExCache) return cache[e - beg];
-        const int cc = col[e];
-        return (cc >= 0 && cc < Ir) ? stc[(int64_t)cc * ldst] : -INFINITY;
-    };
-
-    // ---------------- pass 2: the denominator ----------------
-    float l = 0.f;
-    if (any)
-        for (int64_t e0 = beg; e0 < end; e0 += kWave) {
-            const int64_t e = e0 + lane;
-            if (e < end) l += exp_le0(logit(e0, e) - m);               // a masked entry: exp_le0(-inf) = 0
-        }
-    l = wave_sum(l);
+    const float l = tc.denominator(m);
 
     // ---------------- pass 3: weights, the count, the E best keys ----------------
     int cnt = 0, n = 0;
@@ -85,7 +55,7 @@ __global__ __launch_bounds__(kExWaves* kWave) void attn_explain_kernel(
             unsigned long long key = 0ull;
             if (e < end) {
                 const int cc = col[e];
-                const float w = exp_le0(logit(e0, e) - m) / l;
+                const float w = exp_le0(tc.cached(e0, e) - m) / l;
                 q = cc >= 0 && cc < Ir && w > t;                       // a NaN weight never qualifies
                 key = ((unsigned long long)topk_map(w) << 32) | (0xFFFFFFFFu - (uint32_t)(e - beg));
             }

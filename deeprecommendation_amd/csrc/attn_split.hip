@@ -482,17 +482,6 @@ extern "C" int ncf_attn_forward_split(int mode, const float* pc, int64_t ldpc, c
     const unsigned blocks = (unsigned)((B + pairs_per_wg - 1) / pairs_per_wg + (R < B ? R : B));   // upper bound on sum_r ceil(n_r / ppw)
     const int pp = pairs_per_wg <= 16 ? 16 : (pairs_per_wg <= 32 ? 32 : 64);   // 4 / 8 / 16 waves of 4 pairs
     const size_t lds = ((size_t)64 * (A + Fdim) + pp * 66 + pp + 2 * pp) * 4;
-    auto raise_lds = [&](const void* fn, std::atomic<unsigned long long>& done) -> bool {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (done.load(std::memory_order_relaxed) >> dev & 1ull) return true;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        done.fetch_or(1ull << dev, std::memory_order_relaxed);
-        return true;
-    };
     const bool scaled = mode == NCF_ATT_MLP_SCALED;
 #define LAUNCH_SP(M, W, J)                                                                                              \
     do {                                                                                                                \

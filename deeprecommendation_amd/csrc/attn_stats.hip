@@ -2,12 +2,12 @@
 // valid entry e of u's rated set, sum[c, col_e] += the attention weight of col_e towards c (float64) and count[c, col_e] += 1 —
 // the two (n_items, n_items) tables the reference's eval_model builds on the host from a dense (batch, catalogue) weight matrix
 // (eval.py:101-108, 137-143).  ncf_attn_logits' table ST (attn_cross.hip) holds every logit: a sample's weights are a column
-// lookup over its user's row and a softmax, exactly attn_explain.hip's passes 1-2.
+// lookup over its user's row and a softmax (attn_table.h).
 //
 // Two launches inside the one entry:
-//   attn_stats_softmax_kernel  one wave = one sample, four samples per workgroup, no barrier.  Passes 1-2 of attn_explain_kernel
-//       (same lane ownership, same LDS strip, same summation order: m_s and l_s have attn_explain's bits), written as (m_s, l_s)
-//       to the workspace, 8 bytes per sample.  Sets the sticky flag for a user row or candidate out of range.
+//   attn_stats_softmax_kernel  one wave = one sample, four samples per workgroup, no barrier.  The column softmax of attn_table.h,
+//       which attn_explain_kernel calls too (m_s and l_s have attn_explain's bits), written as (m_s, l_s) to the workspace, 8 bytes
+//       per sample.  Sets the sticky flag for a user row or candidate out of range.
 //   attn_stats_accumulate_kernel  owner computes: one wave (= one workgroup) owns (candidate c, slab of kStSlab columns of the
 //       rated axis) and nobody else touches those cells.  Its accumulators — kStSlab doubles and kStSlab int64 — live in LDS,
 //       are initialised from the caller's tables and written back at the end.  The wave walks c's samples in the order the caller's
@@ -22,13 +22,12 @@
 // No atomics: the additions into a cell happen in the listed order starting from the value already in the table, so two calls
 // give the same bits and a file accumulated in two calls (first half, then second half) gives the bits of one call.  Every loop
 // is bounded by S or by a row's length.
-#include "attn_util.h"
+#include "attn_table.h"
 #include "topk_common.h"
 
 namespace ncf {
 
 constexpr int kStWaves = 4;            // samples per workgroup of the softmax kernel
-constexpr int kStCache = 512;          // logits kept per wave between the two passes (a multiple of 64)
 constexpr int kStSlab = 512;           // rated columns owned by one wave of the accumulation kernel
 constexpr int kStBatch = 8;            // stripes of 64 entries whose loads the accumulation kernel keeps in flight together
 
@@ -36,7 +35,7 @@ __global__ __launch_bounds__(kStWaves* kWave) void attn_stats_softmax_kernel(
     const float* __restrict__ st, int64_t ldst, int64_t Ir, int64_t Ic, const int64_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, int64_t n_rows, const int64_t* __restrict__ user_rows, const int64_t* __restrict__ cands,
     int64_t S, float2* __restrict__ ml, int32_t* __restrict__ oob) {
-    __shared__ float caches[kStWaves][kStCache];
+    __shared__ float caches[kStWaves][kTableCache];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t s = (int64_t)blockIdx.x * kStWaves + wave;
     if (s >= S) return;                                                // wave-uniform; the kernel has no barrier
@@ -44,40 +43,9 @@ __global__ __launch_bounds__(kStWaves* kWave) void attn_stats_softmax_kernel(
     const bool live = row >= 0 && row < n_rows && c >= 0 && c < Ic;
     if (oob && lane == 0 && !live) *oob = 1;                           // sticky
     const int64_t beg = live ? rowptr[row] : 0, end = live ? rowptr[row + 1] : 0;
-    const float* __restrict__ stc = st + (live ? c : 0);
-    float* cache = caches[wave];
-
-    // pass 1: the logits and their exact maximum
-    float m = -INFINITY;
-    for (int64_t e0 = beg; e0 < end; e0 += kWave) {
-        const int64_t e = e0 + lane;
-        float v = -INFINITY;
-        if (e < end) {
-            const int cc = col[e];
-            if (cc >= 0 && cc < Ir) v = stc[(int64_t)cc * ldst];
-        }
-        if (e0 - beg < kStCache) cache[e0 - beg + lane] = v;           // a lane reads back only what it wrote
-        m = fmaxf(m, v);
-    }
-    m = wave_max(m);
-
-    // pass 2: the denominator — per lane in entry order, then the xor butterfly
-    float l = 0.f;
-    if (m != -INFINITY)
-        for (int64_t e0 = beg; e0 < end; e0 += kWave) {
-            const int64_t e = e0 + lane;
-            if (e < end) {
-                float v;
-                if (e0 - beg < kStCache) {
-                    v = cache[e - beg];
-                } else {
-                    const int cc = col[e];
-                    v = (cc >= 0 && cc < Ir) ? stc[(int64_t)cc * ldst] : -INFINITY;
-                }
-                l += exp_le0(v - m);                                   // a masked entry: exp_le0(-inf) = 0
-            }
-        }
-    l = wave_sum(l);
+    const TableColumn tc{st + (live ? c : 0), ldst, Ir, col, beg, end, caches[wave], lane};
+    const float m = tc.max();
+    const float l = tc.denominator(m);
     if (lane == 0) ml[s] = make_float2(m, l);
 }
 

@@ -1,6 +1,7 @@
 // Shared helpers for libncf_hip.so (gfx950 only).  Internal — the public surface is include/ncf_abi.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
@@ -22,6 +23,19 @@ inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NCF_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
     return NCF_OK;
+}
+
+// Raises a kernel's dynamic-LDS limit to 160 KiB, once per device: ``done`` is the caller's static word of one bit per device.
+inline bool raise_lds(const void* fn, std::atomic<unsigned long long>& done) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (done.load(std::memory_order_relaxed) >> dev & 1ull) return true;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    done.fetch_or(1ull << dev, std::memory_order_relaxed);
+    return true;
 }
 
 // Process-wide kernel-selection overrides (ncf_set_option; 0 = choose by shape) and the per-device CU count (abi.hip).

@@ -322,15 +322,20 @@ def _idx(t: Optional[torch.Tensor], B: Optional[int] = None):
     return t
 
 
-_oob_flags = {}
+_flags = {}
+
+
+def _flag(kind, device) -> torch.Tensor:
+    """The sticky int32 flag word of ``kind`` on ``device``: one zeroed tensor per (kind, device), which kernels set and a
+    ``check_*`` reads and clears."""
+    f = _flags.get((kind, device))
+    if f is None:
+        f = _flags[kind, device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return f
 
 
 def _oob_flag(device) -> torch.Tensor:
-    f = _oob_flags.get(device)
-    if f is None:
-        f = torch.zeros(1, dtype=torch.int32, device=device)
-        _oob_flags[device] = f
-    return f
+    return _flag("oob", device)
 
 
 def check_oob(device):
@@ -910,16 +915,9 @@ def dense_to_csr(user_matrix: torch.Tensor, share_rows: bool = True):
     return rowptr, col, val, pair_row
 
 
-_pair_rows_flags = {}
-
-
 def _pair_rows_flag(device) -> torch.Tensor:
     """The sticky overflow flag of pair_rows calls that run inside a training step (nobody reads a per-call flag there)."""
-    f = _pair_rows_flags.get(device)
-    if f is None:
-        f = torch.zeros(1, dtype=torch.int32, device=device)
-        _pair_rows_flags[device] = f
-    return f
+    return _flag("pair_rows", device)
 
 
 def check_pair_rows(device):
@@ -1434,8 +1432,7 @@ def user_profiles(rowptr: torch.Tensor, col: torch.Tensor, rating: torch.Tensor,
     device is."""
     for t, what, dt in ((rowptr, "rowptr", torch.int64), (col, "col", torch.int32), (rating, "rating", torch.float32),
                         (avg, "avg", torch.float64)):
-        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f"user_profiles: {what} must be a contiguous 1-D {dt} tensor")
+        _vec1d("user_profiles", t, what, dt)
     if features.dtype != torch.float32 or (out is not None and out.dtype != torch.float32):
         raise ValueError("user_profiles: features and out must be float32")
     I, F, ldf = _rows2d(features, "features")
@@ -1457,16 +1454,11 @@ def user_profiles(rowptr: torch.Tensor, col: torch.Tensor, rating: torch.Tensor,
 
 KMF_MAX_FACTORS, KMF_MAX_BLOCKS = 256, 1024       # csrc/kmf.hip
 KMF_FLAG_ID, KMF_FLAG_BLOCK, KMF_FLAG_PTR = 1, 2, 4
-_kmf_flags = {}
 
 
 def kmf_flag(device) -> torch.Tensor:
     """The sticky int32 flag word of the KernelMF kernels on ``device`` (bits KMF_FLAG_*)."""
-    f = _kmf_flags.get(device)
-    if f is None:
-        f = torch.zeros(1, dtype=torch.int32, device=device)
-        _kmf_flags[device] = f
-    return f
+    return _flag("kmf", device)
 
 
 def check_kmf(device, flag: Optional[torch.Tensor] = None):
@@ -1491,14 +1483,14 @@ def _kmf_tables(who, PU, QI, F):
     return F
 
 
-def _kmf_vec(who, t, what, dt, n=None):
+def _vec1d(who, t, what, dt, n=None):
     if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
         raise ValueError(f"{who}: {what} must be a contiguous 1-D {dt} tensor")
     if n is not None and t.numel() != n:
         raise ValueError(f"{who}: {what} has {t.numel()} entries, expected {n}")
 
 
-def _kmf_out(who, t, what, dt, n):
+def _out1d(who, t, what, dt, n):
     if t is not None and (not torch.is_tensor(t) or t.dtype != dt or not t.is_contiguous() or t.numel() != n):
         raise ValueError(f"{who}: {what} must be a contiguous {dt} tensor of {n} entries")
 
@@ -1515,21 +1507,21 @@ def kmf_epoch(PU: torch.Tensor, QI: torch.Tensor, F: int, user: torch.Tensor, it
     who = "kmf_epoch"
     F = _kmf_tables(who, PU, QI, F)
     U, I = PU.shape[0], QI.shape[0]
-    _kmf_vec(who, user, "user", torch.int32)
+    _vec1d(who, user, "user", torch.int32)
     n = user.numel()
-    _kmf_vec(who, item, "item", torch.int32, n)
-    _kmf_vec(who, rating, "rating", torch.float32, n)
-    _kmf_vec(who, block_ptr, "block_ptr", torch.int64)
+    _vec1d(who, item, "item", torch.int32, n)
+    _vec1d(who, rating, "rating", torch.float32, n)
+    _vec1d(who, block_ptr, "block_ptr", torch.int64)
     W = int(round((block_ptr.numel() - 1) ** 0.5)) if block_ptr.numel() > 1 else 0
     if W < 1 or W * W + 1 != block_ptr.numel() or W > KMF_MAX_BLOCKS:
         raise ValueError(f"{who}: block_ptr has {block_ptr.numel()} entries, not W * W + 1 for a W in 1 .. {KMF_MAX_BLOCKS}")
-    _kmf_vec(who, user_block, "user_block", torch.int32, U)
-    _kmf_vec(who, item_block, "item_block", torch.int32, I)
+    _vec1d(who, user_block, "user_block", torch.int32, U)
+    _vec1d(who, item_block, "item_block", torch.int32, I)
     n_epochs = int(n_epochs)
     if n_epochs < 0:
         raise ValueError(f"{who}: n_epochs = {n_epochs}")
-    _kmf_out(who, sse, "sse", torch.float64, n_epochs * W)
-    _kmf_out(who, flag, "flag", torch.int32, 1)
+    _out1d(who, sse, "sse", torch.float64, n_epochs * W)
+    _out1d(who, flag, "flag", torch.int32, 1)
     for t, what in ((PU, "PU"), (QI, "QI"), (user, "user"), (item, "item"), (rating, "rating"), (block_ptr, "block_ptr"),
                     (user_block, "user_block"), (item_block, "item_block"), (sse, "sse"), (flag, "flag")):
         if t is not None:
@@ -1556,17 +1548,17 @@ def kmf_fold_users(PU: torch.Tensor, QI: torch.Tensor, F: int, users: torch.Tens
     who = "kmf_fold_users"
     F = _kmf_tables(who, PU, QI, F)
     U, I = PU.shape[0], QI.shape[0]
-    _kmf_vec(who, users, "users", torch.int32)
+    _vec1d(who, users, "users", torch.int32)
     nu = users.numel()
-    _kmf_vec(who, rowptr, "rowptr", torch.int64, nu + 1)
-    _kmf_vec(who, col, "col", torch.int32)
+    _vec1d(who, rowptr, "rowptr", torch.int64, nu + 1)
+    _vec1d(who, col, "col", torch.int32)
     nnz = col.numel()
-    _kmf_vec(who, rating, "rating", torch.float32, nnz)
+    _vec1d(who, rating, "rating", torch.float32, nnz)
     n_epochs = int(n_epochs)
     if n_epochs < 0:
         raise ValueError(f"{who}: n_epochs = {n_epochs}")
-    _kmf_out(who, sse, "sse", torch.float64, n_epochs * nu)
-    _kmf_out(who, flag, "flag", torch.int32, 1)
+    _out1d(who, sse, "sse", torch.float64, n_epochs * nu)
+    _out1d(who, flag, "flag", torch.int32, 1)
     for t, what in ((PU, "PU"), (QI, "QI"), (users, "users"), (rowptr, "rowptr"), (col, "col"), (rating, "rating"), (sse, "sse"),
                     (flag, "flag")):
         if t is not None:
@@ -1583,16 +1575,11 @@ def kmf_fold_users(PU: torch.Tensor, QI: torch.Tensor, F: int, users: torch.Tens
 
 
 KNN_MAX_N, KNN_MAX_TILE, KNN_MAX_STAGE, KNN_MAX_ROWS = 256, 8192, 8192, 65535       # csrc/knn.hip
-_knn_flags = {}
 
 
 def knn_flag(device) -> torch.Tensor:
     """The sticky int32 word of ncf_knn_sim_rows on ``device``: set by a row whose columns do not strictly ascend."""
-    f = _knn_flags.get(device)
-    if f is None:
-        f = torch.zeros(1, dtype=torch.int32, device=device)
-        _knn_flags[device] = f
-    return f
+    return _flag("knn", device)
 
 
 def check_knn(device, flag: Optional[torch.Tensor] = None):
@@ -1606,11 +1593,11 @@ def check_knn(device, flag: Optional[torch.Tensor] = None):
 
 def _knn_csr(who, ptr, idx, val, names, rows=None):
     """Checks one CSR (pointers int64, ids int32, values fp32, contiguous 1-D); returns (rows, nnz)."""
-    _kmf_vec(who, ptr, names[0], torch.int64, None if rows is None else rows + 1)
+    _vec1d(who, ptr, names[0], torch.int64, None if rows is None else rows + 1)
     if ptr.numel() < 1:
         raise ValueError(f"{who}: {names[0]} is empty")
-    _kmf_vec(who, idx, names[1], torch.int32)
-    _kmf_vec(who, val, names[2], torch.float32, idx.numel())
+    _vec1d(who, idx, names[1], torch.int32)
+    _vec1d(who, val, names[2], torch.float32, idx.numel())
     return ptr.numel() - 1, idx.numel()
 
 
@@ -1639,7 +1626,7 @@ def _knn_table(who, nb_pos, nb_sim, nb_cnt):
     I, N = nb_pos.shape
     if not torch.is_tensor(nb_sim) or nb_sim.dtype != torch.float32 or tuple(nb_sim.shape) != (I, N) or not nb_sim.is_contiguous():
         raise ValueError(f"{who}: nb_sim must be a contiguous ({I}, {N}) float32 tensor")
-    _kmf_vec(who, nb_cnt, "nb_cnt", torch.int32, I)
+    _vec1d(who, nb_cnt, "nb_cnt", torch.int32, I)
     if not 1 <= N <= KNN_MAX_N:
         raise ValueError(f"{who}: N = {N} neighbours per item is outside 1 .. {KNN_MAX_N}")
     return I, N
@@ -1649,12 +1636,12 @@ def knn_item_sq(colptr: torch.Tensor, tval: torch.Tensor, out: Optional[torch.Te
     """(I,) fp32 squared norms of the item columns of a transposed ratings CSR (ncf_knn_item_sq, THE CONTRACT in include/ncf_abi.h):
     ``colptr`` (I + 1,) int64, ``tval`` fp32.  Checked before the device is; one launch on the current stream."""
     who = "knn_item_sq"
-    _kmf_vec(who, colptr, "colptr", torch.int64)
+    _vec1d(who, colptr, "colptr", torch.int64)
     if colptr.numel() < 1:
         raise ValueError(f"{who}: colptr is empty")
-    _kmf_vec(who, tval, "tval", torch.float32)
+    _vec1d(who, tval, "tval", torch.float32)
     I = colptr.numel() - 1
-    _kmf_out(who, out, "out", torch.float32, I)
+    _out1d(who, out, "out", torch.float32, I)
     for t, what in ((colptr, "colptr"), (tval, "tval"), (out, "out")):
         if t is not None:
             _dev(t, what)
@@ -1676,7 +1663,7 @@ def knn_sim_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, col
     who = "knn_sim_rows"
     U, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
     I, nnzT = _knn_csr(who, colptr, row, tval, ("colptr", "row", "tval"))
-    _kmf_vec(who, sq, "sq", torch.float32, I)
+    _vec1d(who, sq, "sq", torch.float32, I)
     i0, i1 = _knn_range(who, item_range, I)
     if i1 - i0 > KNN_MAX_ROWS:
         raise ValueError(f"{who}: {i1 - i0} items in one call (at most {KNN_MAX_ROWS})")
@@ -1688,7 +1675,7 @@ def knn_sim_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, col
     if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (i1 - i0, I)
                             or (I > 1 and out.stride(1) != 1)):
         raise ValueError(f"{who}: out must be a ({i1 - i0}, {I}) float32 tensor with unit inner stride")
-    _kmf_out(who, flag, "flag", torch.int32, 1)
+    _out1d(who, flag, "flag", torch.int32, 1)
     for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (colptr, "colptr"), (row, "row"), (tval, "tval"), (sq, "sq"), (out, "out"),
                     (flag, "flag")):
         if t is not None:
@@ -1716,7 +1703,7 @@ def knn_scores(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, users
     check_oob().  Checked before the device is; one launch on the current stream."""
     who = "knn_scores"
     R, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
-    _kmf_vec(who, users, "users", torch.int64)
+    _vec1d(who, users, "users", torch.int64)
     B = users.numel()
     if B > KNN_MAX_ROWS:
         raise ValueError(f"{who}: {B} users in one call (at most {KNN_MAX_ROWS})")
@@ -1749,9 +1736,9 @@ def knn_predict(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, user
     check_oob().  Checked before the device is; one launch on the current stream."""
     who = "knn_predict"
     R, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
-    _kmf_vec(who, users, "users", torch.int64)
+    _vec1d(who, users, "users", torch.int64)
     n = users.numel()
-    _kmf_vec(who, items, "items", torch.int64, n)
+    _vec1d(who, items, "items", torch.int64, n)
     I, N = _knn_table(who, nb_pos, nb_sim, nb_cnt)
     fill = _knn_float(who, fill, "fill")
     for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (items, "items"), (nb_pos, "nb_pos"),
@@ -2309,15 +2296,9 @@ def mlp_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
 RANK_MAX_TARGETS = 128   # targets per row of a fused rank call (include/ncf_abi.h ncf_rank_max_targets); rank_rows takes any number
 DOT_RANK_MAX_D = 256     # the fused dot-product kernel's width limit, as DOT_TOPK_MAX_D
 
-_rank_overflow_flags = {}
-
 
 def _rank_overflow_flag(device) -> torch.Tensor:
-    f = _rank_overflow_flags.get(device)
-    if f is None:
-        f = torch.zeros(1, dtype=torch.int32, device=device)
-        _rank_overflow_flags[device] = f
-    return f
+    return _flag("rank_overflow", device)
 
 
 def check_rank_overflow(device):

@@ -26,17 +26,14 @@ import numpy as np
 import torch
 
 from . import native
-from .recommend import BLOCK_BYTES, _csr, _dot_readout, _fused_tables, _mlp_operands, _resolve_ranked, _score_blocks
+from .recommend import BLOCK_BYTES, _csr, _csr_take, _dot_readout, _fused_tables, _mlp_operands, _rank_blocks, _resolve_ranked, _score_blocks
 
 
 def _take_rows(rowptr, col, rows):
     """The CSR of a row subset: (rowptr', col', entry) with entry = the place of each kept entry in ``col``.  Sizes its result on
     the host (one read)."""
-    cnt = rowptr[rows + 1] - rowptr[rows]
-    new = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=rowptr.device)
-    torch.cumsum(cnt, 0, out=new[1:])
-    row = torch.repeat_interleave(torch.arange(rows.numel(), device=rowptr.device), cnt)
-    entry = rowptr[rows][row] + torch.arange(row.numel(), device=rowptr.device) - new[row]
+    lo = rowptr[rows]
+    new, entry = _csr_take(lo, rowptr[rows + 1] - lo)
     return new, col[entry], entry
 
 
@@ -62,13 +59,7 @@ def _fused_ranks(model, r, users, seen, targets, max_targets):
 
 def _scored_ranks(model, r, users, seen, targets, block_bytes):
     """Score blocks of users through the model and rank each block's targets in its score rows (native.rank_rows)."""
-    trow, tcol = targets
-    rank = torch.empty(tcol.numel(), dtype=torch.int32, device=users.device)
-    # the kernels read col[rowptr[r] ..] and write rank[rowptr[r] ..]: a slice of rowptr indexes the whole arrays
-    with torch.no_grad():
-        ranked = [native.rank_rows(scores, (trow[b0:b1 + 1], tcol), None if seen is None else (seen[0][b0:b1 + 1], seen[1]), rank=rank)[1]
-                  for b0, b1, scores in _score_blocks(model, r, users, block_bytes)]
-    return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])
+    return _rank_blocks(_score_blocks(model, r, users, block_bytes), users.numel(), targets, seen)
 
 
 def rank_of_items(model, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, torch.Tensor], item_ids: Optional[torch.Tensor] = None,

@@ -144,6 +144,77 @@ def _resolve_ranked(model, user_ids, item_ids, exclude, graph, profiles=None, fu
     return _RankedList(graph, user_ids.contiguous(), items, item_ids is None, n_items, seen, B, items.numel())
 
 
+def _user_blocks(n_users, block_bytes, row_bytes, max_rows=None):
+    """Yields ``(b0, b1)``: the users in consecutive blocks of as many rows of ``row_bytes`` as fit ``block_bytes`` (at least one, at
+    most ``max_rows``)."""
+    rows_per_block = max(1, int(block_bytes) // max(1, row_bytes))
+    if max_rows is not None:
+        rows_per_block = min(rows_per_block, max_rows)
+    for b0 in range(0, n_users, rows_per_block):
+        yield b0, min(n_users, b0 + rows_per_block)
+
+
+def _position_lists(**lists):
+    for what, t in lists.items():
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1):
+            raise ValueError(f"{what} must be a 1-D int64 tensor of positions")
+
+
+def _check_k(k):
+    if not 1 <= int(k) <= native.TOPK_MAX_K:
+        raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
+
+
+def _item_positions(idx, items):
+    """Columns of the ranked list (-1: an unused slot) as int64 item positions; ``items`` None: the columns are the positions."""
+    pos = idx.to(torch.int64)
+    return pos if items is None else torch.where(pos >= 0, items[pos.clamp_min(0)], pos)
+
+
+def _select_blocks(blocks, B, k, exclude, items, dev):
+    """The score-then-select tail of every top-K entry point: ``k`` is checked, then the score blocks ``(b0, b1, scores (b1 - b0,
+    I))`` of ``blocks`` (a generator: its own checks run after these) are ranked one by one with native.topk_rows, skipping ``exclude``
+    (a per-user CSR over all ``B`` users, or None), joined, and mapped through ``items`` (_item_positions).  No block (B = 0): empty
+    results on ``dev``."""
+    _check_k(k)
+    seen = None if exclude is None else _csr(exclude, B, "exclude")
+    # the kernel reads seen_col[rowptr[r] ..]: a slice of rowptr indexes the whole col array, no rebasing
+    with torch.no_grad():
+        outs = [native.topk_rows(scores, int(k), None if seen is None else (seen[0][b0:b1 + 1], seen[1])) for b0, b1, scores in blocks]
+    if not outs:
+        return (torch.empty((0, int(k)), dtype=torch.float32, device=dev), torch.empty((0, int(k)), dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev))
+    s, idx, cnt = (torch.cat([o[j] for o in outs]) if len(outs) != 1 else outs[0][j] for j in range(3))
+    return s, _item_positions(idx, items), cnt
+
+
+def _rank_blocks(blocks, B, targets, exclude):
+    """The score-then-rank tail of every ranks entry point: the targets (a per-user CSR over all ``B`` users) of each score block of
+    ``blocks`` are ranked in its score rows with native.rank_rows, skipping ``exclude``.  Returns ``(rank (n_targets,) int32, ranked
+    (B,) int32)``; no block (B = 0): ``ranked`` is empty."""
+    trow, tcol = _csr(targets, B, "targets")
+    seen = None if exclude is None else _csr(exclude, B, "exclude")
+    rank = torch.empty(tcol.numel(), dtype=torch.int32, device=tcol.device)
+    # the kernels read col[rowptr[r] ..] and write rank[rowptr[r] ..]: a slice of rowptr indexes the whole arrays
+    with torch.no_grad():
+        ranked = [native.rank_rows(scores, (trow[b0:b1 + 1], tcol), None if seen is None else (seen[0][b0:b1 + 1], seen[1]), rank=rank)[1]
+                  for b0, b1, scores in blocks]
+    if not ranked:
+        return rank, torch.empty(0, dtype=torch.int32, device=tcol.device)
+    return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])
+
+
+def _csr_take(start, count):
+    """The CSR made of the entry spans ``[start[i], start[i] + count[i])`` of another, in the listed order (a span may be empty or
+    listed twice): ``(rowptr (n + 1) int64, entry)`` with ``entry`` = the place of each kept entry in the source.  Sizes its result on
+    the host (one read)."""
+    n, dev = start.numel(), start.device
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(count, 0, out=rowptr[1:])
+    row = torch.repeat_interleave(torch.arange(n, device=dev), count)
+    return rowptr, start[row] + torch.arange(row.numel(), device=dev) - rowptr[row]
+
+
 def _score_blocks(model, r: _RankedList, users, block_bytes):
     """Yields ``(b0, b1, scores (b1 - b0, I))``: the users scored against the ranked list through the model, in blocks of rows
     whose (user, item) score block stays under ``block_bytes``."""
@@ -151,9 +222,7 @@ def _score_blocks(model, r: _RankedList, users, block_bytes):
         yield from model.catalogue_score_blocks(r.profiles[0], r.profiles[1], users, None if r.all_items else r.items, r.table, block_bytes)
         return
     score = (lambda u, i: model(r.graph, u, i)) if r.graph is not None else model
-    rows_per_block = max(1, int(block_bytes) // max(1, r.I * _PAIR_BYTES))
-    for b0 in range(0, users.numel(), rows_per_block):
-        b1 = min(users.numel(), b0 + rows_per_block)
+    for b0, b1 in _user_blocks(users.numel(), block_bytes, r.I * _PAIR_BYTES):
         with torch.no_grad():
             scores = score(users[b0:b1].repeat_interleave(r.I), r.items.repeat(b1 - b0)).view(b1 - b0, r.I)
         yield b0, b1, scores                  # outside the with: a suspended generator must not hold the grad mode
@@ -185,7 +254,8 @@ def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.
     ``native.topk_rows`` on either route (there is no fused score-and-select kernel for this model).
     Returns ``(scores (B, k) fp32, item_positions (B, k) int64, counts (B,) int32)`` on the device, each row in descending score
     order (ties: lower column first; NaN last); slots past ``counts`` hold position -1 and score -inf.  Score-then-select scores
-    the users in blocks of rows whose (user, item) score block stays under ``block_bytes``; nothing synchronises with the host."""
+    the users in blocks of rows whose (user, item) score block stays under ``block_bytes``; nothing synchronises with the host.
+    An empty ``user_ids`` gives ``(0, k)``, ``(0, k)`` and ``(0,)`` results on every route."""
     r = _resolve_ranked(model, user_ids, item_ids, exclude, graph, profiles, fused)
     if r.profiles is not None:
         fused = False                     # no fused score-and-select kernel for this model: catalogue_scores, then ncf_topk_rows
@@ -193,24 +263,17 @@ def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.
         raise ValueError(f"fused=True needs a dot-product readout; {type(model).__name__} here scores through an MLP")
     if fused and getattr(model, "scoring_dtype", torch.float32) != torch.float32:
         raise ValueError("fused=True takes fp32 tables: the model scores in " + str(model.scoring_dtype))
-    if not 1 <= int(k) <= native.TOPK_MAX_K:
-        raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
+    _check_k(k)
     out = None
     if bool(fused) if fused is not None else (r.graph is not None and _dot_readout(model)):
         out = _fused_top_k(model, r, int(k))
     elif fused is None and not _dot_readout(model):
         out = _fused_mlp_top_k(model, r, int(k))
+    items = None if r.all_items else r.items
     if out is None:
-        # the kernel reads seen_col[rowptr[r] ..]: a slice of rowptr indexes the whole col array, no rebasing
-        with torch.no_grad():
-            outs = [native.topk_rows(scores, k, None if r.seen is None else (r.seen[0][b0:b1 + 1], r.seen[1]))
-                    for b0, b1, scores in _score_blocks(model, r, r.users, block_bytes)]
-        out = tuple(torch.cat([o[j] for o in outs]) if len(outs) != 1 else outs[0][j] for j in range(3))
+        return _select_blocks(_score_blocks(model, r, r.users, block_bytes), r.B, k, r.seen, items, r.users.device)
     s, idx, cnt = out
-    pos = idx.to(torch.int64)
-    if not r.all_items:
-        pos = torch.where(pos >= 0, r.items[pos.clamp_min(0)], pos)
-    return s, pos, cnt
+    return s, _item_positions(idx, items), cnt
 
 
 def _fused_top_k(model, r: _RankedList, k):
@@ -281,11 +344,7 @@ def seen_items(graph, user_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tenso
     order = torch.argsort(src, stable=True)
     s_src, s_dst = src[order], dst[order]
     lo = torch.searchsorted(s_src, user_ids)
-    cnt = torch.searchsorted(s_src, user_ids, right=True) - lo
-    rowptr = torch.zeros(user_ids.numel() + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(cnt, 0, out=rowptr[1:])
-    row = torch.repeat_interleave(torch.arange(user_ids.numel(), device=dev), cnt)
-    pos = lo[row] + torch.arange(row.numel(), device=dev) - rowptr[row]
+    rowptr, pos = _csr_take(lo, torch.searchsorted(s_src, user_ids, right=True) - lo)
     return rowptr, s_dst[pos].to(torch.int32)
 
 
@@ -297,13 +356,8 @@ def rated_exclusion(ratings: SparseRatings, user_ids: torch.Tensor) -> Tuple[tor
     require_gpu(user_ids, ratings.rowptr, ratings.col)
     if user_ids.dtype != torch.int64 or user_ids.dim() != 1:
         raise ValueError("user_ids must be a 1-D int64 tensor of rows of ratings")
-    dev = user_ids.device
     lo = ratings.rowptr[user_ids]
-    cnt = ratings.rowptr[user_ids + 1] - lo
-    rowptr = torch.zeros(user_ids.numel() + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(cnt, 0, out=rowptr[1:])
-    row = torch.repeat_interleave(torch.arange(user_ids.numel(), device=dev), cnt)
-    pos = lo[row] + torch.arange(row.numel(), device=dev) - rowptr[row]
+    rowptr, pos = _csr_take(lo, ratings.rowptr[user_ids + 1] - lo)
     return rowptr, ratings.col[pos].to(torch.int32)
 
 
@@ -316,16 +370,12 @@ def _cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes
             raise ValueError(f"{what} must be a 2-D float32 tensor")
     if user_profiles.shape[1] != item_features.shape[1]:
         raise ValueError(f"user_profiles has {user_profiles.shape[1]} columns, item_features {item_features.shape[1]}")
-    for t, what in ((user_ids, "user_ids"), (item_ids, "item_ids")):
-        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1):
-            raise ValueError(f"{what} must be a 1-D int64 tensor of positions")
+    _position_lists(user_ids=user_ids, item_ids=item_ids)
     require_gpu(user_profiles, item_features, user_ids, item_ids)
     with torch.no_grad():
         items = native.l2_normalize_rows(item_features if item_ids is None else native.gather_concat(item_features, item_ids.contiguous()))
-    rows_per_block = max(1, int(block_bytes) // max(1, items.shape[0] * 4))
     users = user_ids.contiguous()
-    for b0 in range(0, users.numel(), rows_per_block):
-        b1 = min(users.numel(), b0 + rows_per_block)
+    for b0, b1 in _user_blocks(users.numel(), block_bytes, items.shape[0] * 4):
         with torch.no_grad():
             prof = native.l2_normalize_rows(native.gather_concat(user_profiles, users[b0:b1]))
             scores = native.linear(prof, items, None)
@@ -340,20 +390,8 @@ def content_cosine_top_k(user_profiles: torch.Tensor, item_features: torch.Tenso
     (``SparseDynamicProvider.user_profiles``, ``ContentIndexProvider.content``); user_ids, item_ids, exclude, block_bytes and the
     returned ``(scores (B, k), item_positions (B, k) int64, counts (B,) int32)`` as in ``top_k_items``.  A user whose profile is all
     zeros (no ratings) scores 0 against every item, as the reference leaves it, and so gets the first ``k`` columns."""
-    if not 1 <= int(k) <= native.TOPK_MAX_K:
-        raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
-    seen = None if exclude is None else _csr(exclude, user_ids.numel(), "exclude")
-    outs = [native.topk_rows(scores, int(k), None if seen is None else (seen[0][b0:b1 + 1], seen[1]))
-            for b0, b1, scores in _cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes)]
-    if not outs:
-        dev = user_profiles.device
-        return (torch.empty((0, int(k)), dtype=torch.float32, device=dev), torch.empty((0, int(k)), dtype=torch.int64, device=dev),
-                torch.empty(0, dtype=torch.int32, device=dev))
-    s, idx, cnt = (torch.cat([o[j] for o in outs]) if len(outs) != 1 else outs[0][j] for j in range(3))
-    pos = idx.to(torch.int64)
-    if item_ids is not None:
-        pos = torch.where(pos >= 0, item_ids[pos.clamp_min(0)], pos)
-    return s, pos, cnt
+    return _select_blocks(_cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes), user_ids.numel(), k, exclude,
+                          item_ids, user_profiles.device)
 
 
 def content_cosine_ranks(user_profiles: torch.Tensor, item_features: torch.Tensor, user_ids: torch.Tensor,
@@ -361,30 +399,18 @@ def content_cosine_ranks(user_profiles: torch.Tensor, item_features: torch.Tenso
                          exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES):
     """The ranks twin of ``content_cosine_top_k``: ``(rank (n_targets,) int32, ranked (B,) int32)`` of each listed user's held-out
     items under the baseline's cosines, with the meaning ``rank_of_items`` gives them (``ranking_metrics`` takes them as they are)."""
-    B = user_ids.numel()
-    trow, tcol = _csr(targets, B, "targets")
-    seen = None if exclude is None else _csr(exclude, B, "exclude")
-    rank = torch.empty(tcol.numel(), dtype=torch.int32, device=tcol.device)
-    ranked = [native.rank_rows(scores, (trow[b0:b1 + 1], tcol), None if seen is None else (seen[0][b0:b1 + 1], seen[1]), rank=rank)[1]
-              for b0, b1, scores in _cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes)]
-    if not ranked:
-        return rank, torch.empty(0, dtype=torch.int32, device=tcol.device)
-    return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])
+    return _rank_blocks(_cosine_blocks(user_profiles, item_features, user_ids, item_ids, block_bytes), user_ids.numel(), targets, exclude)
 
 
 # ---------------------------------------------------------------------------------------- neighbourhood baseline
 def _knn_blocks(model, ratings, user_ids, item_ids, block_bytes):
     """Yields ``(b0, b1, scores (b1 - b0, I))`` of the listed rows of ``ratings`` under a fitted ``baselines.ItemKNN``: one
     ncf_knn_scores launch per block of users over the whole catalogue, the ranked list's columns gathered from it."""
-    for t, what in ((user_ids, "user_ids"), (item_ids, "item_ids")):
-        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1):
-            raise ValueError(f"{what} must be a 1-D int64 tensor of positions")
+    _position_lists(user_ids=user_ids, item_ids=item_ids)
     model._fitted()
     require_gpu(user_ids, item_ids)
-    rows_per_block = max(1, min(native.KNN_MAX_ROWS, int(block_bytes) // max(1, model.num_items_ * 4)))
     users = user_ids.contiguous()
-    for b0 in range(0, users.numel(), rows_per_block):
-        b1 = min(users.numel(), b0 + rows_per_block)
+    for b0, b1 in _user_blocks(users.numel(), block_bytes, model.num_items_ * 4, native.KNN_MAX_ROWS):
         scores = model.scores(ratings, users[b0:b1])
         yield b0, b1, scores if item_ids is None else scores.index_select(1, item_ids)
 
@@ -397,20 +423,8 @@ def item_knn_top_k(model, ratings, user_ids: torch.Tensor, k: int, item_ids: Opt
     item_positions (B, k) int64, counts (B,) int32)`` as in ``top_k_items`` (``rated_exclusion(ratings, user_ids)`` leaves out what
     a user rated)."""
     model._fitted()
-    if not 1 <= int(k) <= native.TOPK_MAX_K:
-        raise ValueError(f"k = {k} is outside 1 .. {native.TOPK_MAX_K}")
-    seen = None if exclude is None else _csr(exclude, user_ids.numel(), "exclude")
-    outs = [native.topk_rows(scores, int(k), None if seen is None else (seen[0][b0:b1 + 1], seen[1]))
-            for b0, b1, scores in _knn_blocks(model, ratings, user_ids, item_ids, block_bytes)]
-    if not outs:
-        dev = user_ids.device
-        return (torch.empty((0, int(k)), dtype=torch.float32, device=dev), torch.empty((0, int(k)), dtype=torch.int64, device=dev),
-                torch.empty(0, dtype=torch.int32, device=dev))
-    s, idx, cnt = (torch.cat([o[j] for o in outs]) if len(outs) != 1 else outs[0][j] for j in range(3))
-    pos = idx.to(torch.int64)
-    if item_ids is not None:
-        pos = torch.where(pos >= 0, item_ids[pos.clamp_min(0)], pos)
-    return s, pos, cnt
+    return _select_blocks(_knn_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), k, exclude, item_ids,
+                          user_ids.device)
 
 
 def item_knn_ranks(model, ratings, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, torch.Tensor],
@@ -419,15 +433,7 @@ def item_knn_ranks(model, ratings, user_ids: torch.Tensor, targets: Tuple[torch.
     """The ranks twin of ``item_knn_top_k``: ``(rank (n_targets,) int32, ranked (B,) int32)`` of each listed user's held-out items
     under the ItemKNN scores, with the meaning ``rank_of_items`` gives them (``ranking_metrics`` takes them as they are)."""
     model._fitted()
-    B = user_ids.numel()
-    trow, tcol = _csr(targets, B, "targets")
-    seen = None if exclude is None else _csr(exclude, B, "exclude")
-    rank = torch.empty(tcol.numel(), dtype=torch.int32, device=tcol.device)
-    ranked = [native.rank_rows(scores, (trow[b0:b1 + 1], tcol), None if seen is None else (seen[0][b0:b1 + 1], seen[1]), rank=rank)[1]
-              for b0, b1, scores in _knn_blocks(model, ratings, user_ids, item_ids, block_bytes)]
-    if not ranked:
-        return rank, torch.empty(0, dtype=torch.int32, device=tcol.device)
-    return rank, (torch.cat(ranked) if len(ranked) != 1 else ranked[0])
+    return _rank_blocks(_knn_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), targets, exclude)
 
 
 # ---------------------------------------------------------------------------------------- diversified top-K
