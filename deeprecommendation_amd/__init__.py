@@ -4,7 +4,7 @@ _RECOMMEND = ("top_k_items", "recommend_for_user", "seen_items", "rated_exclusio
               "content_cosine_ranks", "attention_statistics", "attention_stat_ratios", "AttentionStats", "diversify_top_k", "item_vectors",
               "item_knn_top_k", "item_knn_ranks")
 _RANKING_EVAL = ("rank_of_items", "ranking_metrics", "eval_full_ranking", "held_out_items", "intra_list_diversity", "catalogue_coverage")
-_BASELINES = ("KernelMF", "ItemKNN")
+_BASELINES = ("KernelMF", "ItemKNN", "ImplicitALS")
 
 
 def __getattr__(name):

@@ -9,7 +9,13 @@ fixed function of its inputs, W included.  There is no host path.
 
 ``ItemKNN`` is the neighbourhood baseline such comparisons are also read against (Sarwar et al. 2001; Surprise KNNBasic, LensKit
 ItemItem): shrunk cosine similarities of the items over the rating matrix, each item's k nearest neighbours, scores from the
-neighbours a user rated (csrc/knn.hip, THE CONTRACT in include/ncf_abi.h).  Its neighbour table is also "more like this item"."""
+neighbours a user rated (csrc/knn.hip, THE CONTRACT in include/ncf_abi.h).  Its neighbour table is also "more like this item".
+
+``ImplicitALS`` is the implicit-feedback baseline a full-catalogue top-K number is usually asked to beat (Hu, Koren & Volinsky 2008;
+implicit's AlternatingLeastSquares; the iALS of Rendle et al. 2021): every stored entry is a preference of 1 held with confidence
+1 + alpha * value, every other pair a preference of 0 with confidence 1, and the two factor tables are solved in turn, each row by
+one Cholesky factorisation on the device (csrc/als.hip, THE CONTRACT in include/ncf_abi.h).  A new user is folded in exactly, by one
+such solve against the fixed item table."""
 import math
 from typing import Optional, Sequence
 
@@ -245,6 +251,28 @@ def _knn_ratings(who, ratings):
     return rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), val.contiguous()
 
 
+def build_transpose(rowptr, col, val, num_items):
+    """``(colptr (I + 1) int64, row int32, tval fp32)``: the CSR by item, torch ops on whatever device the CSR is on.  A stable
+    sort of the entries on their column keeps the users of a column in ascending order."""
+    counts = rowptr[1:] - rowptr[:-1]
+    users = torch.repeat_interleave(torch.arange(counts.numel(), device=col.device), counts)
+    c64 = col.to(torch.int64)
+    order = torch.argsort(c64, stable=True)
+    colptr = torch.zeros(num_items + 1, dtype=torch.int64, device=col.device)
+    inside = c64[(c64 >= 0) & (c64 < num_items)]           # an id outside the items is the kernels' to flag, not bincount's to index
+    colptr[1:] = torch.cumsum(torch.bincount(inside, minlength=num_items), 0)
+    keep = order[(c64[order] >= 0) & (c64[order] < num_items)]
+    return colptr, users[keep].to(torch.int32), val[keep].contiguous()
+
+
+def build_csr(user_pos, item_pos, rating, num_users, num_items):
+    """``(rowptr (U + 1) int64, col int32, val fp32)`` of samples in any order: torch ops on the samples' device."""
+    order = torch.argsort(user_pos * num_items + item_pos, stable=True)
+    rowptr = torch.zeros(num_users + 1, dtype=torch.int64, device=user_pos.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(user_pos, minlength=num_users), 0)
+    return rowptr, item_pos[order].to(torch.int32), rating[order].contiguous()
+
+
 class ItemKNN:
     """Item-item k-nearest-neighbours over the rating matrix (csrc/knn.hip, THE CONTRACT in include/ncf_abi.h): shrunk cosine
     similarities ``s_ij = cos(i, j) * co / (co + shrink)`` of items co-rated by at least ``min_support`` users, the ``k`` largest
@@ -272,19 +300,7 @@ class ItemKNN:
         self.num_items_ = None
 
     # ------------------------------------------------------------------ fit
-    @staticmethod
-    def build_transpose(rowptr, col, val, num_items):
-        """``(colptr (I + 1) int64, row int32, tval fp32)``: the CSR by item, torch ops on whatever device the CSR is on.  A stable
-        sort of the entries on their column keeps the users of a column in ascending order."""
-        counts = rowptr[1:] - rowptr[:-1]
-        users = torch.repeat_interleave(torch.arange(counts.numel(), device=col.device), counts)
-        c64 = col.to(torch.int64)
-        order = torch.argsort(c64, stable=True)
-        colptr = torch.zeros(num_items + 1, dtype=torch.int64, device=col.device)
-        inside = c64[(c64 >= 0) & (c64 < num_items)]           # an id outside the items is the kernels' to flag, not bincount's to index
-        colptr[1:] = torch.cumsum(torch.bincount(inside, minlength=num_items), 0)
-        keep = order[(c64[order] >= 0) & (c64[order] < num_items)]
-        return colptr, users[keep].to(torch.int32), val[keep].contiguous()
+    build_transpose = staticmethod(build_transpose)
 
     def fit_csr(self, rowptr, col, val, num_items, block_bytes: int = 256 << 20, col_tile: int = 0):
         """Fits on a user CSR on the GPU: ``rowptr`` (U + 1) int64, ``col`` int32 item positions strictly ascending inside a row,
@@ -336,13 +352,7 @@ class ItemKNN:
         rowptr, col, val = self.build_csr(user_pos, item_pos, rating, num_users, num_items)
         return self.fit_csr(rowptr, col, val, num_items, **fit_args)
 
-    @staticmethod
-    def build_csr(user_pos, item_pos, rating, num_users, num_items):
-        """``(rowptr (U + 1) int64, col int32, val fp32)`` of samples in any order: torch ops on the samples' device."""
-        order = torch.argsort(user_pos * num_items + item_pos, stable=True)
-        rowptr = torch.zeros(num_users + 1, dtype=torch.int64, device=user_pos.device)
-        rowptr[1:] = torch.cumsum(torch.bincount(user_pos, minlength=num_users), 0)
-        return rowptr, item_pos[order].to(torch.int32), rating[order].contiguous()
+    build_csr = staticmethod(build_csr)
 
     def fit_dataset(self, dataset, device="cuda", **fit_args):
         """fit on the positions and ratings of a FixedPointwiseDataset over an index provider (its ``resident_inputs()``)."""
@@ -409,3 +419,186 @@ class ItemKNN:
         out = native.knn_predict(rowptr, col, val, user_rows, item_pos, self.nb_pos_, self.nb_sim_, self.nb_cnt_, self.weighted_average,
                                  self.fill)
         return out if clip is None else out.clamp(float(clip[0]), float(clip[1]))
+
+
+# ---------------------------------------------------------------------------------------- ImplicitALS
+def _mf_of_tables(user_table, item_table):
+    """The project's MF module over two (rows, F) fp32 tables: zero Linear biases, frozen and in eval mode, on the tables' device."""
+    from .neural_collaborative_filtering.models.mf import MF
+    F = user_table.shape[1]
+    mf = MF(item_dim=item_table.shape[0], user_dim=user_table.shape[0], item_emb=F, user_emb=F).to(user_table.device)
+    with torch.no_grad():
+        for lin, tab in ((mf.user_embeddings[0], user_table), (mf.item_embeddings[0], item_table)):
+            lin.weight = torch.nn.Parameter(tab.contiguous().t(), requires_grad=False)      # id-major, as row_major_embedding_ lays it
+            lin.bias.zero_()
+    return mf.requires_grad_(False).eval()
+
+
+class ImplicitALS:
+    """Implicit-feedback ALS (csrc/als.hip, THE CONTRACT in include/ncf_abi.h): ``n_iters`` iterations of the user half-sweep followed
+    by the item half-sweep, each row the exact minimiser ``(Y^T Y + sum (alpha v) y y^T + reg I)^-1 sum (1 + alpha v) y`` by Cholesky.
+    ``fit`` / ``fit_dataset`` / ``fit_csr``; then ``as_mf()`` (the project's MF with the two tables: every ranking and evaluation
+    function takes it), ``predict``, ``fold_in_users`` (the exact vectors of new users against the fixed item table) and
+    ``recommend_new_users``.  A fit is a fixed function of its inputs, bit for bit.  There is no host path."""
+
+    def __init__(self, n_factors=64, n_iters=15, reg=0.01, alpha=40.0, init_sd=0.01):
+        if isinstance(n_factors, bool) or not isinstance(n_factors, (int, np.integer)) or not 1 <= n_factors <= native.ALS_MAX_FACTORS:
+            raise ValueError(f"ImplicitALS: n_factors = {n_factors!r} (an integer in 1 .. {native.ALS_MAX_FACTORS})")
+        if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
+            raise ValueError(f"ImplicitALS: n_iters = {n_iters!r} (an integer >= 0)")
+        for name, v in (("reg", reg), ("alpha", alpha), ("init_sd", init_sd)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"ImplicitALS: {name} = {v!r} is not a finite number")
+        if not reg > 0 or alpha < 0 or init_sd < 0:
+            raise ValueError(f"ImplicitALS: reg > 0, alpha >= 0 and init_sd >= 0 (got {reg}, {alpha}, {init_sd})")
+        self.n_factors, self.n_iters = int(n_factors), int(n_iters)
+        self.reg, self.alpha, self.init_sd = float(reg), float(alpha), float(init_sd)
+        self.user_factors_ = self.item_factors_ = None      # (U, F) / (I, F) fp32
+        self.item_gram_ = None                              # (F, F) fp32 Gram matrix of the item table: what fold-in solves against
+        self.loss_ = []
+        self._mf = None
+
+    # ------------------------------------------------------------------ fit
+    def fit_csr(self, rowptr, col, val, num_items, generator: Optional[torch.Generator] = None, track_loss: bool = False,
+                block_bytes: int = native.ALS_BLOCK_BYTES):
+        """Fits on a user CSR on the GPU: ``rowptr`` (U + 1) int64, ``col`` int32 item positions strictly ascending inside a row,
+        ``val`` fp32 >= 0 (SparseRatings' arrays as they are).  The tables start as N(0, init_sd) draws from ``generator`` (one
+        normal_ of (U, F), then one of (I, F), on the generator's device), rows without any entry as zeros, which they stay.  With
+        ``track_loss``, ``loss_`` holds the float64 objective after every half-sweep (a diagnostic by torch operations; it
+        synchronises once at the end).  ``block_bytes`` sizes the scratch buffer of rows longer than a segment and changes no bit."""
+        rowptr, col, val = _knn_ratings("ImplicitALS.fit_csr", (rowptr, col, val))
+        I, U = int(num_items), rowptr.numel() - 1
+        if I < 1 or U < 1 or col.numel() == 0:
+            raise ValueError(f"ImplicitALS: nothing to fit ({col.numel()} ratings, {U} users, {I} items)")
+        dev = rowptr.device
+        if dev.type != "cuda" or col.device != dev or val.device != dev:
+            raise RuntimeError(f"ImplicitALS.fit_csr runs on the GPU: the CSR must live on one GPU (got {dev}, {col.device}, {val.device}); "
+                               "there is no CPU path")
+        F = self.n_factors
+        colptr, row, tval = build_transpose(rowptr, col, val, I)
+        tables = []
+        for rows, ptr in ((U, rowptr), (I, colptr)):
+            gdev = generator.device if generator is not None else dev
+            t = torch.empty((rows, F), dtype=torch.float32, device=gdev).normal_(0.0, self.init_sd, generator=generator).to(dev)
+            t[ptr[1:] == ptr[:-1]] = 0.0
+            tables.append(t)
+        X, Y = tables
+        users, items = torch.arange(U, device=dev), torch.arange(I, device=dev)
+        plan_u, plan_i = native.als_plan(rowptr, users, F, block_bytes), native.als_plan(colptr, items, F, block_bytes)
+        entry_user = torch.repeat_interleave(users, rowptr[1:] - rowptr[:-1]) if track_loss else None
+        losses = []
+        for _ in range(self.n_iters):
+            native.als_solve_rows(rowptr, col, val, users, Y, native.als_gram(Y), self.alpha, self.reg, out=X, out_by_row=True, plan=plan_u)
+            if track_loss:
+                losses.append(self._objective(entry_user, col, val, X, Y))
+            native.als_solve_rows(colptr, row, tval, items, X, native.als_gram(X), self.alpha, self.reg, out=Y, out_by_row=True, plan=plan_i)
+            if track_loss:
+                losses.append(self._objective(entry_user, col, val, X, Y))
+        self.user_factors_, self.item_factors_, self.item_gram_ = X, Y, native.als_gram(Y)
+        self.num_users_, self.num_items_, self._mf = U, I, None
+        self.loss_ = [float(v) for v in torch.stack(losses).cpu()] if losses else []
+        self.check()
+        return self
+
+    def _objective(self, entry_user, col, val, X, Y, chunk=1 << 20):
+        """sum over the entries of c (1 - s)^2 - s^2, + sum_u x_u^T (Y^T Y) x_u, + reg (|X|^2 + |Y|^2) as a float64 device scalar, with
+        the alpha and reg the kernels see (their fp32 values)."""
+        alpha, reg = float(np.float32(self.alpha)), float(np.float32(self.reg))
+        X64, Y64 = X.double(), Y.double()
+        acc = ((X64 @ (Y64.t() @ Y64)) * X64).sum() + reg * ((X64 * X64).sum() + (Y64 * Y64).sum())
+        for e0 in range(0, col.numel(), chunk):
+            e1 = min(col.numel(), e0 + chunk)
+            s = (X64[entry_user[e0:e1]] * Y64[col[e0:e1].long()]).sum(1)
+            c = 1.0 + alpha * val[e0:e1].double()
+            acc = acc + (c * (1.0 - s) ** 2 - s * s).sum()
+        return acc
+
+    def fit(self, user_pos, item_pos, rating, num_users, num_items, generator: Optional[torch.Generator] = None, track_loss: bool = False,
+            **fit_args):
+        """Fits on int64 positions and fp32 values that live on the GPU (KernelMF.fit's arguments): the CSR is built on the device by
+        a stable sort on (user, item).  A (user, item) pair given twice raises in check()."""
+        n = user_pos.numel() if torch.is_tensor(user_pos) else None
+        for t, what in ((user_pos, "user_pos"), (item_pos, "item_pos")):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != n:
+                raise ValueError(f"ImplicitALS: {what} must be a 1-D int64 tensor of {n} positions")
+        if not torch.is_tensor(rating) or rating.dtype != torch.float32 or rating.dim() != 1 or rating.numel() != n:
+            raise ValueError(f"ImplicitALS: rating must be a 1-D float32 tensor of {n} entries")
+        num_users, num_items = int(num_users), int(num_items)
+        if n == 0 or num_users < 1 or num_items < 1:
+            raise ValueError(f"ImplicitALS: nothing to fit ({n} ratings, {num_users} users, {num_items} items)")
+        dev = user_pos.device
+        if dev.type != "cuda" or item_pos.device != dev or rating.device != dev:
+            raise RuntimeError(f"ImplicitALS.fit runs on the GPU: the samples must live on one GPU (got {dev}, {item_pos.device}, "
+                               f"{rating.device}); there is no CPU path")
+        rowptr, col, val = build_csr(user_pos, item_pos, rating, num_users, num_items)
+        return self.fit_csr(rowptr, col, val, num_items, generator=generator, track_loss=track_loss, **fit_args)
+
+    def fit_dataset(self, dataset, device="cuda", **fit_args):
+        """fit on the positions and ratings of a FixedPointwiseDataset over an index provider (its ``resident_inputs()``)."""
+        dev = torch.device(device)
+        res = dataset.resident_inputs(dev)
+        if res is None:
+            raise ValueError("ImplicitALS.fit_dataset: the dataset's provider hands out dense rows, not positions")
+        u, i = (t.to(dev) for t in res.tensors)
+        if res.on_chunk is not None:
+            u, i = res.on_chunk(u, i)
+        cp = dataset.content_provider
+        return self.fit(u.contiguous(), i.contiguous(), res.targets.to(dev), cp.get_num_users(), cp.get_num_items(), **fit_args)
+
+    def check(self):
+        """Synchronises.  Raises when a half-sweep of this device met what it refuses (native.check_als): ValueError for a row whose
+        columns do not strictly ascend (a pair given twice), a value that is negative or not finite or a pivot that is not positive,
+        IndexError for an id or a pointer outside its array; each raises once and is then cleared."""
+        self._fitted()
+        native.check_als(self.user_factors_.device)
+
+    def _fitted(self):
+        if self.user_factors_ is None:
+            raise RuntimeError("ImplicitALS: not fitted")
+
+    # ------------------------------------------------------------------ scoring
+    def as_mf(self):
+        """The project's MF module over the two tables (score = x_u . y_i), zero Linear biases, frozen and in eval mode, on the fit's
+        device.  top_k_items, rank_of_items, eval_full_ranking and [state_dict, kwargs] checkpoints work on it as on any MF."""
+        self._fitted()
+        if self._mf is None:
+            self._mf = _mf_of_tables(self.user_factors_, self.item_factors_)
+        return self._mf
+
+    def predict(self, user_pos, item_pos):
+        """(n,) preference scores x_u . y_i for int64 positions on the fit's device: as_mf()'s forward."""
+        _positions(user_pos, "user_pos")
+        _positions(item_pos, "item_pos", user_pos.numel())
+        with torch.no_grad():
+            return self.as_mf()(user_pos.contiguous(), item_pos.contiguous()).view(-1)
+
+    # ------------------------------------------------------------------ fold-in
+    def fold_in_users(self, ratings, user_rows, block_bytes: int = native.ALS_BLOCK_BYTES):
+        """(B, F) fp32 vectors of the rows ``user_rows`` (int64) of ``ratings`` — a SparseRatings or a (rowptr, col, val) tuple over the
+        fitted items, not necessarily the fitted ratings, so new users work: one half-sweep against the fixed item table and its
+        cached Gram matrix, the exact minimiser for each row.  A row without entries gives zeros.  Call check() to learn of refused
+        input."""
+        self._fitted()
+        rowptr, col, val = _knn_ratings("ImplicitALS.fold_in_users", ratings)
+        if not torch.is_tensor(user_rows) or user_rows.dtype != torch.int64 or user_rows.dim() != 1:
+            raise ValueError("ImplicitALS.fold_in_users: user_rows must be a 1-D int64 tensor of rows of ratings")
+        return native.als_solve_rows(rowptr, col, val, user_rows.contiguous(), self.item_factors_, self.item_gram_, self.alpha, self.reg,
+                                     block_bytes=block_bytes)
+
+    def recommend_new_users(self, ratings, user_rows, k, exclude_rated=True, **top_k_args):
+        """``top_k_items``' tuple ``(scores (B, k), item_positions (B, k) int64, counts (B,) int32)`` for the rows ``user_rows`` of
+        ``ratings`` folded in: the ``k`` best items of an MF over the folded vectors and the fitted item table, the rows' own items left
+        out with ``exclude_rated``."""
+        from . import recommend
+        vectors = self.fold_in_users(ratings, user_rows)
+        rowptr, col, _ = _knn_ratings("ImplicitALS.recommend_new_users", ratings)
+        exclude = recommend.rated_exclusion(_RatingsView(rowptr, col), user_rows) if exclude_rated else None
+        users = torch.arange(user_rows.numel(), device=vectors.device)
+        return recommend.top_k_items(_mf_of_tables(vectors, self.item_factors_), users, k, exclude=exclude, **top_k_args)
+
+
+class _RatingsView:
+    """What recommend.rated_exclusion reads of a SparseRatings."""
+
+    def __init__(self, rowptr, col):
+        self.rowptr, self.col = rowptr, col

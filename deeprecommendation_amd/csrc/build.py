@@ -10,7 +10,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ["abi.hip", "gather.hip", "mlp_fused.hip", "linear.hip", "spmm.hip", "attn.hip", "attn_split.hip", "attn_cand.hip", "attn_tail.hip", "attn_cross.hip", "attn_explain.hip", "attn_stats.hip", "mlp_bf16.hip", "mlp_bf16_ws8.hip", "backward.hip", "adam_rows.hip", "exchange.hip", "dense_csr.hip", "pair_rows.hip", "probe.hip", "topk.hip", "dot_topk.hip", "mlp_topk.hip", "mlp_partial.hip", "negsample.hip", "rank.hip", "edge_keep.hip", "gat.hip", "user_profiles.hip", "kmf.hip", "mmr.hip", "knn.hip"]
+SOURCES = ["abi.hip", "gather.hip", "mlp_fused.hip", "linear.hip", "spmm.hip", "attn.hip", "attn_split.hip", "attn_cand.hip", "attn_tail.hip", "attn_cross.hip", "attn_explain.hip", "attn_stats.hip", "mlp_bf16.hip", "mlp_bf16_ws8.hip", "backward.hip", "adam_rows.hip", "exchange.hip", "dense_csr.hip", "pair_rows.hip", "probe.hip", "topk.hip", "dot_topk.hip", "mlp_topk.hip", "mlp_partial.hip", "negsample.hip", "rank.hip", "edge_keep.hip", "gat.hip", "user_profiles.hip", "kmf.hip", "mmr.hip", "knn.hip", "als.hip"]
 LIB = os.path.join(PKG, "libncf_hip.so")
 ARCH = "gfx950"
 # per-file flags.  mlp_bf16.hip: MFMA accumulators in VGPRs instead of AGPRs (the ReLU / bf16 conversion of the hidden
@@ -20,9 +20,11 @@ ARCH = "gfx950"
 # kmf.hip: the same — every product and sum of the SGD update is rounded on its own (the fp32 loop of tests/kmf_ref.py, bit for bit)
 # mmr.hip: the same — every product and sum of a similarity and of an MMR value is rounded on its own (tests/mmr_ref.py, bit for bit)
 # knn.hip: the same — every product, sum, quotient and square root of a similarity and of a score (tests/knn_ref.py, bit for bit)
+# als.hip: the same — every product, sum, quotient and square root of a normal matrix, its Cholesky factor and the substitutions
+# (tests/als_ref.py, bit for bit)
 EXTRA_FLAGS = {"mlp_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "mlp_bf16_ws8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "user_profiles.hip": ["-ffp-contract=off"], "kmf.hip": ["-ffp-contract=off"], "mmr.hip": ["-ffp-contract=off"],
-               "knn.hip": ["-ffp-contract=off"]}
+               "knn.hip": ["-ffp-contract=off"], "als.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

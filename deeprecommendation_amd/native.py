@@ -155,6 +155,10 @@ SIGNATURES = {
                                 ctypes.c_float, _c_int, _c_p, _c_i64, _c_p, _c_p]),
     "ncf_knn_predict": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int,
                                  ctypes.c_float, _c_p, _c_p, _c_p]),
+    "ncf_als_gram_workspace_bytes": (_c_size, [_c_i64, _c_int]),
+    "ncf_als_gram": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_size, _c_p]),
+    "ncf_als_solve_rows": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, ctypes.c_float,
+                                    ctypes.c_float, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "ncf_mmr_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "ncf_mmr_rerank": (_c_int, [_c_p, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, ctypes.c_float, _c_int, _c_p, _c_p,
                                 _c_p, _c_p, _c_p]),
@@ -1750,6 +1754,160 @@ def knn_predict(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, user
     if n:
         _check(lib.ncf_knn_predict(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(users), _ptr(items), n, _ptr(nb_pos), _ptr(nb_sim),
                                    _ptr(nb_cnt), I, N, 1 if weighted_average else 0, fill, _ptr(out), _ptr(_oob_flag(dev)), _stream(rowptr)))
+    return out
+
+
+ALS_MAX_FACTORS, ALS_GRAM_ROWS, ALS_SEG = 128, 256, 512       # include/ncf_abi.h NCF_ALS_*
+ALS_FLAG_COL, ALS_FLAG_PTR, ALS_FLAG_ORDER, ALS_FLAG_VAL, ALS_FLAG_PIVOT = 1, 2, 4, 8, 16
+ALS_BLOCK_BYTES = 256 << 20
+
+
+def als_flag(device) -> torch.Tensor:
+    """The sticky int32 flag word of ncf_als_solve_rows on ``device`` (bits ALS_FLAG_*)."""
+    return _flag("als", device)
+
+
+def check_als(device, flag: Optional[torch.Tensor] = None):
+    """Synchronising check of the ImplicitALS flag word: raises, and clears it, when a half-sweep met a column outside the fixed
+    table or a value that is negative or not finite (each such entry was skipped), a row outside the CSR or a broken pointer pair, a
+    row whose columns do not strictly ascend or a pivot that is not positive (each such row was written as zeros).  IndexError when
+    an id or a pointer was at fault, ValueError otherwise."""
+    f = als_flag(device) if flag is None else flag
+    bits = int(f.item())
+    if bits:
+        f.zero_()
+        what = [w for b, w in ((ALS_FLAG_COL, "a column outside the fixed table"), (ALS_FLAG_PTR, "a row or a row pointer outside the ratings"),
+                               (ALS_FLAG_ORDER, "a row whose columns do not strictly ascend"),
+                               (ALS_FLAG_VAL, "a value that is negative or not finite"),
+                               (ALS_FLAG_PIVOT, "a pivot that is not positive and finite")) if bits & b]
+        raise (IndexError if bits & (ALS_FLAG_COL | ALS_FLAG_PTR) else ValueError)("ImplicitALS: " + ", ".join(what) + f" (flag {bits})")
+
+
+def _als_table(who, t, what, F=None):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{who}: {what} must be a 2-D float32 tensor with unit inner stride")
+    F = t.shape[1] if F is None else _knn_int(who, F, "F", 1, ALS_MAX_FACTORS)
+    if not 1 <= F <= ALS_MAX_FACTORS or t.shape[1] < F:
+        raise ValueError(f"{who}: F = {F} factors with rows of {t.shape[1]} floats (1 .. {ALS_MAX_FACTORS}, at most the row)")
+    return F
+
+
+def als_gram(T: torch.Tensor, F: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(F, F) fp32 Gram matrix of the first ``F`` columns (default: all) of the (rows, >= F) fp32 table ``T`` (ncf_als_gram, THE
+    CONTRACT in include/ncf_abi.h): chunks of 256 rows summed serially, the chunks added in ascending order, the upper triangle the
+    mirror.  Checked before the device is; two launches on the current stream."""
+    who = "als_gram"
+    F = _als_table(who, T, "T", F)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (F, F) or not out.is_contiguous()):
+        raise ValueError(f"{who}: out must be a contiguous ({F}, {F}) float32 tensor")
+    _dev(T, "T")
+    if out is not None:
+        _dev(out, "out")
+    lib = load_library()
+    rows = T.shape[0]
+    if out is None:
+        out = torch.empty((F, F), dtype=torch.float32, device=T.device)
+    nbytes = int(lib.ncf_als_gram_workspace_bytes(rows, F))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=T.device) if nbytes else None
+    _check(lib.ncf_als_gram(_ptr(T), rows, max(T.stride(0), F), F, _ptr(out), _ptr(ws), nbytes, _stream(T)))
+    return out
+
+
+def als_plan(rowptr: torch.Tensor, rows: torch.Tensor, F: int, block_bytes: int = ALS_BLOCK_BYTES):
+    """The plan of a half-sweep over the listed ``rows`` (int64) of a CSR with pointers ``rowptr``: a list of batches ``(k0, k1,
+    seg_base, seg_row, n_slots)`` of consecutive listed rows whose segments beyond the first (rows longer than ALS_SEG entries) fit a
+    scratch buffer of ``block_bytes``.  The bits of a half-sweep do not depend on the batches.  Reads the row lengths on the host (one
+    synchronisation); a row outside the CSR or a broken pointer pair plans as a short row, which the kernel reports."""
+    import numpy as np
+    who = "als_plan"
+    _vec1d(who, rowptr, "rowptr", torch.int64)
+    _vec1d(who, rows, "rows", torch.int64)
+    F = _knn_int(who, F, "F", 1, ALS_MAX_FACTORS)
+    block_bytes = _knn_int(who, block_bytes, "block_bytes", 1, 2 ** 62)
+    R, B = rowptr.numel() - 1, rows.numel()
+    if R < 0:
+        raise ValueError(f"{who}: rowptr is empty")
+    cap = min(block_bytes // (4 * F * F), 2 ** 31 - 1)
+    if B == 0 or R == 0:
+        return [(0, B, None, None, 0)] if B else []
+    inside = (rows >= 0) & (rows < R)
+    r = rows.clamp(0, R - 1)
+    beg, end = rowptr[r], rowptr[r + 1]
+    n = torch.where(inside & (beg >= 0) & (end >= beg) & (end <= rowptr[-1].clamp_min(0)), end - beg, torch.zeros_like(beg))
+    nseg = ((n + (ALS_SEG - 1)) // ALS_SEG).cpu().numpy()
+    nl = np.where(nseg > 1, nseg, 0)
+    if nl.max() > cap:
+        raise ValueError(f"{who}: block_bytes = {block_bytes} holds {cap} segments of {F} x {F} floats; the longest row has {int(nl.max())}")
+    cum = np.cumsum(nl)
+    if cum[-1] == 0:
+        return [(0, B, None, None, 0)]
+    batches, k0, done = [], 0, 0
+    while k0 < B:
+        k1 = int(np.searchsorted(cum, done + cap, side="right"))          # the listed rows [k0, k1) hold at most cap segments
+        part = nl[k0:k1]
+        n_slots = int(part.sum())
+        if n_slots:
+            base = np.where(part > 0, cum[k0:k1] - part - done, -1).astype(np.int64)
+            seg_row = np.repeat(np.arange(k1 - k0, dtype=np.int64), part)
+            batches.append((k0, k1, torch.from_numpy(base).to(rows.device), torch.from_numpy(seg_row).to(rows.device), n_slots))
+        else:
+            batches.append((k0, k1, None, None, 0))
+        k0, done = k1, int(cum[k1 - 1])
+    return batches
+
+
+def als_solve_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, rows: torch.Tensor, T: torch.Tensor, G: torch.Tensor,
+                   alpha: float, reg: float, out: Optional[torch.Tensor] = None, out_by_row: bool = False, plan=None,
+                   block_bytes: int = ALS_BLOCK_BYTES, flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ALS half-sweep (ncf_als_solve_rows, THE CONTRACT in include/ncf_abi.h): for each listed row (``rows`` int64) of the CSR
+    ``rowptr`` int64 / ``col`` int32 strictly ascending in a row / ``val`` fp32 >= 0 over the rows of the fixed (n_t, >= F) fp32 table
+    ``T``, x = (G + sum (alpha v) t t^T + reg I)^-1 sum (1 + alpha v) t by Cholesky.  ``G`` is the contiguous (F, F) Gram matrix
+    (als_gram(T)), which also fixes F.  Returns the (B, F) rows, row k for ``rows[k]``; with ``out_by_row`` they are written to the rows
+    ``rows[k]`` of ``out`` ((R, >= F); required then) and no other row of it is touched.  ``plan``: als_plan's batches for these rows
+    (built here, with one synchronisation, when absent); ``block_bytes`` sizes the scratch buffer of the rows longer than one segment
+    and does not change a bit.  What the kernel refuses sets ``flag`` (default: the device's word, check_als).  Checked before the
+    device is; nothing else synchronises."""
+    who = "als_solve_rows"
+    R, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    _vec1d(who, rows, "rows", torch.int64)
+    B = rows.numel()
+    if not torch.is_tensor(G) or G.dtype != torch.float32 or G.dim() != 2 or G.shape[0] != G.shape[1] or not G.is_contiguous():
+        raise ValueError(f"{who}: G must be a contiguous (F, F) float32 tensor")
+    F = _als_table(who, T, "T", G.shape[0])
+    alpha = _knn_float(who, alpha, "alpha", 0.0)
+    reg = _knn_float(who, reg, "reg", 0.0)
+    if not reg > 0:
+        raise ValueError(f"{who}: reg = {reg} is not > 0")
+    if not isinstance(out_by_row, bool):
+        raise ValueError(f"{who}: out_by_row = {out_by_row!r} is not a bool")
+    block_bytes = _knn_int(who, block_bytes, "block_bytes", 1, 2 ** 62)
+    n_out = R if out_by_row else B
+    if out is None and out_by_row:
+        raise ValueError(f"{who}: out_by_row writes into the caller's table: out is required")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n_out or out.shape[1] < F
+                            or (out.shape[1] > 1 and out.stride(1) != 1)):
+        raise ValueError(f"{who}: out must be a ({n_out}, >= {F}) float32 tensor with unit inner stride")
+    _out1d(who, flag, "flag", torch.int32, 1)
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (rows, "rows"), (T, "T"), (G, "G"), (out, "out"), (flag, "flag")):
+        if t is not None:
+            _dev(t, what)
+    lib = load_library()
+    dev = rowptr.device
+    if out is None:
+        out = torch.empty((B, F), dtype=torch.float32, device=dev)
+    if flag is None:
+        flag = als_flag(dev)
+    if plan is None:
+        plan = als_plan(rowptr, rows, F, block_bytes)
+    ldo = max(out.stride(0), F)
+    for k0, k1, seg_base, seg_row, n_slots in plan:
+        if not 0 <= k0 <= k1 <= B:
+            raise ValueError(f"{who}: the plan lists rows [{k0}, {k1}) of {B}")
+        scratch = torch.empty(n_slots * F * F, dtype=torch.float32, device=dev) if n_slots else None
+        dst = out if out_by_row else out[k0:k1]
+        _check(lib.ncf_als_solve_rows(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(rows[k0:k1]), k1 - k0, _ptr(T), T.shape[0],
+                                      max(T.stride(0), F), F, _ptr(G), alpha, reg, _ptr(dst), ldo, 1 if out_by_row else 0, _ptr(seg_base),
+                                      _ptr(seg_row), n_slots, _ptr(scratch), _ptr(flag), _stream(rowptr)))
     return out
 
 

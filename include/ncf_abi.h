@@ -911,6 +911,71 @@ int ncf_knn_predict(const int64_t* dev_rowptr, const int32_t* dev_col, const flo
                     int32_t* dev_oob_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * ImplicitALS (csrc/als.hip) — implicit-feedback alternating least squares, the baseline a full-catalogue top-K number is usually
+ * asked to beat (Hu, Koren & Volinsky 2008; implicit's AlternatingLeastSquares; the iALS of Rendle et al. 2021).  Replaces: nothing
+ * in the reference; a torch composition builds a dense (rows, F, F) tensor of normal matrices whose summation order is not fixed.
+ * Ratings: a CSR dev_rowptr (R + 1, int64), dev_col (int32 positions into the fixed table T, STRICTLY ASCENDING inside a row) and
+ * dev_val (fp32, finite and >= 0), nnz entries each.  The confidence of a stored entry is 1 + alpha * val, its preference 1.  T is
+ * (n_t, F) fp32 with rows of ldt floats, 1 <= F <= 128 (NCF_ALS_MAX_FACTORS); G is (F, F) fp32, contiguous, only its lower
+ * triangle is read.  One half-sweep recomputes a row u as x_u = A_u^-1 b_u with
+ *       A_u = G + sum over the row's entries of (alpha * val_e) * t_e t_e^T + reg * I,     b_u = sum of (1 + alpha * val_e) * t_e,
+ * t_e being T's row at the entry's column; with G = T^T T that is the exact minimiser of the iALS objective in x_u.
+ * THE CONTRACT, all in fp32, every product, sum, difference, quotient and square root rounded on its own (no FMA; division and
+ * sqrtf are the correctly rounded IEEE operations, hipcc's default for fp32 — csrc/als.hip is built without any fast-math flag):
+ *   Gram (ncf_als_gram): the rows of T are taken in chunks of 256 (NCF_ALS_GRAM_ROWS); chunk c holds rows 256 c .. 256 c + 255.
+ *       P_c[a][b] = +0.0f;  for the chunk's rows t in ascending order, for a >= b:  P_c[a][b] = P_c[a][b] + t[a] * t[b]
+ *       G[a][b] = +0.0f;  for c = 0, 1, ... in that order:  G[a][b] = G[a][b] + P_c[a][b];      G[b][a] = G[a][b]
+ *   Row u (ncf_als_solve_rows), its entries e = 0, 1, ..., n - 1 in stored order, cut into segments of 512 (NCF_ALS_SEG):
+ *       w_e = alpha * val_e
+ *       S_s[a][b] = +0.0f;  for the entries e of segment s in stored order, for a >= b:  S_s[a][b] = S_s[a][b] + (w_e * t_e[a]) * t_e[b]
+ *       A[a][b] = G[a][b];  for s = 0, 1, ... in that order:  A[a][b] = A[a][b] + S_s[a][b];  then  A[a][a] = A[a][a] + reg
+ *       b[a] = +0.0f;  for ALL the row's entries e in stored order:  b[a] = b[a] + (1.0f + w_e) * t_e[a]
+ *   Cholesky A = L L^T on the lower triangle, for j = 0, 1, ..., F - 1:
+ *       s = A[j][j];  for k = 0 .. j - 1 in ascending order:  s = s - L[j][k] * L[j][k];      L[j][j] = sqrtf(s)
+ *       for i > j:  v = A[i][j];  for k = 0 .. j - 1 in ascending order:  v = v - L[i][k] * L[j][k];      L[i][j] = v / L[j][j]
+ *   forward:   for i = 0 .. F - 1:  v = b[i];  for k = 0 .. i - 1 in ascending order:  v = v - L[i][k] * z[k];      z[i] = v / L[i][i]
+ *   backward:  for i = F - 1 .. 0:  v = z[i];  for k = F - 1 .. i + 1 in descending order:  v = v - L[k][i] * x[k];      x[i] = v / L[i][i]
+ *   A row without entries is written as zeros, without a solve.  No float atomics anywhere and one fixed order of every sum: the
+ *   same inputs give the same bits for any grid, CU count or blocking of the rows.
+ * ncf_als_gram: one workgroup per chunk writes P_c into dev_workspace (ncf_als_gram_workspace_bytes(rows, F) bytes: F * F floats
+ * per chunk), a second launch adds the chunks in order and mirrors.  rows == 0 gives G = 0.
+ * ncf_als_solve_rows: the listed rows dev_rows (B, int64) of ANY such CSR of R rows over T's rows — the ratings by user against the
+ * item table, their transpose against the user table, or a foreign CSR against the item table (fold-in of new users).  Row
+ * dev_rows[k] is written to row k of dev_out (rows of ldo floats), or to row dev_rows[k] with out_by_row = 1; no other row of dev_out
+ * is touched.  One workgroup per listed row: T's rows of 16 entries at a time staged in LDS, the lower triangle of A in registers
+ * (tiles of a blocked right-looking elimination, which subtracts the products of every element in exactly the ascending k of the
+ * contract), L in an LDS tile of F x F floats, the two substitutions by one wave.  A row of more than one segment does not become a
+ * serial chain of its normal matrix: the caller lists its segments, one workgroup per segment writes S_s into dev_scratch, and the
+ * row's own workgroup adds them in order — the segment order is the contract, so both forms give the same bits.  The plan:
+ * dev_seg_base (B, int64) is the first slot of listed row k in dev_scratch (n_slots slots of F * F floats), -1 for a row of at most
+ * one segment; dev_seg_row (n_slots, int64) is the k whose segment a slot holds (slot j holds segment j - dev_seg_base[k]).  Both
+ * may be NULL with n_slots == 0, when no listed row is longer than one segment.  The right-hand side b stays one serial sum over
+ * the row's entries in the row's own workgroup (64 entries staged at a time where F >= 64: the tile L will take is free until
+ * then): that chain is the floor of a half-sweep.
+ * The kernels check their own inputs and never dereference an unchecked id; bits of the sticky *dev_flag (when non-NULL):
+ *       bit 0: a column outside [0, n_t) — the entry is skipped (it adds nothing to S, A or b)
+ *       bit 1: a listed row outside [0, R), a pointer pair that decreases or lies outside [0, nnz], or a plan that does not hold the
+ *              row's segments — the row is written as zeros (a listed row outside [0, R) with out_by_row = 1 writes nothing)
+ *       bit 2: a row whose columns do not strictly ascend — the row is written as zeros
+ *       bit 3: a val that is negative or not finite — the entry is skipped
+ *       bit 4: a pivot s that is not > 0 or not finite — the row is written as zeros
+ * Refusals, before any launch, with the entry's name in ncf_last_error(): NCF_EINVAL for a negative size, F outside 1 .. 128,
+ * ld < F, a reg that is not finite or not > 0, an alpha that is not finite or negative, out_by_row not 0 or 1, a float array that
+ * is not 4-byte aligned or an int64 array that is not 8-byte aligned, a workspace that is too small, and a NULL array that the
+ * sizes say is read or written.  A call with nothing to do (B == 0) returns NCF_OK without a launch.
+ * ------------------------------------------------------------------------------------------------ */
+#define NCF_ALS_MAX_FACTORS 128
+#define NCF_ALS_GRAM_ROWS 256
+#define NCF_ALS_SEG 512
+size_t ncf_als_gram_workspace_bytes(int64_t rows, int F);
+int ncf_als_gram(const float* dev_T, int64_t rows, int64_t ld, int F, float* dev_G, void* dev_workspace, size_t workspace_bytes,
+                 ncf_stream_t stream);
+int ncf_als_solve_rows(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t nnz, int64_t R,
+                       const int64_t* dev_rows, int64_t B, const float* dev_T, int64_t n_t, int64_t ldt, int F, const float* dev_G,
+                       float alpha, float reg, float* dev_out, int64_t ldo, int out_by_row, const int64_t* dev_seg_base,
+                       const int64_t* dev_seg_row, int64_t n_slots, float* dev_scratch, int32_t* dev_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Diversified top-K (csrc/mmr.hip) — greedy Maximal Marginal Relevance (MMR) re-ranking of one candidate pool per user, the pools
  * being what ncf_topk_rows / ncf_dot_topk / ncf_mlp_topk return.  Replaces: nothing in the reference, which stops at the relevance
  * list; a torch composition needs a (B, N, N) Gram tensor and K rounds of masked arg-max launches.
