@@ -119,6 +119,68 @@ __device__ __forceinline__ void fused_layer2(const f32x16 (&acc1)[N1 / 32], f32x
     }
 }
 
+// fused_layer2 for ncf_score_fused_partial (mlp_partial.hip) alone: the same steps (same loads, same MFMAs on the same operands in
+// the same order), with the weight stream addressed from a scalar base.  In fused_layer2 every fragment's offset outgrows the load's
+// immediate field and hipcc rebuilds a 64-bit vector address for it (a v_add_co_u32 / v_addc_co_u32 pair or a v_lshl_add_u64, with
+// s_nop pads, between the MFMAs: 33 pairs per tile at 256-128).  Here the fragment of (q = 4 kb + g, nt) is read at
+//   Wp2 + kb's bytes (scalar, one s_add_u32 / s_addc_u32 per k-block) + voff[g] (32-bit VGPR, set up once) + nt KiB (immediate),
+// the SGPR-base form layer 1's loads take.  The two empty asm statements only keep hipcc from folding the parts back together; the
+// scalar part passes through one as an offset, not as a pointer, so the loads stay global loads.  The other kernels keep
+// fused_layer2: their instructions are pinned (see fused_row above), and DESIGN 4.20 has what this form measured.
+// at_step(q) runs ahead of step q: a hook for the diagnostic stamp build, nothing otherwise.
+struct fused_no_hook {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+template <int N1, int N2, class Hook = fused_no_hook>
+__device__ __forceinline__ void fused_layer2_sbase(const f32x16 (&acc1)[N1 / 32], f32x16 (&acc2)[N2 / 32], const float* b2,
+                                                   const float* Wp2, int lane, Hook at_step = Hook()) {
+    constexpr int NT2 = N2 / 32, Q2 = N1 / 8;
+    const int h = lane >> 5;
+    const char* wb = reinterpret_cast<const char*>(Wp2);
+    const char* kbase = wb;
+    uint32_t voff[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        voff[g] = (uint32_t)lane * 16u + g * NT2 * 1024;
+        asm("" : "+v"(voff[g]));
+    }
+    f32x4 w[2][NT2];
+#pragma unroll
+    for (int nt = 0; nt < NT2; ++nt) {  // first-use order: tile nt of b2, then its step-0 fragment
+        fused_load_tile(acc2[nt], b2, nt, h);
+        w[0][nt] = *reinterpret_cast<const f32x4*>(kbase + voff[0] + nt * 1024);
+    }
+#pragma unroll
+    for (int q = 0; q < Q2; ++q) {  // q = 4*kb + g : k-block kb of H1 (= tile kb of acc1), group g
+        const int cur = q & 1, nxt = cur ^ 1;
+        const int kb = q >> 2, g = q & 3;
+        at_step(q);
+        f32x4 hv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hv[j] = fmaxf(acc1[kb][4 * g + j], 0.f);  // ReLU (util.py:15)
+#pragma unroll
+        for (int nt = 0; nt < NT2; ++nt) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                acc2[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cur][nt][j], hv[j], acc2[nt], 0, 0, 0);
+            if (q + 1 < Q2) {
+                if (nt == 0 && ((q + 1) & 3) == 0) {  // the next k-block's base
+                    uint32_t koff = ((q + 1) >> 2) * 4 * NT2 * 1024;
+                    asm("" : "+s"(koff));
+                    kbase = wb + koff;
+                }
+                w[nxt][nt] = *reinterpret_cast<const f32x4*>(kbase + voff[(q + 1) & 3] + nt * 1024);
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT2; ++nt) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMA
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // The 1-wide last layer without its bias: sum_n wl[n] * relu(acc[n]), per lane half over nt, g, j, then half 0 + half 1.
 template <int NT>
 __device__ __forceinline__ float fused_last_sum(const f32x16 (&acc)[NT], const float* wl, int lane) {

@@ -6,11 +6,25 @@
 // not on the pair.  ncf_layer1_partial computes that value once per weight version for every row of A — the same MFMA
 // instructions on the same packed fragments in the same order, with the row of A in the pair's place — and stores it as
 // P[rowsA + 1][N1] in natural neuron order.  ncf_score_fused_partial starts each pair's accumulators from P[ia] and runs
-// layer 1 over table B's groups only; layer 2 and the 1-wide layer are the fused kernel's.  An accumulator register
+// layer 1 over table B's groups only; layer 2 runs the fused kernel's steps with its weight stream addressed from a scalar base
+// (fused_layer2_sbase, mlp_fused.h), the 1-wide layer is the fused kernel's.  An accumulator register
 // stored and loaded back is the same fp32 value, so the scores are bit-identical to ncf_score_fused (denormals, NaN and
 // signed zeros included).  At 128-256-128-1 a 32-pair tile issues 768 MFMAs instead of 1024.
 // Row rowsA of P is what the fused kernel computes for an out-of-range A id (row 0 multiplied by zero at use); a bad id
 // reads it.
+#ifndef NCF_PART_STAMP
+#define NCF_PART_STAMP 0    // 1: diagnostic build, clock readings at six points of the scoring kernel (tools/ab_partial.py --stamp)
+#endif
+#if NCF_PART_STAMP
+#define NCF_STAMP(st, i)                                                                                            \
+    do {                                                                                                            \
+        __builtin_amdgcn_sched_barrier(0);                                                                          \
+        asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(st[2 * (i)]), "=s"(st[2 * (i) + 1])::"memory"); \
+        __builtin_amdgcn_sched_barrier(0);                                                                          \
+    } while (0)
+#else
+#define NCF_STAMP(st, i) do { } while (0)
+#endif
 #include "mlp_fused.h"
 
 #ifndef NCF_PART_WD
@@ -24,6 +38,9 @@
 #endif
 #ifndef NCF_PART_LDS_PF
 #define NCF_PART_LDS_PF 2   // P tiles requested ahead in the LDS form (the only loads on its vector-memory queue); swept 1 .. 8
+#endif
+#ifndef NCF_PART_SBASE
+#define NCF_PART_SBASE 1    // 1: layer 2's weight stream is addressed from a scalar base (fused_layer2_sbase); 0: fused_layer2 (A/B builds)
 #endif
 #ifndef NCF_PART_HYBRID_MAX_PERMILLE
 #define NCF_PART_HYBRID_MAX_PERMILLE 500  // a batch, or a ragged last round, of at most this share of a round goes to ncf_score_fused
@@ -98,7 +115,17 @@ struct PartialArgs {
     const float* Wp1; const float* Wp2; const float* b2;
     const float* wl; const float* bl;
     float* out; int32_t* oob;
+#if NCF_PART_STAMP
+    unsigned long long* stamps;   // diagnostic build only: 12 readings per wave, a buffer of their own
+#endif
 };
+
+#if NCF_PART_STAMP
+// Diagnostic build: shader clock and 100 MHz reference clock at six points of the kernel.  Nothing of it is compiled
+// into the shipped library.
+static unsigned long long* g_stamp_buf = nullptr;
+extern "C" void ncf_partial_stamp_buffer(void* buf) { g_stamp_buf = (unsigned long long*)buf; }
+#endif
 
 // LDS form (LDS = true, partial_in_lds): table B's half of Wp1 is copied once per workgroup into an LDS image in step order
 // (step s = nt*QB + t at wlds[s*64 + lane]: one conflict-free ds_read_b128 per step, counted on lgkmcnt), so the vector-memory
@@ -122,6 +149,10 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
     const int m = lane & 31, h = lane >> 5;
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     const bool live = tile * 32 < a.B;
+#if NCF_PART_STAMP
+    unsigned long long st[12];
+#endif
+    NCF_STAMP(st, 0);
     if (!LDS && !live) return;  // whole wave exits together; the LDS form leaves behind its barrier
     const int64_t p = tile * 32 + m;
     const int64_t pc = p < a.B ? p : a.B - 1;
@@ -161,6 +192,7 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
         for (int i = 0; i < FILL; ++i) wlds[(4 * i + wave) * 64 + lane] = fill[i];
         __syncthreads();
         if (!live) return;
+        NCF_STAMP(st, 1);
         w[0] = wq[0];
         w[1] = wq[64];
         __builtin_amdgcn_sched_barrier(0);  // both reads stay above tile 0: its "1 DS read" groups are for steps 2 ..
@@ -190,16 +222,32 @@ __global__ __launch_bounds__(256, 2) void score_fused_partial_f32_kernel(Partial
         __builtin_amdgcn_sched_barrier(0);
     }
 
-    // ---- layer 2 and the 1-wide layer: the same code as ncf_score_fused's kernel (mlp_fused.h) ----
+    // ---- layer 2 and the 1-wide layer: the steps of ncf_score_fused's kernel (mlp_fused.h), layer 2's weights from a scalar base ----
+    NCF_STAMP(st, 2);
     float score;
     if constexpr (N2 > 0) {
         f32x16 acc2[N2 / 32];
+#if NCF_PART_STAMP
+        fused_layer2_sbase<N1, N2>(acc1, acc2, a.b2, a.Wp2, lane, [&](int q) { if (q == 4) NCF_STAMP(st, 3); });  // 16 MFMAs in
+#elif NCF_PART_SBASE
+        fused_layer2_sbase<N1, N2>(acc1, acc2, a.b2, a.Wp2, lane);
+#else
         fused_layer2<N1, N2>(acc1, acc2, a.b2, a.Wp2, lane);
+#endif
+        NCF_STAMP(st, 4);
         score = fused_last_layer(acc2, a.wl, a.bl, lane);
     } else {
         score = fused_last_layer(acc1, a.wl, a.bl, lane);
     }
     if (h == 0 && p < a.B) a.out[p] = score;
+#if NCF_PART_STAMP
+    __builtin_amdgcn_s_waitcnt(0);   // the score is stored: the exit reading covers it
+    NCF_STAMP(st, 5);
+    if (lane == 0 && a.stamps) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) a.stamps[tile * 12 + i] = st[i];
+    }
+#endif
 }
 
 template <int QB, int N1, int N2>
@@ -297,6 +345,9 @@ extern "C" int ncf_score_fused_partial(int dtype, const void* P, int64_t ldP, co
     a.idxA = idxA; a.idxB = idxB; a.B = head; a.QA = EA / 8;
     a.Wp1 = w.Wp1; a.Wp2 = w.Wp2; a.b2 = w.b2; a.wl = w.wl; a.bl = w.bl;
     a.out = out; a.oob = oob;
+#if NCF_PART_STAMP
+    a.stamps = g_stamp_buf;
+#endif
     partial_dispatch(EB / 8, N1, n_layers == 3 ? dims[2] : 0, &a, s);
     const int rc = check_launch("ncf_score_fused_partial");
     if (rc != NCF_OK || head == B) return rc;

@@ -7,7 +7,10 @@
 Every batch size is checked bit for bit (partial == fused) before it is timed.  --variants adds one column per variant
 library (tools/ab_build.sh, e.g. `ab_build.sh lds0 mlp_partial.hip -DNCF_PART_LDS=0` for the streaming kernel everywhere): its
 ncf_score_fused_partial is timed interleaved with the loaded library's in this process, on the same P, and checked bit for
-bit first.  NCF_HIP_LIBRARY replaces the loaded library itself."""
+bit first.  NCF_HIP_LIBRARY replaces the loaded library itself.
+
+--stamp name=lib,... takes libraries built with -DNCF_PART_STAMP=1 (`ab_build.sh stamp mlp_partial.hip -DNCF_PART_STAMP=1`) and
+prints, for each, where a wave of the scoring kernel spends its cycles and the clock it holds (stamp_table below), then stops."""
 import argparse
 import json
 import os
@@ -20,8 +23,52 @@ sys.path.insert(0, ROOT)
 from deeprecommendation_amd import native  # noqa: E402
 
 
+STAMP_POINTS = ["entry", "first MFMA", "end of layer 1", "layer 2 steady (17th MFMA)", "end of layer 2", "exit"]
+
+
+def stamp_table(name, lib, via, U, I, dev, g, pairs=65536, seconds=2.0):
+    """A -DNCF_PART_STAMP=1 build: every wave reads the shader clock (s_memtime) and the 100 MHz reference (s_memrealtime) at six
+    points and lane 0 stores the readings to a buffer of their own.  Random pairs, launches back to back for `seconds` first (the
+    clock a kernel holds shows only under sustained load); the last launch's readings are kept.  Medians over waves, in shader
+    cycles; clock = d(s_memtime) / d(s_memrealtime) x 100 MHz over the whole wave.  Segment shares only: the stamps cost cycles."""
+    import ctypes
+    import time
+    lib.ncf_partial_stamp_buffer.restype = None
+    lib.ncf_partial_stamp_buffer.argtypes = [ctypes.c_void_p]
+    waves = (pairs + 31) // 32
+    buf = torch.zeros((waves + 4) * 12, dtype=torch.int64, device=dev)
+    batches = [(torch.randint(0, U, (pairs,), device=dev, generator=g), torch.randint(0, I, (pairs,), device=dev, generator=g))
+               for _ in range(8)]
+    out = torch.empty(pairs, 1, device=dev)
+    lib.ncf_partial_stamp_buffer(buf.data_ptr())
+    t0, k = time.time(), 0
+    while time.time() - t0 < seconds:
+        for _ in range(200):
+            via(lib, batches[k % 8][0], batches[k % 8][1], out)
+            k += 1
+        torch.cuda.synchronize()
+    for _ in range(200):
+        via(lib, batches[k % 8][0], batches[k % 8][1], out)
+        k += 1
+    torch.cuda.synchronize()
+    lib.ncf_partial_stamp_buffer(None)
+    st = buf[:waves * 12].view(waves, 6, 2).cpu().double()
+    cyc, ref = st[:, :, 0], st[:, :, 1]
+    seg = (cyc[:, 1:] - cyc[:, :-1]).median(dim=0).values.tolist()
+    life = (cyc[:, 5] - cyc[:, 0])
+    clock = (life / (ref[:, 5] - ref[:, 0]).clamp(min=1) * 100.0).median().item()
+    row = {"segments_cycles": dict(zip([f"{a} -> {b}" for a, b in zip(STAMP_POINTS[:-1], STAMP_POINTS[1:])], seg)),
+           "lifetime_cycles": life.median().item(), "clock_mhz": clock, "launches": k}
+    print(f"stamp build {name}: wave lifetime {row['lifetime_cycles']:.0f} cycles at {clock:.0f} MHz (median of {waves} waves, "
+          f"{k} launches)", flush=True)
+    for label, c in row["segments_cycles"].items():
+        print(f"    {label:48s} {c:9.0f} cycles  {100 * c / row['lifetime_cycles']:5.1f} %", flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stamp", default="", help="name=library,...: print the stamp table of each -DNCF_PART_STAMP=1 build and stop")
     ap.add_argument("--batches", default="16384,32768,40000,65536,262144")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=8)
@@ -63,6 +110,13 @@ def main():
         build.append(e0.elapsed_time(e1) * 1e3)
     result = {"P_bytes": P.numel() * 4, "P_build_us": sorted(build)[len(build) // 2], "batches": {}}
     print(f"P: {P.shape[0]} x {P.shape[1]} fp32 = {P.numel() * 4 / 2**30:.2f} GiB, build median {result['P_build_us']:.0f} us", flush=True)
+
+    for item in filter(None, args.stamp.split(",")):
+        name, path = item.split("=", 1)
+        result.setdefault("stamps", {})[name] = stamp_table(name, native.load_library(os.path.abspath(path)), via, U, I, dev, g)
+    if args.stamp:
+        print(json.dumps(result))
+        return
 
     for Bsz in [int(b) for b in args.batches.split(",")]:
         batches = [(torch.randint(0, U, (Bsz,), device=dev, generator=g), torch.randint(0, I, (Bsz,), device=dev, generator=g))
