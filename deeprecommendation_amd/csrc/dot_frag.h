@@ -73,6 +73,10 @@ inline int dot_check_shape(const char* what, int64_t rows, int64_t cols, int D) 
     return topk_check_size(what, rows, cols);
 }
 
+// ncf_dot_topk's refusal on k and its merge plan (dot_topk.hip), also answered by ncf_ranking_plan (rank.hip)
+int dot_topk_check_k(const char* what, int k);
+TopkMerge dot_topk_plan(int64_t rows, int64_t cols, int tile_cols, int k);
+
 // the operand refusals of a call with rows > 0.  outputs: the caller's output pointers that share the "null argument" refusal are all there
 inline int dot_check_operands(const char* what, const float* tabA, int64_t rowsA, int64_t ldA, const float* tabB, int64_t rowsB, int64_t ldB,
                               const int64_t* idxA, const int64_t* idxB, int64_t rows, int64_t cols, int D, bool outputs) {

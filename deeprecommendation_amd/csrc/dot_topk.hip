@@ -167,12 +167,14 @@ __global__ __launch_bounds__(kDtThreads) void dot_topk_kernel(
 }
 
 // the merge levels after it, over kp keys per tile, in chunks of whole user blocks
-static TopkMerge dot_topk_plan(int64_t rows, int64_t cols, int tile_cols, int k) {
+TopkMerge dot_topk_plan(int64_t rows, int64_t cols, int tile_cols, int k) {
     return topk_merge_plan(rows, (cols + tile_cols - 1) / tile_cols * topk_kp(k), k, kDtBlockUsers);
 }
 
+int dot_topk_check_k(const char* what, int k) { return topk_check_k(what, k, kDtMaxK); }
+
 static int dot_topk_check(int64_t rows, int64_t cols, int D, int k, const char* what) {
-    if (const int rc = topk_check_k(what, k, kDtMaxK)) return rc;
+    if (const int rc = dot_topk_check_k(what, k)) return rc;
     return dot_check_shape(what, rows, cols, D);
 }
 

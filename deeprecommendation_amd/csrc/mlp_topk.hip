@@ -378,6 +378,33 @@ static int mt_check(int64_t rows, int64_t cols, int k, const char* what) {
     return topk_check_size(what, rows, cols);
 }
 
+static int mr_check(int64_t rows, int64_t cols, int max_targets, const char* what) {
+    if (const int rc = rank_check_max_targets(what, max_targets)) return rc;
+    return topk_check_size(what, rows, cols);
+}
+
+// ncf_mlp_topk's column ranges and merge plan; ncf_mlp_rank's column ranges (one target: the top-K floor)
+static TopkMerge mt_plan(int64_t rows, int64_t cols, int k, int* tile_cols) {
+    const int tc = mlp_tile_cols(rows, cols, kMtCols);
+    if (tile_cols) *tile_cols = tc;
+    return mlp_topk_plan(rows, cols, tc, k);
+}
+static int mr_tile_cols(int64_t rows, int64_t cols, int max_targets) {
+    return mlp_tile_cols(rows, cols, max_targets == 1 ? kMtCols : kMrChunkCols);
+}
+
+// what ncf_ranking_plan (rank.hip) answers for the two MLP entry points: the entry's refusals, then the functions its launch calls
+int mlp_ranking_plan(bool rank, int64_t rows, int64_t cols, int k_or_max_targets, const char* what, int* tile_cols, TopkMerge* merge) {
+    if (rank) {
+        if (const int rc = mr_check(rows, cols, k_or_max_targets, what)) return rc;
+        *tile_cols = mr_tile_cols(rows, cols, k_or_max_targets);
+        return NCF_OK;
+    }
+    if (const int rc = mt_check(rows, cols, k_or_max_targets, what)) return rc;
+    *merge = mt_plan(rows, cols, k_or_max_targets, tile_cols);
+    return NCF_OK;
+}
+
 // The refusals both entry points make after their own limit check (mt_check / mr_check), in their order; `what` names the entry
 // point.  n_targets: 0 from ncf_mlp_topk; outputs: the caller's output pointers that share the "null argument" refusal are all
 // there.  rows == 0 passes before any pointer is looked at: the caller returns NCF_OK then.
@@ -434,7 +461,7 @@ extern "C" int ncf_mlp_topk_supported(int dtype, int EA, int EB, int n_layers, c
 extern "C" size_t ncf_mlp_topk_workspace_bytes(int64_t rows, int64_t cols, int user_first, int n_layers, const int* dims, int k) {
     if (mt_check(rows, cols, k, "ncf_mlp_topk_workspace_bytes") != NCF_OK || rows == 0) return 0;
     if (!dims || (n_layers != 2 && n_layers != 3) || dims[1] < 32 || dims[1] % 32) return 0;
-    return mlp_state_bytes(rows, cols, dims[1], user_first) + topk_merge_bytes(mlp_topk_plan(rows, cols, mlp_tile_cols(rows, cols, kMtCols), k));
+    return mlp_state_bytes(rows, cols, dims[1], user_first) + topk_merge_bytes(mt_plan(rows, cols, k, nullptr));
 }
 
 extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t ldA, const void* tabB, int64_t rowsB, int64_t ldB,
@@ -448,8 +475,8 @@ extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t 
         return rc;
     if (rows == 0) return NCF_OK;
     const int K0 = dims[0], N1 = dims[1], N2 = n_layers == 3 ? dims[2] : 0;
-    const int tile_cols = mlp_tile_cols(rows, cols, kMtCols);
-    const TopkMerge p = mlp_topk_plan(rows, cols, tile_cols, k);
+    int tile_cols;
+    const TopkMerge p = mt_plan(rows, cols, k, &tile_cols);
     const size_t state_bytes = mlp_state_bytes(rows, cols, N1, user_first);
     if (const int rc = topk_check_buffers("ncf_mlp_topk", "ncf_mlp_topk_workspace_bytes", seen_rowptr, seen_col, workspace, workspace_bytes,
                                           state_bytes + topk_merge_bytes(p)))
@@ -474,11 +501,6 @@ extern "C" int ncf_mlp_topk(int dtype, const void* tabA, int64_t rowsA, int64_t 
 
 extern "C" int ncf_mlp_rank_supported(int dtype, int EA, int EB, int n_layers, const int* dims, int max_targets) {
     return (mt_shape_ok(dtype, EA, EB, n_layers, dims) && max_targets >= 1 && max_targets <= kRankMaxTargets) ? 1 : 0;
-}
-
-static int mr_check(int64_t rows, int64_t cols, int max_targets, const char* what) {
-    if (const int rc = rank_check_max_targets(what, max_targets)) return rc;
-    return topk_check_size(what, rows, cols);
 }
 
 extern "C" size_t ncf_mlp_rank_workspace_bytes(int64_t rows, int64_t cols, int user_first, int n_layers, const int* dims, int64_t n_targets,
@@ -517,7 +539,7 @@ extern "C" int ncf_mlp_rank(int dtype, const void* tabA, int64_t rowsA, int64_t 
     }
     rank_prepare(nullptr, 0, w.pair_score, rows, cols, seen_rowptr, seen_col, tgt_rowptr, tgt_col, max_targets, true, w, rank, overflow, s);
 
-    const int tile_cols = mlp_tile_cols(rows, cols, max_targets == 1 ? kMtCols : kMrChunkCols);
+    const int tile_cols = mr_tile_cols(rows, cols, max_targets);
     MrArgs a{};
     mlp_prefix_pass(a, tabA, rowsA, ldA, tabB, rowsB, ldB, EA, user_first, user_ids, item_ids, rows, cols, n_layers, dims, packed,
                     seen_rowptr, seen_col, (float*)workspace, oob, s);

@@ -508,3 +508,52 @@ extern "C" int ncf_dot_rank(const float* tabA, int64_t rowsA, int64_t ldA, const
 #undef LAUNCH
     return check_launch("ncf_dot_rank");
 }
+
+// ---------------------------------------------------------------------------------------------------- ncf_ranking_plan
+// Host only.  Every figure comes from the function the entry point's launch calls (topk_rows_plan, dot_topk_tile_cols,
+// dot_topk_plan, mlp_ranking_plan), after the entry point's own refusals on k / max_targets and on the size; the embedding width
+// does not enter a plan, so its refusal is not made.
+extern "C" int ncf_ranking_plan(int entry, int64_t rows, int64_t cols, int k_or_max_targets, int* tile_cols, int64_t* tiles,
+                                int* merge_levels, int64_t* chunk_rows) {
+    const char* what = "ncf_ranking_plan";
+    int tc = kTopkTile;
+    TopkMerge p{};
+    bool merges = false;
+    switch (entry) {
+        case NCF_RANKING_TOPK_ROWS:
+            if (const int rc = topk_check_k(what, k_or_max_targets, kTopkMaxK)) return rc;
+            if (const int rc = topk_check_size(what, rows, cols)) return rc;
+            p = topk_rows_plan(rows, cols, k_or_max_targets);
+            merges = true;
+            break;
+        case NCF_RANKING_RANK_ROWS:
+            if (const int rc = topk_check_size(what, rows, cols)) return rc;
+            break;
+        case NCF_RANKING_DOT_TOPK:
+            if (const int rc = dot_topk_check_k(what, k_or_max_targets)) return rc;
+            if (const int rc = topk_check_size(what, rows, cols)) return rc;
+            tc = dot_topk_tile_cols(rows, cols);
+            p = dot_topk_plan(rows, cols, tc, k_or_max_targets);
+            merges = true;
+            break;
+        case NCF_RANKING_DOT_RANK:
+            if (const int rc = rank_check_max_targets(what, k_or_max_targets)) return rc;
+            if (const int rc = topk_check_size(what, rows, cols)) return rc;
+            tc = dot_topk_tile_cols(rows, cols);
+            break;
+        case NCF_RANKING_MLP_TOPK:
+            if (const int rc = mlp_ranking_plan(false, rows, cols, k_or_max_targets, what, &tc, &p)) return rc;
+            merges = true;
+            break;
+        case NCF_RANKING_MLP_RANK:
+            if (const int rc = mlp_ranking_plan(true, rows, cols, k_or_max_targets, what, &tc, &p)) return rc;
+            break;
+        default:
+            return fail(NCF_EINVAL, "ncf_ranking_plan: entry = %d is not one of NCF_RANKING_*", entry);
+    }
+    if (tile_cols) *tile_cols = tc;
+    if (tiles) *tiles = (cols + tc - 1) / tc;
+    if (merge_levels) *merge_levels = merges ? p.levels : 0;
+    if (chunk_rows) *chunk_rows = merges ? p.chunk : rows;
+    return NCF_OK;
+}

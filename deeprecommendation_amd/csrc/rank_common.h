@@ -97,4 +97,8 @@ void rank_prepare(const float* scores, int64_t ld, const float* pair_score, int6
                   const int32_t* seen_col, const int64_t* tgt_rowptr, const int32_t* tgt_col, int cap, bool single, const RankWs& w,
                   int32_t* rank, int32_t* overflow, hipStream_t s);
 
+// ncf_ranking_plan's answer for ncf_mlp_topk (rank = false: tile_cols and the merge plan) and ncf_mlp_rank (tile_cols), after the
+// entry point's own limit and size refusals; defined beside the launches in mlp_topk.hip
+int mlp_ranking_plan(bool rank, int64_t rows, int64_t cols, int k_or_max_targets, const char* what, int* tile_cols, TopkMerge* merge);
+
 }  // namespace ncf

@@ -304,7 +304,7 @@ int topk_check_buffers(const char* what, const char* query, const int64_t* seen_
 }
 
 // level 0 over the columns; a row longer than one tile leaves its tiles' keys to the merge levels
-static TopkMerge topk_rows_plan(int64_t rows, int64_t cols, int k) {
+TopkMerge topk_rows_plan(int64_t rows, int64_t cols, int k) {
     const int64_t tiles0 = (cols + kTopkTile - 1) / kTopkTile;
     return topk_merge_plan(rows, tiles0 > 1 ? tiles0 * topk_kp(k) : 0, k);
 }

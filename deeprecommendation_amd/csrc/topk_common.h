@@ -108,6 +108,8 @@ struct TopkMerge {
 // align > 1: a chunk of more than `align` rows that does not take every row is rounded down to a multiple of `align`
 TopkMerge topk_merge_plan(int64_t rows, int64_t n1, int k, int64_t align = 1);
 size_t topk_merge_bytes(const TopkMerge& p);
+// ncf_topk_rows' plan: level 0 over the columns, then the merge levels (n1 = 0 for a row of one tile)
+TopkMerge topk_rows_plan(int64_t rows, int64_t cols, int k);
 // The merge levels of rows [r0, r0 + nr) (local row 0 of buffer A = row r0).  scores / ld: the final level re-reads each
 // score from the caller's matrix; null: it recovers the score from the key.
 void topk_merge(const TopkMerge& p, unsigned long long* bufA, const float* scores, int64_t ld, int64_t r0, int64_t nr, int k,

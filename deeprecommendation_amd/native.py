@@ -183,6 +183,7 @@ SIGNATURES = {
     "ncf_mlp_rank_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_int, _c_p, _c_i64, _c_int]),
     "ncf_mlp_rank": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_i64,
                               _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p, _c_p]),
+    "ncf_ranking_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p]),
     "ncf_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _c_i64, _c_p]),
     "ncf_adam_rows": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_i64, ctypes.c_float, ctypes.c_float,
@@ -2548,3 +2549,19 @@ def mlp_rank(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     _check(lib.ncf_mlp_rank(*args, _ptr(rowptr), _ptr(col), _ptr(trow), _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws),
                             nbytes, _ptr(_oob_flag(dev)), _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
     return rank, ranked
+
+
+# ncf_ranking_plan's entry (include/ncf_abi.h enum ncf_ranking_entry)
+RANKING_ENTRIES = {"topk_rows": 0, "rank_rows": 1, "dot_topk": 2, "dot_rank": 3, "mlp_topk": 4, "mlp_rank": 5}
+
+
+def ranking_plan(entry: str, rows: int, cols: int, k_or_max_targets: int = 1):
+    """(tile_cols, tiles, merge_levels, chunk_rows) of the launch the ranking entry point ``entry`` (a key of RANKING_ENTRIES) picks
+    for (rows, cols) and its k (top-K entries) or max_targets (rank entries): columns per workgroup tile / wave range, tiles per
+    row, merge launches after the first level and rows per pass over the key workspace (rank entries: 0 and rows).  The entry
+    point's own refusals raise NativeError.  Host only: no launch, no device."""
+    tc, lv = ctypes.c_int(0), ctypes.c_int(0)
+    tiles, chunk = ctypes.c_int64(0), ctypes.c_int64(0)
+    _check(load_library().ncf_ranking_plan(RANKING_ENTRIES[entry], int(rows), int(cols), int(k_or_max_targets), ctypes.byref(tc),
+                                           ctypes.byref(tiles), ctypes.byref(lv), ctypes.byref(chunk)))
+    return tc.value, tiles.value, lv.value, chunk.value

@@ -1246,6 +1246,26 @@ int ncf_mlp_rank(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, co
                  int32_t* dev_oob_flag, int32_t* dev_overflow_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * ncf_ranking_plan — the launch shape one of the six ranking entry points above picks for (rows, cols) and its k (top-K entries)
+ * or max_targets (rank entries; ignored by NCF_RANKING_RANK_ROWS), answered on the host without launching and without touching the
+ * device (like ncf_linear_plan), by the functions the entry point's own launch calls.  Any output pointer may be NULL.
+ *   *tile_cols     columns per workgroup tile (8192 for the score-matrix entries; 2048 / 4096 / 8192 for the dot entries) or per
+ *                  wave range (32 .. 8192 for the MLP entries; ncf_mlp_rank with max_targets > 1 stays at 512 or above)
+ *   *tiles         ceil(cols / *tile_cols): tiles (ranges) per row
+ *   *merge_levels  merge launches after the first level of a top-K entry (0: the first level finishes alone); 0 for a rank entry
+ *   *chunk_rows    rows per pass of a top-K entry over its key workspace (== rows: one pass; ncf_dot_topk rounds a partial chunk
+ *                  of more than 64 rows down to a multiple of 64); rows for a rank entry
+ * Refusals: those the entry point makes on k / max_targets, rows and cols, with its codes; an unknown entry is NCF_EINVAL.  The
+ * embedding width, the MLP instance and the exclusion / target lists do not enter a plan.
+ * ------------------------------------------------------------------------------------------------ */
+enum ncf_ranking_entry {
+    NCF_RANKING_TOPK_ROWS = 0, NCF_RANKING_RANK_ROWS = 1, NCF_RANKING_DOT_TOPK = 2, NCF_RANKING_DOT_RANK = 3,
+    NCF_RANKING_MLP_TOPK = 4, NCF_RANKING_MLP_RANK = 5
+};
+int ncf_ranking_plan(int entry, int64_t rows, int64_t cols, int k_or_max_targets, int* tile_cols, int64_t* tiles, int* merge_levels,
+                     int64_t* chunk_rows);
+
+/* ------------------------------------------------------------------------------------------------
  * Calibration probe — the bf16 MFMA rate the chip SUSTAINS on random operands (it lowers its clock under matrix load), so that
  * bench.py can state a kernel's fraction of it next to the fraction of the 2.5 PFLOP/s datasheet figure.  Not part of scoring.
  * Launches `blocks` 512-thread workgroups; every wave issues iters * 32 v_mfma_f32_16x16x32_bf16 (16 384 flop each) on register

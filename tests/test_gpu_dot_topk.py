@@ -68,7 +68,8 @@ def test_dot_topk_above_2_20_columns(gpu):
 
 
 def test_dot_topk_many_users_and_strided_tables(gpu):
-    """Tables with leading dimension > D (views), users past one row chunk of the merge levels' workspace bound."""
+    """Tables with leading dimension > D (views) and ten 64-user blocks.  The rows still fit one pass over the key workspace
+    (chunk_rows == rows); the chunked form is test_gpu_rank_forms.test_dot_topk_in_row_chunks."""
     A = _rand(600, 80, 1, gpu)[:, :72]
     B = _rand(20000, 80, 2, gpu)[:, :72]
     _check(A, None, B, None, 50)
