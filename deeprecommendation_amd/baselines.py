@@ -17,21 +17,106 @@ implicit's AlternatingLeastSquares; the iALS of Rendle et al. 2021): every store
 one Cholesky factorisation on the device (csrc/als.hip, THE CONTRACT in include/ncf_abi.h).  A new user is folded in exactly, by one
 such solve against the fixed item table."""
 import math
+from types import SimpleNamespace
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import native
+from .native import _finite, _int_in      # the scalar checks of the bindings: a bool is no integer and no number
 
 ROW_ALIGN = 32      # floats: a table row starts on a 128-byte line, so no line holds rows of two blocks
+INT_MAX = 2 ** 31 - 1
 
 
-def _positions(t, what, n=None):
+def _positions(who, t, what, n=None):
     if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
-        raise ValueError(f"KernelMF: {what} must be a 1-D int64 tensor of positions")
+        raise ValueError(f"{who}: {what} must be a 1-D int64 tensor of positions")
     if n is not None and t.numel() != n:
-        raise ValueError(f"KernelMF: {what} has {t.numel()} entries, expected {n}")
+        raise ValueError(f"{who}: {what} has {t.numel()} entries, expected {n}")
+
+
+def _one_gpu(who, what, *tensors):
+    """The device of tensors a fit reads, which must be one GPU."""
+    devs = [t.device for t in tensors]
+    if devs[0].type != "cuda" or any(d != devs[0] for d in devs):
+        raise RuntimeError(f"{who} runs on the GPU: the {what} must live on one GPU (got {', '.join(str(d) for d in devs)}); "
+                           "there is no CPU path")
+    return devs[0]
+
+
+def _ratings_csr(who, ratings):
+    """A ratings CSR argument: a SparseRatings-like object (rowptr / col / val) or a (rowptr, col, val) tuple, as the kernels take it."""
+    if isinstance(ratings, (tuple, list)) and len(ratings) == 3:
+        rowptr, col, val = ratings
+    elif all(hasattr(ratings, a) for a in ("rowptr", "col", "val")):
+        if getattr(ratings, "pair_row", None) is not None:
+            raise ValueError(f"{who}: the ratings share rows through pair_row; pass the CSR with one row per user")
+        rowptr, col, val = ratings.rowptr, ratings.col, ratings.val
+    else:
+        raise ValueError(f"{who}: ratings must be a SparseRatings or a (rowptr, col, val) tuple")
+    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val")):
+        if not torch.is_tensor(t) or t.dim() != 1:
+            raise ValueError(f"{who}: {what} must be a 1-D tensor")
+    if rowptr.dtype not in (torch.int64, torch.int32) or col.dtype not in (torch.int64, torch.int32) or val.dtype != torch.float32:
+        raise ValueError(f"{who}: rowptr / col must be integer tensors and val float32")
+    if rowptr.numel() < 1 or col.numel() != val.numel():
+        raise ValueError(f"{who}: rowptr is empty or col and val differ in length")
+    return rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), val.contiguous()
+
+
+def _mf_of_tables(user_table, item_table):
+    """The project's MF module over two (rows, F) fp32 tables: zero Linear biases, frozen and in eval mode, on the tables' device."""
+    from .neural_collaborative_filtering.models.mf import MF
+    F = user_table.shape[1]
+    mf = MF(item_dim=item_table.shape[0], user_dim=user_table.shape[0], item_emb=F, user_emb=F).to(user_table.device)
+    with torch.no_grad():
+        for lin, tab in ((mf.user_embeddings[0], user_table), (mf.item_embeddings[0], item_table)):
+            lin.weight = torch.nn.Parameter(tab.contiguous().t(), requires_grad=False)      # id-major, as row_major_embedding_ lays it
+            lin.bias.zero_()
+    return mf.requires_grad_(False).eval()
+
+
+class _Baseline:
+    """The fit front end of the three baselines: the checks of the samples or of the CSR a fit is given, and fit_dataset.  Every
+    message names the concrete class."""
+
+    def _samples(self, user_pos, item_pos, rating, num_users, num_items):
+        """Checks the samples of ``fit`` — int64 positions and fp32 ratings of one length, something to fit, all on one GPU — and
+        returns ``(n, num_users, num_items, device)``."""
+        who = type(self).__name__
+        _positions(who, user_pos, "user_pos")
+        n = user_pos.numel()
+        _positions(who, item_pos, "item_pos", n)
+        if not torch.is_tensor(rating) or rating.dtype != torch.float32 or rating.dim() != 1 or rating.numel() != n:
+            raise ValueError(f"{who}: rating must be a 1-D float32 tensor of {n} entries")
+        num_users, num_items = int(num_users), int(num_items)
+        if n == 0 or num_users < 1 or num_items < 1:
+            raise ValueError(f"{who}: nothing to fit ({n} ratings, {num_users} users, {num_items} items)")
+        return n, num_users, num_items, _one_gpu(f"{who}.fit", "samples", user_pos, item_pos, rating)
+
+    def _csr(self, rowptr, col, val, num_items):
+        """Checks the user CSR of ``fit_csr`` — _ratings_csr's, something to fit, all on one GPU — and returns ``(rowptr int64, col int32,
+        val, num_items, device)``."""
+        who = type(self).__name__
+        rowptr, col, val = _ratings_csr(f"{who}.fit_csr", (rowptr, col, val))
+        I = int(num_items)
+        if I < 1 or rowptr.numel() < 2 or col.numel() == 0:
+            raise ValueError(f"{who}: nothing to fit ({col.numel()} ratings, {rowptr.numel() - 1} users, {I} items)")
+        return rowptr, col, val, I, _one_gpu(f"{who}.fit_csr", "CSR", rowptr, col, val)
+
+    def fit_dataset(self, dataset, device="cuda", **fit_args):
+        """fit on the positions and ratings of a FixedPointwiseDataset over an index provider (its ``resident_inputs()``)."""
+        dev = torch.device(device)
+        res = dataset.resident_inputs(dev)
+        if res is None:
+            raise ValueError(f"{type(self).__name__}.fit_dataset: the dataset's provider hands out dense rows, not positions")
+        u, i = (t.to(dev) for t in res.tensors)
+        if res.on_chunk is not None:
+            u, i = res.on_chunk(u, i)
+        cp = dataset.content_provider
+        return self.fit(u.contiguous(), i.contiguous(), res.targets.to(dev), cp.get_num_users(), cp.get_num_items(), **fit_args)
 
 
 def _deal_blocks(ids, count, W):
@@ -44,7 +129,7 @@ def _deal_blocks(ids, count, W):
     return block, counts
 
 
-class KernelMF:
+class KernelMF(_Baseline):
     """``KernelMF(...).fit(user_pos, item_pos, rating, num_users, num_items)``; then ``predict``, ``as_mf()`` (the project's MF module
     with the baseline's tables: every ranking and evaluation function takes it) and ``update_users`` (fold-in of new ratings).
 
@@ -53,22 +138,15 @@ class KernelMF:
 
     def __init__(self, n_factors=100, n_epochs=100, lr=0.01, reg=1.0, init_mean=0.0, init_sd=0.1, min_rating=0.0, max_rating=5.0,
                  n_blocks=None):
-        if not isinstance(n_factors, (int, np.integer)) or not 1 <= n_factors <= native.KMF_MAX_FACTORS:
-            raise ValueError(f"KernelMF: n_factors = {n_factors!r} (an integer in 1 .. {native.KMF_MAX_FACTORS})")
-        if not isinstance(n_epochs, (int, np.integer)) or n_epochs < 0:
-            raise ValueError(f"KernelMF: n_epochs = {n_epochs!r}")
-        for name, v in (("lr", lr), ("reg", reg), ("init_mean", init_mean), ("init_sd", init_sd), ("min_rating", min_rating),
-                        ("max_rating", max_rating)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-                raise ValueError(f"KernelMF: {name} = {v!r} is not a finite number")
-        if lr <= 0 or reg < 0 or init_sd < 0 or not min_rating < max_rating:
-            raise ValueError(f"KernelMF: lr > 0, reg >= 0, init_sd >= 0 and min_rating < max_rating (got {lr}, {reg}, {init_sd}, "
-                             f"{min_rating}, {max_rating})")
-        if n_blocks is not None and (not isinstance(n_blocks, (int, np.integer)) or not 1 <= n_blocks <= native.KMF_MAX_BLOCKS):
-            raise ValueError(f"KernelMF: n_blocks = {n_blocks!r} (None or an integer in 1 .. {native.KMF_MAX_BLOCKS})")
-        self.n_factors, self.n_epochs, self.lr, self.reg = int(n_factors), int(n_epochs), float(lr), float(reg)
-        self.init_mean, self.init_sd, self.min_rating, self.max_rating = float(init_mean), float(init_sd), float(min_rating), float(max_rating)
-        self.n_blocks = None if n_blocks is None else int(n_blocks)
+        who = "KernelMF"
+        self.n_factors = _int_in(who, n_factors, "n_factors", 1, native.KMF_MAX_FACTORS)
+        self.n_epochs = _int_in(who, n_epochs, "n_epochs", 0, INT_MAX)
+        self.lr, self.reg, self.init_sd = _finite(who, lr, "lr", 0.0), _finite(who, reg, "reg", 0.0), _finite(who, init_sd, "init_sd", 0.0)
+        self.init_mean = _finite(who, init_mean, "init_mean")
+        self.min_rating, self.max_rating = _finite(who, min_rating, "min_rating"), _finite(who, max_rating, "max_rating")
+        if not self.lr > 0 or not self.min_rating < self.max_rating:
+            raise ValueError(f"{who}: lr > 0 and min_rating < max_rating (got {lr}, {min_rating}, {max_rating})")
+        self.n_blocks = None if n_blocks is None else _int_in(who, n_blocks, "n_blocks", 1, native.KMF_MAX_BLOCKS)
         self.user_table_ = self.item_table_ = None      # (U, ld) / (I, ld) fp32: F factors, the bias, padding
         self.global_mean_ = None                        # mu, an fp32 value
         self.n_blocks_ = None
@@ -97,23 +175,12 @@ class KernelMF:
         plus the known side's bias.  With ``at_epochs`` (increasing, within 1 .. n_epochs) the fit stops after those epochs and calls
         ``epoch_callback(self, epoch)`` with the model usable as it then stands: the first k epochs of a fit ARE the k-epoch fit.
         ``train_rmse_[e]`` is sqrt(sum of the epoch's squared errors / n), each error taken before its update."""
-        n = user_pos.numel() if torch.is_tensor(user_pos) else None
-        _positions(user_pos, "user_pos")
-        _positions(item_pos, "item_pos", n)
-        if not torch.is_tensor(rating) or rating.dtype != torch.float32 or rating.dim() != 1 or rating.numel() != n:
-            raise ValueError(f"KernelMF: rating must be a 1-D float32 tensor of {n} entries")
-        num_users, num_items = int(num_users), int(num_items)
-        if n == 0 or num_users < 1 or num_items < 1:
-            raise ValueError(f"KernelMF: nothing to fit ({n} ratings, {num_users} users, {num_items} items)")
         stops = [int(e) for e in at_epochs]
         if any(b <= a for a, b in zip([0] + stops, stops)) or (stops and stops[-1] > self.n_epochs):
             raise ValueError(f"KernelMF: at_epochs = {tuple(at_epochs)!r} must increase within 1 .. n_epochs = {self.n_epochs}")
         if stops and epoch_callback is None:
             raise ValueError("KernelMF: at_epochs without an epoch_callback")
-        dev = user_pos.device
-        if dev.type != "cuda" or item_pos.device != dev or rating.device != dev:
-            raise RuntimeError(f"KernelMF.fit runs on the GPU: the samples must live on one GPU (got {dev}, {item_pos.device}, {rating.device}); "
-                               "there is no CPU path")
+        n, num_users, num_items, dev = self._samples(user_pos, item_pos, rating, num_users, num_items)
         W = self.n_blocks
         if W is None:
             W = min(torch.cuda.get_device_properties(dev).multi_processor_count, num_users, num_items, native.KMF_MAX_BLOCKS)
@@ -167,18 +234,6 @@ class KernelMF:
         if self.user_table_ is None:
             raise RuntimeError("KernelMF: not fitted")
 
-    def fit_dataset(self, dataset, device="cuda", **fit_args):
-        """fit on the positions and ratings of a FixedPointwiseDataset over an index provider (its ``resident_inputs()``)."""
-        dev = torch.device(device)
-        res = dataset.resident_inputs(dev)
-        if res is None:
-            raise ValueError("KernelMF.fit_dataset: the dataset's provider hands out dense rows, not positions")
-        u, i = (t.to(dev) for t in res.tensors)
-        if res.on_chunk is not None:
-            u, i = res.on_chunk(u, i)
-        cp = dataset.content_provider
-        return self.fit(u.contiguous(), i.contiguous(), res.targets.to(dev), cp.get_num_users(), cp.get_num_items(), **fit_args)
-
     # ------------------------------------------------------------------ fold-in
     def update_users(self, rowptr, col, rating, user_pos, n_epochs: Optional[int] = None, lr: Optional[float] = None):
         """The package's update_users: ``n_epochs`` SGD passes (default: the model's) over the ratings of the users ``user_pos``
@@ -186,7 +241,7 @@ class KernelMF:
         positions, ``rating`` fp32) holds user_pos[k]'s ratings.  Rows continue from where they stand (a user without training
         ratings from zero).  Returns the (n_epochs, n_users) float64 sums of squared errors."""
         self._fitted()
-        _positions(user_pos, "user_pos")
+        _positions("KernelMF.update_users", user_pos, "user_pos")
         n_epochs = self.n_epochs if n_epochs is None else int(n_epochs)
         lr = self.lr if lr is None else float(lr)
         if n_epochs < 0 or not math.isfinite(lr) or lr <= 0:
@@ -206,51 +261,24 @@ class KernelMF:
         and [state_dict, kwargs] checkpoints work on it as on any MF."""
         self._fitted()
         if self._mf is None:
-            from .neural_collaborative_filtering.models.mf import MF
             F, pu, qi = self.n_factors, self.user_table_, self.item_table_
             one_u, one_i = pu.new_ones((pu.shape[0], 1)), qi.new_ones((qi.shape[0], 1))
             mu = torch.tensor(self.global_mean_, dtype=torch.float32, device=pu.device)
-            ut = torch.cat([pu[:, :F], (pu[:, F] + mu)[:, None], one_u], 1).contiguous()
-            it = torch.cat([qi[:, :F], one_i, qi[:, F:F + 1]], 1).contiguous()
-            mf = MF(item_dim=qi.shape[0], user_dim=pu.shape[0], item_emb=F + 2, user_emb=F + 2).to(pu.device)
-            with torch.no_grad():
-                for lin, tab in ((mf.user_embeddings[0], ut), (mf.item_embeddings[0], it)):
-                    lin.weight = torch.nn.Parameter(tab.t(), requires_grad=False)      # id-major, as row_major_embedding_ lays it
-                    lin.bias.zero_()
-            self._mf = mf.requires_grad_(False).eval()
+            self._mf = _mf_of_tables(torch.cat([pu[:, :F], (pu[:, F] + mu)[:, None], one_u], 1),
+                                     torch.cat([qi[:, :F], one_i, qi[:, F:F + 1]], 1))
         return self._mf
 
     def predict(self, user_pos, item_pos, clip=True):
         """(n,) predictions for int64 positions on the fit's device: as_mf()'s forward, clamped to [min_rating, max_rating] when
         ``clip`` is set."""
-        _positions(user_pos, "user_pos")
-        _positions(item_pos, "item_pos", user_pos.numel())
+        _positions("KernelMF.predict", user_pos, "user_pos")
+        _positions("KernelMF.predict", item_pos, "item_pos", user_pos.numel())
         with torch.no_grad():
             out = self.as_mf()(user_pos.contiguous(), item_pos.contiguous()).view(-1)
         return out.clamp(self.min_rating, self.max_rating) if clip else out
 
 
 # ---------------------------------------------------------------------------------------- ItemKNN
-def _knn_ratings(who, ratings):
-    """A ratings CSR argument: a SparseRatings-like object (rowptr / col / val) or a (rowptr, col, val) tuple, as the kernels take it."""
-    if isinstance(ratings, (tuple, list)) and len(ratings) == 3:
-        rowptr, col, val = ratings
-    elif all(hasattr(ratings, a) for a in ("rowptr", "col", "val")):
-        if getattr(ratings, "pair_row", None) is not None:
-            raise ValueError(f"{who}: the ratings share rows through pair_row; pass the CSR with one row per user")
-        rowptr, col, val = ratings.rowptr, ratings.col, ratings.val
-    else:
-        raise ValueError(f"{who}: ratings must be a SparseRatings or a (rowptr, col, val) tuple")
-    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val")):
-        if not torch.is_tensor(t) or t.dim() != 1:
-            raise ValueError(f"{who}: {what} must be a 1-D tensor")
-    if rowptr.dtype not in (torch.int64, torch.int32) or col.dtype not in (torch.int64, torch.int32) or val.dtype != torch.float32:
-        raise ValueError(f"{who}: rowptr / col must be integer tensors and val float32")
-    if rowptr.numel() < 1 or col.numel() != val.numel():
-        raise ValueError(f"{who}: rowptr is empty or col and val differ in length")
-    return rowptr.to(torch.int64).contiguous(), col.to(torch.int32).contiguous(), val.contiguous()
-
-
 def build_transpose(rowptr, col, val, num_items):
     """``(colptr (I + 1) int64, row int32, tval fp32)``: the CSR by item, torch ops on whatever device the CSR is on.  A stable
     sort of the entries on their column keeps the users of a column in ascending order."""
@@ -273,7 +301,7 @@ def build_csr(user_pos, item_pos, rating, num_users, num_items):
     return rowptr, item_pos[order].to(torch.int32), rating[order].contiguous()
 
 
-class ItemKNN:
+class ItemKNN(_Baseline):
     """Item-item k-nearest-neighbours over the rating matrix (csrc/knn.hip, THE CONTRACT in include/ncf_abi.h): shrunk cosine
     similarities ``s_ij = cos(i, j) * co / (co + shrink)`` of items co-rated by at least ``min_support`` users, the ``k`` largest
     positive ones kept per item, and scores ``sum s_ij * v_uj`` over the neighbours a user rated, divided by ``sum s_ij`` with
@@ -282,19 +310,13 @@ class ItemKNN:
     function of its inputs, bit for bit.  There is no host path."""
 
     def __init__(self, k=50, shrink=0.0, min_support=1, weighted_average=True, fill=0.0):
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= native.KNN_MAX_N:
-            raise ValueError(f"ItemKNN: k = {k!r} (an integer in 1 .. {native.KNN_MAX_N})")
-        if isinstance(min_support, bool) or not isinstance(min_support, (int, np.integer)) or min_support < 1:
-            raise ValueError(f"ItemKNN: min_support = {min_support!r} (an integer >= 1)")
-        for name, v in (("shrink", shrink), ("fill", fill)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-                raise ValueError(f"ItemKNN: {name} = {v!r} is not a finite number")
-        if shrink < 0:
-            raise ValueError(f"ItemKNN: shrink = {shrink} < 0")
+        who = "ItemKNN"
+        self.k = _int_in(who, k, "k", 1, native.KNN_MAX_N)
+        self.min_support = _int_in(who, min_support, "min_support", 1, INT_MAX)
+        self.shrink, self.fill = _finite(who, shrink, "shrink", 0.0), _finite(who, fill, "fill")
         if not isinstance(weighted_average, (bool, np.bool_)):
-            raise ValueError(f"ItemKNN: weighted_average = {weighted_average!r} is not a bool")
-        self.k, self.shrink, self.min_support = int(k), float(shrink), int(min_support)
-        self.weighted_average, self.fill = bool(weighted_average), float(fill)
+            raise ValueError(f"{who}: weighted_average = {weighted_average!r} is not a bool")
+        self.weighted_average = bool(weighted_average)
         self.nb_pos_ = self.nb_sim_ = self.nb_cnt_ = None      # (I, k) int32 / (I, k) fp32 / (I,) int32
         self.item_sq_ = None                                   # (I,) fp32 squared norms
         self.num_items_ = None
@@ -306,14 +328,7 @@ class ItemKNN:
         """Fits on a user CSR on the GPU: ``rowptr`` (U + 1) int64, ``col`` int32 item positions strictly ascending inside a row,
         ``val`` fp32 (SparseRatings' arrays as they are).  The similarity rows are computed ``block_bytes`` at a time and the table
         selected from each block by native.topk_rows; the table does not depend on the blocking.  Synchronises once, in check()."""
-        rowptr, col, val = _knn_ratings("ItemKNN.fit_csr", (rowptr, col, val))
-        I = int(num_items)
-        if I < 1 or rowptr.numel() < 2 or col.numel() == 0:
-            raise ValueError(f"ItemKNN: nothing to fit ({col.numel()} ratings, {rowptr.numel() - 1} users, {I} items)")
-        dev = rowptr.device
-        if dev.type != "cuda" or col.device != dev or val.device != dev:
-            raise RuntimeError(f"ItemKNN.fit_csr runs on the GPU: the CSR must live on one GPU (got {dev}, {col.device}, {val.device}); "
-                               "there is no CPU path")
+        rowptr, col, val, I, dev = self._csr(rowptr, col, val, num_items)
         colptr, row, tval = self.build_transpose(rowptr, col, val, I)
         sq = native.knn_item_sq(colptr, tval)
         N = self.k
@@ -336,35 +351,11 @@ class ItemKNN:
     def fit(self, user_pos, item_pos, rating, num_users, num_items, **fit_args):
         """Fits on int64 positions and fp32 ratings that live on the GPU (KernelMF.fit's arguments): the CSR is built on the device by
         a stable sort on (user, item).  A (user, item) pair given twice raises in check()."""
-        n = user_pos.numel() if torch.is_tensor(user_pos) else None
-        for t, what in ((user_pos, "user_pos"), (item_pos, "item_pos")):
-            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != n:
-                raise ValueError(f"ItemKNN: {what} must be a 1-D int64 tensor of {n} positions")
-        if not torch.is_tensor(rating) or rating.dtype != torch.float32 or rating.dim() != 1 or rating.numel() != n:
-            raise ValueError(f"ItemKNN: rating must be a 1-D float32 tensor of {n} entries")
-        num_users, num_items = int(num_users), int(num_items)
-        if n == 0 or num_users < 1 or num_items < 1:
-            raise ValueError(f"ItemKNN: nothing to fit ({n} ratings, {num_users} users, {num_items} items)")
-        dev = user_pos.device
-        if dev.type != "cuda" or item_pos.device != dev or rating.device != dev:
-            raise RuntimeError(f"ItemKNN.fit runs on the GPU: the samples must live on one GPU (got {dev}, {item_pos.device}, {rating.device}); "
-                               "there is no CPU path")
+        _, num_users, num_items, _ = self._samples(user_pos, item_pos, rating, num_users, num_items)
         rowptr, col, val = self.build_csr(user_pos, item_pos, rating, num_users, num_items)
         return self.fit_csr(rowptr, col, val, num_items, **fit_args)
 
     build_csr = staticmethod(build_csr)
-
-    def fit_dataset(self, dataset, device="cuda", **fit_args):
-        """fit on the positions and ratings of a FixedPointwiseDataset over an index provider (its ``resident_inputs()``)."""
-        dev = torch.device(device)
-        res = dataset.resident_inputs(dev)
-        if res is None:
-            raise ValueError("ItemKNN.fit_dataset: the dataset's provider hands out dense rows, not positions")
-        u, i = (t.to(dev) for t in res.tensors)
-        if res.on_chunk is not None:
-            u, i = res.on_chunk(u, i)
-        cp = dataset.content_provider
-        return self.fit(u.contiguous(), i.contiguous(), res.targets.to(dev), cp.get_num_users(), cp.get_num_items(), **fit_args)
 
     def check(self):
         """Synchronises.  Raises ValueError when a fit walked a row whose columns do not strictly ascend, and IndexError when a kernel
@@ -391,10 +382,8 @@ class ItemKNN:
         neighbours, in ``top_k_items``' form (past the count: score -inf, position -1).  ``k`` defaults to the table's width."""
         self._fitted()
         k = self.k if k is None else k
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= self.k:
-            raise ValueError(f"ItemKNN.similar_items: k = {k!r} (an integer in 1 .. {self.k})")
-        if not torch.is_tensor(item_pos) or item_pos.dtype != torch.int64 or item_pos.dim() != 1:
-            raise ValueError("ItemKNN.similar_items: item_pos must be a 1-D int64 tensor of positions")
+        k = _int_in("ItemKNN.similar_items", k, "k", 1, self.k)
+        _positions("ItemKNN.similar_items", item_pos, "item_pos")
         pos = self.nb_pos_[item_pos, :k].to(torch.int64)
         sim = self.nb_sim_[item_pos, :k]
         return torch.where(pos >= 0, sim, torch.full_like(sim, float("-inf"))), pos, self.nb_cnt_[item_pos].clamp_max(k)
@@ -405,7 +394,7 @@ class ItemKNN:
         over the fitted items, not necessarily the fitted ratings, so new users work — against the items ``item_range`` = (i0, i1)
         (default: all)."""
         self._fitted()
-        rowptr, col, val = _knn_ratings("ItemKNN.scores", ratings)
+        rowptr, col, val = _ratings_csr("ItemKNN.scores", ratings)
         return native.knn_scores(rowptr, col, val, user_rows.contiguous() if torch.is_tensor(user_rows) else user_rows, self.nb_pos_,
                                  self.nb_sim_, self.nb_cnt_, item_range, self.weighted_average, self.fill, stage_cap)
 
@@ -413,7 +402,7 @@ class ItemKNN:
         """(n,) fp32 scores of the pairs (row ``user_rows[k]`` of ``ratings``, item ``item_pos[k]``), int64 both: ``scores``' values
         bit for bit, clamped to ``clip`` = (lo, hi) when given."""
         self._fitted()
-        rowptr, col, val = _knn_ratings("ItemKNN.predict", ratings)
+        rowptr, col, val = _ratings_csr("ItemKNN.predict", ratings)
         if clip is not None and (len(clip) != 2 or not clip[0] < clip[1]):
             raise ValueError(f"ItemKNN.predict: clip = {clip!r} (None or (lo, hi) with lo < hi)")
         out = native.knn_predict(rowptr, col, val, user_rows, item_pos, self.nb_pos_, self.nb_sim_, self.nb_cnt_, self.weighted_average,
@@ -422,19 +411,7 @@ class ItemKNN:
 
 
 # ---------------------------------------------------------------------------------------- ImplicitALS
-def _mf_of_tables(user_table, item_table):
-    """The project's MF module over two (rows, F) fp32 tables: zero Linear biases, frozen and in eval mode, on the tables' device."""
-    from .neural_collaborative_filtering.models.mf import MF
-    F = user_table.shape[1]
-    mf = MF(item_dim=item_table.shape[0], user_dim=user_table.shape[0], item_emb=F, user_emb=F).to(user_table.device)
-    with torch.no_grad():
-        for lin, tab in ((mf.user_embeddings[0], user_table), (mf.item_embeddings[0], item_table)):
-            lin.weight = torch.nn.Parameter(tab.contiguous().t(), requires_grad=False)      # id-major, as row_major_embedding_ lays it
-            lin.bias.zero_()
-    return mf.requires_grad_(False).eval()
-
-
-class ImplicitALS:
+class ImplicitALS(_Baseline):
     """Implicit-feedback ALS (csrc/als.hip, THE CONTRACT in include/ncf_abi.h): ``n_iters`` iterations of the user half-sweep followed
     by the item half-sweep, each row the exact minimiser ``(Y^T Y + sum (alpha v) y y^T + reg I)^-1 sum (1 + alpha v) y`` by Cholesky.
     ``fit`` / ``fit_dataset`` / ``fit_csr``; then ``as_mf()`` (the project's MF with the two tables: every ranking and evaluation
@@ -442,17 +419,12 @@ class ImplicitALS:
     ``recommend_new_users``.  A fit is a fixed function of its inputs, bit for bit.  There is no host path."""
 
     def __init__(self, n_factors=64, n_iters=15, reg=0.01, alpha=40.0, init_sd=0.01):
-        if isinstance(n_factors, bool) or not isinstance(n_factors, (int, np.integer)) or not 1 <= n_factors <= native.ALS_MAX_FACTORS:
-            raise ValueError(f"ImplicitALS: n_factors = {n_factors!r} (an integer in 1 .. {native.ALS_MAX_FACTORS})")
-        if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
-            raise ValueError(f"ImplicitALS: n_iters = {n_iters!r} (an integer >= 0)")
-        for name, v in (("reg", reg), ("alpha", alpha), ("init_sd", init_sd)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-                raise ValueError(f"ImplicitALS: {name} = {v!r} is not a finite number")
-        if not reg > 0 or alpha < 0 or init_sd < 0:
-            raise ValueError(f"ImplicitALS: reg > 0, alpha >= 0 and init_sd >= 0 (got {reg}, {alpha}, {init_sd})")
-        self.n_factors, self.n_iters = int(n_factors), int(n_iters)
-        self.reg, self.alpha, self.init_sd = float(reg), float(alpha), float(init_sd)
+        who = "ImplicitALS"
+        self.n_factors = _int_in(who, n_factors, "n_factors", 1, native.ALS_MAX_FACTORS)
+        self.n_iters = _int_in(who, n_iters, "n_iters", 0, INT_MAX)
+        self.reg, self.alpha, self.init_sd = _finite(who, reg, "reg", 0.0), _finite(who, alpha, "alpha", 0.0), _finite(who, init_sd, "init_sd", 0.0)
+        if not self.reg > 0:
+            raise ValueError(f"{who}: reg = {reg} is not > 0")
         self.user_factors_ = self.item_factors_ = None      # (U, F) / (I, F) fp32
         self.item_gram_ = None                              # (F, F) fp32 Gram matrix of the item table: what fold-in solves against
         self.loss_ = []
@@ -466,15 +438,8 @@ class ImplicitALS:
         normal_ of (U, F), then one of (I, F), on the generator's device), rows without any entry as zeros, which they stay.  With
         ``track_loss``, ``loss_`` holds the float64 objective after every half-sweep (a diagnostic by torch operations; it
         synchronises once at the end).  ``block_bytes`` sizes the scratch buffer of rows longer than a segment and changes no bit."""
-        rowptr, col, val = _knn_ratings("ImplicitALS.fit_csr", (rowptr, col, val))
-        I, U = int(num_items), rowptr.numel() - 1
-        if I < 1 or U < 1 or col.numel() == 0:
-            raise ValueError(f"ImplicitALS: nothing to fit ({col.numel()} ratings, {U} users, {I} items)")
-        dev = rowptr.device
-        if dev.type != "cuda" or col.device != dev or val.device != dev:
-            raise RuntimeError(f"ImplicitALS.fit_csr runs on the GPU: the CSR must live on one GPU (got {dev}, {col.device}, {val.device}); "
-                               "there is no CPU path")
-        F = self.n_factors
+        rowptr, col, val, I, dev = self._csr(rowptr, col, val, num_items)
+        F, U = self.n_factors, rowptr.numel() - 1
         colptr, row, tval = build_transpose(rowptr, col, val, I)
         tables = []
         for rows, ptr in ((U, rowptr), (I, colptr)):
@@ -517,33 +482,9 @@ class ImplicitALS:
             **fit_args):
         """Fits on int64 positions and fp32 values that live on the GPU (KernelMF.fit's arguments): the CSR is built on the device by
         a stable sort on (user, item).  A (user, item) pair given twice raises in check()."""
-        n = user_pos.numel() if torch.is_tensor(user_pos) else None
-        for t, what in ((user_pos, "user_pos"), (item_pos, "item_pos")):
-            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != n:
-                raise ValueError(f"ImplicitALS: {what} must be a 1-D int64 tensor of {n} positions")
-        if not torch.is_tensor(rating) or rating.dtype != torch.float32 or rating.dim() != 1 or rating.numel() != n:
-            raise ValueError(f"ImplicitALS: rating must be a 1-D float32 tensor of {n} entries")
-        num_users, num_items = int(num_users), int(num_items)
-        if n == 0 or num_users < 1 or num_items < 1:
-            raise ValueError(f"ImplicitALS: nothing to fit ({n} ratings, {num_users} users, {num_items} items)")
-        dev = user_pos.device
-        if dev.type != "cuda" or item_pos.device != dev or rating.device != dev:
-            raise RuntimeError(f"ImplicitALS.fit runs on the GPU: the samples must live on one GPU (got {dev}, {item_pos.device}, "
-                               f"{rating.device}); there is no CPU path")
+        _, num_users, num_items, _ = self._samples(user_pos, item_pos, rating, num_users, num_items)
         rowptr, col, val = build_csr(user_pos, item_pos, rating, num_users, num_items)
         return self.fit_csr(rowptr, col, val, num_items, generator=generator, track_loss=track_loss, **fit_args)
-
-    def fit_dataset(self, dataset, device="cuda", **fit_args):
-        """fit on the positions and ratings of a FixedPointwiseDataset over an index provider (its ``resident_inputs()``)."""
-        dev = torch.device(device)
-        res = dataset.resident_inputs(dev)
-        if res is None:
-            raise ValueError("ImplicitALS.fit_dataset: the dataset's provider hands out dense rows, not positions")
-        u, i = (t.to(dev) for t in res.tensors)
-        if res.on_chunk is not None:
-            u, i = res.on_chunk(u, i)
-        cp = dataset.content_provider
-        return self.fit(u.contiguous(), i.contiguous(), res.targets.to(dev), cp.get_num_users(), cp.get_num_items(), **fit_args)
 
     def check(self):
         """Synchronises.  Raises when a half-sweep of this device met what it refuses (native.check_als): ValueError for a row whose
@@ -567,8 +508,8 @@ class ImplicitALS:
 
     def predict(self, user_pos, item_pos):
         """(n,) preference scores x_u . y_i for int64 positions on the fit's device: as_mf()'s forward."""
-        _positions(user_pos, "user_pos")
-        _positions(item_pos, "item_pos", user_pos.numel())
+        _positions("ImplicitALS.predict", user_pos, "user_pos")
+        _positions("ImplicitALS.predict", item_pos, "item_pos", user_pos.numel())
         with torch.no_grad():
             return self.as_mf()(user_pos.contiguous(), item_pos.contiguous()).view(-1)
 
@@ -579,9 +520,8 @@ class ImplicitALS:
         cached Gram matrix, the exact minimiser for each row.  A row without entries gives zeros.  Call check() to learn of refused
         input."""
         self._fitted()
-        rowptr, col, val = _knn_ratings("ImplicitALS.fold_in_users", ratings)
-        if not torch.is_tensor(user_rows) or user_rows.dtype != torch.int64 or user_rows.dim() != 1:
-            raise ValueError("ImplicitALS.fold_in_users: user_rows must be a 1-D int64 tensor of rows of ratings")
+        rowptr, col, val = _ratings_csr("ImplicitALS.fold_in_users", ratings)
+        _positions("ImplicitALS.fold_in_users", user_rows, "user_rows")
         return native.als_solve_rows(rowptr, col, val, user_rows.contiguous(), self.item_factors_, self.item_gram_, self.alpha, self.reg,
                                      block_bytes=block_bytes)
 
@@ -591,14 +531,7 @@ class ImplicitALS:
         out with ``exclude_rated``."""
         from . import recommend
         vectors = self.fold_in_users(ratings, user_rows)
-        rowptr, col, _ = _knn_ratings("ImplicitALS.recommend_new_users", ratings)
-        exclude = recommend.rated_exclusion(_RatingsView(rowptr, col), user_rows) if exclude_rated else None
+        rowptr, col, _ = _ratings_csr("ImplicitALS.recommend_new_users", ratings)
+        exclude = recommend.rated_exclusion(SimpleNamespace(rowptr=rowptr, col=col), user_rows) if exclude_rated else None
         users = torch.arange(user_rows.numel(), device=vectors.device)
         return recommend.top_k_items(_mf_of_tables(vectors, self.item_factors_), users, k, exclude=exclude, **top_k_args)
-
-
-class _RatingsView:
-    """What recommend.rated_exclusion reads of a SparseRatings."""
-
-    def __init__(self, rowptr, col):
-        self.rowptr, self.col = rowptr, col

@@ -506,8 +506,6 @@ static size_t als_solve_lds(const AlsGeom& g) {
 }
 static size_t als_stage_lds(const AlsGeom& g) { return sizeof(float) * ((size_t)NCF_ALS_STAGE * g.FP + NCF_ALS_STAGE) + sizeof(int) * NCF_ALS_STAGE; }
 
-static bool als_aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace ncf
 
 using namespace ncf;
@@ -524,7 +522,7 @@ extern "C" int ncf_als_gram(const float* T, int64_t rows, int64_t ld, int F, flo
     if (F < 1 || F > NCF_ALS_MAX_FACTORS) return fail(NCF_EINVAL, "%s: F = %d factors (1 .. %d)", who, F, NCF_ALS_MAX_FACTORS);
     if (ld < F) return fail(NCF_EINVAL, "%s: ld = %lld < F = %d", who, (long long)ld, F);
     if (!G || (rows > 0 && !T)) return fail(NCF_EINVAL, "%s: null table or output", who);
-    if (!als_aligned(T, 4) || !als_aligned(G, 4) || !als_aligned(workspace, 4)) return fail(NCF_EINVAL, "%s: a float array is not 4-byte aligned", who);
+    if (!aligned(T, 4) || !aligned(G, 4) || !aligned(workspace, 4)) return fail(NCF_EINVAL, "%s: a float array is not 4-byte aligned", who);
     const size_t need = ncf_als_gram_workspace_bytes(rows, F);
     if (need && (!workspace || workspace_bytes < need))
         return fail(NCF_EINVAL, "%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
@@ -562,10 +560,10 @@ extern "C" int ncf_als_solve_rows(const int64_t* rowptr, const int32_t* col, con
     if (!(reg > 0.f) || !isfinite(reg)) return fail(NCF_EINVAL, "%s: reg must be finite and > 0", who);
     if (!(alpha >= 0.f) || !isfinite(alpha)) return fail(NCF_EINVAL, "%s: alpha must be finite and >= 0", who);
     if (out_by_row != 0 && out_by_row != 1) return fail(NCF_EINVAL, "%s: out_by_row = %d (0 or 1)", who, out_by_row);
-    if (!als_aligned(val, 4) || !als_aligned(col, 4) || !als_aligned(T, 4) || !als_aligned(G, 4) || !als_aligned(out, 4) || !als_aligned(scratch, 4) ||
-        !als_aligned(flag, 4))
+    if (!aligned(val, 4) || !aligned(col, 4) || !aligned(T, 4) || !aligned(G, 4) || !aligned(out, 4) || !aligned(scratch, 4) ||
+        !aligned(flag, 4))
         return fail(NCF_EINVAL, "%s: a float or int32 array is not 4-byte aligned", who);
-    if (!als_aligned(rowptr, 8) || !als_aligned(rows, 8) || !als_aligned(seg_base, 8) || !als_aligned(seg_row, 8))
+    if (!aligned(rowptr, 8) || !aligned(rows, 8) || !aligned(seg_base, 8) || !aligned(seg_row, 8))
         return fail(NCF_EINVAL, "%s: an int64 array is not 8-byte aligned", who);
     if (B > 0 && (!rowptr || !rows || !G || !out)) return fail(NCF_EINVAL, "%s: null pointers, row list, Gram matrix or output", who);
     if (B > 0 && nnz > 0 && (!col || !val)) return fail(NCF_EINVAL, "%s: %lld entries without col / val", who, (long long)nnz);

@@ -31,13 +31,9 @@ struct AttDrop {
     uint32_t seed, thr;   // keep iff hash16 >= thr, thr = round(p * 65536)
     float scale;          // 1 / (1 - thr / 65536)
 };
-__device__ __forceinline__ uint32_t att_mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
 __device__ __forceinline__ f32x4 att_mask4(uint32_t entry, int chunk, const AttDrop& d) {   // 0 or 1/(1-p') per element
-    const uint32_t h0 = att_mix32(entry * 0x9E3779B1U ^ d.seed ^ (uint32_t)chunk * 0x85EBCA77U);
-    const uint32_t h1 = att_mix32(h0 ^ 0x68E31DA4U);
+    const uint32_t h0 = mix32(entry * 0x9E3779B1U ^ d.seed ^ (uint32_t)chunk * 0x85EBCA77U);
+    const uint32_t h1 = mix32(h0 ^ 0x68E31DA4U);
     return f32x4{(h0 & 0xFFFFU) >= d.thr ? d.scale : 0.f, (h0 >> 16) >= d.thr ? d.scale : 0.f,
                  (h1 & 0xFFFFU) >= d.thr ? d.scale : 0.f, (h1 >> 16) >= d.thr ? d.scale : 0.f};
 }
@@ -46,7 +42,7 @@ __device__ __forceinline__ f32x4 att_mask4(uint32_t entry, int chunk, const AttD
 // `attOut[attOut == 0] = -inf`).  Entry e keeps iff element (e, feature 0) of THE MASK under the message seed does; a kept raw score
 // is multiplied by the scale, and a score that is then exactly zero — dropped, or kept and zero — leaves the softmax.
 __device__ __forceinline__ float att_msg_score(float raw, uint32_t entry, const AttDrop& m) {
-    const bool keep = (att_mix32(entry * 0x9E3779B1U ^ m.seed) & 0xFFFFU) >= m.thr;
+    const bool keep = (mix32(entry * 0x9E3779B1U ^ m.seed) & 0xFFFFU) >= m.thr;
     const float s = keep ? raw * m.scale : 0.f;
     return s == 0.f ? -INFINITY : s;
 }
@@ -733,9 +729,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
 #pragma unroll
     for (int k = 0; k < MAXP; ++k) {
         const int j = k < np ? wave + NW * k : 0;
-        const int64_t b = pair_ids[start + j];
-        const int blo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffff)), bhi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-        pcrow[k] = pc + (((int64_t)bhi << 32) | (unsigned)blo) * ldpc;
+        pcrow[k] = pc + uniform64(pair_ids[start + j]) * ldpc;
 #ifdef ATT_SC_SAMEROW      // diagnostic build (wrong results): every slot reads pair 0's row -> the scalar working set shrinks 4x
         pcrow[k] = pcrow[0];
 #endif

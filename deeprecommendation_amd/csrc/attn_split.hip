@@ -108,9 +108,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_split_kernel(const AttnSplitA
 #pragma unroll
     for (int k = 0; k < MAXP; ++k) {
         const int j = k < np ? wave + NW * k : 0;
-        const int64_t b = a.pair_ids[start + j];
-        const int blo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffff)), bhi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-        pcrow[k] = a.pc + (((int64_t)bhi << 32) | (unsigned)blo) * a.ldpc;
+        pcrow[k] = a.pc + uniform64(a.pair_ids[start + j]) * a.ldpc;
 #if ATT_SPLIT_DIAG == 1
         pcrow[k] = a.pc;
 #endif

@@ -177,10 +177,8 @@ extern "C" int ncf_attn_stats(const float* st, int64_t ldst, int64_t Ir, int64_t
         return fail(NCF_EINVAL, "ncf_attn_stats: null pointer");
     if ((!sum || !count) && Ir > 0 && Ic > 0) return fail(NCF_EINVAL, "ncf_attn_stats: null output pointer");
     if (!workspace) return fail(NCF_EINVAL, "ncf_attn_stats: null workspace");
-    auto misaligned = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
-    if (misaligned(st, 4) || misaligned(col, 4) || misaligned(oob, 4) || misaligned(rowptr, 8) || misaligned(user_rows, 8) ||
-        misaligned(cands, 8) || misaligned(order, 8) || misaligned(cand_rowptr, 8) || misaligned(sum, 8) || misaligned(count, 8) ||
-        misaligned(workspace, 8))
+    if (!aligned(st, 4) || !aligned(col, 4) || !aligned(oob, 4) || !aligned(rowptr, 8) || !aligned(user_rows, 8) || !aligned(cands, 8) ||
+        !aligned(order, 8) || !aligned(cand_rowptr, 8) || !aligned(sum, 8) || !aligned(count, 8) || !aligned(workspace, 8))
         return fail(NCF_EINVAL, "ncf_attn_stats: misaligned pointer");
     if (ldst < Ic) return fail(NCF_EINVAL, "ncf_attn_stats: leading dimension of the logit table smaller than its row");
     if (ldsum < Ir || ldcount < Ir) return fail(NCF_EINVAL, "ncf_attn_stats: leading dimension of sum / count smaller than I_r");

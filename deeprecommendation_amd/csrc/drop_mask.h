@@ -14,10 +14,6 @@ struct DropArgs {
     uint32_t seed, thr;   // keep iff hash16 >= thr, thr = round(p * 65536)
     float scale;          // 1 / (1 - thr / 65536)
 };
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {   // lowbias32 (bijective avalanche mix)
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
 __device__ __forceinline__ f32x4 drop4(f32x4 v, uint32_t edge, int chunk, const DropArgs& d) {
     const uint32_t h0 = mix32(edge * 0x9E3779B1U ^ d.seed ^ (uint32_t)chunk * 0x85EBCA77U);
     const uint32_t h1 = mix32(h0 ^ 0x68E31DA4U);

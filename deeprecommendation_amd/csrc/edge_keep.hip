@@ -12,11 +12,6 @@
 
 namespace ncf {
 
-__device__ __forceinline__ uint32_t keep_mix32(uint32_t x) {   // lowbias32, the mix of spmm.hip / negsample.hip
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-
 // true iff key occurs in sorted[0 .. n): lower bound by bisection, n >= 1
 __device__ __forceinline__ bool among_sorted(const int64_t* __restrict__ sorted, int64_t n, int64_t key) {
     int64_t lo = 0, hi = n;
@@ -50,7 +45,7 @@ __global__ __launch_bounds__(256) void edge_keep_kernel(const int64_t* __restric
                 const int64_t src = col[e];
                 kept = kept && src >= 0 && src < N && node_keep[src] != 0;
             }
-            if (thr) kept = kept && (keep_mix32((uint32_t)slot[e] * 0x9E3779B1U ^ seed) >> 16) >= thr;
+            if (thr) kept = kept && (mix32((uint32_t)slot[e] * 0x9E3779B1U ^ seed) >> 16) >= thr;
             if (kept && n_targets > 0) kept = !among_sorted(targets, n_targets, pair_key[e]);
             w_out[e] = kept ? (attr ? attr[e] : 1.f) : 0.f;
             cnt += kept ? 1 : 0;

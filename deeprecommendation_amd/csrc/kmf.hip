@@ -34,12 +34,6 @@ namespace ncf {
 
 enum { KMF_FLAG_ID = 1, KMF_FLAG_BLOCK = 2, KMF_FLAG_PTR = 4 };
 
-__device__ __forceinline__ int64_t kmf_uniform64(int64_t v) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffff));
-    const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 __device__ __forceinline__ float kmf_lane_value(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(64) void kmf_stratum_kernel(
     const int a = blockIdx.x;
     const int ib = a + s >= W ? a + s - W : a + s;
     const int64_t slot = (int64_t)s * W + a;
-    int64_t beg = kmf_uniform64(block_ptr[slot]), end = kmf_uniform64(block_ptr[slot + 1]);
+    int64_t beg = uniform64(block_ptr[slot]), end = uniform64(block_ptr[slot + 1]);
     if (beg < 0 || end > n || end < beg) {                 // a block pointer outside the samples: nothing of the block is read
         if (flag && lane == 0) atomicOr(flag, KMF_FLAG_PTR);
         beg = end = 0;
@@ -199,7 +193,7 @@ __global__ __launch_bounds__(64) void kmf_fold_kernel(
             if (flag && lane == 0) atomicOr(flag, KMF_FLAG_ID);
             continue;
         }
-        int64_t beg = kmf_uniform64(rowptr[k]), end = kmf_uniform64(rowptr[k + 1]);
+        int64_t beg = uniform64(rowptr[k]), end = uniform64(rowptr[k + 1]);
         if (beg < 0 || end > nnz || end < beg) {
             if (flag && lane == 0) atomicOr(flag, KMF_FLAG_PTR);
             beg = end = 0;

@@ -31,12 +31,6 @@
 
 namespace ncf {
 
-__device__ __forceinline__ int64_t knn_uniform64(int64_t v) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffff));
-    const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 // [beg, end) of row r of a CSR with nnz entries; an empty range and the out-of-range flag for a pair outside the entries
 __device__ __forceinline__ void knn_range(const int64_t* __restrict__ ptr, int64_t r, int64_t nnz, int32_t* oob, int64_t& beg, int64_t& end) {
     beg = ptr[r];
@@ -54,8 +48,8 @@ __global__ __launch_bounds__(64) void knn_item_sq_kernel(const int64_t* __restri
     for (int64_t i = blockIdx.x; i < I; i += gridDim.x) {
         int64_t beg, end;
         knn_range(colptr, i, nnz, lane == 0 ? oob : nullptr, beg, end);
-        beg = knn_uniform64(beg);
-        end = knn_uniform64(end);
+        beg = uniform64(beg);
+        end = uniform64(end);
         float part = 0.0f;
         for (int64_t e = beg + lane; e < end; e += 64) {
             const float v = tval[e];
@@ -94,8 +88,8 @@ __global__ __launch_bounds__(64) void knn_sim_rows_kernel(
     __syncthreads();
     int64_t cb, ce;
     knn_range(colptr, i, nnzT, lane == 0 ? oob : nullptr, cb, ce);
-    cb = knn_uniform64(cb);
-    ce = knn_uniform64(ce);
+    cb = uniform64(cb);
+    ce = uniform64(ce);
     for (int64_t p0 = cb; p0 < ce; p0 += 64) {
         const int nb = (int)(ce - p0 < 64 ? ce - p0 : 64);
         int uv = -1;
@@ -114,8 +108,8 @@ __global__ __launch_bounds__(64) void knn_sim_rows_kernel(
             const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wv), g));
             int64_t rb, re;
             knn_range(rowptr, u, nnz, lane == 0 ? oob : nullptr, rb, re);
-            rb = knn_uniform64(rb);
-            re = knn_uniform64(re);
+            rb = uniform64(rb);
+            re = uniform64(re);
             const bool whole = tile == 0 || re - rb <= NCF_KNN_SCAN_MAX;   // tile 0 walks every row whole: it holds the order check
             int64_t e0 = rb;
             if (!whole) {                                  // the first entry with col >= t0 (indices stay inside [rb, re) whatever the row holds)
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(64) void knn_sim_rows_kernel(
                     const int64_t mid = lo + ((hi - lo) >> 1);
                     if ((int64_t)col[mid] < t0) lo = mid + 1; else hi = mid;
                 }
-                e0 = knn_uniform64(lo);
+                e0 = uniform64(lo);
             }
             for (; e0 < re; e0 += 64) {
                 const int64_t e = e0 + lane;

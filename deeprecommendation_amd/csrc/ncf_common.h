@@ -51,6 +51,7 @@ int option(int opt);
 int num_cus();
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }   // bytes: a power of two
 
 // Stream-ordered fill of 32-bit words BY A KERNEL.  hipMemsetAsync is not used in this library: captured into a HIP graph, memset
 // nodes and the kernel nodes around them lost their order from the second back-to-back replay on (ROCm 7.2 — a replayed
@@ -72,6 +73,21 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float bf16_to_f32(unsigned short v) { return __uint_as_float(((unsigned int)v) << 16); }
+
+// lowbias32, a bijective avalanche mix of 32 bits: the hash of every counter-based draw of the library (the dropout masks of
+// spmm.hip / gat.hip / attn.hip, edge_keep.hip's keep rule, negsample.hip's uniforms; include/ncf_abi.h states each formula).
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return x;
+}
+
+// A 64-bit value that is the same in every lane of the wave, moved to scalar registers (two readfirstlanes): a row's [beg, end)
+// then drives scalar loop bounds and addresses.
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffff));
+    const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
 
 // Row of a 32x32 MFMA accumulator held in register r of a lane in half h (= lane >> 5):
 // row = (r & 3) + 8 * (r >> 2) + 4 * h   (MI355X C/D layout, dtype independent).

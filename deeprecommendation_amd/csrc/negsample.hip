@@ -23,15 +23,10 @@ namespace {
 
 constexpr int kCdfUnroll = 8;   // pass 1 keeps 8 independent 256-byte wave loads in flight; rows of <= 512 entries stay in registers
 
-__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {   // the mix of spmm.hip / attn.hip's dropout masks
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-
 // include/ncf_abi.h states this formula; tests restate it in numpy
 __device__ __forceinline__ float slot_uniform(uint32_t seed, uint64_t slot) {
-    uint32_t x = lowbias32((uint32_t)slot * 0x9E3779B1U ^ seed);
-    x = lowbias32(x ^ (uint32_t)(slot >> 32) * 0x85EBCA77U ^ 0x68E31DA4U);
+    uint32_t x = mix32((uint32_t)slot * 0x9E3779B1U ^ seed);
+    x = mix32(x ^ (uint32_t)(slot >> 32) * 0x85EBCA77U ^ 0x68E31DA4U);
     return (float)(x >> 8) * 0x1p-24f;   // 24 bits: exact in fp32, in [0, 1)
 }
 

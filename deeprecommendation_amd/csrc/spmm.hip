@@ -9,7 +9,7 @@
 // segment order.  No float atomics anywhere: the result is bitwise reproducible run to run.
 // The layer-mean accumulator (gnn_ncf.py:351) is fused into the epilogue: sum[row] += y[row].
 #include "ncf_common.h"
-#include "drop_mask.h"   // DropArgs, mix32, drop4: the message dropout mask, shared with gat.hip
+#include "drop_mask.h"   // DropArgs, drop4: the message dropout mask, shared with gat.hip (its hash, mix32, is ncf_common.h's)
 #include <math.h>
 
 namespace ncf {

@@ -32,12 +32,6 @@
 
 namespace ncf {
 
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffff));
-    const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 // VEC: lane l holds columns c0 + 4 l .. c0 + 4 l + 3 (one 16-byte load per row); else columns c0 + l + 64 j, j < 4.
 template <bool VEC>
 __global__ __launch_bounds__(256) void user_profiles_kernel(

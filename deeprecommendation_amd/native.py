@@ -327,6 +327,74 @@ def _idx(t: Optional[torch.Tensor], B: Optional[int] = None):
     return t
 
 
+# ------------------------------------------------------------------ the argument checks of the "who: ..." wrappers
+# Each raises ValueError("<who>: <argument> ...") naming the limit that was broken, and touches no device: a wrapper runs all of
+# them, then _dev_all, and only then loads the library and allocates.
+def _dev_all(*pairs):
+    """The device sweep: every ``(tensor, name)`` pair given must live on the GPU; a None tensor is skipped."""
+    for t, what in pairs:
+        if t is not None:
+            _dev(t, what)
+
+
+def _int_in(who, v, what, lo, hi):
+    """``v`` as an int in lo .. hi; a bool or a float is refused, a numpy integer taken."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+        raise ValueError(f"{who}: {what} = {v!r} (an integer in {lo} .. {hi})")
+    return int(v)
+
+
+def _finite(who, v, what, lo=None):
+    """``v`` as a finite float (>= ``lo`` when given); a bool is refused, a numpy scalar taken."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (lo is not None and v < lo):
+        raise ValueError(f"{who}: {what} = {v!r} is not a finite number" + ("" if lo is None else f" >= {lo}"))
+    return float(v)
+
+
+def _vec1d(who, t, what, dt, n=None):
+    if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous 1-D {dt} tensor")
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{who}: {what} has {t.numel()} entries, expected {n}")
+
+
+def _out1d(who, t, what, dt, n):
+    if t is not None and (not torch.is_tensor(t) or t.dtype != dt or not t.is_contiguous() or t.numel() != n):
+        raise ValueError(f"{who}: {what} must be a contiguous {dt} tensor of {n} entries")
+
+
+def _csr(who, ptr, idx, val, names, rows=None):
+    """Checks one CSR (pointers int64, ids int32, values fp32, contiguous 1-D); returns (rows, nnz)."""
+    _vec1d(who, ptr, names[0], torch.int64, None if rows is None else rows + 1)
+    if ptr.numel() < 1:
+        raise ValueError(f"{who}: {names[0]} is empty")
+    _vec1d(who, idx, names[1], torch.int32)
+    _vec1d(who, val, names[2], torch.float32, idx.numel())
+    return ptr.numel() - 1, idx.numel()
+
+
+def _table_f32(who, t, what, min_cols=1):
+    """A 2-D float32 table of at least ``min_cols`` columns whose inner stride is 1 (any, when it is one column wide)."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{who}: {what} must be a 2-D float32 tensor with unit inner stride")
+    if t.shape[1] < min_cols:
+        raise ValueError(f"{who}: {what} has rows of {t.shape[1]} floats, fewer than the {min_cols} needed")
+
+
+def _out2d(who, out, rows, cols, like, swept, contiguous=False, wider=False):
+    """The optional float32 ``out`` of a wrapper, and the end of its checks: a given ``out`` must be (rows, cols) — (rows, >= cols)
+    with ``wider`` — with unit inner stride and any row stride, or ``contiguous``; then the device sweep over ``swept`` and ``out``;
+    only after both is an absent ``out`` allocated beside ``like``.  Returns the tensor to write."""
+    if out is not None:
+        ok = torch.is_tensor(out) and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == rows
+        ok = ok and (out.shape[1] >= cols if wider else out.shape[1] == cols)
+        if not (ok and (out.is_contiguous() if contiguous else out.shape[1] <= 1 or out.stride(1) == 1)):
+            raise ValueError(f"{who}: out must be a ({rows}, {'>= ' if wider else ''}{cols}) float32 tensor, "
+                             + ("contiguous" if contiguous else "with unit inner stride"))
+    _dev_all(*swept, (out, "out"))
+    return torch.empty((rows, cols), dtype=torch.float32, device=like.device) if out is None else out
+
+
 _flags = {}
 
 
@@ -337,6 +405,37 @@ def _flag(kind, device) -> torch.Tensor:
     if f is None:
         f = _flags[kind, device] = torch.zeros(1, dtype=torch.int32, device=device)
     return f
+
+
+KMF_FLAG_ID, KMF_FLAG_BLOCK, KMF_FLAG_PTR = 1, 2, 4                                             # csrc/kmf.hip
+ALS_FLAG_COL, ALS_FLAG_PTR, ALS_FLAG_ORDER, ALS_FLAG_VAL, ALS_FLAG_PIVOT = 1, 2, 4, 8, 16       # include/ncf_abi.h NCF_ALS_*
+
+# kind -> (model, [(bit, what a kernel met, what check_* raises for it)]).  ncf_knn_sim_rows' word has one meaning whatever its value.
+_FLAG_BITS = {
+    "kmf": ("KernelMF", [(KMF_FLAG_ID, "an id outside its table", IndexError),
+                         (KMF_FLAG_BLOCK, "a sample filed in the wrong block", IndexError),
+                         (KMF_FLAG_PTR, "a block / row pointer outside the samples", IndexError)]),
+    "knn": ("ItemKNN", [(~0, "a row of the ratings CSR does not hold strictly ascending columns", ValueError)]),
+    "als": ("ImplicitALS", [(ALS_FLAG_COL, "a column outside the fixed table", IndexError),
+                            (ALS_FLAG_PTR, "a row or a row pointer outside the ratings", IndexError),
+                            (ALS_FLAG_ORDER, "a row whose columns do not strictly ascend", ValueError),
+                            (ALS_FLAG_VAL, "a value that is negative or not finite", ValueError),
+                            (ALS_FLAG_PIVOT, "a pivot that is not positive and finite", ValueError)]),
+}
+
+
+def _check_flag(kind, device, flag=None):
+    """Synchronising check of ``kind``'s flag word on ``device`` (``flag``: another word): when it is not zero, clears it and raises
+    with the text of every set bit and, where the word has more than one meaning, its value — IndexError when an id or a pointer was at fault, else ValueError, as
+    _FLAG_BITS lists them."""
+    f = _flag(kind, device) if flag is None else flag
+    bits = int(f.item())
+    if bits:
+        f.zero_()
+        model, table = _FLAG_BITS[kind]
+        hit = [(text, exc) for bit, text, exc in table if bits & bit]
+        exc = IndexError if any(e is IndexError for _, e in hit) else table[-1][2]
+        raise exc(f"{model}: " + ", ".join(text for text, _ in hit) + (f" (flag {bits})" if len(table) > 1 else ""))
 
 
 def _oob_flag(device) -> torch.Tensor:
@@ -1435,30 +1534,22 @@ def user_profiles(rowptr: torch.Tensor, col: torch.Tensor, rating: torch.Tensor,
     ``rating`` fp32 of one entry per rating, ``avg`` (U,) float64, ``features`` (I, F) fp32 rows (a column slice is fine).  A column
     outside [0, I) sets the sticky out-of-range flag (check_oob) and adds nothing.  Shapes, dtypes and layout are checked before the
     device is."""
-    for t, what, dt in ((rowptr, "rowptr", torch.int64), (col, "col", torch.int32), (rating, "rating", torch.float32),
-                        (avg, "avg", torch.float64)):
-        _vec1d("user_profiles", t, what, dt)
-    if features.dtype != torch.float32 or (out is not None and out.dtype != torch.float32):
-        raise ValueError("user_profiles: features and out must be float32")
-    I, F, ldf = _rows2d(features, "features")
+    who = "user_profiles"
+    _vec1d(who, avg, "avg", torch.float64)
     U = avg.numel()
-    if rowptr.numel() != U + 1 or col.numel() != rating.numel():
-        raise ValueError(f"user_profiles: rowptr has {rowptr.numel()} entries for {U} users, col {col.numel()} for {rating.numel()} ratings")
-    if out is not None and (out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (U, F)):
-        raise ValueError(f"user_profiles: out must be ({U}, {F}) with unit inner stride")
-    for t, what in ((rowptr, "rowptr"), (col, "col"), (rating, "rating"), (avg, "avg"), (features, "features"), (out, "out")):
-        if t is not None:
-            _dev(t, what)
+    _vec1d(who, rowptr, "rowptr", torch.int64, U + 1)
+    _vec1d(who, col, "col", torch.int32)
+    _vec1d(who, rating, "rating", torch.float32, col.numel())
+    _table_f32(who, features, "features", 0)
+    (I, F), ldf = features.shape, features.stride(0)
+    out = _out2d(who, out, U, F, features, ((rowptr, "rowptr"), (col, "col"), (rating, "rating"), (avg, "avg"), (features, "features")))
     lib = load_library()
-    if out is None:
-        out = torch.empty((U, F), dtype=torch.float32, device=features.device)
     _check(lib.ncf_user_profiles(_ptr(rowptr), _ptr(col), _ptr(rating), col.numel(), _ptr(avg), U, _ptr(features), I, ldf, F, _ptr(out),
                                  out.stride(0), _ptr(_oob_flag(features.device)), _stream(features)))
     return out
 
 
 KMF_MAX_FACTORS, KMF_MAX_BLOCKS = 256, 1024       # csrc/kmf.hip
-KMF_FLAG_ID, KMF_FLAG_BLOCK, KMF_FLAG_PTR = 1, 2, 4
 
 
 def kmf_flag(device) -> torch.Tensor:
@@ -1467,37 +1558,19 @@ def kmf_flag(device) -> torch.Tensor:
 
 
 def check_kmf(device, flag: Optional[torch.Tensor] = None):
-    """Synchronising check of the KernelMF flag word: raises, and clears it, when a kernel met an id outside its table, a sample
-    filed in the wrong block or a broken block / row pointer (each such sample or block was skipped)."""
-    f = kmf_flag(device) if flag is None else flag
-    bits = int(f.item())
-    if bits:
-        f.zero_()
-        what = [w for b, w in ((KMF_FLAG_ID, "an id outside its table"), (KMF_FLAG_BLOCK, "a sample filed in the wrong block"),
-                               (KMF_FLAG_PTR, "a block / row pointer outside the samples")) if bits & b]
-        raise IndexError("KernelMF: " + ", ".join(what) + f" (flag {bits})")
+    """Synchronising check of the KernelMF flag word: raises IndexError, and clears it, when a kernel met an id outside its table, a
+    sample filed in the wrong block or a broken block / row pointer (each such sample or block was skipped)."""
+    _check_flag("kmf", device, flag)
 
 
-def _kmf_tables(who, PU, QI, F):
-    for t, what in ((PU, "PU"), (QI, "QI")):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-            raise ValueError(f"{who}: {what} must be a 2-D float32 tensor with unit inner stride")
+def _kmf_factors(who, PU, QI, F):
+    """F of a KernelMF call, whose two tables hold F factors and the bias in a row."""
     F = int(F)
-    if F < 1 or PU.shape[1] < F + 1 or QI.shape[1] < F + 1:
-        raise ValueError(f"{who}: rows of {PU.shape[1]} / {QI.shape[1]} floats cannot hold F = {F} factors and the bias")
+    if F < 1:
+        raise ValueError(f"{who}: F = {F} is not at least one factor")
+    _table_f32(who, PU, "PU", F + 1)
+    _table_f32(who, QI, "QI", F + 1)
     return F
-
-
-def _vec1d(who, t, what, dt, n=None):
-    if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
-        raise ValueError(f"{who}: {what} must be a contiguous 1-D {dt} tensor")
-    if n is not None and t.numel() != n:
-        raise ValueError(f"{who}: {what} has {t.numel()} entries, expected {n}")
-
-
-def _out1d(who, t, what, dt, n):
-    if t is not None and (not torch.is_tensor(t) or t.dtype != dt or not t.is_contiguous() or t.numel() != n):
-        raise ValueError(f"{who}: {what} must be a contiguous {dt} tensor of {n} entries")
 
 
 def kmf_epoch(PU: torch.Tensor, QI: torch.Tensor, F: int, user: torch.Tensor, item: torch.Tensor, rating: torch.Tensor,
@@ -1510,7 +1583,7 @@ def kmf_epoch(PU: torch.Tensor, QI: torch.Tensor, F: int, user: torch.Tensor, it
     the kernel refuses sets ``flag`` (default: the device's word, check_kmf).  Shapes, dtypes and layout are checked before the device
     is."""
     who = "kmf_epoch"
-    F = _kmf_tables(who, PU, QI, F)
+    F = _kmf_factors(who, PU, QI, F)
     U, I = PU.shape[0], QI.shape[0]
     _vec1d(who, user, "user", torch.int32)
     n = user.numel()
@@ -1527,10 +1600,8 @@ def kmf_epoch(PU: torch.Tensor, QI: torch.Tensor, F: int, user: torch.Tensor, it
         raise ValueError(f"{who}: n_epochs = {n_epochs}")
     _out1d(who, sse, "sse", torch.float64, n_epochs * W)
     _out1d(who, flag, "flag", torch.int32, 1)
-    for t, what in ((PU, "PU"), (QI, "QI"), (user, "user"), (item, "item"), (rating, "rating"), (block_ptr, "block_ptr"),
-                    (user_block, "user_block"), (item_block, "item_block"), (sse, "sse"), (flag, "flag")):
-        if t is not None:
-            _dev(t, what)
+    _dev_all((PU, "PU"), (QI, "QI"), (user, "user"), (item, "item"), (rating, "rating"), (block_ptr, "block_ptr"),
+             (user_block, "user_block"), (item_block, "item_block"), (sse, "sse"), (flag, "flag"))
     lib = load_library()
     if sse is None:
         sse = torch.zeros((n_epochs, W), dtype=torch.float64, device=PU.device)
@@ -1551,23 +1622,17 @@ def kmf_fold_users(PU: torch.Tensor, QI: torch.Tensor, F: int, users: torch.Tens
     no user twice), in place on ``PU``; ``QI`` is only read.  Returns the (n_epochs, n_users) float64 sums of squared errors (``sse``
     when given: overwritten).  Checked before the device is, as kmf_epoch."""
     who = "kmf_fold_users"
-    F = _kmf_tables(who, PU, QI, F)
+    F = _kmf_factors(who, PU, QI, F)
     U, I = PU.shape[0], QI.shape[0]
     _vec1d(who, users, "users", torch.int32)
     nu = users.numel()
-    _vec1d(who, rowptr, "rowptr", torch.int64, nu + 1)
-    _vec1d(who, col, "col", torch.int32)
-    nnz = col.numel()
-    _vec1d(who, rating, "rating", torch.float32, nnz)
+    _, nnz = _csr(who, rowptr, col, rating, ("rowptr", "col", "rating"), nu)
     n_epochs = int(n_epochs)
     if n_epochs < 0:
         raise ValueError(f"{who}: n_epochs = {n_epochs}")
     _out1d(who, sse, "sse", torch.float64, n_epochs * nu)
     _out1d(who, flag, "flag", torch.int32, 1)
-    for t, what in ((PU, "PU"), (QI, "QI"), (users, "users"), (rowptr, "rowptr"), (col, "col"), (rating, "rating"), (sse, "sse"),
-                    (flag, "flag")):
-        if t is not None:
-            _dev(t, what)
+    _dev_all((PU, "PU"), (QI, "QI"), (users, "users"), (rowptr, "rowptr"), (col, "col"), (rating, "rating"), (sse, "sse"), (flag, "flag"))
     lib = load_library()
     if sse is None:
         sse = torch.zeros((n_epochs, nu), dtype=torch.float64, device=PU.device)
@@ -1588,34 +1653,9 @@ def knn_flag(device) -> torch.Tensor:
 
 
 def check_knn(device, flag: Optional[torch.Tensor] = None):
-    """Synchronising check of the ItemKNN flag word: raises, and clears it, when ncf_knn_sim_rows walked a row of the user CSR whose
-    columns do not strictly ascend (a duplicate rating or an unsorted row; the similarities of such a fit are unspecified)."""
-    f = knn_flag(device) if flag is None else flag
-    if int(f.item()):
-        f.zero_()
-        raise ValueError("ItemKNN: a row of the ratings CSR does not hold strictly ascending columns")
-
-
-def _knn_csr(who, ptr, idx, val, names, rows=None):
-    """Checks one CSR (pointers int64, ids int32, values fp32, contiguous 1-D); returns (rows, nnz)."""
-    _vec1d(who, ptr, names[0], torch.int64, None if rows is None else rows + 1)
-    if ptr.numel() < 1:
-        raise ValueError(f"{who}: {names[0]} is empty")
-    _vec1d(who, idx, names[1], torch.int32)
-    _vec1d(who, val, names[2], torch.float32, idx.numel())
-    return ptr.numel() - 1, idx.numel()
-
-
-def _knn_int(who, v, what, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
-        raise ValueError(f"{who}: {what} = {v!r} (an integer in {lo} .. {hi})")
-    return int(v)
-
-
-def _knn_float(who, v, what, lo=None):
-    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (lo is not None and v < lo):
-        raise ValueError(f"{who}: {what} = {v!r} is not a finite number" + ("" if lo is None else f" >= {lo}"))
-    return float(v)
+    """Synchronising check of the ItemKNN flag word: raises ValueError, and clears it, when ncf_knn_sim_rows walked a row of the user
+    CSR whose columns do not strictly ascend (a duplicate rating or an unsorted row; the similarities of such a fit are unspecified)."""
+    _check_flag("knn", device, flag)
 
 
 def _knn_range(who, item_range, I):
@@ -1647,9 +1687,7 @@ def knn_item_sq(colptr: torch.Tensor, tval: torch.Tensor, out: Optional[torch.Te
     _vec1d(who, tval, "tval", torch.float32)
     I = colptr.numel() - 1
     _out1d(who, out, "out", torch.float32, I)
-    for t, what in ((colptr, "colptr"), (tval, "tval"), (out, "out")):
-        if t is not None:
-            _dev(t, what)
+    _dev_all((colptr, "colptr"), (tval, "tval"), (out, "out"))
     lib = load_library()
     if out is None:
         out = torch.empty(I, dtype=torch.float32, device=colptr.device)
@@ -1666,29 +1704,22 @@ def knn_sim_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, col
     choose, else a multiple of 64.  An id outside its range raises at the next check_oob(), a non-ascending row at check_knn()
     (``flag``: another word than the device's).  Checked before the device is; one launch on the current stream."""
     who = "knn_sim_rows"
-    U, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
-    I, nnzT = _knn_csr(who, colptr, row, tval, ("colptr", "row", "tval"))
+    U, nnz = _csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    I, nnzT = _csr(who, colptr, row, tval, ("colptr", "row", "tval"))
     _vec1d(who, sq, "sq", torch.float32, I)
     i0, i1 = _knn_range(who, item_range, I)
     if i1 - i0 > KNN_MAX_ROWS:
         raise ValueError(f"{who}: {i1 - i0} items in one call (at most {KNN_MAX_ROWS})")
-    min_support = _knn_int(who, min_support, "min_support", 1, 2 ** 31 - 1)
-    shrink = _knn_float(who, shrink, "shrink", 0.0)
-    col_tile = _knn_int(who, col_tile, "col_tile", 0, KNN_MAX_TILE)
+    min_support = _int_in(who, min_support, "min_support", 1, 2 ** 31 - 1)
+    shrink = _finite(who, shrink, "shrink", 0.0)
+    col_tile = _int_in(who, col_tile, "col_tile", 0, KNN_MAX_TILE)
     if col_tile % 64:
         raise ValueError(f"{who}: col_tile = {col_tile} is not a multiple of 64")
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (i1 - i0, I)
-                            or (I > 1 and out.stride(1) != 1)):
-        raise ValueError(f"{who}: out must be a ({i1 - i0}, {I}) float32 tensor with unit inner stride")
     _out1d(who, flag, "flag", torch.int32, 1)
-    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (colptr, "colptr"), (row, "row"), (tval, "tval"), (sq, "sq"), (out, "out"),
-                    (flag, "flag")):
-        if t is not None:
-            _dev(t, what)
+    out = _out2d(who, out, i1 - i0, I, rowptr, ((rowptr, "rowptr"), (col, "col"), (val, "val"), (colptr, "colptr"), (row, "row"), (tval, "tval"),
+                                                (sq, "sq"), (flag, "flag")))
     lib = load_library()
     dev = rowptr.device
-    if out is None:
-        out = torch.empty((i1 - i0, I), dtype=torch.float32, device=dev)
     if flag is None:
         flag = knn_flag(dev)
     if i1 > i0 and I:
@@ -1707,26 +1738,19 @@ def knn_scores(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, users
     (0 = the default); the bits do not depend on it.  A row outside the CSR scores as an empty one and raises at the next
     check_oob().  Checked before the device is; one launch on the current stream."""
     who = "knn_scores"
-    R, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    R, nnz = _csr(who, rowptr, col, val, ("rowptr", "col", "val"))
     _vec1d(who, users, "users", torch.int64)
     B = users.numel()
     if B > KNN_MAX_ROWS:
         raise ValueError(f"{who}: {B} users in one call (at most {KNN_MAX_ROWS})")
     I, N = _knn_table(who, nb_pos, nb_sim, nb_cnt)
     i0, i1 = _knn_range(who, item_range, I)
-    fill = _knn_float(who, fill, "fill")
-    stage_cap = _knn_int(who, stage_cap, "stage_cap", 0, KNN_MAX_STAGE)
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (B, i1 - i0)
-                            or (i1 - i0 > 1 and out.stride(1) != 1)):
-        raise ValueError(f"{who}: out must be a ({B}, {i1 - i0}) float32 tensor with unit inner stride")
-    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (nb_pos, "nb_pos"), (nb_sim, "nb_sim"),
-                    (nb_cnt, "nb_cnt"), (out, "out")):
-        if t is not None:
-            _dev(t, what)
+    fill = _finite(who, fill, "fill")
+    stage_cap = _int_in(who, stage_cap, "stage_cap", 0, KNN_MAX_STAGE)
+    out = _out2d(who, out, B, i1 - i0, rowptr, ((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (nb_pos, "nb_pos"),
+                                                (nb_sim, "nb_sim"), (nb_cnt, "nb_cnt")))
     lib = load_library()
     dev = rowptr.device
-    if out is None:
-        out = torch.empty((B, i1 - i0), dtype=torch.float32, device=dev)
     if B and i1 > i0:
         _check(lib.ncf_knn_scores(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(users), B, _ptr(nb_pos), _ptr(nb_sim), _ptr(nb_cnt), I, N,
                                   i0, i1, 1 if weighted_average else 0, fill, stage_cap, _ptr(out), max(out.stride(0), i1 - i0),
@@ -1740,15 +1764,14 @@ def knn_predict(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, user
     value of that user and item, bit for bit.  A row or an item outside its range scores as an empty row and raises at the next
     check_oob().  Checked before the device is; one launch on the current stream."""
     who = "knn_predict"
-    R, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    R, nnz = _csr(who, rowptr, col, val, ("rowptr", "col", "val"))
     _vec1d(who, users, "users", torch.int64)
     n = users.numel()
     _vec1d(who, items, "items", torch.int64, n)
     I, N = _knn_table(who, nb_pos, nb_sim, nb_cnt)
-    fill = _knn_float(who, fill, "fill")
-    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (items, "items"), (nb_pos, "nb_pos"),
-                    (nb_sim, "nb_sim"), (nb_cnt, "nb_cnt")):
-        _dev(t, what)
+    fill = _finite(who, fill, "fill")
+    _dev_all((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (items, "items"), (nb_pos, "nb_pos"), (nb_sim, "nb_sim"),
+             (nb_cnt, "nb_cnt"))
     lib = load_library()
     dev = rowptr.device
     out = torch.empty(n, dtype=torch.float32, device=dev)
@@ -1759,7 +1782,6 @@ def knn_predict(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, user
 
 
 ALS_MAX_FACTORS, ALS_GRAM_ROWS, ALS_SEG = 128, 256, 512       # include/ncf_abi.h NCF_ALS_*
-ALS_FLAG_COL, ALS_FLAG_PTR, ALS_FLAG_ORDER, ALS_FLAG_VAL, ALS_FLAG_PIVOT = 1, 2, 4, 8, 16
 ALS_BLOCK_BYTES = 256 << 20
 
 
@@ -1773,24 +1795,15 @@ def check_als(device, flag: Optional[torch.Tensor] = None):
     table or a value that is negative or not finite (each such entry was skipped), a row outside the CSR or a broken pointer pair, a
     row whose columns do not strictly ascend or a pivot that is not positive (each such row was written as zeros).  IndexError when
     an id or a pointer was at fault, ValueError otherwise."""
-    f = als_flag(device) if flag is None else flag
-    bits = int(f.item())
-    if bits:
-        f.zero_()
-        what = [w for b, w in ((ALS_FLAG_COL, "a column outside the fixed table"), (ALS_FLAG_PTR, "a row or a row pointer outside the ratings"),
-                               (ALS_FLAG_ORDER, "a row whose columns do not strictly ascend"),
-                               (ALS_FLAG_VAL, "a value that is negative or not finite"),
-                               (ALS_FLAG_PIVOT, "a pivot that is not positive and finite")) if bits & b]
-        raise (IndexError if bits & (ALS_FLAG_COL | ALS_FLAG_PTR) else ValueError)("ImplicitALS: " + ", ".join(what) + f" (flag {bits})")
+    _check_flag("als", device, flag)
 
 
-def _als_table(who, t, what, F=None):
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError(f"{who}: {what} must be a 2-D float32 tensor with unit inner stride")
-    F = t.shape[1] if F is None else _knn_int(who, F, "F", 1, ALS_MAX_FACTORS)
-    if not 1 <= F <= ALS_MAX_FACTORS or t.shape[1] < F:
-        raise ValueError(f"{who}: F = {F} factors with rows of {t.shape[1]} floats (1 .. {ALS_MAX_FACTORS}, at most the row)")
-    return F
+def _als_factors(who, T, F=None):
+    """F of an ALS call (default: T's row) within 1 .. ALS_MAX_FACTORS, which the fp32 table ``T`` must hold in a row."""
+    if F is not None:
+        F = _int_in(who, F, "F", 1, ALS_MAX_FACTORS)
+    _table_f32(who, T, "T", 1 if F is None else F)
+    return _int_in(who, T.shape[1], "F", 1, ALS_MAX_FACTORS) if F is None else F
 
 
 def als_gram(T: torch.Tensor, F: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1798,16 +1811,10 @@ def als_gram(T: torch.Tensor, F: Optional[int] = None, out: Optional[torch.Tenso
     CONTRACT in include/ncf_abi.h): chunks of 256 rows summed serially, the chunks added in ascending order, the upper triangle the
     mirror.  Checked before the device is; two launches on the current stream."""
     who = "als_gram"
-    F = _als_table(who, T, "T", F)
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (F, F) or not out.is_contiguous()):
-        raise ValueError(f"{who}: out must be a contiguous ({F}, {F}) float32 tensor")
-    _dev(T, "T")
-    if out is not None:
-        _dev(out, "out")
+    F = _als_factors(who, T, F)
+    out = _out2d(who, out, F, F, T, ((T, "T"),), contiguous=True)
     lib = load_library()
     rows = T.shape[0]
-    if out is None:
-        out = torch.empty((F, F), dtype=torch.float32, device=T.device)
     nbytes = int(lib.ncf_als_gram_workspace_bytes(rows, F))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=T.device) if nbytes else None
     _check(lib.ncf_als_gram(_ptr(T), rows, max(T.stride(0), F), F, _ptr(out), _ptr(ws), nbytes, _stream(T)))
@@ -1823,8 +1830,8 @@ def als_plan(rowptr: torch.Tensor, rows: torch.Tensor, F: int, block_bytes: int 
     who = "als_plan"
     _vec1d(who, rowptr, "rowptr", torch.int64)
     _vec1d(who, rows, "rows", torch.int64)
-    F = _knn_int(who, F, "F", 1, ALS_MAX_FACTORS)
-    block_bytes = _knn_int(who, block_bytes, "block_bytes", 1, 2 ** 62)
+    F = _int_in(who, F, "F", 1, ALS_MAX_FACTORS)
+    block_bytes = _int_in(who, block_bytes, "block_bytes", 1, 2 ** 62)
     R, B = rowptr.numel() - 1, rows.numel()
     if R < 0:
         raise ValueError(f"{who}: rowptr is empty")
@@ -1869,33 +1876,26 @@ def als_solve_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, r
     and does not change a bit.  What the kernel refuses sets ``flag`` (default: the device's word, check_als).  Checked before the
     device is; nothing else synchronises."""
     who = "als_solve_rows"
-    R, nnz = _knn_csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    R, nnz = _csr(who, rowptr, col, val, ("rowptr", "col", "val"))
     _vec1d(who, rows, "rows", torch.int64)
     B = rows.numel()
     if not torch.is_tensor(G) or G.dtype != torch.float32 or G.dim() != 2 or G.shape[0] != G.shape[1] or not G.is_contiguous():
         raise ValueError(f"{who}: G must be a contiguous (F, F) float32 tensor")
-    F = _als_table(who, T, "T", G.shape[0])
-    alpha = _knn_float(who, alpha, "alpha", 0.0)
-    reg = _knn_float(who, reg, "reg", 0.0)
+    F = _als_factors(who, T, G.shape[0])
+    alpha = _finite(who, alpha, "alpha", 0.0)
+    reg = _finite(who, reg, "reg", 0.0)
     if not reg > 0:
         raise ValueError(f"{who}: reg = {reg} is not > 0")
     if not isinstance(out_by_row, bool):
         raise ValueError(f"{who}: out_by_row = {out_by_row!r} is not a bool")
-    block_bytes = _knn_int(who, block_bytes, "block_bytes", 1, 2 ** 62)
-    n_out = R if out_by_row else B
+    block_bytes = _int_in(who, block_bytes, "block_bytes", 1, 2 ** 62)
     if out is None and out_by_row:
         raise ValueError(f"{who}: out_by_row writes into the caller's table: out is required")
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n_out or out.shape[1] < F
-                            or (out.shape[1] > 1 and out.stride(1) != 1)):
-        raise ValueError(f"{who}: out must be a ({n_out}, >= {F}) float32 tensor with unit inner stride")
     _out1d(who, flag, "flag", torch.int32, 1)
-    for t, what in ((rowptr, "rowptr"), (col, "col"), (val, "val"), (rows, "rows"), (T, "T"), (G, "G"), (out, "out"), (flag, "flag")):
-        if t is not None:
-            _dev(t, what)
+    out = _out2d(who, out, R if out_by_row else B, F, rowptr,
+                 ((rowptr, "rowptr"), (col, "col"), (val, "val"), (rows, "rows"), (T, "T"), (G, "G"), (flag, "flag")), wider=True)
     lib = load_library()
     dev = rowptr.device
-    if out is None:
-        out = torch.empty((B, F), dtype=torch.float32, device=dev)
     if flag is None:
         flag = als_flag(dev)
     if plan is None:
@@ -1929,8 +1929,7 @@ def mmr_rerank(vectors: torch.Tensor, scores: torch.Tensor, positions: torch.Ten
     sets the sticky out-of-range flag (check_oob).  Shapes, dtypes and the kernel's limits are checked before the device is; one
     launch on the current stream, nothing synchronises."""
     who = "mmr_rerank"
-    if not torch.is_tensor(vectors) or vectors.dtype != torch.float32 or vectors.dim() != 2 or vectors.stride(1) != 1:
-        raise ValueError(f"{who}: vectors must be a 2-D float32 tensor with unit inner stride")
+    _table_f32(who, vectors, "vectors")
     if not torch.is_tensor(scores) or scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():
         raise ValueError(f"{who}: scores must be a contiguous (B, N) float32 tensor")
     if not torch.is_tensor(positions) or positions.dtype != torch.int64 or positions.dim() != 2 or not positions.is_contiguous():
@@ -1950,9 +1949,7 @@ def mmr_rerank(vectors: torch.Tensor, scores: torch.Tensor, positions: torch.Ten
     lam = float(lam)
     if not 0.0 <= lam <= 1.0:
         raise ValueError(f"{who}: lam = {lam} is outside [0, 1]")
-    for t, what in ((vectors, "vectors"), (scores, "scores"), (positions, "positions"), (counts, "counts")):
-        if t is not None:
-            _dev(t, what)
+    _dev_all((vectors, "vectors"), (scores, "scores"), (positions, "positions"), (counts, "counts"))
     lib = load_library()
     dev = scores.device
     slot = torch.empty((B, k), dtype=torch.int32, device=dev)

@@ -298,6 +298,29 @@ def test_recommend_new_users_is_top_k_on_the_folded_vectors(gpu, fitted):
     fitted.check()
 
 
+def test_fit_dataset_is_the_fit_on_the_providers_positions(gpu):
+    """12 users x 9 items with raw ids (users 3 p + 30, items 7 p + 7), 40 distinct pairs in shuffled order: the tables of fit_dataset
+    are fit's on the provider's positions, bit for bit."""
+    import pandas as pd
+    import deeprecommendation_amd as pkg
+    from deeprecommendation_amd.content_providers.index_providers import IndexProvider
+    from deeprecommendation_amd.neural_collaborative_filtering.datasets.fixed_datasets import FixedPointwiseDataset
+    U, I = 12, 9
+    rng = np.random.RandomState(5)
+    pairs = rng.permutation(U * I)[:40]
+    frame = pd.DataFrame({"userId": pairs // I * 3 + 30, "movieId": pairs % I * 7 + 7, "rating": rng.randint(1, 11, 40) * 0.5})
+    cp = IndexProvider(np.arange(U) * 3 + 30, np.arange(I) * 7 + 7)
+    kw = dict(n_factors=4, n_iters=2, reg=A.REG, alpha=A.ALPHA)
+    a = pkg.ImplicitALS(**kw).fit_dataset(FixedPointwiseDataset(frame, cp), gpu, generator=torch.Generator().manual_seed(1))
+    u = torch.from_numpy(np.asarray(cp.get_user_profile(frame["userId"].values), dtype=np.int64)).to(gpu)
+    i = torch.from_numpy(np.asarray(cp.get_item_profile(frame["movieId"].values), dtype=np.int64)).to(gpu)
+    r = torch.from_numpy(frame["rating"].to_numpy(dtype=np.float32)).to(gpu)
+    b = pkg.ImplicitALS(**kw).fit(u, i, r, U, I, generator=torch.Generator().manual_seed(1))
+    assert torch.equal(a.user_factors_, b.user_factors_) and torch.equal(a.item_factors_, b.item_factors_) and torch.equal(a.item_gram_, b.item_gram_)
+    assert a.user_factors_.shape == (U, 4) and a.item_factors_.shape == (I, 4) and a.user_factors_.any() and a.item_factors_.any()
+    assert torch.equal(u, torch.from_numpy(pairs // I).to(gpu)) and torch.equal(i, torch.from_numpy(pairs % I).to(gpu))
+
+
 def test_planted_blocks_come_back_with_hit_rate_one(gpu):
     import deeprecommendation_amd as pkg
     (rowptr, col, val), held = A.planted_case()
