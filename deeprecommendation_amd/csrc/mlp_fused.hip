@@ -498,6 +498,8 @@ extern "C" int ncf_mlp_pack(int dtype, int n_layers, const int* dims, const void
     }
     hipLaunchKernelGGL(copy_or_zero_kernel, dim3((last + 255) / 256), dim3(256), 0, s, (const float*)W[n_layers - 1], last, P + L.wl);
     hipLaunchKernelGGL(copy_or_zero_kernel, dim3(1), dim3(256), 0, s, bias(n_layers - 1), 1, P + L.bl);
+    // the three pad floats behind bl: no kernel reads them, but the blob is then a function of the weights alone
+    hipLaunchKernelGGL(copy_or_zero_kernel, dim3(1), dim3(256), 0, s, (const float*)nullptr, 3, P + L.bl + 1);
     return check_launch("ncf_mlp_pack");
 }
 
