@@ -190,6 +190,7 @@ SIGNATURES = {
                                ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_i64, _c_p, _c_p]),
     "ncf_negative_cdf": (_c_int, [_c_p, _c_i64, _c_p, ctypes.c_float, _c_p, _c_p, _c_p]),
     "ncf_sample_negatives": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_i64, ctypes.c_uint32, _c_i64, _c_p, _c_p, _c_p]),
+    "ncf_sample_unseen": (_c_int, [_c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_int, ctypes.c_uint32, _c_i64, _c_p, _c_p, _c_p]),
 }
 
 _lib = None
@@ -409,6 +410,7 @@ def _flag(kind, device) -> torch.Tensor:
 
 KMF_FLAG_ID, KMF_FLAG_BLOCK, KMF_FLAG_PTR = 1, 2, 4                                             # csrc/kmf.hip
 ALS_FLAG_COL, ALS_FLAG_PTR, ALS_FLAG_ORDER, ALS_FLAG_VAL, ALS_FLAG_PIVOT = 1, 2, 4, 8, 16       # include/ncf_abi.h NCF_ALS_*
+UNSEEN_FLAG_PICK, UNSEEN_FLAG_FEW = 1, 256                                                      # include/ncf_abi.h NCF_UNSEEN_FLAG_*
 
 # kind -> (model, [(bit, what a kernel met, what check_* raises for it)]).  ncf_knn_sim_rows' word has one meaning whatever its value.
 _FLAG_BITS = {
@@ -422,6 +424,9 @@ _FLAG_BITS = {
                             (ALS_FLAG_VAL, "a value that is negative or not finite", ValueError),
                             (ALS_FLAG_PIVOT, "a pivot that is not positive and finite", ValueError)]),
 }
+# ncf_sample_unseen's word goes through the same _check_flag; _FLAG_BITS stays the table of the three baselines
+_UNSEEN_FLAG_BITS = ("sample_unseen", [(UNSEEN_FLAG_PICK, "a pick outside the users", IndexError),
+                                       (UNSEEN_FLAG_FEW, "a user has fewer unseen items than the draws asked for", ValueError)])
 
 
 def _check_flag(kind, device, flag=None):
@@ -432,7 +437,7 @@ def _check_flag(kind, device, flag=None):
     bits = int(f.item())
     if bits:
         f.zero_()
-        model, table = _FLAG_BITS[kind]
+        model, table = _UNSEEN_FLAG_BITS if kind == "unseen" else _FLAG_BITS[kind]
         hit = [(text, exc) for bit, text, exc in table if bits & bit]
         exc = IndexError if any(e is IndexError for _, e in hit) else table[-1][2]
         raise exc(f"{model}: " + ", ".join(text for text, _ in hit) + (f" (flag {bits})" if len(table) > 1 else ""))
@@ -2307,6 +2312,52 @@ def sample_negatives(rowptr: torch.Tensor, cdf: torch.Tensor, neg: torch.Tensor,
         raise ValueError("out must be a contiguous int64 tensor of n entries")
     _check(lib.ncf_sample_negatives(_ptr(rowptr), _ptr(cdf), _ptr(neg), rows, _ptr(pick), n, int(seed) & 0xFFFFFFFF, int(slot0), _ptr(out),
                                     _ptr(_oob_flag(cdf.device)), _stream(cdf)))
+    return out
+
+
+UNSEEN_MAX_K, UNSEEN_LANE_K = 1024, 8       # include/ncf_abi.h NCF_UNSEEN_*
+
+
+def unseen_flag(device) -> torch.Tensor:
+    """The sticky int32 flag word of ncf_sample_unseen on ``device`` (UNSEEN_FLAG_*)."""
+    return _flag("unseen", device)
+
+
+def check_unseen(device, flag: Optional[torch.Tensor] = None):
+    """Synchronising check of sample_unseen's flag word: raises, and clears it, when a call met a pick outside the users (IndexError)
+    or a user with fewer unseen items than the draws asked for (ValueError); such rows were written as -1."""
+    _check_flag("unseen", device, flag)
+
+
+def sample_unseen(seen: tuple, n_items: int, pick: torch.Tensor, k: int, seed: int, slot0: int = 0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ncf_sample_unseen: ``(n, k)`` int64 — row b holds k distinct items of [0, n_items) that user pick[b] has not seen, each uniform
+    over what is left, a fixed function of (seed, slot0 + b) and the user's row of ``seen`` = (rowptr (users + 1) int64, col int32
+    strictly ascending inside a row): THE CONTRACT in include/ncf_abi.h.  No rejection rounds, no host read.  k <= UNSEEN_LANE_K runs one
+    lane per row, a larger k one wave per row.  A pick outside the users or a user with fewer than k unseen items gets a row of -1
+    and raises at the next check_unseen.  No synchronisation."""
+    who = "sample_unseen"
+    if not (isinstance(seen, (tuple, list)) and len(seen) == 2 and all(torch.is_tensor(t) and t.dim() == 1 for t in seen)):
+        raise ValueError(f"{who}: seen = (rowptr int64 (users + 1), col int32)")
+    rowptr, col = seen
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or not rowptr.is_contiguous() or not col.is_contiguous() or rowptr.numel() < 1:
+        raise ValueError(f"{who}: seen = (rowptr int64 (users + 1), col int32), both contiguous")
+    n_items = _int_in(who, n_items, "n_items", 1, 2 ** 31 - 1)
+    k = _int_in(who, k, "k", 1, UNSEEN_MAX_K)
+    slot0 = _int_in(who, slot0, "slot0", 0, 2 ** 62)
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral):
+        raise ValueError(f"{who}: seed = {seed!r} is not an integer")
+    if not torch.is_tensor(pick) or pick.dtype != torch.int64 or pick.dim() != 1 or not pick.is_contiguous():
+        raise ValueError(f"{who}: pick must be a contiguous 1-D int64 tensor")
+    n = pick.numel()
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (n, k)):
+        raise ValueError(f"{who}: out must be a contiguous ({n}, {k}) int64 tensor")
+    _dev_all((rowptr, "seen rowptr"), (col, "seen col"), (pick, "pick"), (out, "out"))
+    lib = load_library()
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.int64, device=pick.device)
+    _check(lib.ncf_sample_unseen(_ptr(rowptr), _ptr(col), rowptr.numel() - 1, n_items, _ptr(pick), n, k, int(seed) & 0xFFFFFFFF, slot0,
+                                 _ptr(out), _ptr(_flag("unseen", pick.device)), _stream(pick)))
     return out
 
 

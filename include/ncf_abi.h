@@ -1122,6 +1122,47 @@ int ncf_sample_negatives(const int64_t* dev_rowptr, const float* dev_cdf, const 
                          int64_t n, uint32_t seed, int64_t slot0, int64_t* dev_out, int32_t* dev_oob_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Unseen negatives for implicit-feedback training and sampled evaluation (csrc/unseen.hip).
+ * Provides: the sampling of He et al. 2017 (Neural Collaborative Filtering, sections 3.1 and 4.1) — K items a user has not
+ *           interacted with per positive, redrawn every epoch; 99 such items per user as the candidates of leave-one-out
+ *           evaluation.  The reference has neither.
+ * The seen items are one CSR over users: dev_seen_rowptr (users + 1, int64, a valid CSR over dev_seen_col) and the item positions
+ * dev_seen_col (int32), strictly ascending inside a row.
+ *
+ * THE CONTRACT (tests/unseen_ref.py restates it in numpy).  Row b < n of dev_out (n x K, int64, row-major) belongs to user
+ * u = dev_pick[b] and slot s = slot0 + b.  With A the user's seen row, a its length and M = n_items - a, in uint32 arithmetic
+ * unless said otherwise:
+ *       x   = lowbias32((uint32)s * 0x9E3779B1 ^ seed)
+ *       x   = lowbias32(x ^ (uint32)(s >> 32) * 0x85EBCA77 ^ 0x68E31DA4)          (the two rounds of ncf_sample_negatives above)
+ *       h_j = lowbias32(x ^ (uint32)(j + 1) * 0xC2B2AE35)                          j = 0 .. K - 1
+ *       r_j = ((uint64)h_j * (uint64)(M - j)) >> 32                                in [0, M - j)
+ *       dev_out[b, j] = the r_j-th smallest (0-based) element of [0, n_items) \ (A u {dev_out[b, 0 .. j - 1]})
+ *   The draws of a row are distinct and never seen.  Draw j is uniform over the M - j items that are left up to the bias of the
+ *   multiply-shift: the probabilities of two of them differ by at most 2^-32, so each is within a relative (M - j) / 2^32 of
+ *   1 / (M - j) (2^-20 at 4096 items left; at most 1/2).  No rejection and no data-dependent retry: every loop
+ *   has a bound known before it starts (j <= K, binary or 64-way searches over a), so no input can make a wave spin.  No float
+ *   arithmetic and no atomics.  The result depends only on (seed, s, j, A, n_items): a batch drawn in pieces with advancing slot0
+ *   gives the bits of one call, and every launch form gives the same bits.
+ * Launch forms: K <= NCF_UNSEEN_LANE_K one lane per row with the row's draws in registers; above, one wave per row with them in
+ *   LDS (8 K bytes per wave).
+ * Device-side refusals write -1 across the row's K outputs and set the sticky *dev_flag (each condition owns one byte of the
+ * word, which a plain byte store sets):
+ *       NCF_UNSEEN_FLAG_PICK   a pick outside [0, users)
+ *       NCF_UNSEEN_FLAG_FEW    K > M: the user has fewer unseen items than the draws asked for (or a pointer pair that decreases)
+ *   On a seen row that does not ascend strictly the output is unspecified but stays in [0, n_items), and the loops still end.
+ * n == 0 returns NCF_OK without a launch.  NCF_EINVAL, with ncf_last_error() set and nothing launched: K outside 1 ..
+ * NCF_UNSEEN_MAX_K, n_items outside 1 .. 2^31 - 1, a negative users, n or slot0, a NULL dev_seen_rowptr or dev_flag, a NULL
+ * dev_pick or dev_out with n > 0 (dev_seen_col may be NULL when no user has seen anything).
+ * ------------------------------------------------------------------------------------------------ */
+#define NCF_UNSEEN_MAX_K 1024
+#define NCF_UNSEEN_LANE_K 8
+#define NCF_UNSEEN_FLAG_PICK 1
+#define NCF_UNSEEN_FLAG_FEW 256
+int ncf_sample_unseen(const int64_t* dev_seen_rowptr, const int32_t* dev_seen_col, int64_t users, int64_t n_items,
+                      const int64_t* dev_pick, int64_t n, int K, uint32_t seed, int64_t slot0, int64_t* dev_out /* n x K */,
+                      int32_t* dev_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-row top-K with exclusion — the ranking step of a recommendation request.
  * Replaces: DataFrame.sort_values(by='score', ascending=False).iloc[:k] over the whole score vector after
  *           item_features.drop(user_ratings.index) — webapp/backend.py:84, 113-118.
