@@ -12,17 +12,15 @@
 // The tables (pr, feat) are small (catalogue x 64..128 floats) and stay L2 / Infinity-Cache resident; the
 // kernel is bound by gathered cache bandwidth, not by arithmetic.
 #include "ncf_common.h"
-#include "attn_util.h"
+#include "attn_tile.h"
 #include "group_pairs.h"
 #include <math.h>
 #include <atomic>
 #include <type_traits>
 
-#ifndef ATT_UNROLL
-#define ATT_UNROLL 8   // measured (cfg 3, A/B): 2 -> 141.7 us, 4 -> 138.9, 8 -> 133.9, 16 -> 256 (registers)
-#endif
-
 namespace ncf {
+
+constexpr int kAttUnroll = 8;   // measured (cfg 3, A/B): 2 -> 141.7 us, 4 -> 138.9, 8 -> 133.9, 16 -> 256 (registers)
 
 // Training-time dropout of AttentionNet's hidden layer (attention_ncf.py:112-117: Linear, ReLU, Dropout, Linear — one mask element
 // per (pair, rated entry, hidden unit)).  Never stored: element (entry e, units 4c..4c+3) keeps iff a 16-bit slice of a
@@ -90,10 +88,10 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ pc,
                 pcv = *reinterpret_cast<const f32x4*>(pc + b * ldpc + 4 * c);
                 if (MODE == 0) wv = *reinterpret_cast<const f32x4*>(w1 + 4 * c);
             }
-            // ATT_UNROLL entries per lane group are in flight at once: with one dependent (col -> row) load per
+            // kAttUnroll entries per lane group are in flight at once: with one dependent (col -> row) load per
             // iteration the loop ran at one L2/Infinity-Cache round trip per 64/LPA entries (latency-bound, 178 us at
             // cfg 3); the loads of the unrolled steps are independent and overlap.
-            constexpr int U = ATT_UNROLL;
+            constexpr int U = kAttUnroll;
             for (int64_t e0 = beg; e0 < end; e0 += (int64_t)EPI * U) {
                 f32x4 r[U];
                 bool ok[U];
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ pc,
         const int c = lane % LPF, eg = lane / LPF, EPI = 64 / LPF;
         const bool active = c < chunks;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        constexpr int U = ATT_UNROLL;
+        constexpr int U = kAttUnroll;
         for (int64_t e0 = beg; e0 < end; e0 += (int64_t)EPI * U) {
             f32x4 f[U];
             float av[U];
@@ -377,14 +375,10 @@ __global__ __launch_bounds__(256) void attn_backward_kernel(const float* __restr
 //   out[b,:] = bias + (Σ_e exp(s_e - m)·val_e·feat[col_e,:]) / l
 // which is the same weighted sum as attn_kernel's up to fp32 summation order (tests hold both to the oracle at 1e-5).
 // An empty or fully masked row gives l = 0 -> zeros + bias (the nan_to_num case, :208-209).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 // FO = output registers per lane = ceil(Fdim / 64); NPF = 16-byte pieces of a tile each thread stages = (A + Fdim) / 32 rounded up to 4 / 8 / 16
-#ifndef ATT_G_WAVES_PER_SIMD
-#define ATT_G_WAVES_PER_SIMD 2   // one 512-thread workgroup per CU at 198 VGPRs; 4 (two workgroups, 128 VGPRs) spills 74+ registers
-#endif
+constexpr int kAttGWavesPerSimd = 2;   // one 512-thread workgroup per CU at 198 VGPRs; 4 (two workgroups, 128 VGPRs) spills 74+ registers
 template <int MODE, int FO, int NPF>
-__global__ __launch_bounds__(512, ATT_G_WAVES_PER_SIMD) void attn_grouped_kernel(const float* __restrict__ pc, int64_t ldpc, const float* __restrict__ pr,
+__global__ __launch_bounds__(512, kAttGWavesPerSimd) void attn_grouped_kernel(const float* __restrict__ pc, int64_t ldpc, const float* __restrict__ pr,
                                                            int64_t ldpr, int A, const float* __restrict__ w1, float b1,
                                                            const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                            const float* __restrict__ val, int64_t R, int64_t I,
@@ -408,15 +402,9 @@ __global__ __launch_bounds__(512, ATT_G_WAVES_PER_SIMD) void attn_grouped_kernel
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t g = blockIdx.x;
     if (g >= wg_ptr[R]) return;                            // the grid is an upper bound (no host sync for its size)
-    int64_t lo = 0, hi = R;                                // row r with wg_ptr[r] <= g < wg_ptr[r+1]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (wg_ptr[mid] <= g) lo = mid; else hi = mid;
-    }
-    const int64_t r = lo;
-    const int64_t start = grp_ptr[r] + (g - wg_ptr[r]) * ppw;
-    const int64_t left = grp_ptr[r + 1] - start;
-    const int cnt = (int)(left < ppw ? left : ppw);
+    const AttnGroup grp = attn_group_lookup(g, wg_ptr, grp_ptr, R, ppw, (const int32_t*)nullptr);
+    const int64_t r = grp.r, start = grp.start;
+    const int cnt = grp.cnt;
     const int64_t beg = rowptr[r], end = rowptr[r + 1];
     const int A4 = A / 4;
     const bool fvec = (Fdim % 4 == 0) && (ldfeat % 4 == 0);
@@ -622,20 +610,7 @@ __global__ __launch_bounds__(512, ATT_G_WAVES_PER_SIMD) void attn_grouped_kernel
 //   * online softmax as before (running max m, per-LANE partial sums l reduced once at the end, O rescaled per tile).
 // 256-thread workgroups of up to 16 pairs (4 per wave); LDS 64 x (A + Fdim) floats + P (58 KB at config 3): two
 // workgroups per CU, each with its own barriers.
-#ifdef ATT_SC_STAMP   // diagnostic build only: per-phase shader-clock sums of wave 0 of every workgroup -> the buffer passed as wts_off
-#define ATT_STAMP(slot)                                                                                 \
-    do {                                                                                                \
-        unsigned long long t_;                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                              \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                     \
-        __builtin_amdgcn_sched_barrier(0);                                                              \
-        stamp_sum[slot] += t_ - stamp_last;                                                             \
-        stamp_last = t_;                                                                                \
-    } while (0)
-#else
-#define ATT_STAMP(slot) do {} while (0)
-#endif
-
+// The stages are attn_tile.h's, all but the score step (written out below: as a call it measured slower).
 template <int MODE, int CPB, int NW>
 __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float* __restrict__ pc, int64_t ldpc, const float* __restrict__ pr,
                                                                  int64_t ldpr, int A, const float* __restrict__ w1, float b1,
@@ -646,14 +621,15 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
                                                                  const float* __restrict__ feat, int64_t ldfeat, int Fdim,
                                                                  const float* __restrict__ out_bias, float* __restrict__ out, int64_t ldout,
                                                                  float* __restrict__ wts, const int64_t* __restrict__ wts_off) {
-    constexpr int EC = 64, MAXP = 4, PP = MAXP * NW, MT = PP / 16, PS = 66, MAXNT = 4;   // NW = 4 or 8 waves, 4 pairs per wave
+    constexpr int EC = kTileEC, MAXP = kTileMaxP, PP = MAXP * NW, MT = PP / 16, PS = kTilePS, MAXNT = 4;   // NW = 4 or 8 waves, 4 pairs per wave
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int A4 = A / 4, F4 = Fdim / 4;
-    float* prt = reinterpret_cast<float*>(smem);           // [EC][A]     pr tile image (DMA)
-    float* fct = prt + EC * A;                              // [EC][Fdim]  feat tile image (DMA)
-    float* Pm = fct + EC * Fdim;                            // [PP][PS]    p_e * val_e of the current tile, pair-major
-    float* scl = Pm + PP * PS;                              // [PP]        this tile's rescale factor per pair; at the end 1 / l
-    int64_t* pid = reinterpret_cast<int64_t*>(scl + PP);    // [PP]        output row of each pair of the group
+    const AttnTileLds lay = attn_tile_lds(A, Fdim, PP);
+    float* prt = reinterpret_cast<float*>(smem) + lay.prt;
+    float* fct = reinterpret_cast<float*>(smem) + lay.fct;
+    float* Pm = reinterpret_cast<float*>(smem) + lay.Pm;
+    float* scl = reinterpret_cast<float*>(smem) + lay.scl;   // this tile's rescale factor per pair; at the end 1 / l
+    int64_t* pid = reinterpret_cast<int64_t*>(reinterpret_cast<float*>(smem) + lay.pid);
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem;
 
@@ -661,67 +637,23 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t g = blockIdx.x;
     if (g >= wg_ptr[R]) return;                            // the grid is an upper bound (no host sync for its size)
-    int64_t lo = 0, hi = R;                                // row r with wg_ptr[r] <= g < wg_ptr[r+1]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (wg_ptr[mid] <= g) lo = mid; else hi = mid;
-    }
-    const int64_t r = lo;
-    const int64_t start = grp_ptr[r] + (g - wg_ptr[r]) * ppw;
-    const int64_t left = grp_ptr[r + 1] - start;
-    const int cnt = (int)(left < ppw ? left : ppw);
+    const AttnGroup grp = attn_group_lookup(g, wg_ptr, grp_ptr, R, ppw, (const int32_t*)nullptr);
+    const int64_t r = grp.r, start = grp.start;
+    const int cnt = grp.cnt;
     const int64_t beg = rowptr[r], end = rowptr[r + 1];
 
     // LDS starts as zeros: slots of pairs / entries that nothing writes then hold finite values (0 x garbage must not
-    // make a NaN in the MFMA of a VALID pair; rows of unused pairs are never stored)
+    // make a NaN in the MFMA of a VALID pair; rows of unused pairs are never stored), and a masked entry's DMA is skipped
     {
-        const int total4 = (EC * (A + Fdim) + PP * PS + PP + 2 * PP) / 4;
+        const int total4 = lay.floats / 4;
         for (int i = tid; i < total4; i += (int)blockDim.x) reinterpret_cast<f32x4*>(smem)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    // DMA pieces of one tile: the pr image is EC*A4 chunks = A4 wave-instructions, the feat image F4; wave w issues pieces
-    // w, w+4, ...  A piece's lane writes chunk `j` of entry `e` of the image and fetches SOURCE chunk j ^ (e & 15) of
-    // that row when rows are whole 256-byte bank rows (A % 64 == 0): the reader applies the same XOR.
+    // rows of the pr image are source-swizzled when they are whole 256-byte bank rows (A % 64 == 0)
     const bool swz = (A4 % 16) == 0;
     const int shA = (A4 & (A4 - 1)) == 0 ? __builtin_ctz(A4) : -1, shF = (F4 & (F4 - 1)) == 0 ? __builtin_ctz(F4) : -1;
-    // the tile's own entry of this lane: column and rating, loaded two tiles ahead of their use — unconditionally (index
-    // clamped into the row) and back to back: a dependent load would need a vmcnt wait, and every vmcnt wait also drains the
-    // tile DMAs in flight.  Validity (inside the row, column inside the catalogue) is decided when the values are used.
-    auto load_cv = [&](int64_t e0, int& c, float& v) {
-        const int64_t e = e0 + lane < end ? e0 + lane : (end > beg ? end - 1 : beg);
-        c = end > beg ? col[e] : -1;
-        v = end > beg ? val[e] : 0.f;
-    };
-    auto valid_c = [&](int64_t e0, int c) { return (e0 + lane < end && c >= 0 && c < I) ? c : -1; };
-    auto issue = [&](const float* tab, int64_t ld, int X4, int shX, bool xorj, unsigned lds_base, int cols) {
-        // `cols` = this lane's col of the tile being fetched (or -1).  A piece (one wave-instruction, 64 chunks) covers
-        // RPP = 64 / X4 whole rows when rows are a power of two of chunks: the row's col then comes from 1 / 2 / 4 readlanes
-        // (no LDS round trip, nothing to wait for) and every piece costs a dozen instructions.
-        const int rpp = shX >= 0 ? 64 >> shX : 0;
-        if (rpp >= 1 && rpp <= 4) {
-            const int sub = lane >> shX, j = lane & (X4 - 1);
-            for (int piece = wave; piece < X4; piece += NW) {   // wave-uniform trip count
-                const int e0p = piece * rpp;
-                int ci = __builtin_amdgcn_readlane(cols, e0p);
-                if (rpp >= 2) { const int c1 = __builtin_amdgcn_readlane(cols, e0p + 1); ci = sub == 1 ? c1 : ci; }
-                if (rpp == 4) {
-                    const int c2 = __builtin_amdgcn_readlane(cols, e0p + 2), c3 = __builtin_amdgcn_readlane(cols, e0p + 3);
-                    ci = sub == 2 ? c2 : (sub == 3 ? c3 : ci);
-                }
-                const int jj = xorj ? (j ^ ((e0p + sub) & 15)) : j;
-                if (ci >= 0) dma16(tab + (int64_t)ci * ld + 4 * jj, lds_base + (unsigned)piece * 1024u);
-            }
-            return;
-        }
-        for (int piece = wave; piece < X4; piece += NW) {  // general row widths: (entry, chunk) by division, col by a shuffle
-            const int gi = piece * 64 + lane;
-            const int e = shX >= 0 ? gi >> shX : gi / X4;
-            const int j = shX >= 0 ? gi & (X4 - 1) : gi - e * X4;
-            const int ci = __shfl(cols, e);
-            if (ci >= 0) dma16(tab + (int64_t)ci * ld + 4 * (xorj ? (j ^ (e & 15)) : j), lds_base + (unsigned)piece * 1024u);
-        }
-    };
-    auto issue_pr = [&](int cols) { issue(pr, ldpr, A4, shA, swz, lds0, cols); };
-    auto issue_feat = [&](int cols) { issue(feat, ldfeat, F4, shF, false, lds0 + (unsigned)(EC * A * 4), cols); };
+    const TileEntries<decltype(col), decltype(val)> ent{col, val, beg, end, I, lane};    // loaded two tiles ahead of their use
+    auto issue_pr = [&](int cols) { tile_issue<false, NW>(pr, ldpr, A4, shA, swz, lds0, cols, lane, wave); };
+    auto issue_feat = [&](int cols) { tile_issue<false, NW>(feat, ldfeat, F4, shF, false, lds0 + (unsigned)(EC * A * 4), cols, lane, wave); };
 
     // the wave's pairs: slots j = wave + NW*k; their pc rows are wave-uniform pointers (scalar loads)
     const int np = cnt > wave ? (cnt - wave + NW - 1) / NW : 0;
@@ -730,9 +662,6 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
     for (int k = 0; k < MAXP; ++k) {
         const int j = k < np ? wave + NW * k : 0;
         pcrow[k] = pc + uniform64(pair_ids[start + j]) * ldpc;
-#ifdef ATT_SC_SAMEROW      // diagnostic build (wrong results): every slot reads pair 0's row -> the scalar working set shrinks 4x
-        pcrow[k] = pcrow[0];
-#endif
     }
     // MFMA roles: a job = one 16-pair x 16-feature tile of O over all 16 k-steps (4 entries each) of a tile; MT * NTILES jobs
     const int NTILES = (Fdim + 15) / 16;
@@ -754,30 +683,24 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
     // next barrier (the tile loop's, or the one before the output stage when the row is empty), so no barrier is added.
     if (tid < PP) pid[tid] = tid < cnt ? pair_ids[start + tid] : -1;
     if (ntiles > 0) {
-        load_cv(beg, c_cur, v_cur);
-        load_cv(beg + EC, c_nxt, v_nxt);
-        c_cur = valid_c(beg, c_cur);
-        c_nxt = valid_c(beg + EC, c_nxt);
+        ent.load(beg, c_cur, v_cur);
+        ent.load(beg + EC, c_nxt, v_nxt);
+        c_cur = ent.valid(beg, c_cur);
+        c_nxt = ent.valid(beg + EC, c_nxt);
         issue_pr(c_cur);
     }
     const int sw = swz ? (lane & 15) : 0;
     const int g4 = lane >> 4, i16 = lane & 15;
-#ifdef ATT_SC_STAMP
-    unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last)::"memory");
-#endif
     for (int64_t t = 0; t < ntiles; ++t) {
         const int64_t e0 = beg + t * EC;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of pr(t) have landed (and its col / val loads) ...
         __syncthreads();                                   // ... and everybody's; the MFMAs of tile t-1 have read fct / Pm / scl
         if (t > 0) {                                       // rotate the look-ahead registers HERE: nothing is in flight, no wait
             c_cur = c_nxt; v_cur = v_nxt;
-            c_nxt = valid_c(e0 + EC, c_nn); v_nxt = v_nn;
+            c_nxt = ent.valid(e0 + EC, c_nn); v_nxt = v_nn;
         }
-        ATT_STAMP(0);
         issue_feat(c_cur);                                 // lands under the scoring below (read after the third barrier)
-        load_cv(e0 + 2 * EC, c_nn, v_nn);
-        ATT_STAMP(1);
+        ent.load(e0 + 2 * EC, c_nn, v_nn);
 
         const bool ok = c_cur >= 0;
         const float vl = ok ? v_cur : 0.f;
@@ -789,7 +712,6 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
             f32x4 row[CPB];
 #pragma unroll
             for (int c = 0; c < CPB; ++c) row[c] = *reinterpret_cast<const f32x4*>(myrow + 4 * ((blk + c) ^ sw));
-            ATT_STAMP(2);
             if (blk + CPB >= A4) {                         // last a-block: once every wave holds its rows the pr image is free
                 // raw barrier: __syncthreads() would wait vmcnt(0) first, i.e. for the feat DMA issued a moment ago
                 __builtin_amdgcn_sched_barrier(0);
@@ -798,8 +720,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
                 __builtin_amdgcn_sched_barrier(0);
                 if (t + 1 < ntiles) issue_pr(c_nxt);       // tile t+1 lands under this tile's arithmetic
             }
-            ATT_STAMP(3);
-            // Scalar operands arrive G chunks at a time, one step ahead: a wait on scalar loads is always lgkmcnt(0)
+            // The score step stays WRITTEN OUT here (attn_tile.h's tile_score_block is the same text with the loads through the
+            // constant address space): called as a function, every instance of this kernel measured 1.0 - 1.5 us slower at cfg 3
+            // (DESIGN.md).  Scalar operands arrive G chunks at a time, one step ahead: a wait on scalar loads is always lgkmcnt(0)
             // (they return out of order), so the order inside a step is  wait(step s)  ->  issue loads(step s+1)  ->
             // VALU(step s): the next step's loads fly under this step's arithmetic, and the live scalars stay at two
             // steps' worth (all of them at once would be 1024 SGPRs: spilled through v_writelane / v_readlane).
@@ -835,10 +758,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
                                 const f32x4 ww = ws[cur][gk];
                                 const f32x2 w01 = {ww[0], ww[1]}, w23 = {ww[2], ww[3]};
                                 f32x2 u, v;
-                                if (MODE == 3) {
-                                    // operands scaled by 2^-64 (w1 by 2^64): relu(p + q) IS the [0, 1] clamp of the sum, an output
-                                    // modifier of the packed add — one instruction for two elements where gfx950 has no packed fp32
-                                    // max (2 x v_max_f32 otherwise); powers of two scale exactly: same bits as the unscaled relu
+                                if (MODE == 3) {               // relu(p + q) on 2^-64-scaled operands = the [0, 1] clamp of the packed add
                                     asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(u) : "v"(p01), "s"(q01));
                                     asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(v) : "v"(p23), "s"(q23));
                                 } else {
@@ -860,71 +780,24 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
             if (np > 2) score_block(std::integral_constant<int, 4>{});
             else if (np == 2) score_block(std::integral_constant<int, 2>{});
             else if (np == 1) score_block(std::integral_constant<int, 1>{});
-            ATT_STAMP(4);
         }
-        // Epilogue of the tile, the wave's pairs side by side (branch-free, so that the four dependency chains of DPP steps
-        // and exponentials interleave): tile maximum, running maximum, rescale factor, p_e.
         float sc[MAXP], mx[MAXP];
+        tile_scores<MODE>(s2, t2, ok, b1, sc, mx);
 #pragma unroll
         for (int k = 0; k < MAXP; ++k) {
-            const float ssum = (s2[k][0] + t2[k][0]) + (s2[k][1] + t2[k][1]);
-            sc[k] = ok ? ssum + (MODE != 2 ? b1 : 0.f) : -INFINITY;
-            mx[k] = sc[k];
-        }
-        wave_reduce_dpp_n<MAXP>(mx, [](float x, float y) { return fmaxf(x, y); });
-#pragma unroll
-        for (int k = 0; k < MAXP; ++k) {
-            const float mnew = fmaxf(m[k], mx[k]);
-            const bool any = mnew != -INFINITY;            // wave-uniform; false: nothing valid so far, m, l, O stay 0
-            const float scale = any ? exp_le0(m[k] - mnew) : 1.f;       // exp(-inf) = 0 on the first valid tile
-            const float pe = (any && ok) ? exp_le0(sc[k] - mnew) : 0.f;
-            l[k] = l[k] * scale + pe;                      // per-lane partial sum; lanes are added once, after the last tile
-            m[k] = mnew;
+            const SoftmaxStep st = tile_softmax_step(m[k], l[k], mx[k], sc[k], ok);
             if (k < np) {                                  // wave-uniform
                 const int j = wave + NW * k;
                 if (wts && e0 + lane < end)                // raw score now, normalised in place after the last tile
                     wts[wts_off[pid[j]] + (e0 - beg) + lane] = sc[k];
-                Pm[j * PS + lane] = pe * vl;               // attended_user_matrix entry (:212)
-                if (lane == 0) scl[j] = scale;
+                Pm[j * PS + lane] = st.pe * vl;            // attended_user_matrix entry (:212)
+                if (lane == 0) scl[j] = st.scale;
             }
         }
-        ATT_STAMP(5);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's pieces of feat(t) (and of pr(t+1)) have landed; P written
         __builtin_amdgcn_s_barrier();                      // P, scl and the feat image of this tile are complete
-        ATT_STAMP(6);
-        {
-            // jobs: (16-pair row tile mt, 16-feature column tile nt) = (j % MT, j / MT) for j = wave, wave + NW, ...
-#pragma unroll
-            for (int n = 0; n < MAXNT; ++n) {
-                const int job = wave + NW * n;
-                const int mt = job % MT, nt = job / MT;
-                if (nt >= NTILES) break;                   // wave-uniform
-                const f32x4 s4 = *reinterpret_cast<const f32x4*>(scl + 16 * mt + 4 * g4);   // accumulator register i holds pair row 16*mt + 4*g4 + i
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[n][i] *= s4[i];
-                const float* fb = fct + 16 * nt + i16;
-                const float* pa = Pm + (16 * mt + i16) * PS + g4;
-#pragma unroll
-                for (int q0 = 0; q0 < EC / 4; q0 += 8) {    // 8 k-steps' operands first (16 LDS reads in flight), then their chain
-                    float av[8], bv[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {           // A[i = pair][k = 4q + g4], B[k][j = feature]
-                        av[q] = pa[4 * (q0 + q)];
-                        bv[q] = fb[(4 * (q0 + q) + g4) * Fdim];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc[n], 0, 0, 0);
-                }
-            }
-        }
-        ATT_STAMP(7);
+        tile_aggregate<NW, MT, MAXNT>(acc, fct, Pm, scl, Fdim, NTILES, wave, g4, i16);
     }
-#ifdef ATT_SC_STAMP
-    if (lane == 0 && wave == 0 && !wts && wts_off) {
-        unsigned long long* dbg = (unsigned long long*)wts_off;
-        for (int i = 0; i < 8; ++i) dbg[blockIdx.x * 8 + i] = stamp_sum[i];
-    }
-#endif
     float linv[MAXP];
 #pragma unroll
     for (int k = 0; k < MAXP; ++k) {
@@ -938,22 +811,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_grouped_sc_kernel(const float
     for (int k = 0; k < MAXP; ++k)
         if (k < np && lane == 0) scl[wave + NW * k] = linv[k];
     __syncthreads();
-    {
-#pragma unroll
-        for (int n = 0; n < MAXNT; ++n) {
-            const int job = wave + NW * n;
-            const int mt = job % MT, nt = job / MT;
-            if (nt >= NTILES) break;
-            const f32x4 s4 = *reinterpret_cast<const f32x4*>(scl + 16 * mt + 4 * g4);
-            const int f = 16 * nt + i16;
-            const float bias = (out_bias && f < Fdim) ? out_bias[f] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = 16 * mt + 4 * g4 + i;
-                if (row < cnt && f < Fdim) out[pid[row] * ldout + f] = acc[n][i] * s4[i] + bias;
-            }
-        }
-    }
+    tile_store_scaled<NW, MT, MAXNT>(acc, scl, pid, cnt, Fdim, NTILES, out_bias, out, ldout, wave, g4, i16);
     if (wts) {                                             // attention weights (:224): softmax of the stored raw scores
 #pragma unroll
         for (int k = 0; k < MAXP; ++k) {
@@ -1236,9 +1094,9 @@ static AttnGroupedPlan plan_attn_grouped(int mode, bool scaled, int A, int Fdim,
     // min(R, B) rows are non-empty (R may be a whole user base with B pairs of a few users: device-resident evaluation)
     const int64_t blocks = (int64_t)(unsigned)((B + pairs_per_wg - 1) / pairs_per_wg + (R < B ? R : B));
     const int A4 = A / 4;
-    const int pp = pairs_per_wg <= 16 ? 16 : 32;
+    const int pp = attn_tile_pairs(pairs_per_wg);      // 16 or 32: the entry takes pairs_per_wg <= 32
     const int jobs = (pp / 16) * ((Fdim + 15) / 16);   // 16 x 16 output tiles of the aggregation; at most 4 per wave
-    const size_t lds2 = ((size_t)64 * (A + Fdim) + pp * 66 + pp + 2 * pp) * 4;
+    const size_t lds2 = attn_tile_lds(A, Fdim, pp).bytes();
     const bool sc_ok = fvec && lds2 <= 160 * 1024 && jobs <= 4 * (pp / 4);
     const int force = option(NCF_OPT_ATTN_GROUPED_KERNEL);
     if (sc_ok && force != 1) {

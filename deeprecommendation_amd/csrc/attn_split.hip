@@ -20,24 +20,10 @@
 // Same arithmetic per (pair, entry) as the round-2 kernel; the split only changes where the softmax partials are merged, i.e. the
 // fp32 summation order (held to 1e-5 against the per-pair kernel and the oracle).  Fixed split: bitwise reproducible run to run.
 #include "ncf_common.h"
-#include "attn_util.h"
+#include "attn_tile.h"
 #include <math.h>
 #include <atomic>
 #include <type_traits>
-
-#ifndef ATT_SPLIT_DIAG
-#define ATT_SPLIT_DIAG 0   // diagnostic builds (wrong results): 1 = every slot reads pc row 0 (scalar loads all hit), 2 = no tile DMA,
-#endif                     // 3 = no score loop, 4 = no aggregation, 5 = 2 + 3 + 4, 6 = exit after the prologue
-#ifndef ATT_SPLIT_G
-#define ATT_SPLIT_G 1      // 16-byte chunks of pc (per pair) and of w1 per scalar-load step: 1 = 20 SGPRs per step and buffer, 2 = 40
-#endif
-#ifndef ATT_SPLIT_PF
-#define ATT_SPLIT_PF 0     // 1 = the NEXT row block's pc / w1 lines are touched (one scalar load per 64-byte line) when this block starts:
-                           // measured SLOWER (28.2 vs 25.7 us at cfg 3): the extra wait per block costs more than the misses it gathers
-#endif
-#ifndef ATT_SPLIT_DB
-#define ATT_SPLIT_DB 0   // 1: row blocks double buffered in registers (64 VGPRs of rows: spills at the 128-register budget)
-#endif
 
 namespace ncf {
 
@@ -51,27 +37,24 @@ struct AttnSplitArgs {
     float b1;
 };
 
-// pc rows and w1 are read-only for the whole launch and wave-uniform: through the CONSTANT address space hipcc reads them with
-// scalar loads (through a generic pointer of a by-value struct it cannot prove the memory invariant and emits vector loads)
-typedef const f32x4 __attribute__((address_space(4))) * const_f32x4_ptr;
-
-constexpr int kPartHead = 4;   // floats in front of a partial's O: m, l, (2 unused: O stays 16-byte aligned)
-
 // MODE 0: MLP (relu + w1 dot), 2: cosine (dot of normalised rows), 3: MLP on 2^-64-scaled operands (relu = clamp)
 // NW = 4 / 8 / 16 waves x 4 pairs (a user's pairs share the staged tile: 64 pairs per workgroup halve the gathered bytes per pair of
 // 32, and a (user, tile) unit of a 64-pairs-per-user batch is ONE workgroup per CU instead of two or three); FD = Fdim (compile-time: the aggregation's B-operand reads walk the feat image with a stride of Fdim floats —
 // with a run-time stride hipcc keeps 16 precomputed addresses per lane, and spills them)
+// The stages are attn_tile.h's.  pc rows and w1 travel through the CONSTANT address space (LoadConst: the arguments are a by-value
+// struct), one 16-byte chunk per pair (+ w1's) per scalar-load step: 20 SGPRs per step and buffer.
 template <int MODE, int NW, int FD>
 __global__ __launch_bounds__(64 * NW, 4) void attn_split_kernel(const AttnSplitArgs a) {
-    constexpr int EC = 64, MAXP = 4, PP = MAXP * NW, MT = PP / 16, PS = 66, CB = 8;
+    constexpr int EC = kTileEC, MAXP = kTileMaxP, PP = MAXP * NW, MT = PP / 16, PS = kTilePS, CB = 8;
     constexpr int Fdim = FD, F4 = FD / 4, NTILES = FD / 16, NJ = (MT * NTILES + NW - 1) / NW;   // NJ = 16x16 aggregation tiles per wave
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int A = a.A, A4 = A >> 2;
-    float* prt = reinterpret_cast<float*>(smem);           // [EC][A]     pr tile image (DMA)
-    float* fct = prt + EC * A;                              // [EC][Fdim]  feat tile image (DMA)
-    float* Pm = fct + EC * Fdim;                            // [PP][PS]    p_e * val_e of the current tile, pair-major
-    float* scl = Pm + PP * PS;                              // [PP]        this tile's rescale factor per pair
-    int64_t* pid = reinterpret_cast<int64_t*>(scl + PP);    // [PP]        output row of each pair of the group
+    const AttnTileLds lay = attn_tile_lds(A, Fdim, PP);
+    float* prt = reinterpret_cast<float*>(smem) + lay.prt;
+    float* fct = reinterpret_cast<float*>(smem) + lay.fct;
+    float* Pm = reinterpret_cast<float*>(smem) + lay.Pm;
+    float* scl = reinterpret_cast<float*>(smem) + lay.scl;
+    int64_t* pid = reinterpret_cast<int64_t*>(reinterpret_cast<float*>(smem) + lay.pid);
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem;
 
@@ -80,20 +63,9 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_split_kernel(const AttnSplitA
     const int64_t g = blockIdx.x;
     const int split = blockIdx.y;
     if (g >= a.wg_ptr[a.R]) return;                        // the grid is an upper bound (no host sync for its size)
-    int64_t r;
-    if (a.wg_row) {
-        r = a.wg_row[g];
-    } else {                                               // row r with wg_ptr[r] <= g < wg_ptr[r+1]
-        int64_t lo = 0, hi = a.R;
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (a.wg_ptr[mid] <= g) lo = mid; else hi = mid;
-        }
-        r = lo;
-    }
-    const int64_t start = a.grp_ptr[r] + (g - a.wg_ptr[r]) * a.ppw;
-    const int64_t left = a.grp_ptr[r + 1] - start;
-    const int cnt = (int)(left < a.ppw ? left : a.ppw);
+    const AttnGroup grp = attn_group_lookup(g, a.wg_ptr, a.grp_ptr, a.R, a.ppw, a.wg_row);   // wg_row: written by the grouping pass
+    const int64_t r = grp.r, start = grp.start;
+    const int cnt = grp.cnt;
     const int64_t rbeg = a.rowptr[r], rend = a.rowptr[r + 1];
     // this workgroup's slice of the row's tiles
     const int64_t row_tiles = (rend - rbeg + EC - 1) / EC;
@@ -109,50 +81,16 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_split_kernel(const AttnSplitA
     for (int k = 0; k < MAXP; ++k) {
         const int j = k < np ? wave + NW * k : 0;
         pcrow[k] = a.pc + uniform64(a.pair_ids[start + j]) * a.ldpc;
-#if ATT_SPLIT_DIAG == 1
-        pcrow[k] = a.pc;
-#endif
     }
     if (tid < PP) pid[tid] = tid < cnt ? a.pair_ids[start + tid] : -1;
 
     const bool swz = (A4 % 16) == 0;
     const int shA = (A4 & (A4 - 1)) == 0 ? __builtin_ctz(A4) : -1;
     constexpr int shF = (F4 & (F4 - 1)) == 0 ? __builtin_ctz(F4) : -1;
-    // the tile's own entry of this lane: column and rating, loaded ahead of their use, unconditionally (index clamped into the
-    // slice) and back to back.  A masked entry (outside the slice / the catalogue) gathers row 0 and weighs 0.
-    auto load_cv = [&](int64_t e0, int& c, float& v) {
-        const int64_t e = e0 + lane < end ? e0 + lane : (end > beg ? end - 1 : beg);
-        c = end > beg ? a.col[e] : -1;
-        v = end > beg ? a.val[e] : 0.f;
-    };
-    auto valid_c = [&](int64_t e0, int c) { return (e0 + lane < end && c >= 0 && c < a.I) ? c : -1; };
-    auto issue = [&](const float* tab, int ld, int X4, int shX, bool xorj, unsigned lds_base, int cols) {
-        const int rpp = shX >= 0 ? 64 >> shX : 0;          // whole rows per piece (one wave-instruction, 64 chunks)
-        if (rpp >= 1 && rpp <= 4) {
-            const int sub = lane >> shX, j = lane & (X4 - 1);
-            for (int piece = wave; piece < X4; piece += NW) {   // wave-uniform trip count
-                const int e0p = piece * rpp;
-                int ci = __builtin_amdgcn_readlane(cols, e0p);
-                if (rpp >= 2) { const int c1 = __builtin_amdgcn_readlane(cols, e0p + 1); ci = sub == 1 ? c1 : ci; }
-                if (rpp == 4) {
-                    const int c2 = __builtin_amdgcn_readlane(cols, e0p + 2), c3 = __builtin_amdgcn_readlane(cols, e0p + 3);
-                    ci = sub == 2 ? c2 : (sub == 3 ? c3 : ci);
-                }
-                const int jj = xorj ? (j ^ ((e0p + sub) & 15)) : j;
-                if (ATT_SPLIT_DIAG != 2 && ATT_SPLIT_DIAG < 5) dma16(tab + (int64_t)(ci >= 0 ? ci : 0) * ld + 4 * jj, lds_base + (unsigned)piece * 1024u);
-            }
-            return;
-        }
-        for (int piece = wave; piece < X4; piece += NW) {  // general row widths: (entry, chunk) by division, col by a shuffle
-            const int gi = piece * 64 + lane;
-            const int e = shX >= 0 ? gi >> shX : gi / X4;
-            const int j = shX >= 0 ? gi & (X4 - 1) : gi - e * X4;
-            const int ci = __shfl(cols, e);
-            dma16(tab + (int64_t)(ci >= 0 ? ci : 0) * ld + 4 * (xorj ? (j ^ (e & 15)) : j), lds_base + (unsigned)piece * 1024u);
-        }
-    };
-    auto issue_pr = [&](int cols) { issue(a.pr, a.ldpr, A4, shA, swz, lds0, cols); };
-    auto issue_feat = [&](int cols) { issue(a.feat, a.ldfeat, F4, shF, false, lds0 + (unsigned)(EC * A * 4), cols); };
+    // nothing zero-fills LDS: a masked entry (outside the slice / the catalogue) gathers row 0 and weighs 0
+    const TileEntries<decltype(a.col), decltype(a.val)> ent{a.col, a.val, beg, end, a.I, lane};
+    auto issue_pr = [&](int cols) { tile_issue<true, NW>(a.pr, a.ldpr, A4, shA, swz, lds0, cols, lane, wave); };
+    auto issue_feat = [&](int cols) { tile_issue<true, NW>(a.feat, a.ldfeat, F4, shF, false, lds0 + (unsigned)(EC * A * 4), cols, lane, wave); };
 
     f32x4 acc[NJ];
 #pragma unroll
@@ -164,10 +102,10 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_split_kernel(const AttnSplitA
     int c_cur = -1, c_nxt = -1;
     float v_cur = 0.f, v_nxt = 0.f;
     if (ntiles > 0) {
-        load_cv(beg, c_cur, v_cur);
-        load_cv(beg + EC, c_nxt, v_nxt);
-        c_cur = valid_c(beg, c_cur);
-        c_nxt = valid_c(beg + EC, c_nxt);
+        ent.load(beg, c_cur, v_cur);
+        ent.load(beg + EC, c_nxt, v_nxt);
+        c_cur = ent.valid(beg, c_cur);
+        c_nxt = ent.valid(beg + EC, c_nxt);
         issue_pr(c_cur);
         issue_feat(c_cur);
     }
@@ -175,179 +113,45 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_split_kernel(const AttnSplitA
     const int g4 = lane >> 4, i16 = lane & 15;
     const float* myrow = prt + lane * A;
     const int NB = A4 / CB;
-    // Scalar-cache prefetch (ATT_SPLIT_PF, off: measured slower).  A workgroup's pc rows are read exactly once, so every 64-byte line is a
-    // compulsory scalar-cache miss, and with all loads hitting (ablation) the kernel is 5.5 us shorter.  touch_block(b) reads one 16-byte
-    // chunk of every line of row block b with ordinary, compiler-visible scalar loads and throws the values away, so that a block's misses
-    // are taken together.  It did not pay: 28.2 vs 25.7 us.  (A first attempt used inline-asm s_load_dwordx16 into "reserved" SGPRs: hipcc
-    // spilled and reused them under the loads in flight and the kernel hung — scalar loads the compiler cannot see are not an option.)
-    auto touch_block = [&](int blk) {
-#if ATT_SPLIT_PF
-        f32x4 pf[2 * MAXP + 2];
-#pragma unroll
-        for (int k = 0; k < MAXP; ++k) {
-            const float* rowp = pcrow[k < np ? k : 0];
-            pf[2 * k] = *(const_f32x4_ptr)(rowp + 32 * blk);
-            pf[2 * k + 1] = *(const_f32x4_ptr)(rowp + 32 * blk + 16);
-        }
-        const float* wp = MODE != 2 ? a.w1 : pcrow[0];
-        pf[2 * MAXP] = *(const_f32x4_ptr)(wp + 32 * blk);
-        pf[2 * MAXP + 1] = *(const_f32x4_ptr)(wp + 32 * blk + 16);
-#pragma unroll
-        for (int i = 0; i < 2 * MAXP + 2; ++i) asm volatile("" ::"s"(pf[i][0]));   // a use: the loads stay, their wait sits here
-#endif
-    };
     for (int64_t t = 0; t < ntiles; ++t) {
         const int64_t e0 = beg + t * EC;
-        touch_block(0);                                    // lands under the DMA wait and the barrier
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of pr(t) / feat(t) have landed (and col / val) ...
         __syncthreads();                                   // ... and everybody's; pid is written
         const bool ok = c_cur >= 0;
         const float vl = ok ? v_cur : 0.f;
         int c_nn = -1;
         float v_nn = 0.f;
-        if (t + 2 < ntiles) load_cv(e0 + 2 * EC, c_nn, v_nn);   // wave-uniform
+        if (t + 2 < ntiles) ent.load(e0 + 2 * EC, c_nn, v_nn);   // wave-uniform
 
         f32x2 s2[MAXP], t2[MAXP];
 #pragma unroll
         for (int k = 0; k < MAXP; ++k) { s2[k] = f32x2{0.f, 0.f}; t2[k] = f32x2{0.f, 0.f}; }
-        auto read_rows = [&](f32x4 (&row)[CB], int blk) {
-#pragma unroll
-            for (int c = 0; c < CB; ++c) row[c] = *reinterpret_cast<const f32x4*>(myrow + 4 * ((blk * CB + c) ^ sw));
-        };
-        // Scalar operands arrive one 16-byte chunk per pair (+ w1's) at a time, one step ahead: a wait on scalar loads is always
-        // lgkmcnt(0) (they return out of order), so a step is  wait(step s) -> issue loads(step s+1) -> VALU(step s).
-        auto score_block = [&](const f32x4 (&row)[CB], int blk, auto slots) {
-            constexpr int NS = decltype(slots)::value;     // slots computed: 1, 2 or 4 (>= np)
-            constexpr int G = ATT_SPLIT_G, NST = CB / G;   // 16-byte chunks per step
-            f32x4 qs[2][NS][G], ws[2][G];
-            auto load_step = [&](int st, int slot) {           // constant address space + uniform address = s_load_dwordx4 / x8
-#pragma unroll
-                for (int gk = 0; gk < G; ++gk) {
-                    if (MODE != 2) ws[slot][gk] = *(const_f32x4_ptr)(a.w1 + 4 * (blk * CB + st * G + gk));
-#pragma unroll
-                    for (int k = 0; k < NS; ++k) qs[slot][k][gk] = *(const_f32x4_ptr)(pcrow[k] + 4 * (blk * CB + st * G + gk));
-                }
-            };
-            load_step(0, 0);
-#pragma unroll
-            for (int st = 0; st < NST; ++st) {
-                const int cur = st & 1;
-                asm volatile("" ::"s"(qs[cur][0][0][0]));  // the compiler's wait for step st sits HERE, before the next issue
-                __builtin_amdgcn_sched_barrier(0);
-                if (st + 1 < NST) load_step(st + 1, cur ^ 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int gk = 0; gk < G; ++gk) {
-                    const int c = st * G + gk;
-                    const f32x2 p01 = {row[c][0], row[c][1]}, p23 = {row[c][2], row[c][3]};
-#pragma unroll
-                    for (int k = 0; k < NS; ++k) {
-                        const f32x4 q = qs[cur][k][gk];
-                        const f32x2 q01 = {q[0], q[1]}, q23 = {q[2], q[3]};
-                        if (MODE == 0 || MODE == 3) {
-                            const f32x4 ww = ws[cur][gk];
-                            const f32x2 w01 = {ww[0], ww[1]}, w23 = {ww[2], ww[3]};
-                            f32x2 u, v;
-                            if (MODE == 3) {               // relu(p + q) on 2^-64-scaled operands = the [0, 1] clamp of the packed add
-                                asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(u) : "v"(p01), "s"(q01));
-                                asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(v) : "v"(p23), "s"(q23));
-                            } else {
-                                u = p01 + q01, v = p23 + q23;
-                                u = __builtin_elementwise_max(u, (f32x2){0.f, 0.f});
-                                v = __builtin_elementwise_max(v, (f32x2){0.f, 0.f});
-                            }
-                            s2[k] = u * w01 + s2[k];
-                            t2[k] = v * w23 + t2[k];
-                        } else {
-                            s2[k] = p01 * q01 + s2[k];
-                            t2[k] = p23 * q23 + t2[k];
-                        }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        auto score_dispatch = [&](const f32x4 (&row)[CB], int blk) {
-            if (ATT_SPLIT_DIAG == 3 || ATT_SPLIT_DIAG >= 5) return;
-            if (np > 2) score_block(row, blk, std::integral_constant<int, 4>{});
-            else if (np == 2) score_block(row, blk, std::integral_constant<int, 2>{});
-            else if (np == 1) score_block(row, blk, std::integral_constant<int, 1>{});
-        };
-#if ATT_SPLIT_DB
-        {
-            f32x4 rA[CB], rB[CB];
-            read_rows(rA, 0);
-            for (int blk = 0; blk < NB; blk += 2) {        // row blocks double buffered: block b+1 is read under block b's arithmetic
-                if (blk + 1 < NB) read_rows(rB, blk + 1);
-                score_dispatch(rA, blk);
-                if (blk + 1 < NB) {
-                    if (blk + 2 < NB) read_rows(rA, blk + 2);
-                    score_dispatch(rB, blk + 1);
-                }
-            }
-        }
-#else
-        for (int blk = 0; blk < NB; ++blk) {               // four waves per SIMD cover a block's LDS reads
+        // Row blocks of CB chunks, one at a time: four waves per SIMD cover a block's LDS reads.  (Double buffering the blocks in
+        // registers spills at the 128-register budget, and touching the next block's pc / w1 lines ahead measured slower: DESIGN.md.)
+        for (int blk = 0; blk < NB; ++blk) {
             f32x4 rA[CB];
-            read_rows(rA, blk);
-            if (blk + 1 < NB) touch_block(blk + 1);
-            score_dispatch(rA, blk);
+#pragma unroll
+            for (int c = 0; c < CB; ++c) rA[c] = *reinterpret_cast<const f32x4*>(myrow + 4 * ((blk * CB + c) ^ sw));
+            tile_score<MODE, 1, CB>(np, rA, a.w1, pcrow, blk * CB, s2, t2, LoadConst{});
         }
-#endif
-        // Epilogue of the tile, the wave's pairs side by side: tile maximum, running maximum, rescale factor, p_e.
         float sc[MAXP], mx[MAXP];
+        tile_scores<MODE>(s2, t2, ok, a.b1, sc, mx);
 #pragma unroll
         for (int k = 0; k < MAXP; ++k) {
-            const float ssum = (s2[k][0] + t2[k][0]) + (s2[k][1] + t2[k][1]);
-            sc[k] = ok ? ssum + (MODE != 2 ? a.b1 : 0.f) : -INFINITY;
-            mx[k] = sc[k];
-        }
-        wave_reduce_dpp_n<MAXP>(mx, [](float x, float y) { return fmaxf(x, y); });
-#pragma unroll
-        for (int k = 0; k < MAXP; ++k) {
-            const float mnew = fmaxf(m[k], mx[k]);
-            const bool any = mnew != -INFINITY;            // wave-uniform; false: nothing valid so far, m, l, O stay 0
-            const float scale = any ? exp_le0(m[k] - mnew) : 1.f;
-            const float pe = (any && ok && k < np) ? exp_le0(sc[k] - mnew) : 0.f;
-            l[k] = l[k] * scale + pe;                      // per-lane partial sum; lanes are added once, after the last tile
-            m[k] = mnew;
+            const SoftmaxStep st = tile_softmax_step(m[k], l[k], mx[k], sc[k], ok && k < np);
             const int j = wave + NW * k;                   // every slot of the wave writes (slots beyond np: zeros) — nothing
-            Pm[j * PS + lane] = pe * vl;                   // uninitialised ever reaches an MFMA
-            if (lane == 0) scl[j] = (k < np) ? scale : 0.f;
+            Pm[j * PS + lane] = st.pe * vl;                // uninitialised ever reaches an MFMA
+            if (lane == 0) scl[j] = (k < np) ? st.scale : 0.f;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                      // P and scl of this tile are complete; every wave is done with the pr image
         if (t + 1 < ntiles) issue_pr(c_nxt);               // tile t+1's rows land under this tile's aggregation
-        {
-            // jobs: (16-pair row tile mt, 16-feature column tile nt) = (j % MT, j / MT) for j = wave, wave + NW, ...
-#pragma unroll
-            for (int n = 0; n < NJ; ++n) {
-                const int job = wave + NW * n;
-                const int mt = job % MT, nt = job / MT;
-                if (nt >= NTILES || ATT_SPLIT_DIAG == 4 || ATT_SPLIT_DIAG >= 5) break;   // wave-uniform
-                const f32x4 s4 = *reinterpret_cast<const f32x4*>(scl + 16 * mt + 4 * g4);   // accumulator register i holds pair row 16*mt + 4*g4 + i
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[n][i] *= s4[i];
-                const float* fb = fct + 16 * nt + i16;
-                const float* pa = Pm + (16 * mt + i16) * PS + g4;
-#pragma unroll
-                for (int q0 = 0; q0 < EC / 4; q0 += 8) {    // 8 k-steps' operands first (16 LDS reads in flight), then their chain
-                    float av[8], bv[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {           // A[i = pair][k = 4q + g4], B[k][j = feature]
-                        av[q] = pa[4 * (q0 + q)];
-                        bv[q] = fb[(4 * (q0 + q) + g4) * Fdim];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc[n], 0, 0, 0);
-                }
-            }
-        }
+        tile_aggregate<NW, MT, NJ>(acc, fct, Pm, scl, Fdim, NTILES, wave, g4, i16);
         if (t + 1 < ntiles) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of the feat image / P have returned
             __builtin_amdgcn_s_barrier();
             c_cur = c_nxt; v_cur = v_nxt;
-            c_nxt = valid_c(e0 + 2 * EC, c_nn); v_nxt = v_nn;
+            c_nxt = ent.valid(e0 + 2 * EC, c_nn); v_nxt = v_nn;
             issue_feat(c_cur);
         }
     }
@@ -383,24 +187,10 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_split_kernel(const AttnSplitA
     for (int k = 0; k < MAXP; ++k)
         if (lane == 0) scl[wave + NW * k] = (k < np && lt[k] > 0.f) ? 1.0f / lt[k] : 0.f;
     __syncthreads();
-#pragma unroll
-    for (int n = 0; n < NJ; ++n) {
-        const int job = wave + NW * n;
-        const int mt = job % MT, nt = job / MT;
-        if (nt >= NTILES) break;
-        const f32x4 s4 = *reinterpret_cast<const f32x4*>(scl + 16 * mt + 4 * g4);
-        const int f = 16 * nt + i16;
-        const float bias = (a.out_bias && f < Fdim) ? a.out_bias[f] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = 16 * mt + 4 * g4 + i;
-            if (row < cnt && f < Fdim) a.out[pid[row] * a.ldout + f] = acc[n][i] * s4[i] + bias;
-        }
-    }
+    tile_store_scaled<NW, MT, NJ>(acc, scl, pid, cnt, Fdim, NTILES, a.out_bias, a.out, a.ldout, wave, g4, i16);
 }
 
-// out[b, :] = sum_s O_s e^(m_s - M) / sum_s l_s e^(m_s - M) + bias, M = max_s m_s  (slices in index order: deterministic).
-// A pair whose slices are all empty (no rated entry: the nan_to_num case, attention_ncf.py:208-209) gets the bias alone.
+// out[b, :] = the merge of pair b's slice partials + bias (merge_partials, attn_tile.h), four features per thread
 __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restrict__ part, int ldpart, int nsplit, int64_t B, int Fdim,
                                                            const float* __restrict__ out_bias, float* __restrict__ out, int64_t ldout) {
     const int F4 = Fdim >> 2;
@@ -408,25 +198,10 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
     if (i >= B * F4) return;
     const int64_t b = i / F4;
     const int c = (int)(i - b * F4);
-    const float* p0 = part + b * nsplit * (int64_t)ldpart;
-    float M = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p0[(int64_t)s * ldpart]);
-    float L = 0.f;
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < nsplit; ++s) {
-        const float* ps = p0 + (int64_t)s * ldpart;
-        const float ms = ps[0];
-        const float w = (ms == -INFINITY) ? 0.f : exp_le0(ms - M);
-        L += ps[1] * w;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(ps + kPartHead + 4 * c);
-        o += v * w;
-    }
-    const float inv = L > 0.f ? 1.0f / L : 0.f;
-    f32x4 bias = {0.f, 0.f, 0.f, 0.f};
-    if (out_bias) bias = *reinterpret_cast<const f32x4*>(out_bias + 4 * c);
+    const f32x4 o = merge_partials<false>(part + b * nsplit * (int64_t)ldpart, nsplit, ldpart, c, out_bias);
     float* dst = out + b * ldout + 4 * c;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) dst[j] = o[j] * inv + bias[j];
+    for (int j = 0; j < 4; ++j) dst[j] = o[j];
 }
 
 }  // namespace ncf
@@ -442,9 +217,7 @@ extern "C" int ncf_attn_split_supported(int mode, int A, int Fdim, int pairs_per
     if (mode != NCF_ATT_MLP && mode != NCF_ATT_COS && mode != NCF_ATT_MLP_SCALED) return 0;
     if (A <= 0 || A % 32 || A > 256 || (Fdim != 64 && Fdim != 128)) return 0;
     if (pairs_per_wg < 1 || pairs_per_wg > 64) return 0;
-    const int pp = pairs_per_wg <= 16 ? 16 : (pairs_per_wg <= 32 ? 32 : 64);
-    const size_t lds = ((size_t)64 * (A + Fdim) + pp * 66 + pp + 2 * pp) * 4;
-    return lds <= 160 * 1024;
+    return attn_tile_lds(A, Fdim, attn_tile_pairs(pairs_per_wg)).bytes() <= 160 * 1024;
 }
 
 extern "C" int ncf_attn_forward_split(int mode, const float* pc, int64_t ldpc, const float* pr, int64_t ldpr, int A, const float* w1,
@@ -478,8 +251,8 @@ extern "C" int ncf_attn_forward_split(int mode, const float* pc, int64_t ldpc, c
     a.ppw = pairs_per_wg; a.nsplit = nsplit; a.ldpart = Fdim + kPartHead;
     a.b1 = b1;
     const unsigned blocks = (unsigned)((B + pairs_per_wg - 1) / pairs_per_wg + (R < B ? R : B));   // upper bound on sum_r ceil(n_r / ppw)
-    const int pp = pairs_per_wg <= 16 ? 16 : (pairs_per_wg <= 32 ? 32 : 64);   // 4 / 8 / 16 waves of 4 pairs
-    const size_t lds = ((size_t)64 * (A + Fdim) + pp * 66 + pp + 2 * pp) * 4;
+    const int pp = attn_tile_pairs(pairs_per_wg);   // 4 / 8 / 16 waves of 4 pairs
+    const size_t lds = attn_tile_lds(A, Fdim, pp).bytes();
     const bool scaled = mode == NCF_ATT_MLP_SCALED;
 #define LAUNCH_SP(M, W, J)                                                                                              \
     do {                                                                                                                \

@@ -12,12 +12,8 @@
 // the same 256 KB of weights, and 256 workgroups asking for all of it at once queue on their XCD's L2).
 // No bit-identity with mlp_fused.hip's k order is claimed (another summation order; 1e-5 of the oracle holds).
 #include "ncf_common.h"
-#include "attn_util.h"
+#include "attn_tile.h"
 #include <type_traits>
-
-#ifndef ATT_TAIL_DIAG
-#define ATT_TAIL_DIAG 0   // diagnostic builds (wrong results): 1 = no merge (partials not read), 2 = no layers 1 / 2, 3 = exit at once,
-#endif                    // 4 = layers without their weight loads (one fragment reused)
 
 namespace ncf {
 
@@ -30,8 +26,6 @@ struct TailArgs {
     float* out;
     int64_t B;
 };
-
-constexpr int kTailHead = 4;   // floats in front of a partial's O (attn_split.hip kPartHead)
 
 // PACKED: W1 / W2 in MFMA operand order (ncf_attn_tail_pack_weight: [k-block][column tile][lane][4]) — a wave's load of a weight
 // fragment is then ONE contiguous 1 KB run instead of 16 rows x 64 bytes.  Measured at the cfg 3 shape: 12.8 -> 9.8 us.  The same
@@ -46,7 +40,6 @@ __global__ __launch_bounds__(512, 2) void attn_tail_kernel(const TailArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i16 = lane & 15, g4 = lane >> 4;
     const int64_t row0 = (int64_t)blockIdx.x * TM;
-    if (ATT_TAIL_DIAG == 3) { if (tid == 0) a.out[row0] = 0.f; return; }
 
     // ---- the input tile: cat(candidate_emb, user_emb) (:219, candidate first) ----
     for (int o = tid; o < TM * (K0 / 4); o += 512) {
@@ -57,47 +50,8 @@ __global__ __launch_bounds__(512, 2) void attn_tail_kernel(const TailArgs a) {
             v = *reinterpret_cast<const f32x4*>(a.cand + b * a.ldcand + 4 * c);
         } else {
             const int cu = c - EA / 4;
-            if (a.part && ATT_TAIL_DIAG != 1) {   // out = sum_s O_s e^(m_s - M) / sum_s l_s e^(m_s - M) + bias, slices in index order (attn_combine_kernel's order)
-                const float* p0 = a.part + b * a.nsplit * (int64_t)a.ldpart;
-                float M = -INFINITY;
-                float L = 0.f;
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (a.nsplit <= 8) {                       // the usual case: every slice's (m, l) and O chunk requested at once — a loop over
-                    const int ns = a.nsplit;               // a run-time count is a chain of dependent round trips
-                    f32x2 ml[8];
-                    f32x4 ov[8];
-#pragma unroll
-                    for (int s = 0; s < 8; ++s) {
-                        const float* ps = p0 + (int64_t)(s < ns ? s : ns - 1) * a.ldpart;
-                        ml[s] = *reinterpret_cast<const f32x2*>(ps);
-                        ov[s] = *reinterpret_cast<const f32x4*>(ps + kTailHead + 4 * cu);
-                    }
-#pragma unroll
-                    for (int s = 0; s < 8; ++s) M = s < ns ? fmaxf(M, ml[s][0]) : M;
-#pragma unroll
-                    for (int s = 0; s < 8; ++s) {
-                        if (s < ns) {
-                            const float w = (ml[s][0] == -INFINITY) ? 0.f : exp_le0(ml[s][0] - M);
-                            L += ml[s][1] * w;
-                            acc += ov[s] * w;
-                        }
-                    }
-                } else {
-                    for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, p0[(int64_t)s * a.ldpart]);
-                    for (int s = 0; s < a.nsplit; ++s) {
-                        const float* ps = p0 + (int64_t)s * a.ldpart;
-                        const float ms = ps[0];
-                        const float w = (ms == -INFINITY) ? 0.f : exp_le0(ms - M);
-                        L += ps[1] * w;
-                        acc += *reinterpret_cast<const f32x4*>(ps + kTailHead + 4 * cu) * w;
-                    }
-                }
-                const float inv = L > 0.f ? 1.0f / L : 0.f;
-                f32x4 bias = {0.f, 0.f, 0.f, 0.f};
-                if (a.ubias) bias = *reinterpret_cast<const f32x4*>(a.ubias + 4 * cu);
-                v = acc * inv + bias;
-            } else if (ATT_TAIL_DIAG == 1) {
-                v = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (a.part) {   // the merge of the slice partials, slices in index order: attn_combine_kernel's bits (merge_partials, attn_tile.h)
+                v = merge_partials<true>(a.part + b * a.nsplit * (int64_t)a.ldpart, a.nsplit, a.ldpart, cu, a.ubias);
             } else {
                 v = *reinterpret_cast<const f32x4*>(a.user + b * a.lduser + 4 * cu);
             }
@@ -142,7 +96,7 @@ __global__ __launch_bounds__(512, 2) void attn_tail_kernel(const TailArgs a) {
 #pragma unroll
                     for (int t = 0; t < T; ++t) {
                         wv[t] = ring[d][t];
-                        if (ATT_TAIL_DIAG != 4) ring[d][t] = *reinterpret_cast<const f32x4*>(wrow[t] + WSTEP * kn);
+                        ring[d][t] = *reinterpret_cast<const f32x4*>(wrow[t] + WSTEP * kn);
                     }
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
@@ -164,9 +118,9 @@ __global__ __launch_bounds__(512, 2) void attn_tail_kernel(const TailArgs a) {
         }
     };
     static_assert(N1 % (16 * NWV) == 0 && N2 % (16 * NWV) == 0, "column tiles are dealt evenly over the waves");
-    if (ATT_TAIL_DIAG != 2) layer(std::integral_constant<int, N1 / 16 / NWV>{}, xs, XS, K0, a.W1, a.b1, h1, H1S);
+    layer(std::integral_constant<int, N1 / 16 / NWV>{}, xs, XS, K0, a.W1, a.b1, h1, H1S);
     __syncthreads();
-    if (ATT_TAIL_DIAG != 2) layer(std::integral_constant<int, N2 / 16 / NWV>{}, h1, H1S, N1, a.W2, a.b2, h2, H2S);
+    layer(std::integral_constant<int, N2 / 16 / NWV>{}, h1, H1S, N1, a.W2, a.b2, h2, H2S);
     __syncthreads();
     // last layer (N2 -> 1, no activation): wave 0, lane (pair, quarter): a quarter of the dot each, quarters added in order
     if (wave == 0) {
@@ -228,7 +182,7 @@ extern "C" int ncf_attn_tail(const float* cand, int64_t ldcand, int EA, const fl
         !aligned16(W2) || (ubias && !aligned16(ubias)))
         return fail(NCF_EINVAL, "ncf_attn_tail: operands must be 16-byte aligned with leading dimensions that are multiples of 4");
     TailArgs a{};
-    a.cand = cand; a.ldcand = ldcand; a.part = part; a.nsplit = nsplit; a.ldpart = UE + kTailHead; a.user = user; a.lduser = lduser;
+    a.cand = cand; a.ldcand = ldcand; a.part = part; a.nsplit = nsplit; a.ldpart = UE + kPartHead; a.user = user; a.lduser = lduser;
     a.ubias = ubias; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.out = out; a.B = B;
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((B + 15) / 16);

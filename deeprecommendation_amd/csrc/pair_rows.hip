@@ -16,7 +16,7 @@
 #include "ncf_common.h"
 
 #ifndef PR_UNROLL
-#define PR_UNROLL 4           // entries per lane group in flight (independent col -> row loads), as ATT_UNROLL in attn.hip
+#define PR_UNROLL 4           // entries per lane group in flight (independent col -> row loads), as kAttUnroll in attn.hip
 #endif
 
 namespace ncf {
