@@ -12,6 +12,7 @@
 // The tables (pr, feat) are small (catalogue x 64..128 floats) and stay L2 / Infinity-Cache resident; the
 // kernel is bound by gathered cache bandwidth, not by arithmetic.
 #include "ncf_common.h"
+#include "drop_mask.h"   // drop_threshold, mask_hash: the one drop rule and mask hash of the library
 #include "attn_tile.h"
 #include "group_pairs.h"
 #include <math.h>
@@ -30,10 +31,9 @@ struct AttDrop {
     float scale;          // 1 / (1 - thr / 65536)
 };
 __device__ __forceinline__ f32x4 att_mask4(uint32_t entry, int chunk, const AttDrop& d) {   // 0 or 1/(1-p') per element
-    const uint32_t h0 = mix32(entry * 0x9E3779B1U ^ d.seed ^ (uint32_t)chunk * 0x85EBCA77U);
-    const uint32_t h1 = mix32(h0 ^ 0x68E31DA4U);
-    return f32x4{(h0 & 0xFFFFU) >= d.thr ? d.scale : 0.f, (h0 >> 16) >= d.thr ? d.scale : 0.f,
-                 (h1 & 0xFFFFU) >= d.thr ? d.scale : 0.f, (h1 >> 16) >= d.thr ? d.scale : 0.f};
+    const MaskHash h = mask_hash(entry, chunk, d.seed);
+    return f32x4{(h.h0 & 0xFFFFU) >= d.thr ? d.scale : 0.f, (h.h0 >> 16) >= d.thr ? d.scale : 0.f,
+                 (h.h1 & 0xFFFFU) >= d.thr ? d.scale : 0.f, (h.h1 >> 16) >= d.thr ? d.scale : 0.f};
 }
 
 // Training-time message dropout (attention_ncf.py:184-189: F.dropout over the (pair, rated entry) logits, then
@@ -960,10 +960,8 @@ static int attn_forward_impl(const char* who, int mode, const float* pc, int64_t
 }
 
 static bool att_drop_args(float p, uint32_t seed, AttDrop& d) {
-    d.seed = seed;
-    d.thr = (uint32_t)(p * 65536.f + 0.5f);
-    if (d.thr > 65535u) d.thr = 65535u;
-    d.scale = 65536.f / (float)(65536u - d.thr);
+    const DropThreshold t = drop_threshold(p);
+    d = AttDrop{seed, t.thr, t.scale};
     return d.thr != 0;
 }
 

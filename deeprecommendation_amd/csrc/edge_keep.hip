@@ -8,6 +8,8 @@
 // segment are counted across the wave and lane 0 adds the count to deg_out[row] with one INTEGER atomic add: integer sums do not
 // depend on arrival order, so the degrees (and with them every coefficient) are bitwise reproducible.  No MFMA, no LDS.
 #include "ncf_common.h"
+#include "drop_mask.h"   // drop_threshold: the one drop rule
+#include "seg_walk.h"    // wave_walk / wave_blocks, seg_row, wave_sum
 #include <math.h>
 
 namespace ncf {
@@ -31,11 +33,10 @@ __global__ __launch_bounds__(256) void edge_keep_kernel(const int64_t* __restric
                                                         const uint8_t* __restrict__ node_keep, float* __restrict__ w_out,
                                                         int32_t* __restrict__ deg_out) {
     const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t s = wave0; s < n_seg; s += nwaves) {
+    const WaveWalk walk = wave_walk(blockDim.x);
+    for (int64_t s = walk.first; s < n_seg; s += walk.stride) {
         const int64_t beg = segptr[s], end = segptr[s + 1];
-        const int64_t row = row_of ? (int64_t)row_of[s] : s;
+        const int64_t row = seg_row(row_of, s);
         const bool row_ok = row >= 0 && row < N;
         const bool dst_kept = row_ok && (!node_keep || node_keep[row] != 0);
         int cnt = 0;
@@ -50,8 +51,7 @@ __global__ __launch_bounds__(256) void edge_keep_kernel(const int64_t* __restric
             w_out[e] = kept ? (attr ? attr[e] : 1.f) : 0.f;
             cnt += kept ? 1 : 0;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+        cnt = wave_sum(cnt);
         if (lane == 0 && cnt > 0 && row_ok) atomicAdd(deg_out + row, cnt);
     }
 }
@@ -66,18 +66,14 @@ extern "C" int ncf_edge_keep(const int64_t* segptr, const int32_t* row_of, int64
                              ncf_stream_t stream) {
     if (n_seg < 0 || N < 0 || n_targets < 0) return fail(NCF_EINVAL, "ncf_edge_keep: negative size");
     if (!isfinite(p) || !(p >= 0.f && p <= 1.f)) return fail(NCF_EINVAL, "ncf_edge_keep: p = %g is not in [0, 1]", (double)p);
-    uint32_t thr = (uint32_t)(p * 65536.f + 0.5f);
-    if (thr > 65535u) thr = 65535u;
+    const uint32_t thr = drop_threshold(p).thr;
     if (!segptr || (N > 0 && !deg_out) || (n_seg > 0 && (!col || !w_out))) return fail(NCF_EINVAL, "ncf_edge_keep: null pointer");
     if (n_targets > 0 && (!pair_key || !targets_sorted)) return fail(NCF_EINVAL, "ncf_edge_keep: target masking needs pair_key and the sorted targets");
     if (thr > 0 && !slot) return fail(NCF_EINVAL, "ncf_edge_keep: message dropout (thr = %u) needs the per-entry slot", thr);
     hipStream_t s = (hipStream_t)stream;
     fill_u32_async(deg_out, 0u, (size_t)N * sizeof(int32_t), s);
-    if (n_seg > 0) {
-        int64_t blocks = (n_seg + 3) / 4;
-        if (blocks > 256 * 64) blocks = 256 * 64;
-        hipLaunchKernelGGL(edge_keep_kernel, dim3((unsigned)blocks), dim3(256), 0, s, segptr, row_of, n_seg, N, col, attr, pair_key,
+    if (n_seg > 0)
+        hipLaunchKernelGGL(edge_keep_kernel, dim3(wave_blocks(n_seg)), dim3(256), 0, s, segptr, row_of, n_seg, N, col, attr, pair_key,
                            targets_sorted, n_targets, slot, thr, seed, node_keep, w_out, deg_out);
-    }
     return check_launch("ncf_edge_keep");
 }

@@ -1,11 +1,9 @@
-// LightGAT training step (gnn_ncf.py:151-177): the per-destination edge softmax over the edges a step keeps, and the gradient
-// through it.  All three entries walk the level-0 SEGMENTS of the prepared CSR (spmm.hip: a segment is a contiguous entry range of
-// one row, at most seg_len long), so hub rows spread over many waves; split rows are finished by a per-row pass.  No float atomics,
-// no tickets, every sum in a fixed order: bitwise repeatable run to run.
+// LightGAT training step (gnn_ncf.py:151-177): the gradient through the per-destination edge softmax over the edges a step keeps.
+// (The softmax itself, ncf_gat_edge_softmax, is edge_softmax.hip's: one set of kernels for scoring and training.)  Both entries walk
+// the level-0 SEGMENTS of the prepared CSR (seg_walk.h: a segment is a contiguous entry range of one row, at most seg_len long), so
+// hub rows spread over many waves; split rows are finished by a per-row pass.  No float atomics, no tickets, every sum in a fixed
+// order: bitwise repeatable run to run.
 //
-//   ncf_gat_edge_softmax    alpha_e = exp(s[col_e] - M_r) / (sum_kept exp(.) + 1e-16), coef_e = attr_e alpha_e.  The three passes and
-//                           the operation order of spmm.hip's edge softmax, with the predicate "in range AND kept": keep == NULL
-//                           gives those kernels' bits.  4-byte scalars only (col, keep, s gathered from an N-float table).
 //   ncf_gat_edge_grad       g_e = attr_e <dY[row_e], drop_e(z[col_e])>,  S_r = sum_r alpha_e g_e,  dlogit_e = alpha_e (g_e - S_r).
 //                           HBM-bound like the SpMM: per entry one z row (4 D bytes) + col 4 + alpha 4 + attr 4 read, g 4 written,
 //                           then 12 bytes in the apply pass (g, alpha read; dlogit written).  The segment's dY row chunk stays in
@@ -20,118 +18,11 @@
 //                           spmm_seg_kernel on scalars (a segment that is the first and last of its row writes out[row], any other
 //                           its partial sum), re-applied level by level by native.gat_source_reduce as SegmentedCSR.spmm does.
 #include "ncf_common.h"
-#include "drop_mask.h"
+#include "drop_mask.h"   // DropArgs, drop4: the message dropout mask
+#include "seg_walk.h"    // wave_walk / wave_blocks, seg_row, the first / last rule, RowLanes, dispatch_lpr
 #include <math.h>
 
 namespace ncf {
-
-__device__ __forceinline__ bool gat_counts(const int32_t* __restrict__ col, const float* __restrict__ keep, int64_t e, int64_t Ns,
-                                           int64_t& c) {
-    c = col[e];
-    return c >= 0 && c < Ns && (!keep || keep[e] != 0.f);
-}
-
-// ---- softmax, row form: one wave per row (edge_softmax_kernel of spmm.hip with the keep predicate)
-__global__ __launch_bounds__(256) void gat_softmax_row_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                              const float* __restrict__ attr, const float* __restrict__ keep,
-                                                              const float* __restrict__ s, int64_t n_rows, int64_t Ns,
-                                                              float* __restrict__ alpha, float* __restrict__ coef) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t r = wave0; r < n_rows; r += nwaves) {
-        const int64_t beg = rowptr[r], end = rowptr[r + 1];
-        float mx = -INFINITY;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            int64_t c;
-            if (gat_counts(col, keep, e, Ns, c)) mx = fmaxf(mx, s[c]);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        float sm = 0.f;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            int64_t c;
-            if (gat_counts(col, keep, e, Ns, c)) sm += expf(s[c] - mx);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sm += __shfl_xor(sm, off);
-        const float den = sm + 1e-16f;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            int64_t c;
-            const float a = gat_counts(col, keep, e, Ns, c) ? expf(s[c] - mx) / den : 0.f;
-            alpha[e] = a;
-            if (coef) coef[e] = attr[e] * a;
-        }
-    }
-}
-
-// ---- softmax, segmented form: the three passes of ncf_edge_softmax_segmented
-__global__ __launch_bounds__(256) void gat_softmax_seg_stats_kernel(const int64_t* __restrict__ segptr, int64_t n_seg, const int32_t* __restrict__ col,
-                                                                    const float* __restrict__ keep, const float* __restrict__ s, int64_t Ns,
-                                                                    float* __restrict__ segm, float* __restrict__ segl) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t g = wave0; g < n_seg; g += nwaves) {
-        const int64_t beg = segptr[g], end = segptr[g + 1];
-        float mx = -INFINITY;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            int64_t c;
-            if (gat_counts(col, keep, e, Ns, c)) mx = fmaxf(mx, s[c]);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        float sm = 0.f;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            int64_t c;
-            if (gat_counts(col, keep, e, Ns, c)) sm += expf(s[c] - mx);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sm += __shfl_xor(sm, off);
-        if (lane == 0) { segm[g] = mx; segl[g] = sm; }
-    }
-}
-
-__global__ __launch_bounds__(256) void gat_softmax_row_stats_kernel(const int64_t* __restrict__ seg_first, int64_t n_rows, const float* __restrict__ segm,
-                                                                    const float* __restrict__ segl, float* __restrict__ rowm, float* __restrict__ rowden) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t r = wave0; r < n_rows; r += nwaves) {
-        const int64_t beg = seg_first[r], end = seg_first[r + 1];
-        float mx = -INFINITY;
-        for (int64_t g = beg + lane; g < end; g += 64) mx = fmaxf(mx, segm[g]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        float sm = 0.f;
-        for (int64_t g = beg + lane; g < end; g += 64) {
-            const float m = segm[g];
-            if (m != -INFINITY) sm += segl[g] * expf(m - mx);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sm += __shfl_xor(sm, off);
-        if (lane == 0) { rowm[r] = mx; rowden[r] = sm + 1e-16f; }
-    }
-}
-
-__global__ __launch_bounds__(256) void gat_softmax_seg_apply_kernel(const int64_t* __restrict__ segptr, const int32_t* __restrict__ row_of, int64_t n_seg,
-                                                                    int64_t n_rows, const int32_t* __restrict__ col, const float* __restrict__ attr,
-                                                                    const float* __restrict__ keep, const float* __restrict__ s, int64_t Ns,
-                                                                    const float* __restrict__ rowm, const float* __restrict__ rowden,
-                                                                    float* __restrict__ alpha, float* __restrict__ coef) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t g = wave0; g < n_seg; g += nwaves) {
-        const int64_t beg = segptr[g], end = segptr[g + 1];
-        const int64_t r = row_of[g];
-        const bool row_ok = r >= 0 && r < n_rows;
-        const float mx = row_ok ? rowm[r] : 0.f, den = row_ok ? rowden[r] : 1.f;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            int64_t c;
-            const float a = (gat_counts(col, keep, e, Ns, c) && row_ok) ? expf(s[c] - mx) / den : 0.f;
-            alpha[e] = a;
-            if (coef) coef[e] = attr[e] * a;
-        }
-    }
-}
 
 // ---- gradient, pass 1: g_e into g_out[e], the segment's sum of alpha_e g_e into segsum[seg]
 template <int LPR, bool DROP>
@@ -141,17 +32,14 @@ __global__ __launch_bounds__(256) void gat_edge_dot_kernel(const int64_t* __rest
                                                            const float* __restrict__ dY, int64_t ldy, const float* __restrict__ z,
                                                            int64_t Nz, int64_t ldz, int chunks, float* __restrict__ g_out,
                                                            float* __restrict__ segsum, DropArgs drop) {
-    constexpr int EPI = 64 / LPR;  // entries per wave-instruction
-    constexpr int UNROLL = 4;
+    constexpr int EPI = RowLanes<LPR>::EPI, UNROLL = RowLanes<LPR>::UNROLL;
     const int lane = threadIdx.x & 63;
-    const int c = lane % LPR;       // 16-byte chunk of the row this lane owns
-    const int eg = lane / LPR;      // which of the EPI concurrent entries
-    const bool active = c < chunks;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t s = wave0; s < n_seg; s += nwaves) {
+    const int c = RowLanes<LPR>::chunk(lane), eg = RowLanes<LPR>::entry(lane);
+    const bool active = c < chunks;   // the chunk lies inside the row
+    const WaveWalk walk = wave_walk(blockDim.x);
+    for (int64_t s = walk.first; s < n_seg; s += walk.stride) {
         const int64_t beg = segptr[s], end = segptr[s + 1];
-        const int64_t row = row_of ? (int64_t)row_of[s] : s;
+        const int64_t row = seg_row(row_of, s);
         f32x4 dy = {0.f, 0.f, 0.f, 0.f};
         if (active && row >= 0 && row < n_rows && end > beg) dy = *reinterpret_cast<const f32x4*>(dY + row * ldy + 4 * c);
         float sacc = 0.f;
@@ -201,8 +89,8 @@ __global__ __launch_bounds__(256) void gat_edge_dot_kernel(const int64_t* __rest
 __global__ __launch_bounds__(256) void gat_row_sum_kernel(const int64_t* __restrict__ seg_first, int64_t n_rows, const float* __restrict__ segsum,
                                                           float* __restrict__ rowsum) {
     const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t r = wave0; r < n_rows; r += nwaves) {
+    const WaveWalk walk = wave_walk(blockDim.x);
+    for (int64_t r = walk.first; r < n_rows; r += walk.stride) {
         const int64_t beg = seg_first[r], end = seg_first[r + 1];
         float sm = 0.f;
         for (int64_t g = beg + lane; g < end; g += 64) sm += segsum[g];
@@ -217,10 +105,10 @@ __global__ __launch_bounds__(256) void gat_dlogit_kernel(const int64_t* __restri
                                                          int64_t n_rows, const float* __restrict__ alpha, const float* __restrict__ S,
                                                          float* __restrict__ g) {
     const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t sg = wave0; sg < n_seg; sg += nwaves) {
+    const WaveWalk walk = wave_walk(blockDim.x);
+    for (int64_t sg = walk.first; sg < n_seg; sg += walk.stride) {
         const int64_t beg = segptr[sg], end = segptr[sg + 1];
-        const int64_t r = row_of ? (int64_t)row_of[sg] : sg;      // S is per row when rows are split, else per segment = per row
+        const int64_t r = seg_row(row_of, sg);                        // S is per row when rows are split, else per segment = per row
         const float Sr = (r >= 0 && r < n_rows) ? S[r] : 0.f;
         for (int64_t e = beg + lane; e < end; e += 64) {
             const float a = alpha[e];
@@ -234,8 +122,8 @@ __global__ __launch_bounds__(256) void gat_reduce_kernel(const int64_t* __restri
                                                          const int32_t* __restrict__ idx, const float* __restrict__ val, int64_t n_val,
                                                          float* __restrict__ out, int64_t n_rows, float* __restrict__ partial) {
     const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t s = wave0; s < n_seg; s += nwaves) {
+    const WaveWalk walk = wave_walk(blockDim.x);
+    for (int64_t s = walk.first; s < n_seg; s += walk.stride) {
         const int64_t beg = segptr[s], end = segptr[s + 1];
         float acc = 0.f;
         for (int64_t k = beg + lane; k < end; k += 64) {
@@ -245,9 +133,9 @@ __global__ __launch_bounds__(256) void gat_reduce_kernel(const int64_t* __restri
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
         if (lane == 0) {
-            const int64_t row = row_of ? (int64_t)row_of[s] : s;
-            const bool first = !row_of || s == 0 || row_of[s - 1] != row;
-            const bool last = !row_of || s == n_seg - 1 || row_of[s + 1] != row;
+            const int64_t row = seg_row(row_of, s);
+            const bool first = seg_opens_row(row_of, s, row);
+            const bool last = seg_closes_row(row_of, s, n_seg, row);
             if (first && last) {
                 if (row >= 0 && row < n_rows) out[row] = acc;
             } else if (partial) {
@@ -255,12 +143,6 @@ __global__ __launch_bounds__(256) void gat_reduce_kernel(const int64_t* __restri
             }
         }
     }
-}
-
-static unsigned wave_blocks(int64_t n) {
-    int64_t b = (n + 3) / 4;
-    if (b > 256 * 64) b = 256 * 64;
-    return (unsigned)b;
 }
 
 template <int LPR>
@@ -278,37 +160,6 @@ static void launch_edge_dot(const int64_t* segptr, const int32_t* row_of, int64_
 }  // namespace ncf
 
 using namespace ncf;
-
-extern "C" size_t ncf_gat_edge_softmax_workspace_bytes(int64_t n_seg, int64_t n_rows) {
-    return (size_t)(2 * (n_seg > 0 ? n_seg : 0) + 2 * (n_rows > 0 ? n_rows : 0)) * sizeof(float);
-}
-
-extern "C" int ncf_gat_edge_softmax(const int64_t* segptr, const int32_t* row_of, int64_t n_seg, const int64_t* seg_first, int64_t n_rows,
-                                    const int32_t* col, const float* attr, const float* keep, const float* s, int64_t Ns, float* alpha_out,
-                                    float* coef_out, void* workspace, size_t workspace_bytes, ncf_stream_t stream) {
-    if (n_rows < 0 || n_seg < 0 || Ns < 0) return fail(NCF_EINVAL, "ncf_gat_edge_softmax: negative size");
-    if (!row_of && n_seg != n_rows) return fail(NCF_EINVAL, "ncf_gat_edge_softmax: without row_of the segments are the rows");
-    if (n_rows == 0 || n_seg == 0) return NCF_OK;
-    if (!segptr || !col || !s || !alpha_out || (attr && !coef_out) || (row_of && (!seg_first || !workspace)))
-        return fail(NCF_EINVAL, "ncf_gat_edge_softmax: null pointer");
-    if (row_of && workspace_bytes < ncf_gat_edge_softmax_workspace_bytes(n_seg, n_rows))
-        return fail(NCF_EWORKSPACE, "ncf_gat_edge_softmax: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float* coef = attr ? coef_out : nullptr;
-    if (!row_of) {
-        hipLaunchKernelGGL(gat_softmax_row_kernel, dim3(wave_blocks(n_rows)), dim3(256), 0, st, segptr, col, attr, keep, s, n_rows, Ns, alpha_out, coef);
-        return check_launch("ncf_gat_edge_softmax");
-    }
-    float* segm = (float*)workspace;
-    float* segl = segm + n_seg;
-    float* rowm = segl + n_seg;
-    float* rowden = rowm + n_rows;
-    hipLaunchKernelGGL(gat_softmax_seg_stats_kernel, dim3(wave_blocks(n_seg)), dim3(256), 0, st, segptr, n_seg, col, keep, s, Ns, segm, segl);
-    hipLaunchKernelGGL(gat_softmax_row_stats_kernel, dim3(wave_blocks(n_rows)), dim3(256), 0, st, seg_first, n_rows, segm, segl, rowm, rowden);
-    hipLaunchKernelGGL(gat_softmax_seg_apply_kernel, dim3(wave_blocks(n_seg)), dim3(256), 0, st, segptr, row_of, n_seg, n_rows, col, attr, keep, s,
-                       Ns, rowm, rowden, alpha_out, coef);
-    return check_launch("ncf_gat_edge_softmax");
-}
 
 extern "C" size_t ncf_gat_edge_grad_workspace_bytes(int64_t n_seg, int64_t n_rows) {
     return (size_t)((n_seg > 0 ? n_seg : 0) + (n_rows > 0 ? n_rows : 0)) * sizeof(float);
@@ -334,10 +185,9 @@ extern "C" int ncf_gat_edge_grad(const int64_t* segptr, const int32_t* row_of, i
     float* rowsum = segsum + n_seg;
     const DropArgs d = drop_args(nullptr, seed, p);
     const int chunks = D / 4;
-    if (chunks <= 8) launch_edge_dot<8>(segptr, row_of, n_seg, n_rows, col, attr, alpha, dY, ldy, z, Nz, ldz, chunks, dlogit_out, segsum, d, st);
-    else if (chunks <= 16) launch_edge_dot<16>(segptr, row_of, n_seg, n_rows, col, attr, alpha, dY, ldy, z, Nz, ldz, chunks, dlogit_out, segsum, d, st);
-    else if (chunks <= 32) launch_edge_dot<32>(segptr, row_of, n_seg, n_rows, col, attr, alpha, dY, ldy, z, Nz, ldz, chunks, dlogit_out, segsum, d, st);
-    else launch_edge_dot<64>(segptr, row_of, n_seg, n_rows, col, attr, alpha, dY, ldy, z, Nz, ldz, chunks, dlogit_out, segsum, d, st);
+    dispatch_lpr(chunks, [&](auto lpr) {
+        launch_edge_dot<decltype(lpr)::value>(segptr, row_of, n_seg, n_rows, col, attr, alpha, dY, ldy, z, Nz, ldz, chunks, dlogit_out, segsum, d, st);
+    });
     if (row_of) hipLaunchKernelGGL(gat_row_sum_kernel, dim3(wave_blocks(n_rows)), dim3(256), 0, st, seg_first, n_rows, segsum, rowsum);
     hipLaunchKernelGGL(gat_dlogit_kernel, dim3(wave_blocks(n_seg)), dim3(256), 0, st, segptr, row_of, n_seg, n_rows, alpha, row_of ? rowsum : segsum,
                        dlogit_out);

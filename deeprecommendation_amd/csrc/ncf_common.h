@@ -75,10 +75,17 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float bf16_to_f32(unsigned short v) { return __uint_as_float(((unsigned int)v) << 16); }
 
 // lowbias32, a bijective avalanche mix of 32 bits: the hash of every counter-based draw of the library (the dropout masks of
-// spmm.hip / gat.hip / attn.hip, edge_keep.hip's keep rule, negsample.hip's uniforms; include/ncf_abi.h states each formula).
+// drop_mask.h, edge_keep.hip's keep rule, slot_hash below; include/ncf_abi.h states each formula).
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
+}
+
+// THE SLOT HASH (include/ncf_abi.h, under ncf_sample_negatives): two rounds of mix32 over (seed, 64-bit slot).  negsample.hip turns
+// it into a uniform, unseen.hip into the ranks of a row's draws.
+__device__ __forceinline__ uint32_t slot_hash(uint32_t seed, uint64_t slot) {
+    const uint32_t x = mix32((uint32_t)slot * 0x9E3779B1U ^ seed);
+    return mix32(x ^ (uint32_t)(slot >> 32) * 0x85EBCA77U ^ 0x68E31DA4U);
 }
 
 // A 64-bit value that is the same in every lane of the wave, moved to scalar registers (two readfirstlanes): a row's [beg, end)

@@ -25,9 +25,7 @@ constexpr int kCdfUnroll = 8;   // pass 1 keeps 8 independent 256-byte wave load
 
 // include/ncf_abi.h states this formula; tests restate it in numpy
 __device__ __forceinline__ float slot_uniform(uint32_t seed, uint64_t slot) {
-    uint32_t x = mix32((uint32_t)slot * 0x9E3779B1U ^ seed);
-    x = mix32(x ^ (uint32_t)(slot >> 32) * 0x85EBCA77U ^ 0x68E31DA4U);
-    return (float)(x >> 8) * 0x1p-24f;   // 24 bits: exact in fp32, in [0, 1)
+    return (float)(slot_hash(seed, slot) >> 8) * 0x1p-24f;   // 24 bits: exact in fp32, in [0, 1)
 }
 
 __device__ __forceinline__ float neg_weight(float r, float w) { return w == 0.f ? 1.f : powf(r, w); }   // numpy: 0 ** 0 == 1

@@ -8,8 +8,11 @@
 // (`row_of` maps segment -> destination); their partial sums go to `partial` and a second kernel adds them in
 // segment order.  No float atomics anywhere: the result is bitwise reproducible run to run.
 // The layer-mean accumulator (gnn_ncf.py:351) is fused into the epilogue: sum[row] += y[row].
+// Also here: the small per-edge kernels (degrees, edge coefficients, row scaling).  The segment walk is seg_walk.h's, the dropout
+// mask drop_mask.h's, LightGAT's edge softmax edge_softmax.hip's.
 #include "ncf_common.h"
-#include "drop_mask.h"   // DropArgs, drop4: the message dropout mask, shared with gat.hip (its hash, mix32, is ncf_common.h's)
+#include "drop_mask.h"   // DropArgs, drop4: the message dropout mask, shared with gat.hip
+#include "seg_walk.h"    // wave_walk / wave_blocks, seg_row, the first / last rule, RowLanes, dispatch_lpr
 #include <math.h>
 
 namespace ncf {
@@ -33,15 +36,12 @@ __global__ __launch_bounds__(256) void spmm_seg_kernel(const int64_t* __restrict
                                                        int64_t Nz, int64_t ldz, int chunks, float* __restrict__ y,
                                                        int64_t ldy, float* __restrict__ sum, int64_t ldsum,
                                                        float* __restrict__ partial, DropArgs drop = DropArgs{}) {
-    constexpr int EPI = 64 / LPR;  // edges per wave-instruction
-    constexpr int UNROLL = 4;
+    constexpr int EPI = RowLanes<LPR>::EPI, UNROLL = RowLanes<LPR>::UNROLL;
     const int lane = threadIdx.x & 63;
-    const int c = lane % LPR;       // 16-byte chunk of the row this lane owns
-    const int eg = lane / LPR;      // which of the EPI concurrent edges
-    const bool active = c < chunks;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t s = wave0; s < n_seg; s += nwaves) {
+    const int c = RowLanes<LPR>::chunk(lane), eg = RowLanes<LPR>::entry(lane);
+    const bool active = c < chunks;   // the chunk lies inside the row
+    const WaveWalk walk = wave_walk(blockDim.x);
+    for (int64_t s = walk.first; s < n_seg; s += walk.stride) {
         const int64_t beg = segptr[s], end = segptr[s + 1];
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         for (int64_t e0 = beg; e0 < end; e0 += EPI * UNROLL) {
@@ -71,9 +71,9 @@ __global__ __launch_bounds__(256) void spmm_seg_kernel(const int64_t* __restrict
         }
         acc = reduce_groups<LPR>(acc);
         if (eg == 0 && active) {
-            const int64_t row = row_of ? row_of[s] : s;
-            const bool first = !row_of || s == 0 || row_of[s - 1] != row;
-            const bool last = !row_of || s == n_seg - 1 || row_of[s + 1] != row;
+            const int64_t row = seg_row(row_of, s);
+            const bool first = seg_opens_row(row_of, s, row);
+            const bool last = seg_closes_row(row_of, s, n_seg, row);
             if (first && last) {
                 *reinterpret_cast<f32x4*>(y + row * ldy + 4 * c) = acc;
                 if (sum) {
@@ -97,8 +97,7 @@ __global__ __launch_bounds__(256) void spmm_fix_kernel(const int32_t* __restrict
     const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) / LPR;
     for (int64_t s = grp; s < n_seg; s += ngrp) {
         const int32_t row = row_of[s];
-        const bool first = s == 0 || row_of[s - 1] != row;
-        const bool last = s == n_seg - 1 || row_of[s + 1] != row;
+        const bool first = seg_opens_row<true>(row_of, s, row), last = seg_closes_row<true>(row_of, s, n_seg, row);
         if (!first || last || c >= chunks) continue;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         for (int64_t t = s; t < n_seg && row_of[t] == row; ++t)
@@ -145,123 +144,15 @@ __global__ void scale_rows_kernel(const float* __restrict__ in, int64_t ldin, in
     }
 }
 
-// LightGAT edge attention (gnn_ncf.py:151-177 with PyG softmax): for destination row r with incoming edges e,
-//   out[e] = (attr ? attr[e] : 1) * exp(s[col[e]] - max_r) / (sum_r exp(s[col[.]] - max_r) + 1e-16)
-// where s[n] = w_j . x[n] is the SOURCE half of AttNet(cat(x_j, x_i)); the destination half w_i . x_i + b is constant
-// inside a softmax group and cancels.  One wave per row, two passes over 4-byte scalars (L2-resident).
-__global__ __launch_bounds__(256) void edge_softmax_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                           const float* __restrict__ attr, const float* __restrict__ s,
-                                                           int64_t n_rows, int64_t Ns, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t r = wave0; r < n_rows; r += nwaves) {
-        const int64_t beg = rowptr[r], end = rowptr[r + 1];
-        float mx = -INFINITY;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            const int64_t c = col[e];
-            if (c >= 0 && c < Ns) mx = fmaxf(mx, s[c]);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        float sm = 0.f;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            const int64_t c = col[e];
-            if (c >= 0 && c < Ns) sm += expf(s[c] - mx);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sm += __shfl_xor(sm, off);
-        const float den = sm + 1e-16f;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            const int64_t c = col[e];
-            const float a = (c >= 0 && c < Ns) ? expf(s[c] - mx) / den : 0.f;
-            out[e] = attr ? attr[e] * a : a;  // weight * a_scores * W(x_j), :174 / :176
-        }
-    }
-}
-
-
-// The same softmax over the SEGMENTS of the SpMM (rows longer than 512 edges are split; a hub item of BASELINE config 4 has 4 M
-// in-edges: one wave walking them three times is ~0.2 s, the whole 100 M-edge graph otherwise ~1 ms).  Three passes, every one
-// parallel over segments or rows, no atomics, fixed order (bitwise repeatable):
-//   1. per segment (one wave):  m_seg = max s[col[e]],  l_seg = sum exp(s[col[e]] - m_seg)
-//   2. per row (one wave over the row's segments [seg_first[r], seg_first[r+1])):  M = max m_seg,  L = sum l_seg exp(m_seg - M)
-//   3. per segment:  out[e] = (attr ? attr[e] : 1) * exp(s[col[e]] - M_row) / (L_row + 1e-16)
-__global__ __launch_bounds__(256) void edge_softmax_seg_stats_kernel(const int64_t* __restrict__ segptr, int64_t n_seg, const int32_t* __restrict__ col,
-                                                                     const float* __restrict__ s, int64_t Ns, float* __restrict__ segm,
-                                                                     float* __restrict__ segl) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t g = wave0; g < n_seg; g += nwaves) {
-        const int64_t beg = segptr[g], end = segptr[g + 1];
-        float mx = -INFINITY;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            const int64_t c = col[e];
-            if (c >= 0 && c < Ns) mx = fmaxf(mx, s[c]);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        float sm = 0.f;
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            const int64_t c = col[e];
-            if (c >= 0 && c < Ns) sm += expf(s[c] - mx);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sm += __shfl_xor(sm, off);
-        if (lane == 0) { segm[g] = mx; segl[g] = sm; }
-    }
-}
-
-__global__ __launch_bounds__(256) void edge_softmax_row_stats_kernel(const int64_t* __restrict__ seg_first, int64_t n_rows, const float* __restrict__ segm,
-                                                                     const float* __restrict__ segl, float* __restrict__ rowm, float* __restrict__ rowden) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t r = wave0; r < n_rows; r += nwaves) {
-        const int64_t beg = seg_first[r], end = seg_first[r + 1];
-        float mx = -INFINITY;
-        for (int64_t g = beg + lane; g < end; g += 64) mx = fmaxf(mx, segm[g]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        float sm = 0.f;
-        for (int64_t g = beg + lane; g < end; g += 64) {
-            const float m = segm[g];
-            if (m != -INFINITY) sm += segl[g] * expf(m - mx);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sm += __shfl_xor(sm, off);
-        if (lane == 0) { rowm[r] = mx; rowden[r] = sm + 1e-16f; }
-    }
-}
-
-__global__ __launch_bounds__(256) void edge_softmax_seg_apply_kernel(const int64_t* __restrict__ segptr, const int32_t* __restrict__ row_of, int64_t n_seg,
-                                                                     const int32_t* __restrict__ col, const float* __restrict__ attr,
-                                                                     const float* __restrict__ s, int64_t Ns, const float* __restrict__ rowm,
-                                                                     const float* __restrict__ rowden, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t g = wave0; g < n_seg; g += nwaves) {
-        const int64_t beg = segptr[g], end = segptr[g + 1];
-        const int64_t r = row_of[g];
-        const float mx = rowm[r], den = rowden[r];
-        for (int64_t e = beg + lane; e < end; e += 64) {
-            const int64_t c = col[e];
-            const float a = (c >= 0 && c < Ns) ? expf(s[c] - mx) / den : 0.f;
-            out[e] = attr ? attr[e] * a : a;
-        }
-    }
-}
-
 template <int LPR>
 static void launch_spmm(const int64_t* segptr, const int32_t* row_of, int64_t n_seg, const int32_t* col, const float* coef,
                         const float* z, int64_t Nz, int64_t ldz, int chunks, float* y, int64_t ldy, float* sum, int64_t ldsum,
                         float* partial, bool fixup, hipStream_t s, const DropArgs* drop = nullptr) {
-    int64_t blocks = (n_seg + 3) / 4;
-    if (blocks > 256 * 64) blocks = 256 * 64;
     if (drop)
-        hipLaunchKernelGGL((spmm_seg_kernel<LPR, true>), dim3((unsigned)blocks), dim3(256), 0, s, segptr, row_of, n_seg, col, coef, z, Nz,
+        hipLaunchKernelGGL((spmm_seg_kernel<LPR, true>), dim3(wave_blocks(n_seg)), dim3(256), 0, s, segptr, row_of, n_seg, col, coef, z, Nz,
                            ldz, chunks, y, ldy, sum, ldsum, partial, *drop);
     else
-        hipLaunchKernelGGL((spmm_seg_kernel<LPR, false>), dim3((unsigned)blocks), dim3(256), 0, s, segptr, row_of, n_seg, col, coef, z, Nz,
+        hipLaunchKernelGGL((spmm_seg_kernel<LPR, false>), dim3(wave_blocks(n_seg)), dim3(256), 0, s, segptr, row_of, n_seg, col, coef, z, Nz,
                            ldz, chunks, y, ldy, sum, ldsum, partial, DropArgs{});
     if (row_of && fixup) {
         int64_t fb = (n_seg * LPR + 255) / 256;
@@ -290,10 +181,9 @@ static int spmm_impl(const char* who, int dtype, const int64_t* segptr, const in
     const int chunks = D / 4;
     const float* zf = (const float*)z;
     float* yf = (float*)y;
-    if (chunks <= 8) launch_spmm<8>(segptr, row_of, n_seg, col, coef, zf, Nz, ldz, chunks, yf, ldy, sum, ldsum, partial, fixup != 0, s, drop);
-    else if (chunks <= 16) launch_spmm<16>(segptr, row_of, n_seg, col, coef, zf, Nz, ldz, chunks, yf, ldy, sum, ldsum, partial, fixup != 0, s, drop);
-    else if (chunks <= 32) launch_spmm<32>(segptr, row_of, n_seg, col, coef, zf, Nz, ldz, chunks, yf, ldy, sum, ldsum, partial, fixup != 0, s, drop);
-    else launch_spmm<64>(segptr, row_of, n_seg, col, coef, zf, Nz, ldz, chunks, yf, ldy, sum, ldsum, partial, fixup != 0, s, drop);
+    dispatch_lpr(chunks, [&](auto lpr) {
+        launch_spmm<decltype(lpr)::value>(segptr, row_of, n_seg, col, coef, zf, Nz, ldz, chunks, yf, ldy, sum, ldsum, partial, fixup != 0, s, drop);
+    });
     return check_launch(who);
 }
 
@@ -340,40 +230,4 @@ extern "C" int ncf_scale_rows(const float* in, int64_t ldin, int64_t N, int D, f
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, ldin, N, D, divisor, out, ldout);
     return check_launch("ncf_scale_rows");
-}
-
-extern "C" int ncf_edge_softmax_csr(const int64_t* rowptr, const int32_t* col, const float* attr, const float* s, int64_t n_rows,
-                                    int64_t Ns, float* out, ncf_stream_t stream) {
-    if (n_rows < 0 || Ns < 0) return fail(NCF_EINVAL, "ncf_edge_softmax_csr: bad sizes");
-    if (n_rows == 0) return NCF_OK;
-    if (!rowptr || !s) return fail(NCF_EINVAL, "ncf_edge_softmax_csr: null pointer");
-    int64_t blocks = (n_rows + 3) / 4;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(edge_softmax_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, attr, s, n_rows, Ns, out);
-    return check_launch("ncf_edge_softmax_csr");
-}
-
-extern "C" size_t ncf_edge_softmax_segmented_workspace_bytes(int64_t n_seg, int64_t n_rows) {
-    return (size_t)(2 * (n_seg > 0 ? n_seg : 0) + 2 * (n_rows > 0 ? n_rows : 0)) * sizeof(float);
-}
-
-extern "C" int ncf_edge_softmax_segmented(const int64_t* segptr, const int32_t* row_of, int64_t n_seg, const int64_t* seg_first, int64_t n_rows,
-                                          const int32_t* col, const float* attr, const float* s, int64_t Ns, float* out, void* workspace,
-                                          size_t workspace_bytes, ncf_stream_t stream) {
-    if (n_rows < 0 || n_seg < 0 || Ns < 0) return fail(NCF_EINVAL, "ncf_edge_softmax_segmented: bad sizes");
-    if (n_rows == 0 || n_seg == 0) return NCF_OK;
-    if (!segptr || !row_of || !seg_first || !s || !workspace) return fail(NCF_EINVAL, "ncf_edge_softmax_segmented: null pointer");
-    if (workspace_bytes < ncf_edge_softmax_segmented_workspace_bytes(n_seg, n_rows)) return fail(NCF_EWORKSPACE, "ncf_edge_softmax_segmented: workspace too small");
-    float* segm = (float*)workspace;
-    float* segl = segm + n_seg;
-    float* rowm = segl + n_seg;
-    float* rowden = rowm + n_rows;
-    hipStream_t st = (hipStream_t)stream;
-    int64_t bs = (n_seg + 3) / 4, br = (n_rows + 3) / 4;
-    if (bs > 256 * 64) bs = 256 * 64;
-    if (br > 256 * 64) br = 256 * 64;
-    hipLaunchKernelGGL(edge_softmax_seg_stats_kernel, dim3((unsigned)bs), dim3(256), 0, st, segptr, n_seg, col, s, Ns, segm, segl);
-    hipLaunchKernelGGL(edge_softmax_row_stats_kernel, dim3((unsigned)br), dim3(256), 0, st, seg_first, n_rows, segm, segl, rowm, rowden);
-    hipLaunchKernelGGL(edge_softmax_seg_apply_kernel, dim3((unsigned)bs), dim3(256), 0, st, segptr, row_of, n_seg, col, attr, s, Ns, rowm, rowden, out);
-    return check_launch("ncf_edge_softmax_segmented");
 }

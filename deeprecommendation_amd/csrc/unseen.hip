@@ -29,10 +29,6 @@ namespace {
 constexpr int kLaneK = NCF_UNSEEN_LANE_K;   // the lane form's largest K
 constexpr int kWaves = 4;                   // waves (rows in flight) per block of the wave form
 
-__device__ __forceinline__ uint32_t slot_hash(uint32_t seed, uint64_t slot) {   // ncf_sample_negatives' two rounds
-    uint32_t x = mix32((uint32_t)slot * 0x9E3779B1U ^ seed);
-    return mix32(x ^ (uint32_t)(slot >> 32) * 0x85EBCA77U ^ 0x68E31DA4U);
-}
 __device__ __forceinline__ uint32_t draw_rank(uint32_t x, int j, uint32_t left) {   // r_j in [0, left)
     return __umulhi(mix32(x ^ (uint32_t)(j + 1) * 0xC2B2AE35U), left);
 }

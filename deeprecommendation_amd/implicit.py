@@ -223,7 +223,7 @@ def fit_implicit(model, data: ImplicitFeedback, *, negatives: int = 4, loss: str
     for epoch in range(epochs):
         model.train()
         order = torch.randperm(n, device=dev) if shuffle else torch.arange(n, device=dev)
-        draw_seed = epoch_seed(seed, epoch) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())   # host generator
+        draw_seed = epoch_seed(seed, epoch) if seed is not None else native.host_seed()   # host generator
         running = torch.zeros((), dtype=torch.float64, device=dev)
         for s in range(0, n, batch_size):
             pick = order[s:s + batch_size]

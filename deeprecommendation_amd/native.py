@@ -288,6 +288,12 @@ def _check(rc: int):
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
+def host_seed() -> int:
+    """A 31-bit seed for the library's counter-based draws (dropout masks, the keep rule, the samplers) from torch's default HOST
+    generator: one draw per call, no device synchronisation, and torch.manual_seed makes a run repeat."""
+    return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+
+
 def _stream(t: torch.Tensor) -> int:
     """torch's current stream on t's device as a raw hipStream_t (every launch of the library goes there).  The raw accessor costs
     0.3 us where torch.cuda.current_stream() builds a Stream object (2.3 us, five times per AttentionNCF forward)."""
@@ -713,17 +719,15 @@ def spmm_csr(segptr: torch.Tensor, row_of: Optional[torch.Tensor], col: torch.Te
         y = torch.empty((N, D), dtype=torch.float32, device=z.device)
     if row_of is not None and partial is None:
         partial = torch.empty((n_seg, D), dtype=torch.float32, device=z.device)
+    args = (NCF_F32, _ptr(segptr), _ptr(row_of), n_seg, _ptr(col), _ptr(coef), _ptr(z), Nz, ldz, D, _ptr(y), y.stride(0), _ptr(acc_sum),
+            0 if acc_sum is None else acc_sum.stride(0), _ptr(partial), 1 if fixup else 0)
     if dropout is not None and dropout[0] > 0:
         p, seed, eid = dropout
         if eid is not None and (eid.dtype != torch.int32 or eid.numel() != col.numel()):
             raise TypeError("edge ids must be int32, one per CSR entry")
-        _check(lib.ncf_spmm_csr_dropout(NCF_F32, _ptr(segptr), _ptr(row_of), n_seg, _ptr(col), _ptr(coef), _ptr(z), Nz, ldz, D, _ptr(y),
-                                        y.stride(0), _ptr(acc_sum), 0 if acc_sum is None else acc_sum.stride(0), _ptr(partial),
-                                        1 if fixup else 0, _ptr(eid), int(seed) & 0xFFFFFFFF, float(p), _stream(z)))
-        return y
-    _check(lib.ncf_spmm_csr(NCF_F32, _ptr(segptr), _ptr(row_of), n_seg, _ptr(col), _ptr(coef), _ptr(z), Nz, ldz, D, _ptr(y),
-                            y.stride(0), _ptr(acc_sum), 0 if acc_sum is None else acc_sum.stride(0), _ptr(partial),
-                            1 if fixup else 0, _stream(z)))
+        _check(lib.ncf_spmm_csr_dropout(*args, _ptr(eid), int(seed) & 0xFFFFFFFF, float(p), _stream(z)))
+    else:
+        _check(lib.ncf_spmm_csr(*args, _stream(z)))
     return y
 
 
@@ -1996,20 +2000,22 @@ def edge_softmax_csr(rowptr: torch.Tensor, col: torch.Tensor, attr: Optional[tor
     _dev(s, "s")
     if out is None:
         out = torch.empty(max(col.numel(), 1), dtype=torch.float32, device=s.device)[:col.numel()]
+    n_rows = rowptr.numel() - 1
     if segments is not None and segments[1] is not None:
         segptr, row_of, seg_first = segments
-        n_seg, n_rows = segptr.numel() - 1, rowptr.numel() - 1
+        n_seg = _gat_segments("edge_softmax_csr", segptr, row_of, seg_first, n_rows, col, ((attr, "attr"),))
         nbytes = lib.ncf_edge_softmax_segmented_workspace_bytes(n_seg, n_rows)
-        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=s.device)
         _check(lib.ncf_edge_softmax_segmented(_ptr(segptr), _ptr(row_of), n_seg, _ptr(seg_first), n_rows, _ptr(col), _ptr(attr), _ptr(s), s.numel(),
-                                              _ptr(out), _ptr(ws), nbytes, _stream(s)))
+                                              _ptr(out), _ptr(_gat_ws(None, nbytes, s.device)), nbytes, _stream(s)))
         return out
-    _check(lib.ncf_edge_softmax_csr(_ptr(rowptr), _ptr(col), _ptr(attr), _ptr(s), rowptr.numel() - 1, s.numel(), _ptr(out), _stream(s)))
+    _gat_segments("edge_softmax_csr", rowptr, None, None, n_rows, col, ((attr, "attr"),))
+    _check(lib.ncf_edge_softmax_csr(_ptr(rowptr), _ptr(col), _ptr(attr), _ptr(s), n_rows, s.numel(), _ptr(out), _stream(s)))
     return out
 
 
 def _gat_segments(fn, segptr, row_of, seg_first, n_rows, col, per_entry):
-    """The refusals the three LightGAT wrappers share: level-0 segments of a CSR by destination and its per-entry arrays."""
+    """The refusals the edge softmax and the LightGAT wrappers share: level-0 segments of a CSR by destination (row_of None: its rows)
+    and its per-entry arrays.  Returns the number of segments."""
     if segptr.dtype != torch.int64 or col.dtype != torch.int32 or not segptr.is_contiguous() or not col.is_contiguous():
         raise TypeError(f"{fn}: segptr must be contiguous int64 and col contiguous int32")
     n_seg = segptr.numel() - 1

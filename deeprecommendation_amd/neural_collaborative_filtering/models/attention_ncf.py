@@ -622,9 +622,9 @@ class AttentionNCF(_ScoringMixin, NCF):
         if not self.use_cos_sim_instead and self.att_dense:
             drop = self.AttentionNet[2]
             if self.training and isinstance(drop, nn.Dropout) and drop.p > 0:
-                hidden = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+                hidden = native.host_seed()
         if self._message_dropout_active() and self.message_dropout_on_device:
-            msg = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            msg = native.host_seed()
         return hidden, msg
 
     def _forward_train(self, candidate_items, rated_items, user_matrix, return_attention_weights, pair_split=None):

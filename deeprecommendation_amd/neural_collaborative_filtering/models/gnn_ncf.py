@@ -197,39 +197,40 @@ class PreparedGraph:
         coef = norm if self.attr is None else self.attr * norm
         return torch.where(masked, torch.zeros_like(coef), coef).contiguous()
 
+    def _kept_edges(self, attr, user_ids, item_ids, mask_targets, node_keep, message):
+        """ncf_edge_keep over the CSR for one batch: (w, deg) with w = ``attr`` (None: 1) where the entry is kept and 0 where it is
+        removed, deg = the kept entries per row.  The targets are sorted on the device; duplicates stay: no size on the host."""
+        _, _, pair_key, slot = self.train_state()
+        targets = None
+        if mask_targets:
+            targets = torch.sort(user_ids.long() * self.N + item_ids.long()).values.contiguous()
+        p, seed = message if message is not None else (0.0, 0)
+        return native.edge_keep(self.segptr, self.row_of, self.N, self.col, attr, pair_key, targets, slot if p > 0 else None, p, seed, node_keep)
+
     def batch_coef(self, user_ids, item_ids, mask_targets=True, node_keep=None, message=None):
         """Coefficients of one training batch under the reference's three train-only edge removals (gnn_ncf.py:246-296, 314-320):
         the batch's target edges (``mask_targets``), node dropout (``node_keep``: (N,) uint8, see GraphNCF._draw_node_keep) and
         message dropout (``message`` = (p, seed)), applied by ncf_edge_keep in one pass over the CSR, which also counts the
         degrees of the remaining edges; ncf_edge_coef then normalises the kept weights.  A removed edge and every edge of a row
         left without edges get coefficient 0 — the CSR itself stays as it is.  Nothing here needs a value on the host."""
-        dst_of, src, pair_key, slot = self.train_state()
-        targets = None
-        if mask_targets:
-            targets = torch.sort(user_ids.long() * self.N + item_ids.long()).values.contiguous()   # duplicates stay: no size on the host
-        p, seed = message if message is not None else (0.0, 0)
-        w, deg = native.edge_keep(self.segptr, self.row_of, self.N, self.col, self.attr, pair_key, targets,
-                                  slot if p > 0 else None, p, seed, node_keep)
+        dst_of, src, _, _ = self.train_state()
+        w, deg = self._kept_edges(self.attr, user_ids, item_ids, mask_targets, node_keep, message)
         return native.edge_coef(src, dst_of, w, deg.to(torch.float32))
 
     def gat_workspace(self):
-        """One uint8 buffer per graph for the LightGAT training kernels (ncf_gat_edge_softmax needs 2 floats per segment and per row,
-        ncf_gat_edge_grad one of each; the calls of a step run one after another on one stream, so they share it)."""
+        """One uint8 buffer per graph for the LightGAT training kernels, as large as the larger of what ncf_gat_edge_softmax and
+        ncf_gat_edge_grad ask for (the calls of a step run one after another on one stream, so they share it)."""
         if getattr(self, "_gat_ws", None) is None:
-            n_seg = self.segptr.numel() - 1
-            self._gat_ws = torch.empty(max(4 * (2 * n_seg + 2 * self.N), 4), dtype=torch.uint8, device=self.col.device)
+            lib, n_seg = native.load_library(), self.segptr.numel() - 1
+            nbytes = max(lib.ncf_gat_edge_softmax_workspace_bytes(n_seg, self.N), lib.ncf_gat_edge_grad_workspace_bytes(n_seg, self.N))
+            self._gat_ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.col.device)
         return self._gat_ws
 
     def batch_keep(self, user_ids, item_ids, mask_targets=True, node_keep=None, message=None):
         """The same edge set as ``batch_coef`` as a per-entry indicator for LightGAT: (E,) float32, exactly 1 where the entry is kept
         and 0 where it is removed (ncf_edge_keep with attr = None).  The edge weight goes to the softmax separately, so a kept edge
         whose weight happens to be 0 still counts in its destination's group, as in the reference."""
-        _, _, pair_key, slot = self.train_state()
-        targets = None
-        if mask_targets:
-            targets = torch.sort(user_ids.long() * self.N + item_ids.long()).values.contiguous()
-        p, seed = message if message is not None else (0.0, 0)
-        return native.edge_keep(self.segptr, self.row_of, self.N, self.col, None, pair_key, targets, slot if p > 0 else None, p, seed, node_keep)[0]
+        return self._kept_edges(None, user_ids, item_ids, mask_targets, node_keep, message)[0]
 
 
 class _ConvBase(nn.Module):
@@ -529,24 +530,22 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
         userIds, itemIds = userIds.long().contiguous(), itemIds.long().contiguous()
         conv = self.gnn_convs[0]
         p = float((conv.W if not conv.hetero else conv.user2item_W)[1].p) if self.training else 0.0
-        seed0 = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0     # host generator: no device sync
+        seed0 = native.host_seed() if p > 0 else 0     # host generator: no device sync
         p_node = float(self.node_dropout or 0.0) if self.training else 0.0
         p_msg = float(self.message_dropout or 0.0) if self.training else 0.0
-        coef = keep = None
-        if p_node > 0.0 or p_msg > 0.0:
-            # one edge set per call, shared by all layers (gnn_ncf.py:322-333); seeds drawn after seed0: seed0, node_seed, seed
-            node_keep = None
-            if p_node > 0.0:
-                node_keep = self._draw_node_keep(prep.N, userIds, itemIds, p_node, int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
-            message = (p_msg, int(torch.randint(0, 2 ** 31 - 1, (1,)).item())) if p_msg > 0.0 else None
+        # one edge set per call, shared by all layers (gnn_ncf.py:322-333); seeds drawn after seed0: seed0, node_seed, seed
+        node_keep = self._draw_node_keep(prep.N, userIds, itemIds, p_node, native.host_seed()) if p_node > 0.0 else None
+        message = (p_msg, native.host_seed()) if p_msg > 0.0 else None
+        masked = bool(self.training and mask_targets)      # a dropout is active only in training
+        dropped = node_keep is not None or message is not None
+        coef, keep = (None if gat else prep.coef), None    # every edge of the graph
+        if dropped or masked:
             if gat:
-                keep = prep.batch_keep(userIds, itemIds, mask_targets, node_keep, message)
-            else:
-                coef = prep.batch_coef(userIds, itemIds, mask_targets, node_keep, message)
-        elif gat:
-            keep = prep.batch_keep(userIds, itemIds, True, None, None) if (self.training and mask_targets) else None
-        else:
-            coef = prep.masked_coef(userIds, itemIds) if (self.training and mask_targets) else prep.coef
+                keep = prep.batch_keep(userIds, itemIds, masked, node_keep, message)
+            elif dropped:
+                coef = prep.batch_coef(userIds, itemIds, masked, node_keep, message)
+            else:                                          # targets only: the torch-op predecessor of batch_coef
+                coef = prep.masked_coef(userIds, itemIds)
         D = x.shape[1]
         hs = [x]
         for layer in range(len(self.gnn_convs)):

@@ -21,6 +21,7 @@ import torch
 from torch import optim
 from torch.utils.data import DataLoader
 
+from .. import native
 from .datasets.base import PointwiseDataset, RankingDataset
 from .eval import eval_model
 from .util import cap_host_threads, load_model
@@ -144,7 +145,7 @@ def train_model(model, train_dataset, val_dataset: PointwiseDataset, lr, weight_
         model.train()
         if pairs is not None:
             order = torch.randperm(n, device=device) if shuffle else torch.arange(n, device=device)
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())    # torch's default (host) generator: no device sync
+            seed = native.host_seed()    # torch's default (host) generator: no device sync
             running = torch.zeros((), dtype=torch.float64, device=device)
             for s in range(0, n, batch_size):
                 batch = pairs.batch(order[s:s + batch_size], seed, s)   # slots numbered across the epoch
@@ -173,7 +174,6 @@ def train_model(model, train_dataset, val_dataset: PointwiseDataset, lr, weight_
                 running += loss.detach().double()
             train_sum_loss = float(running.item())   # the epoch's only host synchronisation
             if on_batch is not None:                 # batches built on the device: their sticky flags, already on the host's side
-                from .. import native
                 native.check_pair_rows(device)
                 native.check_oob(device)
         else:

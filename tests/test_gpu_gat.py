@@ -1,4 +1,4 @@
-"""GPU: the LightGAT training kernels (csrc/gat.hip) against tests/gat_ref.py — the softmax over kept entries (bit-identical to the
+"""GPU: the LightGAT training kernels (csrc/gat.hip, csrc/edge_softmax.hip) against tests/gat_ref.py — the softmax over kept entries (bit-identical to the
 scoring softmax without a keep mask, exact cases bitwise, random and peaked scores against float64), the per-edge gradient (exact
 cases bitwise on every launch form, random data under the rounding-count bound), the ordered reduce per source, the refusals —
 and GraphNCF(convType='LightGAT') training steps on the HIP blocks against a CPU copy of the model on the graph of kept edges."""
@@ -67,6 +67,9 @@ def test_softmax_without_keep_has_the_bits_of_the_scoring_softmax(gpu, lengths, 
         assert torch.equal((attr * alpha).view(torch.int32), want.view(torch.int32))
     alpha2, coef2 = native.gat_edge_softmax(segptr, row_of, seg_first, len(lengths), col, attr, None, s)
     assert torch.equal(alpha.view(torch.int32), alpha2.view(torch.int32)) and torch.equal(coef.view(torch.int32), coef2.view(torch.int32))
+    # "kept" taken by every entry: an all-ones keep is no keep at all
+    alpha1, coef1 = native.gat_edge_softmax(segptr, row_of, seg_first, len(lengths), col, attr, torch.ones(E, device=gpu), s)
+    assert torch.equal(alpha1.view(torch.int32), alpha.view(torch.int32)) and torch.equal(coef1.view(torch.int32), coef.view(torch.int32))
 
 
 @pytest.mark.parametrize("weighted", [True, False])
