@@ -16,6 +16,9 @@ layers; loss, dropout masks and the optimizer stay torch ops (the reference's tr
                    SpmmFn, ds through ncf_gat_edge_grad (per-edge dot product, softmax backward per destination) and
                    ncf_gat_source_reduce (ordered sum per source over the transposed CSR)
   AttnFn         : grouped item-item attention (ncf_attn_forward_grouped) with its backward (ncf_attn_backward_grouped)
+  DotSoftmaxLossFn : full-catalogue softmax cross-entropy of a dot-product readout without the B x N logits: forward ncf_dot_lse
+                   + ncf_gather_dot for the target logits; backward ncf_dot_softmax_grad in its two roles, the user rows summed
+                   into the table's gradient in a fixed order
 """
 import torch
 
@@ -163,6 +166,26 @@ class SpmmFn(torch.autograd.Function):
         return dZ, None, None, None
 
 
+def ordered_scatter_rows(src: torch.Tensor, idx: torch.Tensor, rows: int) -> torch.Tensor:
+    """(rows, E) fp32: row r = the sum of the rows p of ``src`` (P, E) with idx[p] == r, in ascending p — GatherPairOrderedFn's
+    fixed-order sum (a stable sort of the ids is the CSR the segmented SpMM reads), so equal inputs give equal bits.  Ids outside
+    [0, rows) add nothing.  A width that is no multiple of 4 keeps ncf_scatter_add_rows (float atomics: not repeatable)."""
+    e = src.shape[1]
+    if e % 4:
+        d = torch.zeros((rows, e), dtype=torch.float32, device=src.device)
+        native.scatter_add_rows(src, idx, d)
+        return d
+    idx = torch.where((idx >= 0) & (idx < rows), idx, torch.full_like(idx, rows))           # bad ids: a spare row that is dropped
+    rowptr = torch.zeros(rows + 2, dtype=torch.int64, device=src.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(idx, minlength=rows + 1), 0)
+    order = torch.argsort(idx, stable=True).to(torch.int32)
+    d = torch.empty((rows + 1, e), dtype=torch.float32, device=src.device)
+    for c0 in range(0, e, 256):
+        c1 = min(c0 + 256, e)
+        native.spmm_csr(rowptr, None, order, None, src[:, c0:c1], rows + 1, y=d[:, c0:c1])
+    return d[:rows]
+
+
 class GatherPairOrderedFn(torch.autograd.Function):
     """cat(table[idxA], table[idxB]) — GatherConcatFn with both halves read from ONE table — whose backward adds the 2 B gradient
     rows of each table row in a fixed order: the ids are sorted (stable), and the sorted positions are the entries of a CSR by
@@ -189,16 +212,39 @@ class GatherPairOrderedFn(torch.autograd.Function):
             native.scatter_add_rows(dX[:, e:], idxB, d)
             return d, None, None
         src = torch.cat((dX[:, :e], dX[:, e:]), dim=0)                # row p < B: the idxA half of pair p; row B + p: its idxB half
-        idx = torch.cat((idxA, idxB))
-        idx = torch.where((idx >= 0) & (idx < rows), idx, torch.full_like(idx, rows))       # bad ids: a spare row that is dropped
-        rowptr = torch.zeros(rows + 2, dtype=torch.int64, device=dX.device)
-        rowptr[1:] = torch.cumsum(torch.bincount(idx, minlength=rows + 1), 0)
-        order = torch.argsort(idx, stable=True).to(torch.int32)
-        d = torch.empty((rows + 1, e), dtype=torch.float32, device=dX.device)
-        for c0 in range(0, e, 256):
-            c1 = min(c0 + 256, e)
-            native.spmm_csr(rowptr, None, order, None, src[:, c0:c1], rows + 1, y=d[:, c0:c1])
-        return d[:rows], None, None
+        return ordered_scatter_rows(src, torch.cat((idxA, idxB)), rows), None, None
+
+
+class DotSoftmaxLossFn(torch.autograd.Function):
+    """loss (B,) fp32: ``logsumexp_j(scale * <U[users[b]], Q[j]>) - scale * <U[users[b]], Q[targets[b]]>`` over EVERY row j of the
+    item table Q (N, D) — softmax cross-entropy of the positive over the whole catalogue — for a user table U (rows, D) and
+    ``users`` (B,) int64 rows of it (None: row b itself, B = rows).  Nothing of size B x N is built in either direction
+    (csrc/dot_softmax.hip); the logits' scores are native.gather_dot's bits.
+
+    Backward: dQ is dense (every item is in every denominator).  The B gradient rows of the users are summed into dU in a fixed
+    order (ordered_scatter_rows), so a step repeats bit for bit; with ``users`` None they ARE dU — MF.softmax_loss passes the rows
+    GatherColumnsFn gathered, whose backward hands (ids, rows) to optim.RowSparseAdam."""
+
+    @staticmethod
+    def forward(ctx, user_table, item_table, users, targets, scale):
+        U, Q = user_table.contiguous(), item_table.contiguous()
+        scale = native._finite("DotSoftmaxLossFn", scale, "scale")
+        targets = targets.contiguous()
+        lse = native.dot_lse(U, users, Q, None, scale)
+        zt = native.gather_dot(U, users, Q, targets, B=targets.numel()).view(-1) * scale
+        ctx.save_for_backward(U, Q, users, targets, lse)
+        ctx.scale = scale
+        return lse - zt
+
+    @staticmethod
+    def backward(ctx, g):
+        U, Q, users, targets, lse = ctx.saved_tensors
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        dA, dQ = native.dot_softmax_grad(U, users, Q, None, targets, lse, g.contiguous().float(), ctx.scale, need=need)
+        dU = None
+        if dA is not None:
+            dU = dA if users is None else ordered_scatter_rows(dA, users, U.shape[0])
+        return dU, dQ, None, None, None
 
 
 class GatSpmmFn(torch.autograd.Function):

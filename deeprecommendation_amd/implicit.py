@@ -7,7 +7,8 @@ sets the neural ones against.
 ``leave_one_out``       the split: one held-out item per user, on the host.
 ``ImplicitFeedback``    the distinct positives and their sorted CSR on the device; ``negatives`` is one ``native.sample_unseen`` call
                         (csrc/unseen.hip, THE CONTRACT in include/ncf_abi.h): no rejection rounds, no host read.
-``fit_implicit``        the epoch loop in ``train_model``'s resident style for BasicNCF / MF / GraphNCF on index ids.
+``fit_implicit``        the epoch loop in ``train_model``'s resident style for BasicNCF / MF / GraphNCF on index ids; loss="softmax"
+                        (the dot-product models) scores each positive against the whole catalogue and draws no negatives.
 ``sampled_candidates``  each user's fixed candidate list; ``eval_sampled`` ranks the held-out item in it (``rank_sampled``: the ranks).
 
 Users and items are POSITIONS throughout: 0 .. n_users - 1 and 0 .. n_items - 1, the rows and columns of the seen CSR.  Everything past
@@ -24,7 +25,7 @@ from . import native
 from .baselines import build_csr
 
 _M32 = 0xFFFFFFFF
-LOSSES = ("bce", "bpr")
+LOSSES = ("bce", "bpr", "softmax")
 
 
 def _lowbias32(x: np.ndarray) -> np.ndarray:
@@ -185,9 +186,21 @@ def _scorer(who, model, graph):
                     f"(forward(graph, users, items)), not a {type(model).__name__}")
 
 
+def _softmax_scorer(who, model, graph):
+    """``loss(users, items)`` (per-row full-catalogue softmax loss over POSITIONS) of a dot-product model, or TypeError naming them."""
+    from .neural_collaborative_filtering.models.gnn_ncf import GraphNCF
+    from .neural_collaborative_filtering.models.mf import MF
+    if isinstance(model, GraphNCF) and model.MLP is None:
+        return lambda u, i, scale: model.softmax_loss(graph.to(u.device), u + graph.num_items, i, scale)
+    if isinstance(model, MF):
+        return model.softmax_loss
+    raise TypeError(f'{who}: loss = "softmax" takes a dot-product model, an MF or a GraphNCF(use_dot_product=True), not a '
+                    f"{type(model).__name__}" + (" with an MLP readout" if isinstance(model, GraphNCF) else ""))
+
+
 def fit_implicit(model, data: ImplicitFeedback, *, negatives: int = 4, loss: str = "bce", epochs: int, batch_size: int, lr: float,
                  weight_decay: float = 0.0, optimizer=None, graph=None, seed: Optional[int] = None, shuffle: bool = True,
-                 on_epoch: Optional[Callable] = None) -> dict:
+                 on_epoch: Optional[Callable] = None, scale: float = 1.0) -> dict:
     """Trains ``model`` on the positives of ``data`` against unseen negatives drawn on the device, in ``train_model``'s resident style:
     per epoch one permutation drawn on the device, a batch is a gather of positives plus ONE ``native.sample_unseen`` call (slots
     numbered across the epoch, so the draw does not depend on the batch size), the running loss stays on the device (one host read
@@ -197,6 +210,14 @@ def fit_implicit(model, data: ImplicitFeedback, *, negatives: int = 4, loss: str
     ``BCEWithLogitsLoss(reduction="sum")``; ``train_loss`` divides the epoch's sum by its n * (1 + negatives) scored pairs.
     loss="bpr": the same forward; each positive's score is paired with each of its negatives' under
     ``RankingDataset.calculate_loss`` (sum of -log sigmoid(pos - neg)); ``train_loss`` divides by the n * negatives pairs.
+    loss="softmax" (MF, GraphNCF(use_dot_product=True); another model raises TypeError): softmax cross-entropy of each positive
+    over the WHOLE catalogue, ``model.softmax_loss(u, i, scale)`` summed over the batch (autograd.DotSoftmaxLossFn: the B x n_items
+    logits are never built); no negatives are drawn and ``negatives`` is ignored; ``scale`` (finite, > 0) multiplies the logits;
+    ``train_loss`` divides the epoch's sum by its n positives.  ``batch_size`` is at most native.DOT_SOFTMAX_MAX_ROWS (65 536, the
+    rows one ncf_dot_lse call takes); a larger one raises ValueError.  The loss kernels use no float atomics and the user rows'
+    gradients are summed in a fixed order when the embedding width is a multiple of 4, so an MF of such a width fitted twice from
+    the same state of torch's generators gives the same bits (tests/test_gpu_dot_softmax.py); another width keeps the atomic row
+    scatter, and a GraphNCF's step is as repeatable as its propagation backward, which this loss does not change.
     The sampler's seed is drawn per epoch from torch's host generator, or is ``epoch_seed(seed, epoch)`` when ``seed`` is given.
     The optimiser defaults to ``FusedAdam(lr, weight_decay)``.  ``on_epoch(epoch, model)`` runs after every epoch (evaluate there);
     training stops when it returns False.  Returns ``{"train_loss": [...]}``."""
@@ -204,9 +225,13 @@ def fit_implicit(model, data: ImplicitFeedback, *, negatives: int = 4, loss: str
     score = _scorer(who, model, graph)
     if loss not in LOSSES:
         raise ValueError(f"{who}: loss = {loss!r} (one of {', '.join(LOSSES)})")
-    K = native._int_in(who, negatives, "negatives", 1, native.UNSEEN_MAX_K)
+    softmax = _softmax_scorer(who, model, graph) if loss == "softmax" else None
+    scale = native._finite(who, scale, "scale")
+    if not scale > 0:
+        raise ValueError(f"{who}: scale = {scale!r} is not > 0")
+    K = 0 if softmax else native._int_in(who, negatives, "negatives", 1, native.UNSEEN_MAX_K)
     epochs = native._int_in(who, epochs, "epochs", 0, 2 ** 31 - 1)
-    batch_size = native._int_in(who, batch_size, "batch_size", 1, 2 ** 31 - 1)
+    batch_size = native._int_in(who, batch_size, "batch_size", 1, native.DOT_SOFTMAX_MAX_ROWS if softmax else 2 ** 31 - 1)
     if seed is not None and (isinstance(seed, bool) or not isinstance(seed, numbers.Integral)):
         raise ValueError(f"{who}: seed = {seed!r} is not an integer")
     if not isinstance(data, ImplicitFeedback):
@@ -218,7 +243,7 @@ def fit_implicit(model, data: ImplicitFeedback, *, negatives: int = 4, loss: str
         from .optim import FusedAdam
         optimizer = FusedAdam(model.parameters(), lr=lr, weight_decay=weight_decay)
     bce = torch.nn.BCEWithLogitsLoss(reduction="sum")
-    scored = n * (1 + K) if loss == "bce" else n * K
+    scored = n if softmax else n * (1 + K) if loss == "bce" else n * K
     history = {"train_loss": []}
     for epoch in range(epochs):
         model.train()
@@ -228,6 +253,13 @@ def fit_implicit(model, data: ImplicitFeedback, *, negatives: int = 4, loss: str
         for s in range(0, n, batch_size):
             pick = order[s:s + batch_size]
             u, i = data.users[pick], data.items[pick]
+            if softmax:
+                optimizer.zero_grad()
+                batch_loss = softmax(u, i, scale).sum()
+                batch_loss.backward()
+                optimizer.step()
+                running += batch_loss.detach().double()
+                continue
             neg = data.negatives(u, K, draw_seed, s)
             B = u.numel()
             optimizer.zero_grad()

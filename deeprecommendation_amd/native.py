@@ -184,6 +184,13 @@ SIGNATURES = {
     "ncf_mlp_rank": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_i64,
                               _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p, _c_p]),
     "ncf_ranking_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p]),
+    "ncf_dot_softmax_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p]),
+    "ncf_dot_lse_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
+    "ncf_dot_lse": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, ctypes.c_float, _c_p, _c_p,
+                             _c_p, _c_size, _c_p, _c_p]),
+    "ncf_dot_softmax_grad_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_int]),
+    "ncf_dot_softmax_grad": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p,
+                                      ctypes.c_float, _c_int, _c_p, _c_p, _c_size, _c_p, _c_p]),
     "ncf_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _c_i64, _c_p]),
     "ncf_adam_rows": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_i64, ctypes.c_float, ctypes.c_float,
@@ -2619,3 +2626,63 @@ def ranking_plan(entry: str, rows: int, cols: int, k_or_max_targets: int = 1):
     _check(load_library().ncf_ranking_plan(RANKING_ENTRIES[entry], int(rows), int(cols), int(k_or_max_targets), ctypes.byref(tc),
                                            ctypes.byref(tiles), ctypes.byref(lv), ctypes.byref(chunk)))
     return tc.value, tiles.value, lv.value, chunk.value
+
+
+# ------------------------------------------------------------------ full-catalogue softmax loss of a dot-product readout
+# ncf_dot_softmax_plan's kind (include/ncf_abi.h enum ncf_dot_softmax_kind)
+DOT_SOFTMAX_KINDS = {"lse": 0, "grad_rows": 1, "grad_items": 2}
+DOT_SOFTMAX_MAX_ROWS = 65536        # listed rows per call (include/ncf_abi.h: rows <= 65536); more is NCF_EUNSUPPORTED
+
+
+def dot_softmax_plan(kind: str, rows: int, cols: int, D: int):
+    """(tile, tiles, chunk_rows) of the launch ``dot_lse`` (kind "lse") or one role of ``dot_softmax_grad`` ("grad_rows": the batch
+    rows walk the catalogue; "grad_items": the catalogue's rows walk the batch) picks for a (rows, cols) problem of width D: the
+    walk's tile, its number of tiles, and the resident rows per pass over the partial-output workspace.  Host only."""
+    tile, tiles, chunk = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _check(load_library().ncf_dot_softmax_plan(DOT_SOFTMAX_KINDS[kind], int(rows), int(cols), int(D), ctypes.byref(tile),
+                                               ctypes.byref(tiles), ctypes.byref(chunk)))
+    return tile.value, tiles.value, chunk.value
+
+
+def dot_lse(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], scale: float = 1.0,
+            return_max: bool = False):
+    """ncf_dot_lse: ``lse`` (B,) fp32, the log-sum-exp over every column c of the list idxB (every row of tabB with idxB None) of
+    ``scale * <tabA[idxA[b]], tabB[idxB[c]]>`` (operands as dot_topk; the score bits are gather_dot's), without the B x I logit
+    matrix.  ``return_max``: (lse, max logit per row, exact).  Output and workspace from the caching allocator on the current
+    stream; no sync.  An id outside its table sets the sticky flag check_oob reads."""
+    lib = load_library()
+    args, (B, I, D, dev) = _dot_operands("dot_lse", tabA, idxA, tabB, idxB)
+    lse = torch.empty(B, dtype=torch.float32, device=dev)
+    mx = torch.empty(B, dtype=torch.float32, device=dev) if return_max else None
+    nbytes = lib.ncf_dot_lse_workspace_bytes(B, I, D)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    _check(lib.ncf_dot_lse(*args, float(scale), _ptr(lse), _ptr(mx), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
+    return (lse, mx) if return_max else lse
+
+
+def dot_softmax_grad(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor],
+                     targets: torch.Tensor, lse: torch.Tensor, g: torch.Tensor, scale: float = 1.0, need=(True, True)):
+    """ncf_dot_softmax_grad in both roles: ``(dA_rows (B, D), dQ (I, D))``, the gradients of ``sum_b g[b] * (lse[b] - z[b, targets[b]])``
+    (``lse`` from dot_lse with the same operands and scale) by the listed rows (one gradient row per LISTED row) and by the
+    columns of the list.  ``targets`` (B,) int64 columns of the list, ``lse`` / ``g`` (B,) fp32.  ``need``: a role that is False
+    is not run and returns None.  Each role takes its own workspace from the caching allocator; deterministic; no sync."""
+    lib = load_library()
+    who = "dot_softmax_grad"
+    args, (B, I, D, dev) = _dot_operands(who, tabA, idxA, tabB, idxB)
+    _vec1d(who, targets, "targets", torch.int64, B)
+    _vec1d(who, lse, "lse", torch.float32, B)
+    _vec1d(who, g, "g", torch.float32, B)
+    _dev_all((targets, "targets"), (lse, "lse"), (g, "g"))
+    outs = []
+    for items, rows_out in ((0, B), (1, I)):
+        if not need[items]:
+            outs.append(None)
+            continue
+        out = torch.empty((rows_out, D), dtype=torch.float32, device=dev)
+        nbytes = lib.ncf_dot_softmax_grad_workspace_bytes(B, I, D, items)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        _check(lib.ncf_dot_softmax_grad(*args, _ptr(targets), _ptr(lse), _ptr(g), float(scale), items, _ptr(out), _ptr(ws), nbytes,
+                                        _ptr(_oob_flag(dev)), _stream(tabA)))
+        del ws
+        outs.append(out)
+    return tuple(outs)

@@ -509,6 +509,14 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
     def _forward_train_hip(self, graph, userIds, itemIds, mask_targets):
         """gnn_ncf.py:298-367 with autograd recording, on the HIP blocks: per-node hoisted Linear (LinearFn), aggregation
         (SpmmFn, with the per-edge message dropout of gnn_ncf.py:22-31 regenerated inside the kernel), row gather + MLP."""
+        combined = self._combined_train_hip(graph, userIds, itemIds, mask_targets)
+        if combined is None:
+            return None
+        return self._readout(combined, itemIds.long().contiguous(), userIds.long().contiguous(), ordered=self.convType == 'LightGAT')
+
+    def _combined_train_hip(self, graph, userIds, itemIds, mask_targets):
+        """The propagated node table (items first, then users) of _forward_train_hip's step, with autograd recording; None for a
+        graph that keeps to the torch ops."""
         from ...autograd import GatSpmmFn, LinearFn, SpmmFn
         dev = userIds.device
         graph = graph.to(dev)
@@ -566,8 +574,22 @@ class GraphNCF(_ScoringMixin, GNN_NCF):
                 s = torch.cat((LinearFn.apply(x[:I], ai.weight[:, :D], None, False), LinearFn.apply(x[I:], au.weight[:, :D], None, False)), dim=0)
                 x = GatSpmmFn.apply(z, s, prep, keep, drop, ai.weight, ai.bias, au.weight, au.bias)
             hs.append(x)
-        combined = torch.cat(hs, dim=1) if self.concat else torch.mean(torch.stack(hs, dim=0), dim=0)
-        return self._readout(combined, itemIds, userIds, ordered=gat)
+        return torch.cat(hs, dim=1) if self.concat else torch.mean(torch.stack(hs, dim=0), dim=0)
+
+    def softmax_loss(self, graph, userIds, itemIds, scale: float = 1.0, mask_targets=True):
+        """Per-row softmax cross-entropy of each positive (userIds[b], itemIds[b]) over the WHOLE catalogue for the dot-product
+        readout (use_dot_product=True): ``DotSoftmaxLossFn`` over this step's propagated node table, whose first
+        graph.num_items rows are the catalogue; ``userIds`` are graph NODES (user u is node graph.num_items + u), ``itemIds`` item
+        nodes, as in forward.  (B,) fp32 with autograd; the B x num_items logits are never built."""
+        from ...autograd import DotSoftmaxLossFn
+        if self.MLP is not None:
+            raise TypeError("GraphNCF.softmax_loss needs the dot-product readout (use_dot_product=True)")
+        require_gpu(userIds, itemIds)
+        combined = self._combined_train_hip(graph, userIds, itemIds, mask_targets) if self._hip_training_possible(graph, userIds) else None
+        if combined is None:
+            raise RuntimeError("GraphNCF.softmax_loss runs on the HIP training blocks: this graph or layer type keeps to the torch ops")
+        combined = combined.contiguous()
+        return DotSoftmaxLossFn.apply(combined, combined[:graph.num_items], userIds.long().contiguous(), itemIds.long().contiguous(), scale)
 
     def _readout(self, combined, itemIds, userIds, ordered):
         """gnn_ncf.py:354-365 on the HIP blocks: cat(item, user) rows -> MLP, or their dot product.  ``ordered`` (the LightGAT step):

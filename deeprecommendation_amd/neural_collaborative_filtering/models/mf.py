@@ -54,3 +54,18 @@ class MF(_ScoringMixin, NCF):
         u = native.linear(X_user.float().contiguous(), self._dense_weight("user", ue, cache), ue.bias.detach())
         i = native.linear(X_item.float().contiguous(), self._dense_weight("item", ie, cache), ie.bias.detach())
         return native.gather_dot(u, None, i, None, B=u.shape[0])
+
+    def softmax_loss(self, users, items, scale: float = 1.0):
+        """Per-row softmax cross-entropy of each positive (users[b], items[b]) over the WHOLE catalogue:
+        ``logsumexp_j(scale * <u_b, q_j>) - scale * <u_b, q_items[b]>``, (B,) fp32, with autograd — ``DotSoftmaxLossFn``, which never
+        builds the B x num_items logits.  The tables are the embedding Linears on one-hot ids, ``weight.t() + bias``.  When both
+        weights are marked by optim.RowSparseAdam the user rows come from GatherColumnsFn, whose backward hands (ids, gradient
+        rows) to the optimiser; the item table's gradient is dense either way (every item is in every denominator)."""
+        from ...autograd import DotSoftmaxLossFn, GatherColumnsFn
+        require_gpu(users, items)
+        ue, ie = self.user_embeddings[0], self.item_embeddings[0]
+        users, items = users.long().contiguous(), items.long().contiguous()
+        item_table = ie.weight.t() + ie.bias
+        if getattr(ue.weight, "_ncf_row_grads", None) is not None and getattr(ie.weight, "_ncf_row_grads", None) is not None:
+            return DotSoftmaxLossFn.apply(GatherColumnsFn.apply(ue.weight, ue.bias, users), item_table, None, items, scale)
+        return DotSoftmaxLossFn.apply(ue.weight.t() + ue.bias, item_table, users, items, scale)

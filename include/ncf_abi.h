@@ -1307,6 +1307,43 @@ int ncf_ranking_plan(int entry, int64_t rows, int64_t cols, int k_or_max_targets
                      int64_t* chunk_rows);
 
 /* ------------------------------------------------------------------------------------------------
+ * Full-catalogue softmax cross-entropy for a dot-product readout, without a rows x cols matrix (csrc/dot_softmax.hip; fp32 only).
+ * Operands as ncf_dot_topk: listed row b is dev_tabA[dev_idxA[b]] (dev_tabA[b] with dev_idxA NULL), catalogue column j is
+ * dev_tabB[dev_idxB[j]] (dev_tabB[j] with dev_idxB NULL), D = 1 .. 256, rows <= 65536, cols <= 2^24.
+ *   s_bj = <row b, column j>   bit-identical to ncf_gather_dot's fp32 kernel for that pair
+ *   z_bj = s_bj * scale        one rounded fp32 product; scale finite and > 0
+ * ncf_dot_lse:  dev_lse[b] = m_b + log sum_j exp(z_bj - m_b), m_b = max_j z_bj (exact; written to dev_max when it is not NULL).
+ *   The loss of row b with target column t is dev_lse[b] - z_bt.
+ * ncf_dot_softmax_grad:  with w_bj = g_b * scale * (exp(z_bj - lse_b) - [j == t_b]), g_b the upstream gradient of row b's loss,
+ *   items == 0:  dev_out (rows, D) contiguous, row b = sum_j w_bj * column j      (one row per LISTED row: repeated ids stay apart)
+ *   items != 0:  dev_out (cols, D) contiguous, row j = sum_b w_bj * row b
+ *   dev_targets (rows) int64 columns in [0, cols), dev_lse / dev_g (rows) fp32.
+ * Determinism: no float atomics; a walk that is split into tiles is merged in ascending tile order, so two calls on the same
+ * inputs give the same bits.  exp / log are the device library's: results are held to float64 at a tolerance, not bit for bit.
+ * Out-of-range ids: an id of dev_idxA / dev_idxB outside its table, or a target outside [0, cols), sets *dev_oob_flag; such a
+ * listed row gets a zero gradient row and adds nothing to the columns' (its lse is that of a zero row), such a column is in no
+ * denominator and gets a zero gradient row.  Nothing is read or written out of bounds.
+ * Workspace (16-byte aligned, >= the query; never grows with rows x cols): ncf_dot_lse keeps 8 bytes per (row, column tile);
+ * ncf_dot_softmax_grad keeps tiles x chunk_rows x D floats only when its walk is split (<= 32 MiB, rows taken in chunks).
+ * ncf_dot_softmax_plan answers, without launching, the walk tile, the number of tiles and the rows per chunk of
+ * kind = NCF_DOT_SOFTMAX_LSE / _GRAD_ROWS (items == 0) / _GRAD_ITEMS (items != 0); any output pointer may be NULL.
+ * Refusals: NCF_EUNSUPPORTED for D, rows or cols outside the ranges; NCF_EINVAL for a NULL argument, a leading dimension < D,
+ * rows > rowsA without dev_idxA (cols > rowsB without dev_idxB), a scale that is not finite and > 0, an unknown kind;
+ * NCF_EWORKSPACE for a short workspace.  rows == 0 returns NCF_OK and launches nothing.
+ * ------------------------------------------------------------------------------------------------ */
+enum ncf_dot_softmax_kind { NCF_DOT_SOFTMAX_LSE = 0, NCF_DOT_SOFTMAX_GRAD_ROWS = 1, NCF_DOT_SOFTMAX_GRAD_ITEMS = 2 };
+int ncf_dot_softmax_plan(int kind, int64_t rows, int64_t cols, int D, int64_t* tile, int64_t* tiles, int64_t* chunk_rows);
+size_t ncf_dot_lse_workspace_bytes(int64_t rows, int64_t cols, int D);
+int ncf_dot_lse(const float* dev_tabA, int64_t rowsA, int64_t ldA, const float* dev_tabB, int64_t rowsB, int64_t ldB,
+                const int64_t* dev_idxA, const int64_t* dev_idxB, int64_t rows, int64_t cols, int D, float scale, float* dev_lse,
+                float* dev_max, void* dev_workspace, size_t workspace_bytes, int32_t* dev_oob_flag, ncf_stream_t stream);
+size_t ncf_dot_softmax_grad_workspace_bytes(int64_t rows, int64_t cols, int D, int items);
+int ncf_dot_softmax_grad(const float* dev_tabA, int64_t rowsA, int64_t ldA, const float* dev_tabB, int64_t rowsB, int64_t ldB,
+                         const int64_t* dev_idxA, const int64_t* dev_idxB, int64_t rows, int64_t cols, int D,
+                         const int64_t* dev_targets, const float* dev_lse, const float* dev_g, float scale, int items, float* dev_out,
+                         void* dev_workspace, size_t workspace_bytes, int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Calibration probe — the bf16 MFMA rate the chip SUSTAINS on random operands (it lowers its clock under matrix load), so that
  * bench.py can state a kernel's fraction of it next to the fraction of the 2.5 PFLOP/s datasheet figure.  Not part of scoring.
  * Launches `blocks` 512-thread workgroups; every wave issues iters * 32 v_mfma_f32_16x16x32_bf16 (16 384 flop each) on register

@@ -1,12 +1,15 @@
-"""Implicit-feedback MF and BasicNCF beside the ImplicitALS baseline, all three under one evaluation, on the device.
+"""Implicit-feedback MF (sampled loss and full-catalogue softmax) and BasicNCF beside the ImplicitALS baseline, all under one
+evaluation, on the device.
 
     python tools/implicit_neural.py RATINGS [--min-rating 0] [--negatives 4] [--loss bce] [--epochs 20] [--batch-size 65536]
                                             [--lr 0.001] [--factors 64] [--candidates 99] [--als-iters 15] [--seed 0]
+                                            [--softmax-scale 1.0]
 
 RATINGS is a sample file (CSV with userId, movieId, rating and, optionally, timestamp columns; ``.csv`` may be left off).  Every
 rating of at least ``--min-rating`` is an interaction.  ``leave_one_out`` holds out one item per user (the latest with a timestamp
 column, a seeded pick without), the rest trains: MF and BasicNCF by ``fit_implicit`` (``--negatives`` unseen items per positive, redrawn
-every epoch on the device), ImplicitALS by its own solver on the same pairs with value 1.  Each model is then reported twice: by
+every epoch on the device), a second MF by ``fit_implicit(loss="softmax")`` (each positive against the whole catalogue, no
+negatives; ``--softmax-scale`` multiplies the logits), ImplicitALS by its own solver on the same pairs with value 1.  Each model is then reported twice: by
 ``eval_sampled`` (the held-out item among ``--candidates`` sampled unseen items, the same lists for every model) and by
 ``eval_full_ranking`` (the held-out item against the whole catalogue, the training items left out)."""
 import argparse
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--candidates", type=int, default=99)
     ap.add_argument("--als-iters", type=int, default=15)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--softmax-scale", type=float, default=1.0)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     path = args.ratings if os.path.exists(args.ratings) else args.ratings + ".csv"
@@ -68,11 +72,13 @@ def main():
     torch.manual_seed(args.seed)
     F = args.factors
     for name, model in (("MF", MF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F)),
-                        ("BasicNCF", BasicNCF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F, mlp_dense_layers=[2 * F, F]))):
+                        ("BasicNCF", BasicNCF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F, mlp_dense_layers=[2 * F, F])),
+                        ("MF softmax", MF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F))):
         def on_epoch(epoch, m, name=name):
             print(f"{name} epoch {epoch + 1}: sampled HR@10 {eval_sampled(m, users, held, candidates)['hr@10']:.4f}", flush=True)
-        hist = fit_implicit(model, data, negatives=args.negatives, loss=args.loss, epochs=args.epochs, batch_size=args.batch_size,
-                            lr=args.lr, seed=args.seed, on_epoch=on_epoch)
+        loss = "softmax" if name == "MF softmax" else args.loss
+        hist = fit_implicit(model, data, negatives=args.negatives, loss=loss, epochs=args.epochs, batch_size=args.batch_size,
+                            lr=args.lr, seed=args.seed, on_epoch=on_epoch, scale=args.softmax_scale)
         print(f"{name}: train loss {hist['train_loss'][0]:.4f} -> {hist['train_loss'][-1]:.4f}")
         report(name, model)
     als = ImplicitALS(n_factors=F, n_iters=args.als_iters)
