@@ -15,7 +15,12 @@ neighbours a user rated (csrc/knn.hip, THE CONTRACT in include/ncf_abi.h).  Its 
 implicit's AlternatingLeastSquares; the iALS of Rendle et al. 2021): every stored entry is a preference of 1 held with confidence
 1 + alpha * value, every other pair a preference of 0 with confidence 1, and the two factor tables are solved in turn, each row by
 one Cholesky factorisation on the device (csrc/als.hip, THE CONTRACT in include/ncf_abi.h).  A new user is folded in exactly, by one
-such solve against the fixed item table."""
+such solve against the fixed item table.
+
+``EASE`` is the closed-form item-item baseline that most often wins that comparison (Steck 2019, "Embarrassingly Shallow Autoencoders
+for Sparse Data"): W = the off-diagonal of (X^T X + reg 1)^-1 with every column divided by minus its diagonal entry, scores X W.  No
+epochs, no seeds, one hyper-parameter; the Gram matrix, its inversion (a blocked Gauss-Jordan elimination whose updates are fp32
+MFMA GEMMs), the weights and the scores all run on the device (csrc/ease.hip, THE CONTRACT in include/ncf_abi.h)."""
 import math
 from types import SimpleNamespace
 from typing import Optional, Sequence
@@ -79,7 +84,7 @@ def _mf_of_tables(user_table, item_table):
 
 
 class _Baseline:
-    """The fit front end of the three baselines: the checks of the samples or of the CSR a fit is given, and fit_dataset.  Every
+    """The fit front end of the baselines: the checks of the samples or of the CSR a fit is given, and fit_dataset.  Every
     message names the concrete class."""
 
     def _samples(self, user_pos, item_pos, rating, num_users, num_items):
@@ -535,3 +540,105 @@ class ImplicitALS(_Baseline):
         exclude = recommend.rated_exclusion(SimpleNamespace(rowptr=rowptr, col=col), user_rows) if exclude_rated else None
         users = torch.arange(user_rows.numel(), device=vectors.device)
         return recommend.top_k_items(_mf_of_tables(vectors, self.item_factors_), users, k, exclude=exclude, **top_k_args)
+
+
+# ---------------------------------------------------------------------------------------- EASE
+class EASE(_Baseline):
+    """The closed-form item-item autoencoder (csrc/ease.hip, THE CONTRACT in include/ncf_abi.h): ``weights_`` = W with
+    ``W[i][j] = -P[i][j] / P[j][j]`` off the diagonal and 0 on it, ``P = (X^T X + reg 1)^-1``, and scores ``X W``.  ``binary`` fits on
+    1.0 for every stored entry.  ``fit`` / ``fit_dataset`` / ``fit_csr`` (with ``at_regs``: one model per reg from one Gram matrix);
+    then ``scores``, ``predict``, ``similar_items``; ``recommend.ease_top_k`` / ``ease_ranks`` rank with it.  A fit is a fixed
+    function of its inputs, bit for bit.  There is no host path."""
+
+    def __init__(self, reg=500.0, binary=False):
+        who = "EASE"
+        self.reg = _finite(who, reg, "reg", 0.0)
+        if not self.reg > 0:
+            raise ValueError(f"{who}: reg = {reg} is not > 0")
+        if not isinstance(binary, (bool, np.bool_)):
+            raise ValueError(f"{who}: binary = {binary!r} is not a bool")
+        self.binary = bool(binary)
+        self.weights_ = None                                # (I, I) fp32
+        self.num_items_ = None
+
+    # ------------------------------------------------------------------ fit
+    def fit_csr(self, rowptr, col, val, num_items, block_bytes: int = 256 << 20, at_regs: Optional[Sequence[float]] = None):
+        """Fits on a user CSR on the GPU: ``rowptr`` (U + 1) int64, ``col`` int32 item positions strictly ascending inside a row,
+        ``val`` fp32 (SparseRatings' arrays as they are).  The Gram rows are computed ``block_bytes`` at a time, which changes no
+        bit.  With ``at_regs`` the Gram matrix is computed once and a list of fitted models is returned, one per reg, each with the
+        bits of its own fit; otherwise this model is fitted and returned.  Synchronises once, in check()."""
+        regs = None if at_regs is None else [EASE(reg=r, binary=self.binary).reg for r in at_regs]
+        rowptr, col, val, I, dev = self._csr(rowptr, col, val, num_items)
+        if I > native.EASE_MAX_ITEMS:
+            raise ValueError(f"EASE: {I} items (at most {native.EASE_MAX_ITEMS})")
+        if self.binary:
+            val = torch.ones_like(val)
+        colptr, row, tval = build_transpose(rowptr, col, val, I)
+        G = torch.empty((I, I), dtype=torch.float32, device=dev)
+        rows = max(1, int(block_bytes) // (4 * I))
+        for i0 in range(0, I, rows):
+            i1 = min(I, i0 + rows)
+            native.ease_gram(rowptr, col, val, colptr, row, tval, (i0, i1), out=G[i0:i1])
+        if regs is None:
+            self._finish(G, I)
+            return self
+        models = []
+        for k, reg in enumerate(regs):
+            m = EASE(reg=reg, binary=self.binary)
+            m._finish(G.clone() if k + 1 < len(regs) else G, I)
+            models.append(m)
+        return models
+
+    def _finish(self, G, I):
+        """G -> weights_, in place, and the check."""
+        self.weights_, self.num_items_ = native.ease_weights(native.ease_invert(G, self.reg)), I
+        self.check()
+
+    def fit(self, user_pos, item_pos, rating, num_users, num_items, **fit_args):
+        """Fits on int64 positions and fp32 ratings that live on the GPU (KernelMF.fit's arguments): the CSR is built on the device by
+        a stable sort on (user, item).  A (user, item) pair given twice raises in check()."""
+        _, num_users, num_items, _ = self._samples(user_pos, item_pos, rating, num_users, num_items)
+        rowptr, col, val = build_csr(user_pos, item_pos, rating, num_users, num_items)
+        return self.fit_csr(rowptr, col, val, num_items, **fit_args)
+
+    def check(self):
+        """Synchronises.  Raises ValueError when a fit walked a row whose columns do not strictly ascend or met a pivot that is not
+        positive and finite (the weights are then zeros), and IndexError when a kernel of this device met an id outside its range;
+        each raises once and is then cleared."""
+        self._fitted()
+        dev = self.weights_.device
+        native.check_ease(dev)
+        native.check_oob(dev)
+
+    def _fitted(self):
+        if self.weights_ is None:
+            raise RuntimeError("EASE: not fitted")
+
+    # ------------------------------------------------------------------ scoring
+    def _ratings(self, who, ratings):
+        rowptr, col, val = _ratings_csr(who, ratings)
+        return rowptr, col, (torch.ones_like(val) if self.binary else val)
+
+    def scores(self, ratings, user_rows, item_range=None, stage_cap: int = 0):
+        """(B, i1 - i0) fp32 scores of the rows ``user_rows`` (int64) of ``ratings`` — a SparseRatings or a (rowptr, col, val) tuple
+        over the fitted items, not necessarily the fitted ratings, so new users work — against the items ``item_range`` = (i0, i1)
+        (default: all).  A ``binary`` model reads every stored entry as 1.0."""
+        self._fitted()
+        rowptr, col, val = self._ratings("EASE.scores", ratings)
+        return native.ease_scores(rowptr, col, val, user_rows.contiguous() if torch.is_tensor(user_rows) else user_rows, self.weights_,
+                                  item_range, stage_cap)
+
+    def predict(self, ratings, user_rows, item_pos):
+        """(n,) fp32 scores of the pairs (row ``user_rows[k]`` of ``ratings``, item ``item_pos[k]``), int64 both: ``scores``' values bit
+        for bit."""
+        self._fitted()
+        rowptr, col, val = self._ratings("EASE.predict", ratings)
+        return native.ease_predict(rowptr, col, val, user_rows, item_pos, self.weights_)
+
+    def similar_items(self, item_pos, k: int):
+        """"More like this": ``(scores (n, k) fp32, item_positions (n, k) int64, counts (n,) int32)`` — the ``k`` largest entries of
+        the listed rows of ``weights_``, in ``top_k_items``' form and order (native.topk_rows)."""
+        self._fitted()
+        _positions("EASE.similar_items", item_pos, "item_pos")
+        s, idx, cnt = native.topk_rows(self.weights_.index_select(0, item_pos), k)
+        return s, idx.to(torch.int64), cnt

@@ -16,6 +16,7 @@
 // (include/ncf_abi.h) is rounded on its own.  The pragma below says the same to a build that forgets the flag.  hipcc's default fp32
 // division and square root are correctly rounded and are relied on; no fast-math flag may be added to this file.
 #include "ncf_common.h"
+#include "gram_walk.h"
 
 #include <math.h>
 
@@ -24,22 +25,11 @@
 #define NCF_KNN_MAX_N 256
 #define NCF_KNN_DEFAULT_TILE 2048         // columns per tile: 8 bytes of LDS each (16 KiB per one-wave workgroup)
 #define NCF_KNN_MAX_TILE 8192             // 64 KiB
-#define NCF_KNN_SCAN_MAX 128              // a row of at most this many entries is walked whole (two steps); a longer one from a binary search
 #define NCF_KNN_DEFAULT_STAGE 2048        // entries of a user's row staged in LDS by ncf_knn_scores (8 bytes each)
 #define NCF_KNN_MAX_STAGE 8192
 #define NCF_KNN_SCORE_THREADS 256
 
 namespace ncf {
-
-// [beg, end) of row r of a CSR with nnz entries; an empty range and the out-of-range flag for a pair outside the entries
-__device__ __forceinline__ void knn_range(const int64_t* __restrict__ ptr, int64_t r, int64_t nnz, int32_t* oob, int64_t& beg, int64_t& end) {
-    beg = ptr[r];
-    end = ptr[r + 1];
-    if (beg < 0 || end > nnz || end < beg) {
-        if (oob) atomicOr(oob, 1);
-        beg = end = 0;
-    }
-}
 
 // sq[i] of the contract: one wave per item
 __global__ __launch_bounds__(64) void knn_item_sq_kernel(const int64_t* __restrict__ colptr, const float* __restrict__ tval, int64_t nnz,
@@ -47,7 +37,7 @@ __global__ __launch_bounds__(64) void knn_item_sq_kernel(const int64_t* __restri
     const int lane = threadIdx.x;
     for (int64_t i = blockIdx.x; i < I; i += gridDim.x) {
         int64_t beg, end;
-        knn_range(colptr, i, nnz, lane == 0 ? oob : nullptr, beg, end);
+        csr_range(colptr, i, nnz, lane == 0 ? oob : nullptr, beg, end);
         beg = uniform64(beg);
         end = uniform64(end);
         float part = 0.0f;
@@ -81,66 +71,7 @@ __global__ __launch_bounds__(64) void knn_sim_rows_kernel(
     const int64_t t0 = (int64_t)tile * T;
     const int64_t t1 = t0 + T < I ? t0 + T : I;
     const int tl = (int)(t1 - t0);
-    for (int j = lane; j < tl; j += 64) {
-        dot[j] = 0.0f;
-        co[j] = 0;
-    }
-    __syncthreads();
-    int64_t cb, ce;
-    knn_range(colptr, i, nnzT, lane == 0 ? oob : nullptr, cb, ce);
-    cb = uniform64(cb);
-    ce = uniform64(ce);
-    for (int64_t p0 = cb; p0 < ce; p0 += 64) {
-        const int nb = (int)(ce - p0 < 64 ? ce - p0 : 64);
-        int uv = -1;
-        float wv = 0.f;
-        bool ok = false;
-        if (lane < nb) {
-            uv = row[p0 + lane];
-            wv = tval[p0 + lane];
-            ok = uv >= 0 && (int64_t)uv < U;
-            if (!ok && oob) atomicOr(oob, 1);
-        }
-        const uint64_t live = __ballot(ok);
-        for (int g = 0; g < nb; ++g) {
-            if (!((live >> g) & 1)) continue;              // nothing is read through a flagged user
-            const int u = __builtin_amdgcn_readlane(uv, g);
-            const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wv), g));
-            int64_t rb, re;
-            knn_range(rowptr, u, nnz, lane == 0 ? oob : nullptr, rb, re);
-            rb = uniform64(rb);
-            re = uniform64(re);
-            const bool whole = tile == 0 || re - rb <= NCF_KNN_SCAN_MAX;   // tile 0 walks every row whole: it holds the order check
-            int64_t e0 = rb;
-            if (!whole) {                                  // the first entry with col >= t0 (indices stay inside [rb, re) whatever the row holds)
-                int64_t lo = rb, hi = re;
-                while (lo < hi) {
-                    const int64_t mid = lo + ((hi - lo) >> 1);
-                    if ((int64_t)col[mid] < t0) lo = mid + 1; else hi = mid;
-                }
-                e0 = uniform64(lo);
-            }
-            for (; e0 < re; e0 += 64) {
-                const int64_t e = e0 + lane;
-                bool past = false;
-                if (e < re) {
-                    const int c = col[e];
-                    if (tile == 0 && e > rb && col[e - 1] >= c && order) atomicOr(order, 1);
-                    if (c < 0 || (int64_t)c >= I) {
-                        if (oob) atomicOr(oob, 1);
-                    } else if ((int64_t)c >= t0 && (int64_t)c < t1) {
-                        const int j = (int)((int64_t)c - t0);
-                        const float t = w * val[e];
-                        dot[j] = dot[j] + t;
-                        co[j] = co[j] + 1;
-                    }
-                    past = (int64_t)c >= t1;
-                }
-                if (!whole && __ballot(past)) break;       // an ascending row has nothing of this tile further on
-            }
-            __syncthreads();                               // this user's LDS writes before the next user's reads
-        }
-    }
+    gram_row_walk<true>(rowptr, col, val, nnz, U, colptr, row, tval, nnzT, I, i, tile, t0, t1, dot, co, oob, order);   // gram_walk.h
     const float sqi = sq[i];
     const float ri = sqrtf(sqi);
     float* orow = out + (int64_t)blockIdx.y * ldo;
@@ -208,7 +139,7 @@ __global__ __launch_bounds__(NCF_KNN_SCORE_THREADS) void knn_scores_kernel(
     if (u < 0 || u >= R) {                                 // nothing is read through this row: it scores as an empty one
         if (oob && threadIdx.x == 0) atomicOr(oob, 1);
     } else {
-        knn_range(rowptr, u, nnz, threadIdx.x == 0 ? oob : nullptr, rb, re);
+        csr_range(rowptr, u, nnz, threadIdx.x == 0 ? oob : nullptr, rb, re);
     }
     if (re - rb > 0x7fffffff) re = rb + 0x7fffffff;
     const int n = (int)(re - rb);
@@ -244,7 +175,7 @@ __global__ __launch_bounds__(256) void knn_predict_kernel(
         if (oob) atomicOr(oob, 1);
     } else {
         int64_t rb, re;
-        knn_range(rowptr, u, nnz, oob, rb, re);
+        csr_range(rowptr, u, nnz, oob, rb, re);
         if (re - rb > 0x7fffffff) re = rb + 0x7fffffff;
         r = knn_score_one(col + rb, val + rb, (int)(re - rb), nb_pos, nb_sim, nb_cnt, I, N, i, weighted, fill, oob);
     }

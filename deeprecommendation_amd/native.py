@@ -159,6 +159,14 @@ SIGNATURES = {
     "ncf_als_gram": (_c_int, [_c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_size, _c_p]),
     "ncf_als_solve_rows": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_p, ctypes.c_float,
                                     ctypes.c_float, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p]),
+    "ncf_ease_gram": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p,
+                               _c_p]),
+    "ncf_ease_invert_workspace_bytes": (_c_size, [_c_i64]),
+    "ncf_ease_invert": (_c_int, [_c_p, _c_i64, _c_i64, ctypes.c_float, _c_p, _c_size, _c_p, _c_p]),
+    "ncf_ease_weights": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p]),
+    "ncf_ease_scores": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_p, _c_i64,
+                                 _c_p, _c_p]),
+    "ncf_ease_predict": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
     "ncf_mmr_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "ncf_mmr_rerank": (_c_int, [_c_p, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, ctypes.c_float, _c_int, _c_p, _c_p,
                                 _c_p, _c_p, _c_p]),
@@ -423,6 +431,7 @@ def _flag(kind, device) -> torch.Tensor:
 
 KMF_FLAG_ID, KMF_FLAG_BLOCK, KMF_FLAG_PTR = 1, 2, 4                                             # csrc/kmf.hip
 ALS_FLAG_COL, ALS_FLAG_PTR, ALS_FLAG_ORDER, ALS_FLAG_VAL, ALS_FLAG_PIVOT = 1, 2, 4, 8, 16       # include/ncf_abi.h NCF_ALS_*
+EASE_FLAG_ORDER, EASE_FLAG_PIVOT = 1, 2                                                         # include/ncf_abi.h NCF_EASE_FLAG_*
 UNSEEN_FLAG_PICK, UNSEEN_FLAG_FEW = 1, 256                                                      # include/ncf_abi.h NCF_UNSEEN_FLAG_*
 
 # kind -> (model, [(bit, what a kernel met, what check_* raises for it)]).  ncf_knn_sim_rows' word has one meaning whatever its value.
@@ -442,6 +451,11 @@ _UNSEEN_FLAG_BITS = ("sample_unseen", [(UNSEEN_FLAG_PICK, "a pick outside the us
                                        (UNSEEN_FLAG_FEW, "a user has fewer unseen items than the draws asked for", ValueError)])
 
 
+# and so does EASE's word
+_EASE_FLAG_BITS = ("EASE", [(EASE_FLAG_ORDER, "a row of the ratings CSR does not hold strictly ascending columns", ValueError),
+                            (EASE_FLAG_PIVOT, "a pivot of the inversion that is not positive and finite", ValueError)])
+
+
 def _check_flag(kind, device, flag=None):
     """Synchronising check of ``kind``'s flag word on ``device`` (``flag``: another word): when it is not zero, clears it and raises
     with the text of every set bit and, where the word has more than one meaning, its value — IndexError when an id or a pointer was at fault, else ValueError, as
@@ -450,7 +464,7 @@ def _check_flag(kind, device, flag=None):
     bits = int(f.item())
     if bits:
         f.zero_()
-        model, table = _UNSEEN_FLAG_BITS if kind == "unseen" else _FLAG_BITS[kind]
+        model, table = _UNSEEN_FLAG_BITS if kind == "unseen" else _EASE_FLAG_BITS if kind == "ease" else _FLAG_BITS[kind]
         hit = [(text, exc) for bit, text, exc in table if bits & bit]
         exc = IndexError if any(e is IndexError for _, e in hit) else table[-1][2]
         raise exc(f"{model}: " + ", ".join(text for text, _ in hit) + (f" (flag {bits})" if len(table) > 1 else ""))
@@ -1794,6 +1808,136 @@ def knn_predict(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, user
     if n:
         _check(lib.ncf_knn_predict(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(users), _ptr(items), n, _ptr(nb_pos), _ptr(nb_sim),
                                    _ptr(nb_cnt), I, N, 1 if weighted_average else 0, fill, _ptr(out), _ptr(_oob_flag(dev)), _stream(rowptr)))
+    return out
+
+
+EASE_BLOCK, EASE_MAX_ITEMS, EASE_MAX_ROWS, EASE_MAX_STAGE = 128, 65535, 65535, 8192       # include/ncf_abi.h NCF_EASE_BLOCK, csrc/ease.hip
+
+
+def ease_flag(device) -> torch.Tensor:
+    """The sticky int32 flag word of the EASE kernels on ``device`` (bits EASE_FLAG_*)."""
+    return _flag("ease", device)
+
+
+def check_ease(device, flag: Optional[torch.Tensor] = None):
+    """Synchronising check of the EASE flag word: raises ValueError, and clears it, when ncf_ease_gram walked a row of the user CSR
+    whose columns do not strictly ascend or ncf_ease_invert met a pivot that is not positive and finite (its output is zeros)."""
+    _check_flag("ease", device, flag)
+
+
+def _ease_matrix(who, M, what, square=True):
+    """A 2-D float32 matrix with unit inner stride, square unless told otherwise, at most EASE_MAX_ITEMS wide; returns (rows, ld)."""
+    _table_f32(who, M, what, 0)
+    if square and M.shape[0] != M.shape[1]:
+        raise ValueError(f"{who}: {what} must be square, got {tuple(M.shape)}")
+    if M.shape[1] > EASE_MAX_ITEMS:
+        raise ValueError(f"{who}: {M.shape[1]} items (at most {EASE_MAX_ITEMS})")
+    return M.shape[0], max(M.stride(0), M.shape[1]) if M.shape[0] > 1 else M.shape[1]
+
+
+def ease_gram(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, colptr: torch.Tensor, row: torch.Tensor, tval: torch.Tensor,
+              item_range=None, out: Optional[torch.Tensor] = None, flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The rows ``item_range`` = (i0, i1) (default: all) of the Gram matrix X^T X as a dense (i1 - i0, I) fp32 tensor (ncf_ease_gram,
+    THE CONTRACT in include/ncf_abi.h): knn_sim_rows' arguments and walk, no float atomics, one fixed order, G == G^T bit for bit.  An
+    id outside its range raises at the next check_oob(), a non-ascending row at check_ease() (``flag``: another word than the
+    device's).  Checked before the device is; one launch on the current stream."""
+    who = "ease_gram"
+    U, nnz = _csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    I, nnzT = _csr(who, colptr, row, tval, ("colptr", "row", "tval"))
+    if I > EASE_MAX_ITEMS:
+        raise ValueError(f"{who}: {I} items (at most {EASE_MAX_ITEMS})")
+    i0, i1 = _knn_range(who, item_range, I)
+    _out1d(who, flag, "flag", torch.int32, 1)
+    out = _out2d(who, out, i1 - i0, I, rowptr, ((rowptr, "rowptr"), (col, "col"), (val, "val"), (colptr, "colptr"), (row, "row"), (tval, "tval"),
+                                                (flag, "flag")))
+    lib = load_library()
+    dev = rowptr.device
+    if flag is None:
+        flag = ease_flag(dev)
+    if i1 > i0 and I:
+        _check(lib.ncf_ease_gram(_ptr(rowptr), _ptr(col), _ptr(val), nnz, U, _ptr(colptr), _ptr(row), _ptr(tval), nnzT, I, i0, i1, _ptr(out),
+                                 max(out.stride(0), I), _ptr(_oob_flag(dev)), _ptr(flag), _stream(rowptr)))
+    return out
+
+
+def ease_invert(A: torch.Tensor, lam: float, flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adds ``lam`` to the diagonal of the square fp32 matrix ``A`` (unit inner stride, any row stride) and replaces it IN PLACE by its
+    inverse (ncf_ease_invert, THE CONTRACT in include/ncf_abi.h): blocked Gauss-Jordan without pivoting, panels of EASE_BLOCK, every
+    update a tiled fp32 MFMA GEMM; the same bits on every run.  ``A`` must be symmetric positive semi-definite: a pivot that is not
+    positive and finite gives zeros and raises at check_ease() (``flag``: another word than the device's).  Returns ``A``.  Checked
+    before the device is; 1 + 3 * ceil(N / EASE_BLOCK) launches on the current stream."""
+    who = "ease_invert"
+    N, lda = _ease_matrix(who, A, "A")
+    lam = _finite(who, lam, "lam")
+    if not lam > 0:
+        raise ValueError(f"{who}: lam = {lam} is not > 0")
+    _out1d(who, flag, "flag", torch.int32, 1)
+    _dev_all((A, "A"), (flag, "flag"))
+    lib = load_library()
+    if N:
+        nbytes = int(lib.ncf_ease_invert_workspace_bytes(N))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+        _check(lib.ncf_ease_invert(_ptr(A), N, lda, lam, _ptr(ws), nbytes, _ptr(ease_flag(A.device) if flag is None else flag), _stream(A)))
+    return A
+
+
+def ease_weights(P: torch.Tensor, diag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Replaces the square fp32 matrix ``P`` IN PLACE by the EASE weights W[i][j] = -(P[i][j] / P[j][j]), W[j][j] = +0.0
+    (ncf_ease_weights): the correctly rounded division, bit for bit tests/ease_ref.py.  ``diag`` (N,) fp32 receives P's diagonal.
+    Returns ``P``.  Checked before the device is; two launches on the current stream."""
+    who = "ease_weights"
+    N, ldp = _ease_matrix(who, P, "P")
+    _out1d(who, diag, "diag", torch.float32, N)
+    _dev_all((P, "P"), (diag, "diag"))
+    lib = load_library()
+    if N:
+        if diag is None:
+            diag = torch.empty(N, dtype=torch.float32, device=P.device)
+        _check(lib.ncf_ease_weights(_ptr(P), N, ldp, _ptr(diag), _stream(P)))
+    return P
+
+
+def ease_scores(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, users: torch.Tensor, W: torch.Tensor, item_range=None,
+                stage_cap: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, i1 - i0) fp32 EASE scores s = sum of val_e * W[col_e][j] of the rows ``users`` (int64) of a ratings CSR against the items
+    ``item_range`` (default: all) of the (I, I) fp32 weights ``W`` (ncf_ease_scores, THE CONTRACT in include/ncf_abi.h).  The CSR need
+    not be the fitted one.  ``stage_cap``: rows of at most that many entries are staged in LDS (0 = the default); the bits do not
+    depend on it.  A row outside the CSR scores as an empty one, a column outside the items adds nothing; both raise at the next
+    check_oob().  ``out``: a (B, >= i1 - i0) tensor to write into.  Checked before the device is; one launch on the current stream."""
+    who = "ease_scores"
+    R, nnz = _csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    _vec1d(who, users, "users", torch.int64)
+    B = users.numel()
+    if B > EASE_MAX_ROWS:
+        raise ValueError(f"{who}: {B} users in one call (at most {EASE_MAX_ROWS})")
+    I, ldw = _ease_matrix(who, W, "W")
+    i0, i1 = _knn_range(who, item_range, I)
+    stage_cap = _int_in(who, stage_cap, "stage_cap", 0, EASE_MAX_STAGE)
+    out = _out2d(who, out, B, i1 - i0, rowptr, ((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (W, "W")), wider=True)
+    lib = load_library()
+    if B and i1 > i0:
+        _check(lib.ncf_ease_scores(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(users), B, _ptr(W), I, ldw, i0, i1, stage_cap, _ptr(out),
+                                   max(out.stride(0), i1 - i0), _ptr(_oob_flag(rowptr.device)), _stream(rowptr)))
+    return out
+
+
+def ease_predict(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, users: torch.Tensor, items: torch.Tensor,
+                 W: torch.Tensor) -> torch.Tensor:
+    """(n,) fp32 EASE scores of the pairs (``users[k]`` row of the CSR, ``items[k]``), both int64 (ncf_ease_predict): ease_scores' value
+    of that user and item, bit for bit.  A row or an item outside its range scores 0 and raises at the next check_oob().  Checked
+    before the device is; one launch on the current stream."""
+    who = "ease_predict"
+    R, nnz = _csr(who, rowptr, col, val, ("rowptr", "col", "val"))
+    _vec1d(who, users, "users", torch.int64)
+    n = users.numel()
+    _vec1d(who, items, "items", torch.int64, n)
+    I, ldw = _ease_matrix(who, W, "W")
+    _dev_all((rowptr, "rowptr"), (col, "col"), (val, "val"), (users, "users"), (items, "items"), (W, "W"))
+    lib = load_library()
+    out = torch.empty(n, dtype=torch.float32, device=rowptr.device)
+    if n:
+        _check(lib.ncf_ease_predict(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(users), _ptr(items), n, _ptr(W), I, ldw, _ptr(out),
+                                    _ptr(_oob_flag(rowptr.device)), _stream(rowptr)))
     return out
 
 

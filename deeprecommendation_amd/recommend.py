@@ -9,6 +9,8 @@
                        the reference's content-based baseline: cosine of a user's fixed profile and an item's feature row.
 ``item_knn_top_k`` / ``item_knn_ranks``
                        the neighbourhood baseline: a fitted ``baselines.ItemKNN`` scored over the catalogue (ncf_knn_scores) and ranked.
+``ease_top_k`` / ``ease_ranks``
+                       the closed-form item-item baseline: a fitted ``baselines.EASE`` scored over the catalogue (ncf_ease_scores) and ranked.
 ``diversify_top_k``    greedy MMR re-ranking of the pools those two return (native.mmr_rerank, one launch): relevance traded against the
                        similarity to what is already in the list.  ``item_vectors`` gives a model's own item space for it.
 ``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
@@ -434,6 +436,38 @@ def item_knn_ranks(model, ratings, user_ids: torch.Tensor, targets: Tuple[torch.
     under the ItemKNN scores, with the meaning ``rank_of_items`` gives them (``ranking_metrics`` takes them as they are)."""
     model._fitted()
     return _rank_blocks(_knn_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), targets, exclude)
+
+
+# ---------------------------------------------------------------------------------------- EASE baseline
+def _ease_blocks(model, ratings, user_ids, item_ids, block_bytes):
+    """Yields ``(b0, b1, scores (b1 - b0, I))`` of the listed rows of ``ratings`` under a fitted ``baselines.EASE``: one ncf_ease_scores
+    launch per block of users over the whole catalogue, the ranked list's columns gathered from it."""
+    _position_lists(user_ids=user_ids, item_ids=item_ids)
+    model._fitted()
+    require_gpu(user_ids, item_ids)
+    users = user_ids.contiguous()
+    for b0, b1 in _user_blocks(users.numel(), block_bytes, model.num_items_ * 4, native.EASE_MAX_ROWS):
+        scores = model.scores(ratings, users[b0:b1])
+        yield b0, b1, scores if item_ids is None else scores.index_select(1, item_ids)
+
+
+def ease_top_k(model, ratings, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
+               exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES):
+    """The EASE baseline's recommendations: the ``k`` items with the largest EASE score for each listed user.  model: a fitted
+    ``baselines.EASE``; every other argument and the returned ``(scores (B, k), item_positions (B, k) int64, counts (B,) int32)`` as in
+    ``item_knn_top_k``."""
+    model._fitted()
+    return _select_blocks(_ease_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), k, exclude, item_ids,
+                          user_ids.device)
+
+
+def ease_ranks(model, ratings, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, torch.Tensor],
+               item_ids: Optional[torch.Tensor] = None, exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               block_bytes: int = BLOCK_BYTES):
+    """The ranks twin of ``ease_top_k``: ``(rank (n_targets,) int32, ranked (B,) int32)`` of each listed user's held-out items under
+    the EASE scores, with the meaning ``rank_of_items`` gives them (``ranking_metrics`` takes them as they are)."""
+    model._fitted()
+    return _rank_blocks(_ease_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), targets, exclude)
 
 
 # ---------------------------------------------------------------------------------------- diversified top-K

@@ -976,6 +976,66 @@ int ncf_als_solve_rows(const int64_t* dev_rowptr, const int32_t* dev_col, const 
                        const int64_t* dev_seg_row, int64_t n_slots, float* dev_scratch, int32_t* dev_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * EASE (csrc/ease.hip) — the closed-form item-item baseline (Steck 2019, "Embarrassingly Shallow Autoencoders for Sparse Data"):
+ *       G = X^T X (I x I, X the U x I rating matrix),   P = (G + lambda 1)^-1,
+ *       W[i][j] = -P[i][j] / P[j][j] (i != j),  W[j][j] = 0,       score(u, j) = sum over i of X[u][i] W[i][j].
+ * Replaces: nothing in the reference; a torch composition needs the dense (U, I) matrix, X^T X in no fixed order and
+ * torch.linalg.inv.  Ratings: ItemKNN's user CSR (columns STRICTLY ASCENDING inside a row) and its transpose, as ncf_knn_sim_rows
+ * takes them.  Every dense matrix is fp32 with rows of ld floats, 4-byte aligned, at most 65535 wide.
+ * THE CONTRACT (csrc/ease.hip is built with -ffp-contract=off and without any fast-math flag):
+ *   Gram (ncf_ease_gram), row i:  G[i][j] = +0.0f for every j; then
+ *       for the users u of column i in ascending order, for every entry (j, v_uj) of row u:  G[i][j] = G[i][j] + v_ui * v_uj
+ *     each product and each sum rounded on its own; it is ncf_knn_sim_rows' walk (csrc/gram_walk.h).  Two items share their users in
+ *     one order, so G == G^T bit for bit.
+ *   Inversion (ncf_ease_invert): A[i][i] = A[i][i] + lambda, then A is replaced IN PLACE by its inverse by blocked right-looking
+ *     Gauss-Jordan elimination without pivoting, panels K = [k0, k0 + nb) of nb = NCF_EASE_BLOCK in ascending order:
+ *       D = A[K][K]^-1 by scalar Gauss-Jordan in fp32 (step k: p = a[k][k]; a[k][j] = a[k][j] / p, a[k][k] = 1 / p;
+ *           a[i][k] = -(a[i][k] * (1 / p)); a[i][j] = a[i][j] - a[i][k] * (a[k][j] / p), each operation rounded on its own)
+ *       R = D * E (nb x N), E = the rows K of A with the columns K replaced by the identity
+ *       A[i][j] = A0[i][j] + sum over k of C[i][k] * R[k][j], A0 = A with the rows K and the columns K zeroed, C = -A[:][K] with the
+ *           rows K replaced by the identity — which also leaves R in the rows K, -A[:][K] D in the columns K and D in (K, K)
+ *     Every sum over k of R and of the update is ONE chain acc = fmaf(a_k, b_k, acc) in ascending k from the stated start, on
+ *     v_mfma_f32_32x32x2_f32: no split-K, no float atomics, so the same input gives the same bits on every run.  The result is NOT
+ *     a bit-exact function a host can restate cheaply; tests hold it to the float64 inverse (tests/ease_ref.py).  2 N^3 FLOP.
+ *     A pivot p that is not > 0 or not finite sets bit NCF_EASE_FLAG_PIVOT of the sticky *dev_flag (when non-NULL) and the whole
+ *     output is written as zeros; the kernels reach their end.
+ *   Weights (ncf_ease_weights), IN PLACE:  d[j] = P[j][j] (copied to dev_diag first);  W[i][j] = -(P[i][j] / d[j]) for i != j with
+ *     the correctly rounded division, W[j][j] = +0.0f.
+ *   Score of (user row u, item j) (ncf_ease_scores, ncf_ease_predict):  s = +0.0f; for the row's entries e in stored order:
+ *       s = s + val_e * W[col_e][j],  the product and the sum rounded on their own.
+ * ncf_ease_gram writes the rows [i0, i1) of G into dev_G (i1 - i0, I), rows of ldg floats.  A user, an item or a pointer pair
+ * outside its array sets the sticky *dev_oob_flag (when non-NULL) and adds nothing; a row of the user CSR whose columns do not
+ * strictly ascend sets bit NCF_EASE_FLAG_ORDER of *dev_flag (the result of such a row is unspecified, no address leaves the arrays).
+ * ncf_ease_invert: dev_workspace of ncf_ease_invert_workspace_bytes(N) bytes, 256-byte aligned, is scratch (the panel's D, C and R).
+ * ncf_ease_scores: the listed rows dev_users (B, int64) of ANY ratings CSR of R rows over the same items against the items [i0, i1),
+ * into dev_out (B, i1 - i0) rows of ldo floats.  One workgroup per (user, 1024 columns), lanes own columns; a row of at most
+ * stage_cap entries is staged in LDS first (0: 2048; at most 8192), a longer one is read from global memory, with the same bits.  A
+ * user row outside [0, R) scores as an empty row and sets *dev_oob_flag; a column id outside [0, I) sets it and adds nothing.
+ * ncf_ease_predict: the same device function for n pairs (dev_users[k], dev_items[k]) (int64): predict(u, j) == scores[u, j] bit for
+ * bit.  A pair with a row or an item outside its range scores 0 and sets the flag.
+ * Refusals, before any launch, with the entry's name in ncf_last_error(): NCF_EINVAL for a negative size, an item range outside
+ * [0, I), ld below the width, a lambda that is not finite or not > 0, a stage_cap outside 0 .. 8192, a misaligned array, a NULL array
+ * that the sizes say is read or written, and a workspace that is too small; NCF_EUNSUPPORTED for more than 65535 items, or users in
+ * one ncf_ease_scores call.  A call with nothing to do returns NCF_OK without a launch.
+ * ------------------------------------------------------------------------------------------------ */
+#define NCF_EASE_BLOCK 128
+#define NCF_EASE_FLAG_ORDER 1
+#define NCF_EASE_FLAG_PIVOT 2
+int ncf_ease_gram(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t nnz, int64_t U,
+                  const int64_t* dev_colptr, const int32_t* dev_row, const float* dev_tval, int64_t nnzT, int64_t I, int64_t i0,
+                  int64_t i1, float* dev_G, int64_t ldg, int32_t* dev_oob_flag, int32_t* dev_flag, ncf_stream_t stream);
+size_t ncf_ease_invert_workspace_bytes(int64_t N);
+int ncf_ease_invert(float* dev_A, int64_t N, int64_t lda, float lambda, void* dev_workspace, size_t workspace_bytes, int32_t* dev_flag,
+                    ncf_stream_t stream);
+int ncf_ease_weights(float* dev_P, int64_t N, int64_t ldp, float* dev_diag, ncf_stream_t stream);
+int ncf_ease_scores(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t nnz, int64_t R,
+                    const int64_t* dev_users, int64_t B, const float* dev_W, int64_t I, int64_t ldw, int64_t i0, int64_t i1,
+                    int stage_cap, float* dev_out, int64_t ldo, int32_t* dev_oob_flag, ncf_stream_t stream);
+int ncf_ease_predict(const int64_t* dev_rowptr, const int32_t* dev_col, const float* dev_val, int64_t nnz, int64_t R,
+                     const int64_t* dev_users, const int64_t* dev_items, int64_t n, const float* dev_W, int64_t I, int64_t ldw,
+                     float* dev_out, int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Diversified top-K (csrc/mmr.hip) — greedy Maximal Marginal Relevance (MMR) re-ranking of one candidate pool per user, the pools
  * being what ncf_topk_rows / ncf_dot_topk / ncf_mlp_topk return.  Replaces: nothing in the reference, which stops at the relevance
  * list; a torch composition needs a (B, N, N) Gram tensor and K rounds of masked arg-max launches.
