@@ -38,11 +38,6 @@
 #ifndef NCF_ALS_SMALL_BLOCKS
 #define NCF_ALS_SMALL_BLOCKS 5            // ... and R < 8
 #endif
-#define NCF_ALS_FLAG_COL 1
-#define NCF_ALS_FLAG_PTR 2
-#define NCF_ALS_FLAG_ORDER 4
-#define NCF_ALS_FLAG_VAL 8
-#define NCF_ALS_FLAG_PIVOT 16
 
 namespace ncf {
 

@@ -32,8 +32,6 @@
 
 namespace ncf {
 
-enum { KMF_FLAG_ID = 1, KMF_FLAG_BLOCK = 2, KMF_FLAG_PTR = 4 };
-
 __device__ __forceinline__ float kmf_lane_value(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(64) void kmf_stratum_kernel(
     const int64_t slot = (int64_t)s * W + a;
     int64_t beg = uniform64(block_ptr[slot]), end = uniform64(block_ptr[slot + 1]);
     if (beg < 0 || end > n || end < beg) {                 // a block pointer outside the samples: nothing of the block is read
-        if (flag && lane == 0) atomicOr(flag, KMF_FLAG_PTR);
+        if (flag && lane == 0) atomicOr(flag, NCF_KMF_FLAG_PTR);
         beg = end = 0;
     }
     const int c0 = 4 * lane;
@@ -128,9 +126,9 @@ __global__ __launch_bounds__(64) void kmf_stratum_kernel(
             iv = item[e0 + lane];
             rv = rating[e0 + lane];
             if (!(uv >= 0 && (int64_t)uv < U && iv >= 0 && (int64_t)iv < I)) {
-                if (flag) atomicOr(flag, KMF_FLAG_ID);
+                if (flag) atomicOr(flag, NCF_KMF_FLAG_ID);
             } else if (user_block[uv] != a || item_block[iv] != ib) {
-                if (flag) atomicOr(flag, KMF_FLAG_BLOCK);
+                if (flag) atomicOr(flag, NCF_KMF_FLAG_BLOCK);
             } else {
                 ok = true;
             }
@@ -190,12 +188,12 @@ __global__ __launch_bounds__(64) void kmf_fold_kernel(
     for (int64_t k = blockIdx.x; k < n_users; k += gridDim.x) {
         const int u = __builtin_amdgcn_readfirstlane(users[k]);
         if (!(u >= 0 && (int64_t)u < U)) {                 // nothing is read or written through this id
-            if (flag && lane == 0) atomicOr(flag, KMF_FLAG_ID);
+            if (flag && lane == 0) atomicOr(flag, NCF_KMF_FLAG_ID);
             continue;
         }
         int64_t beg = uniform64(rowptr[k]), end = uniform64(rowptr[k + 1]);
         if (beg < 0 || end > nnz || end < beg) {
-            if (flag && lane == 0) atomicOr(flag, KMF_FLAG_PTR);
+            if (flag && lane == 0) atomicOr(flag, NCF_KMF_FLAG_PTR);
             beg = end = 0;
         }
         float* prow = PU + (int64_t)u * ldu;
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(64) void kmf_fold_kernel(
                     iv = col[e0 + lane];
                     rv = rating[e0 + lane];
                     ok = iv >= 0 && (int64_t)iv < I;
-                    if (!ok && flag) atomicOr(flag, KMF_FLAG_ID);
+                    if (!ok && flag) atomicOr(flag, NCF_KMF_FLAG_ID);
                 }
                 const uint64_t live = __ballot(ok);
                 for (int g = 0; g < nb; ++g) {

@@ -277,10 +277,16 @@ def set_option(name: str, value) -> None:
     _check(lib.ncf_set_option(name.encode(), int(value)))
 
 
+def _query(fn, ins, outs):
+    """A host-only query of the library: calls ``fn(*ins, &cell, ...)`` with one zeroed cell per ctypes type of ``outs``, in order,
+    under _check, and returns the cells' values as a tuple."""
+    cells = [t() for t in outs]
+    _check(fn(*ins, *map(ctypes.byref, cells)))
+    return tuple([c.value for c in cells])
+
+
 def get_option(name: str) -> int:
-    v = ctypes.c_int(0)
-    _check(load_library().ncf_get_option(name.encode(), ctypes.byref(v)))
-    return v.value
+    return _query(load_library().ncf_get_option, (name.encode(),), (_c_int,))[0]
 
 
 def _options_from_environment(lib) -> None:
@@ -417,6 +423,12 @@ def _out2d(who, out, rows, cols, like, swept, contiguous=False, wider=False):
     return torch.empty((rows, cols), dtype=torch.float32, device=like.device) if out is None else out
 
 
+def _workspace(nbytes, device) -> torch.Tensor:
+    """The scratch of one call: ``nbytes`` as the entry's *_workspace_bytes said, and never an empty tensor (whose pointer is null).
+    The C call is told ``nbytes``, not the padded size."""
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
 _flags = {}
 
 
@@ -429,45 +441,47 @@ def _flag(kind, device) -> torch.Tensor:
     return f
 
 
-KMF_FLAG_ID, KMF_FLAG_BLOCK, KMF_FLAG_PTR = 1, 2, 4                                             # csrc/kmf.hip
-ALS_FLAG_COL, ALS_FLAG_PTR, ALS_FLAG_ORDER, ALS_FLAG_VAL, ALS_FLAG_PIVOT = 1, 2, 4, 8, 16       # include/ncf_abi.h NCF_ALS_*
-EASE_FLAG_ORDER, EASE_FLAG_PIVOT = 1, 2                                                         # include/ncf_abi.h NCF_EASE_FLAG_*
-UNSEEN_FLAG_PICK, UNSEEN_FLAG_FEW = 1, 256                                                      # include/ncf_abi.h NCF_UNSEEN_FLAG_*
+# the bits of the flag words with several meanings (include/ncf_abi.h NCF_<name>; tests/test_abi_symbols.py compares them)
+KMF_FLAG_ID, KMF_FLAG_BLOCK, KMF_FLAG_PTR = 1, 2, 4
+ALS_FLAG_COL, ALS_FLAG_PTR, ALS_FLAG_ORDER, ALS_FLAG_VAL, ALS_FLAG_PIVOT = 1, 2, 4, 8, 16
+EASE_FLAG_ORDER, EASE_FLAG_PIVOT = 1, 2
+UNSEEN_FLAG_PICK, UNSEEN_FLAG_FEW = 1, 256
 
-# kind -> (model, [(bit, what a kernel met, what check_* raises for it)]).  ncf_knn_sim_rows' word has one meaning whatever its value.
-_FLAG_BITS = {
+# kind -> (prefix of the message or None, [(bit, what a kernel met, what check_* raises for it)], whether the message ends in the
+# word's value).  A word with one meaning whatever its value has the one row of bit ~0.
+_FLAG_WORDS = {
+    "oob": (None, [(~0, "index out of range in an embedding gather", IndexError)], False),
+    "pair_rows": (None, [(~0, "a pair's rated entries did not fit the capacity pair_rows was given (max_row_len too small)",
+                          OverflowError)], False),
+    "rank_overflow": (None, [(~0, "a row has more targets than the max_targets the rank call was given", OverflowError)], False),
     "kmf": ("KernelMF", [(KMF_FLAG_ID, "an id outside its table", IndexError),
                          (KMF_FLAG_BLOCK, "a sample filed in the wrong block", IndexError),
-                         (KMF_FLAG_PTR, "a block / row pointer outside the samples", IndexError)]),
-    "knn": ("ItemKNN", [(~0, "a row of the ratings CSR does not hold strictly ascending columns", ValueError)]),
+                         (KMF_FLAG_PTR, "a block / row pointer outside the samples", IndexError)], True),
+    "knn": ("ItemKNN", [(~0, "a row of the ratings CSR does not hold strictly ascending columns", ValueError)], False),
     "als": ("ImplicitALS", [(ALS_FLAG_COL, "a column outside the fixed table", IndexError),
                             (ALS_FLAG_PTR, "a row or a row pointer outside the ratings", IndexError),
                             (ALS_FLAG_ORDER, "a row whose columns do not strictly ascend", ValueError),
                             (ALS_FLAG_VAL, "a value that is negative or not finite", ValueError),
-                            (ALS_FLAG_PIVOT, "a pivot that is not positive and finite", ValueError)]),
+                            (ALS_FLAG_PIVOT, "a pivot that is not positive and finite", ValueError)], True),
+    "ease": ("EASE", [(EASE_FLAG_ORDER, "a row of the ratings CSR does not hold strictly ascending columns", ValueError),
+                      (EASE_FLAG_PIVOT, "a pivot of the inversion that is not positive and finite", ValueError)], True),
+    "unseen": ("sample_unseen", [(UNSEEN_FLAG_PICK, "a pick outside the users", IndexError),
+                                 (UNSEEN_FLAG_FEW, "a user has fewer unseen items than the draws asked for", ValueError)], True),
 }
-# ncf_sample_unseen's word goes through the same _check_flag; _FLAG_BITS stays the table of the three baselines
-_UNSEEN_FLAG_BITS = ("sample_unseen", [(UNSEEN_FLAG_PICK, "a pick outside the users", IndexError),
-                                       (UNSEEN_FLAG_FEW, "a user has fewer unseen items than the draws asked for", ValueError)])
-
-
-# and so does EASE's word
-_EASE_FLAG_BITS = ("EASE", [(EASE_FLAG_ORDER, "a row of the ratings CSR does not hold strictly ascending columns", ValueError),
-                            (EASE_FLAG_PIVOT, "a pivot of the inversion that is not positive and finite", ValueError)])
 
 
 def _check_flag(kind, device, flag=None):
     """Synchronising check of ``kind``'s flag word on ``device`` (``flag``: another word): when it is not zero, clears it and raises
-    with the text of every set bit and, where the word has more than one meaning, its value — IndexError when an id or a pointer was at fault, else ValueError, as
-    _FLAG_BITS lists them."""
+    with the text of every set bit and, where _FLAG_WORDS says so, its value — IndexError when an id or a pointer was at fault, else
+    the type of the word's last row."""
     f = _flag(kind, device) if flag is None else flag
     bits = int(f.item())
     if bits:
         f.zero_()
-        model, table = _UNSEEN_FLAG_BITS if kind == "unseen" else _EASE_FLAG_BITS if kind == "ease" else _FLAG_BITS[kind]
-        hit = [(text, exc) for bit, text, exc in table if bits & bit]
-        exc = IndexError if any(e is IndexError for _, e in hit) else table[-1][2]
-        raise exc(f"{model}: " + ", ".join(text for text, _ in hit) + (f" (flag {bits})" if len(table) > 1 else ""))
+        prefix, rows, numbered = _FLAG_WORDS[kind]
+        hit = [(text, exc) for bit, text, exc in rows if bits & bit]
+        exc = IndexError if any(e is IndexError for _, e in hit) else rows[-1][2]
+        raise exc((f"{prefix}: " if prefix else "") + ", ".join(text for text, _ in hit) + (f" (flag {bits})" if numbered else ""))
 
 
 def _oob_flag(device) -> torch.Tensor:
@@ -476,10 +490,7 @@ def _oob_flag(device) -> torch.Tensor:
 
 def check_oob(device):
     """Synchronising check of the sticky out-of-range flag (torch indexing raises IndexError in the reference)."""
-    f = _oob_flag(device)
-    if int(f.item()) != 0:
-        f.zero_()
-        raise IndexError("index out of range in an embedding gather")
+    _check_flag("oob", device)
 
 
 # ------------------------------------------------------------------ K1
@@ -601,7 +612,7 @@ def mlp_forward(x: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequen
     n = len(weights)
     d = _dims_array(dims)
     ws_bytes = lib.ncf_mlp_workspace_bytes(NCF_F32, B, n, d)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     if out is None:
         out = torch.empty((B, dims[-1]), dtype=torch.float32, device=x.device)
     _, _, ldo = _rows2d(out, "out")
@@ -892,6 +903,23 @@ def scale_rows(x: torch.Tensor, divisor: float, out: Optional[torch.Tensor] = No
 
 
 # ------------------------------------------------------------------ K3
+def _attn_operands(mode, pc, pr, w1, csr=None, feat=None, checked=True):
+    """The operands the attention entry points share: ((mode, pc, ldpc, pr, ldpr, A, w1) as the ABI takes them — b1 follows where an
+    entry has one —, the pointers of the CSR triple, (feat, ldf, Fdim), (B, I, A, Fdim)).  ``checked``: the operands must agree and
+    the CSR be (int64, int32, fp32); attn_backward takes what its forward checked."""
+    _dev(pc, "pc")
+    B, A, ldpc = _rows2d(pc, "pc")
+    I, A2, ldpr = _rows2d(pr, "pr")
+    I2, Fdim, ldf = (I, 0, 0) if feat is None else _rows2d(feat, "feat")
+    if checked:
+        if A != A2 or I != I2:
+            raise ValueError("attention operand shapes disagree")
+        if csr is not None and (csr[0].dtype != torch.int64 or csr[1].dtype != torch.int32 or csr[2].dtype != torch.float32):
+            raise TypeError("CSR must be (int64 rowptr, int32 col, fp32 val)")
+    return ((mode, _ptr(pc), ldpc, _ptr(pr), ldpr, A, _ptr(w1)), () if csr is None else (_ptr(csr[0]), _ptr(csr[1]), _ptr(csr[2])),
+            (_ptr(feat), ldf, Fdim), (B, I, A, Fdim))
+
+
 def attn_forward(mode: int, pc: torch.Tensor, pr: torch.Tensor, w1: Optional[torch.Tensor], b1: float,
                  rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, feat: torch.Tensor,
                  out_bias: Optional[torch.Tensor] = None, dropout: Optional[tuple] = None, msg_dropout: Optional[tuple] = None):
@@ -899,30 +927,17 @@ def attn_forward(mode: int, pc: torch.Tensor, pr: torch.Tensor, w1: Optional[tor
     ``msg_dropout`` = (p, seed): the message dropout over the (pair, rated entry) logits (ncf_attn_forward_train; ``b1`` then takes
     part in the reference's ``== 0`` test).  None or p == 0 for it: exactly the calls made without the argument."""
     lib = load_library()
-    _dev(pc, "pc")
-    B, A, ldpc = _rows2d(pc, "pc")
-    I, A2, ldpr = _rows2d(pr, "pr")
-    I2, Fdim, ldf = _rows2d(feat, "feat")
-    if A != A2 or I != I2:
-        raise ValueError("attention operand shapes disagree")
-    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float32:
-        raise TypeError("CSR must be (int64 rowptr, int32 col, fp32 val)")
+    head, csr, ft, (B, I, _, Fdim) = _attn_operands(mode, pc, pr, w1, (rowptr, col, val), feat)
     out = torch.empty((B, Fdim), dtype=torch.float32, device=pc.device)
     wts = torch.empty(max(col.numel(), 1), dtype=torch.float32, device=pc.device)
     if msg_dropout is not None and msg_dropout[0] > 0:
         p, seed = dropout if dropout is not None else (0.0, 0)
-        _check(lib.ncf_attn_forward_train(mode, _ptr(pc), ldpc, _ptr(pr), ldpr, A, _ptr(w1), float(b1), _ptr(rowptr), _ptr(col), _ptr(val),
-                                          B, I, _ptr(feat), ldf, Fdim, _ptr(out_bias), _ptr(out), out.stride(0), _ptr(wts),
-                                          int(seed) & 0xFFFFFFFF, float(p), int(msg_dropout[1]) & 0xFFFFFFFF, float(msg_dropout[0]),
-                                          _stream(pc)))
-        return out, wts[:col.numel()]
-    if dropout is not None and dropout[0] > 0:
-        _check(lib.ncf_attn_forward_dropout(mode, _ptr(pc), ldpc, _ptr(pr), ldpr, A, _ptr(w1), float(b1), _ptr(rowptr), _ptr(col), _ptr(val),
-                                            B, I, _ptr(feat), ldf, Fdim, _ptr(out_bias), _ptr(out), out.stride(0), _ptr(wts),
-                                            int(dropout[1]) & 0xFFFFFFFF, float(dropout[0]), _stream(pc)))
-        return out, wts[:col.numel()]
-    _check(lib.ncf_attn_forward(mode, _ptr(pc), ldpc, _ptr(pr), ldpr, A, _ptr(w1), float(b1), _ptr(rowptr), _ptr(col), _ptr(val),
-                                B, I, _ptr(feat), ldf, Fdim, _ptr(out_bias), _ptr(out), out.stride(0), _ptr(wts), _stream(pc)))
+        fn, draws = lib.ncf_attn_forward_train, (int(seed) & 0xFFFFFFFF, float(p), int(msg_dropout[1]) & 0xFFFFFFFF, float(msg_dropout[0]))
+    elif dropout is not None and dropout[0] > 0:
+        fn, draws = lib.ncf_attn_forward_dropout, (int(dropout[1]) & 0xFFFFFFFF, float(dropout[0]))
+    else:
+        fn, draws = lib.ncf_attn_forward, ()
+    _check(fn(*head, float(b1), *csr, B, I, *ft, _ptr(out_bias), _ptr(out), out.stride(0), _ptr(wts), *draws, _stream(pc)))
     return out, wts[:col.numel()]
 
 
@@ -931,10 +946,7 @@ def attn_backward(mode: int, pc, pr, w1, rowptr, col, val, feat, wts, dout, drop
     """Gradients of attn_forward: (d_pc (B, A), d_pr (I, A), d_w1 (A,) or None, d_feat (I, Fdim)); d b1 is exactly zero.
     ``msg_dropout`` = the forward's (p, seed): only p is used (ncf_attn_backward_train needs no mask)."""
     lib = load_library()
-    _dev(pc, "pc")
-    B, A, ldpc = _rows2d(pc, "pc")
-    I, _, ldpr = _rows2d(pr, "pr")
-    _, Fdim, ldf = _rows2d(feat, "feat")
+    head, csr, ft, (B, I, A, Fdim) = _attn_operands(mode, pc, pr, w1, (rowptr, col, val), feat, checked=False)
     dout = dout.contiguous()
     d_pc = torch.empty((B, A), dtype=torch.float32, device=pc.device)
     d_pr = torch.zeros((I, A), dtype=torch.float32, device=pc.device)
@@ -944,14 +956,11 @@ def attn_backward(mode: int, pc, pr, w1, rowptr, col, val, feat, wts, dout, drop
     scratch = torch.empty(max(col.numel(), 1), dtype=torch.float32, device=pc.device)
     p, seed = (dropout if dropout is not None else (0.0, 0))
     if msg_dropout is not None and msg_dropout[0] > 0:
-        _check(lib.ncf_attn_backward_train(mode, _ptr(pc), ldpc, _ptr(pr), ldpr, A, _ptr(w1), _ptr(rowptr), _ptr(col), _ptr(val), B, I, _ptr(feat),
-                                           ldf, Fdim, _ptr(wts), _ptr(dout), dout.stride(0), _ptr(d_pc), A, _ptr(d_pr), A, _ptr(part),
-                                           _ptr(d_feat), Fdim, _ptr(scratch), int(seed) & 0xFFFFFFFF, float(p), float(msg_dropout[0]),
-                                           _stream(pc)))
+        fn, draws = lib.ncf_attn_backward_train, (float(msg_dropout[0]),)
     else:
-        _check(lib.ncf_attn_backward(mode, _ptr(pc), ldpc, _ptr(pr), ldpr, A, _ptr(w1), _ptr(rowptr), _ptr(col), _ptr(val), B, I, _ptr(feat), ldf, Fdim,
-                                     _ptr(wts), _ptr(dout), dout.stride(0), _ptr(d_pc), A, _ptr(d_pr), A, _ptr(part), _ptr(d_feat), Fdim,
-                                     _ptr(scratch), int(seed) & 0xFFFFFFFF, float(p), _stream(pc)))
+        fn, draws = lib.ncf_attn_backward, ()
+    _check(fn(*head, *csr, B, I, *ft, _ptr(wts), _ptr(dout), dout.stride(0), _ptr(d_pc), A, _ptr(d_pr), A, _ptr(part), _ptr(d_feat), Fdim,
+              _ptr(scratch), int(seed) & 0xFFFFFFFF, float(p), *draws, _stream(pc)))
     return d_pc, d_pr, (colsum(part) if mlp and B > 0 else (torch.zeros(A, device=pc.device) if mlp else None)), d_feat
 
 
@@ -967,12 +976,10 @@ def attn_grouped_plan(mode: int, A: int, Fdim: int, ldfeat: Optional[int] = None
     """(form, kernel MODE, CPB or FO, NW or NPF, LDS bytes, grid_x) of the kernel ncf_attn_forward_grouped runs for the shape under
     the current attn_grouped_kernel option; form by name (ATTN_GROUPED_FORMS): "sc" = attn_grouped_sc_kernel<MODE, CPB, NW>, "lds" =
     attn_grouped_kernel<MODE, FO, NPF>.  Host only: no launch, no device.  Raises NativeError where the launch would refuse."""
-    form, km, a, b = (ctypes.c_int(0) for _ in range(4))
-    lds, gx = ctypes.c_int64(0), ctypes.c_int64(0)
-    _check(load_library().ncf_attn_grouped_plan(int(mode), int(A), int(Fdim), int(Fdim if ldfeat is None else ldfeat), int(pairs_per_wg),
-                                                int(B), int(n_rows), ctypes.byref(form), ctypes.byref(km), ctypes.byref(a),
-                                                ctypes.byref(b), ctypes.byref(lds), ctypes.byref(gx)))
-    return ATTN_GROUPED_FORMS[form.value], km.value, a.value, b.value, lds.value, gx.value
+    form, *rest = _query(load_library().ncf_attn_grouped_plan,
+                         (int(mode), int(A), int(Fdim), int(Fdim if ldfeat is None else ldfeat), int(pairs_per_wg), int(B), int(n_rows)),
+                         (_c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64))
+    return (ATTN_GROUPED_FORMS[form], *rest)
 
 
 def attn_backward_supported(mode: int, A: int, Fdim: int) -> bool:
@@ -1007,7 +1014,7 @@ def group_pairs(pair_row: torch.Tensor, n_rows: int, pairs_per_wg: int):
     # workgroup -> CSR row (the grid bound of the grouped kernels: every non-empty row adds at most one partly filled workgroup)
     wg_row = torch.empty((B + int(pairs_per_wg) - 1) // int(pairs_per_wg) + min(R, B) + 1, dtype=torch.int32, device=dev)
     nbytes = lib.ncf_group_pairs_workspace_bytes(R)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     _check(lib.ncf_group_pairs_rows(_ptr(pair_row), B, R, int(pairs_per_wg), _ptr(grp_ptr), _ptr(pair_ids), _ptr(wg_ptr), _ptr(wg_row),
                                     _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(pair_row)))
     return Grouping(grp_ptr, pair_ids[:B], wg_ptr, wg_row)
@@ -1042,7 +1049,7 @@ def dense_to_csr(user_matrix: torch.Tensor, share_rows: bool = True):
         return torch.zeros(1, dtype=torch.int64, device=dev), col, val, pair_row
     rowptr = torch.empty(B + 1, dtype=torch.int64, device=dev)     # [0, counts...] from the kernels; the cumulative sum runs in place
     nbytes = lib.ncf_dense_csr_workspace_bytes(B)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     _check(lib.ncf_dense_csr_rows(_ptr(user_matrix), ld, B, I, 1 if share_rows else 0, _ptr(pair_row), _ptr(rowptr), _ptr(ws), nbytes, _stream(user_matrix)))
     torch.cumsum(rowptr, 0, out=rowptr)
     _check(lib.ncf_dense_csr_fill(_ptr(user_matrix), ld, B, I, _ptr(rowptr), _ptr(pair_row), _ptr(col), _ptr(val), _stream(user_matrix)))
@@ -1056,10 +1063,7 @@ def _pair_rows_flag(device) -> torch.Tensor:
 
 def check_pair_rows(device):
     """Synchronising check of the sticky flag a pair_rows call sets when a pair's entries did not fit its capacity."""
-    f = _pair_rows_flag(device)
-    if int(f.item()) != 0:
-        f.zero_()
-        raise OverflowError("a pair's rated entries did not fit the capacity pair_rows was given (max_row_len too small)")
+    _check_flag("pair_rows", device)
 
 
 def pair_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, pair_row: torch.Tensor, capacity: int, mask=None,
@@ -1252,8 +1256,8 @@ def attn_candidates(x: torch.Tensor, Wi, bi: Optional[torch.Tensor], Wc: torch.T
         grp = Grouping(grp_ptr, pair_ids[:B], wg_ptr, wg_row)
     if packed:
         nbytes = lib.ncf_attn_candidates_packed_workspace_bytes(B, N1, R if pair_row is not None else -1)
-    if nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if nbytes:                                # without a grouping the LDS-staged form has no scratch and takes a null pointer
+        ws = _workspace(nbytes, dev)
     tail = (_ptr(bi), N1, _ptr(Wc), _ptr(b0), N2, _ptr(emb), emb.stride(0), _ptr(pc), pc.stride(0), _ptr(pair_row), R, int(pairs_per_wg),
             _ptr(grp_ptr), _ptr(pair_ids), _ptr(wg_ptr), _ptr(wg_row), _ptr(ws), nbytes,
             _ptr(_oob_flag(dev)) if pair_row is not None else None, _stream(x))
@@ -1346,14 +1350,7 @@ def attn_forward_grouped(mode: int, pc: torch.Tensor, pr: torch.Tensor, w1: Opti
     for this batch skips the sort.  Where ncf_attn_split_supported() holds (and no weights are asked for) the call takes the
     entry-split form (``nsplit`` slices of each rated set; default from the batch's sizes; 1 = one workgroup per group)."""
     lib = load_library()
-    _dev(pc, "pc")
-    B, A, ldpc = _rows2d(pc, "pc")
-    I, A2, ldpr = _rows2d(pr, "pr")
-    I2, Fdim, ldf = _rows2d(feat, "feat")
-    if A != A2 or I != I2:
-        raise ValueError("attention operand shapes disagree")
-    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float32:
-        raise TypeError("CSR must be (int64 rowptr, int32 col, fp32 val)")
+    head, csr, ft, (B, I, A, Fdim) = _attn_operands(mode, pc, pr, w1, (rowptr, col, val), feat)
     if pair_row.numel() != B:
         raise ValueError("pair_row must name one CSR row per pair")
     R = rowptr.numel() - 1
@@ -1371,10 +1368,9 @@ def attn_forward_grouped(mode: int, pc: torch.Tensor, pr: torch.Tensor, w1: Opti
         # entry-split form (round 3): (group of pairs) x (slice of the rated set) workgroups + a merge of the softmax partials
         ns = int(nsplit) if nsplit is not None else default_attn_nsplit(B, R, col.numel() if nnz_hint is None else int(nnz_hint), int(pairs_per_wg))
         nbytes = lib.ncf_attn_split_workspace_bytes(B, Fdim, ns)
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=pc.device) if ns > 1 else None
-        _check(lib.ncf_attn_forward_split(mode, _ptr(pc), ldpc, _ptr(pr), ldpr, A, _ptr(w1), float(b1), _ptr(rowptr), _ptr(col),
-                                          _ptr(val), R, I, _ptr(grp_ptr), _ptr(pair_ids), _ptr(wg_ptr), _ptr(wg_row), B,
-                                          int(pairs_per_wg), _ptr(feat), ldf, Fdim, _ptr(out_bias), _ptr(out), out.stride(0),
+        ws = _workspace(nbytes, pc.device) if ns > 1 else None
+        _check(lib.ncf_attn_forward_split(*head, float(b1), *csr, R, I, _ptr(grp_ptr), _ptr(pair_ids), _ptr(wg_ptr), _ptr(wg_row), B,
+                                          int(pairs_per_wg), *ft, _ptr(out_bias), _ptr(out), out.stride(0),
                                           ns, 0 if (leave_partials and ns > 1) else 1, _ptr(ws), nbytes, _stream(pc)))
         if leave_partials and ns > 1:
             return AttnPartials(ws, ns, Fdim, B)
@@ -1386,10 +1382,8 @@ def attn_forward_grouped(mode: int, pc: torch.Tensor, pr: torch.Tensor, w1: Opti
         # expanded nnz without a host sync is not available: size by the upper bound B * (longest row) would be wasteful,
         # so this one size is read back (return_weights is the explanation / plotting path, not the scoring loop)
         wts = torch.empty(max(int(lens.sum().item()), 1), dtype=torch.float32, device=pc.device)
-    _check(lib.ncf_attn_forward_grouped(mode, _ptr(pc), ldpc, _ptr(pr), ldpr, A, _ptr(w1), float(b1), _ptr(rowptr), _ptr(col),
-                                        _ptr(val), R, I, _ptr(grp_ptr), _ptr(pair_ids), _ptr(wg_ptr), B, int(pairs_per_wg),
-                                        _ptr(feat), ldf, Fdim, _ptr(out_bias), _ptr(out), out.stride(0), _ptr(wts), _ptr(wts_off),
-                                        _stream(pc)))
+    _check(lib.ncf_attn_forward_grouped(*head, float(b1), *csr, R, I, _ptr(grp_ptr), _ptr(pair_ids), _ptr(wg_ptr), B, int(pairs_per_wg),
+                                        *ft, _ptr(out_bias), _ptr(out), out.stride(0), _ptr(wts), _ptr(wts_off), _stream(pc)))
     return (out, wts) if return_weights else out
 
 
@@ -1398,17 +1392,14 @@ def attn_logits(mode: int, pc: torch.Tensor, pr: torch.Tensor, w1: Optional[torc
     """The logit table of a catalogue (ncf_attn_logits): ST (I_r, I_c) fp32, ST[e, i] = the attention logit of candidate i (row of
     ``pc``) against rated item e (row of ``pr``); modes and operands as ``attn_forward``.  One launch on the current stream."""
     lib = load_library()
-    _dev(pc, "pc")
-    Ic, A, ldpc = _rows2d(pc, "pc")
-    Ir, A2, ldpr = _rows2d(pr, "pr")
-    if A != A2:
-        raise ValueError("attention operand shapes disagree")
+    (_, ppc, ldpc, ppr, ldpr, A, pw1), _, _, (Ic, Ir, _, _) = _attn_operands(mode, pc, pr, w1)
     if out is None:
         out = torch.empty((Ir, Ic), dtype=torch.float32, device=pc.device)
     Ir2, Ic2, ldst = _rows2d(out, "out")
     if (Ir2, Ic2) != (Ir, Ic) or out.dtype != torch.float32:
         raise ValueError(f"out must be ({Ir}, {Ic}) fp32")
-    _check(lib.ncf_attn_logits(int(mode), _ptr(pc), ldpc, Ic, _ptr(pr), ldpr, Ir, A, _ptr(w1), float(b1), _ptr(out), ldst, _stream(pc)))
+    # this entry takes each table's rows beside its pointer, so the shared head is taken apart
+    _check(lib.ncf_attn_logits(int(mode), ppc, ldpc, Ic, ppr, ldpr, Ir, A, pw1, float(b1), _ptr(out), ldst, _stream(pc)))
     return out
 
 
@@ -1420,10 +1411,7 @@ def attn_cross_supported(Fdim: int) -> bool:
 def attn_cross_plan(Fdim: int, U: int = 1, I: int = 1):
     """(nb, entry_tile, LDS bytes, grid_x) of the launch ``attn_cross`` would make: attn_cross_kernel<nb, entry_tile>.  Host only;
     raises NativeError where the call would refuse."""
-    nb, te = ctypes.c_int(0), ctypes.c_int(0)
-    lds, gx = ctypes.c_int64(0), ctypes.c_int64(0)
-    _check(load_library().ncf_attn_cross_plan(int(Fdim), int(U), int(I), ctypes.byref(nb), ctypes.byref(te), ctypes.byref(lds), ctypes.byref(gx)))
-    return nb.value, te.value, lds.value, gx.value
+    return _query(load_library().ncf_attn_cross_plan, (int(Fdim), int(U), int(I)), (_c_int, _c_int, _c_i64, _c_i64))
 
 
 def attn_cross(ST: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, user_rows: torch.Tensor,
@@ -1540,8 +1528,8 @@ def attn_stats(ST: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, user_r
     key = torch.where((cands >= 0) & (cands < Ic), cands, torch.full_like(cands, Ic))      # out of range: after every bucket
     skey, order = torch.sort(key, stable=True)                                              # within a bucket: ascending sample index
     cand_rowptr = torch.searchsorted(skey, torch.arange(Ic + 1, dtype=torch.int64, device=ST.device))
-    nbytes = int(lib.ncf_attn_stats_workspace_bytes(S))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=ST.device)
+    nbytes = lib.ncf_attn_stats_workspace_bytes(S)
+    ws = _workspace(nbytes, ST.device)
     _check(lib.ncf_attn_stats(_ptr(ST), ldst, Ir, Ic, _ptr(rowptr), _ptr(col), rowptr.numel() - 1, _ptr(user_rows), _ptr(cands), S,
                               _ptr(order), _ptr(cand_rowptr), _ptr(sum), sum.stride(0), _ptr(count), count.stride(0),
                               _ptr(_oob_flag(ST.device)), _ptr(ws), nbytes, _stream(ST)))
@@ -1875,8 +1863,8 @@ def ease_invert(A: torch.Tensor, lam: float, flag: Optional[torch.Tensor] = None
     _dev_all((A, "A"), (flag, "flag"))
     lib = load_library()
     if N:
-        nbytes = int(lib.ncf_ease_invert_workspace_bytes(N))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+        nbytes = lib.ncf_ease_invert_workspace_bytes(N)
+        ws = _workspace(nbytes, A.device)
         _check(lib.ncf_ease_invert(_ptr(A), N, lda, lam, _ptr(ws), nbytes, _ptr(ease_flag(A.device) if flag is None else flag), _stream(A)))
     return A
 
@@ -1975,8 +1963,8 @@ def als_gram(T: torch.Tensor, F: Optional[int] = None, out: Optional[torch.Tenso
     out = _out2d(who, out, F, F, T, ((T, "T"),), contiguous=True)
     lib = load_library()
     rows = T.shape[0]
-    nbytes = int(lib.ncf_als_gram_workspace_bytes(rows, F))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=T.device) if nbytes else None
+    nbytes = lib.ncf_als_gram_workspace_bytes(rows, F)
+    ws = _workspace(nbytes, T.device) if nbytes else None          # rows == 0: no chunk to write, and the entry takes a null pointer
     _check(lib.ncf_als_gram(_ptr(T), rows, max(T.stride(0), F), F, _ptr(out), _ptr(ws), nbytes, _stream(T)))
     return out
 
@@ -2189,7 +2177,7 @@ def _gat_ws(workspace, nbytes, device):
     if workspace is not None and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == device \
             and workspace.numel() >= max(nbytes, 4):
         return workspace
-    return torch.empty(max(nbytes, 4), dtype=torch.uint8, device=device)
+    return _workspace(nbytes, device)
 
 
 def gat_edge_softmax(segptr: torch.Tensor, row_of: Optional[torch.Tensor], seg_first: Optional[torch.Tensor], n_rows: int, col: torch.Tensor,
@@ -2293,11 +2281,8 @@ LINEAR_FORMS = {0: "none", 1: "tiled", 2: "rowdot", 3: "rs", 4: "rsp"}    # ncf_
 def linear_plan(M: int, N: int, K: int):
     """(form, nt, kslices, col_blocks, grid_x) of the kernel a Linear of M rows, N outputs and K inputs runs under the current
     linear_kernel / linear_kslices options; form by name (LINEAR_FORMS).  Host only: no launch, no device."""
-    form, nt, ks, cb = (ctypes.c_int(0) for _ in range(4))
-    gx = ctypes.c_int64(0)
-    _check(load_library().ncf_linear_plan(int(M), int(N), int(K), ctypes.byref(form), ctypes.byref(nt), ctypes.byref(ks),
-                                          ctypes.byref(cb), ctypes.byref(gx)))
-    return LINEAR_FORMS[form.value], nt.value, ks.value, cb.value, gx.value
+    form, *rest = _query(load_library().ncf_linear_plan, (int(M), int(N), int(K)), (_c_int, _c_int, _c_int, _c_int, _c_i64))
+    return (LINEAR_FORMS[form], *rest)
 
 
 # ------------------------------------------------------------------ backward (training step)
@@ -2312,7 +2297,7 @@ def gemm_tn(A: torch.Tensor, Bm: torch.Tensor, out: Optional[torch.Tensor] = Non
     if out is None:
         out = torch.empty((N1, N2), dtype=torch.float32, device=A.device)
     nb = lib.ncf_gemm_tn_workspace_bytes(M, N1, N2)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=A.device)
+    ws = _workspace(nb, A.device)
     _check(lib.ncf_gemm_tn(_ptr(A), lda, _ptr(Bm), ldb, M, N1, N2, _ptr(out), out.stride(0), _ptr(ws), nb, _stream(A)))
     return out
 
@@ -2323,7 +2308,7 @@ def colsum(X: torch.Tensor) -> torch.Tensor:
     M, N, ld = _rows2d(X, "X")
     out = torch.empty(N, dtype=torch.float32, device=X.device)
     nb = lib.ncf_colsum_workspace_bytes(M, N)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=X.device)
+    ws = _workspace(nb, X.device)
     _check(lib.ncf_colsum(_ptr(X), ld, M, N, _ptr(out), _ptr(ws), nb, _stream(X)))
     return out
 
@@ -2551,7 +2536,7 @@ def _topk_outputs(R, k, nbytes, dev):
     out_score = torch.empty((R, max(k, 0)), dtype=torch.float32, device=dev)
     out_idx = torch.empty((R, max(k, 0)), dtype=torch.int32, device=dev)
     out_count = torch.empty(R, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     return out_score, out_idx, out_count, ws
 
 
@@ -2667,10 +2652,7 @@ def _rank_overflow_flag(device) -> torch.Tensor:
 
 def check_rank_overflow(device):
     """Synchronising check of the sticky flag a fused rank call sets when a row has more targets than its ``max_targets``."""
-    f = _rank_overflow_flag(device)
-    if int(f.item()) != 0:
-        f.zero_()
-        raise OverflowError("a row has more targets than the max_targets the rank call was given")
+    _check_flag("rank_overflow", device)
 
 
 def _rank_outputs(R, col, nbytes, dev, rank):
@@ -2683,7 +2665,7 @@ def _rank_outputs(R, col, nbytes, dev, rank):
     elif rank.dtype != torch.int32 or rank.numel() != n or not rank.is_contiguous() or rank.device != dev:
         raise ValueError("rank must be a contiguous int32 tensor with one entry per target")
     ranked = torch.empty(R, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     rank_arg = rank
     if n == 0:                                  # a valid CSR with no entries: the kernels still want pointers
         col = torch.empty(1, dtype=torch.int32, device=dev)
@@ -2765,11 +2747,8 @@ def ranking_plan(entry: str, rows: int, cols: int, k_or_max_targets: int = 1):
     for (rows, cols) and its k (top-K entries) or max_targets (rank entries): columns per workgroup tile / wave range, tiles per
     row, merge launches after the first level and rows per pass over the key workspace (rank entries: 0 and rows).  The entry
     point's own refusals raise NativeError.  Host only: no launch, no device."""
-    tc, lv = ctypes.c_int(0), ctypes.c_int(0)
-    tiles, chunk = ctypes.c_int64(0), ctypes.c_int64(0)
-    _check(load_library().ncf_ranking_plan(RANKING_ENTRIES[entry], int(rows), int(cols), int(k_or_max_targets), ctypes.byref(tc),
-                                           ctypes.byref(tiles), ctypes.byref(lv), ctypes.byref(chunk)))
-    return tc.value, tiles.value, lv.value, chunk.value
+    return _query(load_library().ncf_ranking_plan, (RANKING_ENTRIES[entry], int(rows), int(cols), int(k_or_max_targets)),
+                  (_c_int, _c_i64, _c_int, _c_i64))
 
 
 # ------------------------------------------------------------------ full-catalogue softmax loss of a dot-product readout
@@ -2782,10 +2761,7 @@ def dot_softmax_plan(kind: str, rows: int, cols: int, D: int):
     """(tile, tiles, chunk_rows) of the launch ``dot_lse`` (kind "lse") or one role of ``dot_softmax_grad`` ("grad_rows": the batch
     rows walk the catalogue; "grad_items": the catalogue's rows walk the batch) picks for a (rows, cols) problem of width D: the
     walk's tile, its number of tiles, and the resident rows per pass over the partial-output workspace.  Host only."""
-    tile, tiles, chunk = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    _check(load_library().ncf_dot_softmax_plan(DOT_SOFTMAX_KINDS[kind], int(rows), int(cols), int(D), ctypes.byref(tile),
-                                               ctypes.byref(tiles), ctypes.byref(chunk)))
-    return tile.value, tiles.value, chunk.value
+    return _query(load_library().ncf_dot_softmax_plan, (DOT_SOFTMAX_KINDS[kind], int(rows), int(cols), int(D)), (_c_i64, _c_i64, _c_i64))
 
 
 def dot_lse(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], scale: float = 1.0,
@@ -2799,7 +2775,7 @@ def dot_lse(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor
     lse = torch.empty(B, dtype=torch.float32, device=dev)
     mx = torch.empty(B, dtype=torch.float32, device=dev) if return_max else None
     nbytes = lib.ncf_dot_lse_workspace_bytes(B, I, D)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     _check(lib.ncf_dot_lse(*args, float(scale), _ptr(lse), _ptr(mx), _ptr(ws), nbytes, _ptr(_oob_flag(dev)), _stream(tabA)))
     return (lse, mx) if return_max else lse
 
@@ -2824,7 +2800,7 @@ def dot_softmax_grad(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: tor
             continue
         out = torch.empty((rows_out, D), dtype=torch.float32, device=dev)
         nbytes = lib.ncf_dot_softmax_grad_workspace_bytes(B, I, D, items)
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        ws = _workspace(nbytes, dev)
         _check(lib.ncf_dot_softmax_grad(*args, _ptr(targets), _ptr(lse), _ptr(g), float(scale), items, _ptr(out), _ptr(ws), nbytes,
                                         _ptr(_oob_flag(dev)), _stream(tabA)))
         del ws

@@ -832,6 +832,9 @@ int ncf_user_profiles(const int64_t* dev_rowptr, const int32_t* dev_col, const f
  * ld < F + 1, W outside 1 .. 1024, a NULL table or plan array, NULL samples with n > 0, a non-finite lr or reg; NCF_EUNSUPPORTED
  * for F > 256.
  * ------------------------------------------------------------------------------------------------ */
+#define NCF_KMF_FLAG_ID 1
+#define NCF_KMF_FLAG_BLOCK 2
+#define NCF_KMF_FLAG_PTR 4
 int ncf_kmf_epoch(float* dev_PU, int64_t ldu, int64_t U, float* dev_QI, int64_t ldq, int64_t I, int F,
                   const int32_t* dev_user, const int32_t* dev_item, const float* dev_rating, int64_t n,
                   const int64_t* dev_block_ptr, const int32_t* dev_user_block, const int32_t* dev_item_block, int W,
@@ -967,6 +970,11 @@ int ncf_knn_predict(const int64_t* dev_rowptr, const int32_t* dev_col, const flo
 #define NCF_ALS_MAX_FACTORS 128
 #define NCF_ALS_GRAM_ROWS 256
 #define NCF_ALS_SEG 512
+#define NCF_ALS_FLAG_COL 1
+#define NCF_ALS_FLAG_PTR 2
+#define NCF_ALS_FLAG_ORDER 4
+#define NCF_ALS_FLAG_VAL 8
+#define NCF_ALS_FLAG_PIVOT 16
 size_t ncf_als_gram_workspace_bytes(int64_t rows, int F);
 int ncf_als_gram(const float* dev_T, int64_t rows, int64_t ld, int F, float* dev_G, void* dev_workspace, size_t workspace_bytes,
                  ncf_stream_t stream);

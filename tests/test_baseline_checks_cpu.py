@@ -107,7 +107,7 @@ FLAG_CHECKS = {"kmf": (native.check_kmf, native.kmf_flag), "knn": (native.check_
 @pytest.mark.parametrize("kind", sorted(FLAG_CHECKS))
 def test_flag_check_raises_the_listed_type_names_every_set_bit_and_clears_the_word(kind):
     check, _ = FLAG_CHECKS[kind]
-    model, table = native._FLAG_BITS[kind]
+    model, table, _ = native._FLAG_WORDS[kind]
     flag = torch.zeros(1, dtype=torch.int32)
     check(CPU, flag=flag)                                                  # a zero word raises nothing
     words = [(bit & 0x7fffffff, [text], exc) for bit, text, exc in table]
@@ -125,9 +125,11 @@ def test_flag_check_raises_the_listed_type_names_every_set_bit_and_clears_the_wo
 
 
 def test_flag_tables_list_the_documented_types():
-    types = {kind: [exc for _, _, exc in table] for kind, (_, table) in native._FLAG_BITS.items()}
-    assert types == {"kmf": [IndexError] * 3, "knn": [ValueError], "als": [IndexError, IndexError, ValueError, ValueError, ValueError]}
-    assert [bit for bit, _, _ in native._FLAG_BITS["als"][1]] == [native.ALS_FLAG_COL, native.ALS_FLAG_PTR, native.ALS_FLAG_ORDER,
+    types = {kind: [exc for _, _, exc in table] for kind, (_, table, _) in native._FLAG_WORDS.items()}
+    assert types == {"kmf": [IndexError] * 3, "knn": [ValueError], "als": [IndexError, IndexError, ValueError, ValueError, ValueError],
+                     "ease": [ValueError] * 2, "unseen": [IndexError, ValueError], "oob": [IndexError], "pair_rows": [OverflowError],
+                     "rank_overflow": [OverflowError]}
+    assert [bit for bit, _, _ in native._FLAG_WORDS["als"][1]] == [native.ALS_FLAG_COL, native.ALS_FLAG_PTR, native.ALS_FLAG_ORDER,
                                                                   native.ALS_FLAG_VAL, native.ALS_FLAG_PIVOT]
     flag = torch.full((1,), native.ALS_FLAG_ORDER | native.ALS_FLAG_PTR, dtype=torch.int32)
     with pytest.raises(IndexError, match="a row or a row pointer outside the ratings, a row whose columns do not strictly ascend"):
@@ -143,6 +145,98 @@ def test_flag_check_without_an_override_reads_the_device_word():
             assert int(word(CPU)) == 0
         finally:
             word(CPU).zero_()
+
+
+# kind -> (its public check, its public accessor, whether the check takes flag=)
+WORD_CHECKS = {"oob": (native.check_oob, native._oob_flag, False), "pair_rows": (native.check_pair_rows, native._pair_rows_flag, False),
+               "rank_overflow": (native.check_rank_overflow, native._rank_overflow_flag, False),
+               "kmf": (native.check_kmf, native.kmf_flag, True), "knn": (native.check_knn, native.knn_flag, True),
+               "als": (native.check_als, native.als_flag, True), "ease": (native.check_ease, native.ease_flag, True),
+               "unseen": (native.check_unseen, native.unseen_flag, True)}
+# (kind, word, exception, message) as the checks raised them before they shared one table: every single bit, every pair of bits of
+# a word with several meanings (an IndexError bit beside a ValueError bit raises IndexError), and all of them
+RECORDED = [
+    ("oob", 1, IndexError, "index out of range in an embedding gather"),
+    ("oob", 7, IndexError, "index out of range in an embedding gather"),
+    ("oob", -1, IndexError, "index out of range in an embedding gather"),
+    ("pair_rows", 1, OverflowError, "a pair's rated entries did not fit the capacity pair_rows was given (max_row_len too small)"),
+    ("pair_rows", 3, OverflowError, "a pair's rated entries did not fit the capacity pair_rows was given (max_row_len too small)"),
+    ("rank_overflow", 1, OverflowError, "a row has more targets than the max_targets the rank call was given"),
+    ("rank_overflow", 5, OverflowError, "a row has more targets than the max_targets the rank call was given"),
+    ("kmf", 1, IndexError, "KernelMF: an id outside its table (flag 1)"),
+    ("kmf", 2, IndexError, "KernelMF: a sample filed in the wrong block (flag 2)"),
+    ("kmf", 4, IndexError, "KernelMF: a block / row pointer outside the samples (flag 4)"),
+    ("kmf", 3, IndexError, "KernelMF: an id outside its table, a sample filed in the wrong block (flag 3)"),
+    ("kmf", 5, IndexError, "KernelMF: an id outside its table, a block / row pointer outside the samples (flag 5)"),
+    ("kmf", 6, IndexError, "KernelMF: a sample filed in the wrong block, a block / row pointer outside the samples (flag 6)"),
+    ("kmf", 7, IndexError, "KernelMF: an id outside its table, a sample filed in the wrong block, a block / row pointer outside the samples (flag 7)"),
+    ("knn", 1, ValueError, "ItemKNN: a row of the ratings CSR does not hold strictly ascending columns"),
+    ("knn", 6, ValueError, "ItemKNN: a row of the ratings CSR does not hold strictly ascending columns"),
+    ("knn", 2147483647, ValueError, "ItemKNN: a row of the ratings CSR does not hold strictly ascending columns"),
+    ("knn", -1, ValueError, "ItemKNN: a row of the ratings CSR does not hold strictly ascending columns"),
+    ("als", 1, IndexError, "ImplicitALS: a column outside the fixed table (flag 1)"),
+    ("als", 2, IndexError, "ImplicitALS: a row or a row pointer outside the ratings (flag 2)"),
+    ("als", 4, ValueError, "ImplicitALS: a row whose columns do not strictly ascend (flag 4)"),
+    ("als", 8, ValueError, "ImplicitALS: a value that is negative or not finite (flag 8)"),
+    ("als", 16, ValueError, "ImplicitALS: a pivot that is not positive and finite (flag 16)"),
+    ("als", 3, IndexError, "ImplicitALS: a column outside the fixed table, a row or a row pointer outside the ratings (flag 3)"),
+    ("als", 5, IndexError, "ImplicitALS: a column outside the fixed table, a row whose columns do not strictly ascend (flag 5)"),
+    ("als", 9, IndexError, "ImplicitALS: a column outside the fixed table, a value that is negative or not finite (flag 9)"),
+    ("als", 17, IndexError, "ImplicitALS: a column outside the fixed table, a pivot that is not positive and finite (flag 17)"),
+    ("als", 6, IndexError, "ImplicitALS: a row or a row pointer outside the ratings, a row whose columns do not strictly ascend (flag 6)"),
+    ("als", 10, IndexError, "ImplicitALS: a row or a row pointer outside the ratings, a value that is negative or not finite (flag 10)"),
+    ("als", 18, IndexError, "ImplicitALS: a row or a row pointer outside the ratings, a pivot that is not positive and finite (flag 18)"),
+    ("als", 12, ValueError, "ImplicitALS: a row whose columns do not strictly ascend, a value that is negative or not finite (flag 12)"),
+    ("als", 20, ValueError, "ImplicitALS: a row whose columns do not strictly ascend, a pivot that is not positive and finite (flag 20)"),
+    ("als", 24, ValueError, "ImplicitALS: a value that is negative or not finite, a pivot that is not positive and finite (flag 24)"),
+    ("als", 31, IndexError, "ImplicitALS: a column outside the fixed table, a row or a row pointer outside the ratings, a row whose columns do not "
+                            "strictly ascend, a value that is negative or not finite, a pivot that is not positive and finite (flag 31)"),
+    ("ease", 1, ValueError, "EASE: a row of the ratings CSR does not hold strictly ascending columns (flag 1)"),
+    ("ease", 2, ValueError, "EASE: a pivot of the inversion that is not positive and finite (flag 2)"),
+    ("ease", 3, ValueError, "EASE: a row of the ratings CSR does not hold strictly ascending columns, a pivot of the inversion that is not positive "
+                            "and finite (flag 3)"),
+    ("unseen", 1, IndexError, "sample_unseen: a pick outside the users (flag 1)"),
+    ("unseen", 256, ValueError, "sample_unseen: a user has fewer unseen items than the draws asked for (flag 256)"),
+    ("unseen", 257, IndexError, "sample_unseen: a pick outside the users, a user has fewer unseen items than the draws asked for (flag 257)"),
+]
+
+
+def test_the_recorded_rows_cover_every_kind_every_bit_and_a_mixed_pair():
+    assert {kind for kind, *_ in RECORDED} == set(WORD_CHECKS) == set(native._FLAG_WORDS)
+    for kind, (_, rows, _) in native._FLAG_WORDS.items():
+        words = {word for k, word, _, _ in RECORDED if k == kind}
+        assert all((1 if bit == ~0 else bit) in words for bit, _, _ in rows), kind
+        if len(rows) > 1:
+            assert any(bin(w).count("1") == 2 for w in words), kind
+    mixed = [("als", native.ALS_FLAG_PTR | native.ALS_FLAG_ORDER, IndexError), ("unseen", native.UNSEEN_FLAG_PICK | native.UNSEEN_FLAG_FEW, IndexError)]
+    assert all(m in [r[:3] for r in RECORDED] for m in mixed)
+
+
+@pytest.mark.parametrize("kind,word,exc,message", RECORDED, ids=[f"{r[0]}-{r[1]}" for r in RECORDED])
+def test_every_flag_word_raises_what_it_raised_before_the_checks_shared_a_table(kind, word, exc, message):
+    check, accessor, takes_flag = WORD_CHECKS[kind]
+    device_word = accessor(CPU)
+    assert device_word is accessor(CPU) and device_word.dtype == torch.int32 and device_word.numel() == 1
+    try:
+        check(CPU)                                                         # a zero word raises nothing
+        device_word.fill_(word)
+        with pytest.raises(exc) as e:
+            check(CPU)
+        assert type(e.value) is exc and str(e.value) == message
+        assert int(device_word) == 0
+        check(CPU)
+        if takes_flag:                                                     # another word: the same message, the device's word untouched
+            other = torch.full((1,), word, dtype=torch.int32)
+            with pytest.raises(exc) as e:
+                check(CPU, flag=other)
+            assert type(e.value) is exc and str(e.value) == message
+            assert int(other) == 0 and int(device_word) == 0
+            check(CPU, flag=other)
+            device_word.fill_(word)                                        # and with the override the device's word is not read
+            check(CPU, flag=other)
+            assert int(device_word) == word
+    finally:
+        device_word.zero_()
 
 
 # ------------------------------------------------------------------ the fit front end
