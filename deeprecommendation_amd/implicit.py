@@ -167,22 +167,23 @@ class ImplicitFeedback:
 
 
 def _scorer(who, model, graph):
-    """``score(users, items)`` of a supported model over user and item POSITIONS, or TypeError naming the three.  A GraphNCF scores
+    """``score(users, items)`` of a supported model over user and item POSITIONS, or TypeError naming them.  A GraphNCF scores
     graph nodes, where user u is node graph.num_items + u (IndexGraphProvider.get_user_nodeID): the offset is added here."""
     from .neural_collaborative_filtering.models.basic_ncf import BasicNCF
     from .neural_collaborative_filtering.models.gnn_ncf import GraphNCF
     from .neural_collaborative_filtering.models.mf import MF
+    from .neural_collaborative_filtering.models.neumf import NeuMF
     if isinstance(model, GraphNCF):
         if graph is None:
             raise ValueError(f"{who}: a GraphNCF needs graph=")
         if not hasattr(graph, "num_items"):
             raise ValueError(f"{who}: graph= must be the provider's GraphData")
         return lambda u, i: model(graph.to(u.device), u + graph.num_items, i)
-    if isinstance(model, (BasicNCF, MF)):
+    if isinstance(model, (BasicNCF, MF, NeuMF)):
         if graph is not None:
             raise ValueError(f"{who}: graph= goes with a GraphNCF, not a {type(model).__name__}")
         return model
-    raise TypeError(f"{who}: takes a BasicNCF or an MF in index form (forward(users, items)) or a GraphNCF with graph= "
+    raise TypeError(f"{who}: takes a BasicNCF, a NeuMF or an MF in index form (forward(users, items)) or a GraphNCF with graph= "
                     f"(forward(graph, users, items)), not a {type(model).__name__}")
 
 

@@ -192,6 +192,17 @@ SIGNATURES = {
     "ncf_mlp_rank": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_i64,
                               _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_size, _c_p, _c_p, _c_p]),
     "ncf_ranking_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p]),
+    "ncf_neumf_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    "ncf_neumf_score": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_int,
+                                 _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "ncf_neumf_topk_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_p, _c_int, _c_int]),
+    "ncf_neumf_topk": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_int, _c_int, _c_int,
+                                _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_size,
+                                _c_p, _c_p]),
+    "ncf_neumf_rank_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int, _c_p, _c_int, _c_i64, _c_int]),
+    "ncf_neumf_rank": (_c_int, [_c_int, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_int, _c_int, _c_int,
+                                _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p,
+                                _c_p, _c_size, _c_p, _c_p, _c_p]),
     "ncf_dot_softmax_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p]),
     "ncf_dot_lse_workspace_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
     "ncf_dot_lse": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_int, ctypes.c_float, _c_p, _c_p,
@@ -2575,9 +2586,26 @@ def _dot_operands(fn, tabA, idxA, tabB, idxB):
     return (_ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(idxA), _ptr(idxB), B, I, D), (B, I, D, tabA.device)
 
 
-def _mlp_operands(fn, tabA, idxA, tabB, idxB, packed, user_first):
+def _gmf_operands(fn, tabA, tabB, gmf):
+    """The GMF term ``gmf`` = (gmfA, gmfB, w) of a NeuMF call, checked for the public function ``fn`` against the tower's tables:
+    (D, ldGA, ldGB)."""
+    gmfA, gmfB, w = gmf
+    _table_f32(fn, gmfA, "gmfA"), _table_f32(fn, gmfB, "gmfB")
+    D = gmfA.shape[1]
+    if gmfB.shape[1] != D:
+        raise ValueError(f"{fn}: the GMF tables are {D} and {gmfB.shape[1]} wide")
+    if gmfA.shape[0] != tabA.shape[0] or gmfB.shape[0] != tabB.shape[0]:
+        raise ValueError(f"{fn}: a GMF table must have the rows of its side's tower table "
+                         f"({gmfA.shape[0]} / {tabA.shape[0]} users, {gmfB.shape[0]} / {tabB.shape[0]} items)")
+    _vec1d(fn, w, "w", torch.float32, D)
+    _dev_all((gmfA, "gmfA"), (gmfB, "gmfB"), (w, "w"))
+    return D, gmfA.stride(0), gmfB.stride(0)
+
+
+def _mlp_operands(fn, tabA, idxA, tabB, idxB, packed, user_first, gmf=None):
     """The operands mlp_topk and mlp_rank share, checked for the public function ``fn``: (the ABI arguments up to the packed blob,
-    (B, I, dims array, dev)).  user_first=False: the users are tabB's rows and idxB."""
+    (B, I, dims array, dev)).  user_first=False: the users are tabB's rows and idxB.  With ``gmf`` = (gmfA, gmfB, w) the arguments
+    are those of the NeuMF entries (users first), up to w."""
     _dev(tabA, "tabA"), _dev(tabB, "tabB")
     rowsA, EA, ldA = _rows2d(tabA, "tabA")
     rowsB, EB, ldB = _rows2d(tabB, "tabB")
@@ -2590,6 +2618,13 @@ def _mlp_operands(fn, tabA, idxA, tabB, idxB, packed, user_first):
     nB = idxB.numel() if idxB is not None else rowsB
     user_ids, item_ids, B, I = (idxA, idxB, nA, nB) if user_first else (idxB, idxA, nB, nA)
     d = _dims_array(packed.dims)
+    if gmf is not None:
+        if not user_first:
+            raise ValueError(f"{fn}: users first only")
+        D, ldGA, ldGB = _gmf_operands(fn, tabA, tabB, gmf)
+        args = (packed.dt, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, _ptr(gmf[0]), ldGA, _ptr(gmf[1]), ldGB, EA, EB, D, _ptr(user_ids),
+                _ptr(item_ids), B, I, packed.n_layers, d, _ptr(packed.blob), _ptr(gmf[2]))
+        return args, (B, I, d, tabA.device)
     args = (packed.dt, _ptr(tabA), rowsA, ldA, _ptr(tabB), rowsB, ldB, EA, EB, 1 if user_first else 0, _ptr(user_ids), _ptr(item_ids), B, I,
             packed.n_layers, d, _ptr(packed.blob))
     return args, (B, I, d, tabA.device)
@@ -2630,14 +2665,22 @@ def mlp_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     of the list, out_count (B,) int32) like topk_rows.  A shape without a fused instance, a bf16 blob or k > MLP_TOPK_MAX_K raise
     NativeError with code NCF_EUNSUPPORTED and launch nothing.  Outputs and workspace from the caching allocator on the current
     stream; no sync."""
+    return _mlp_topk("mlp_topk", tabA, idxA, tabB, idxB, packed, k, seen, user_first, None)
+
+
+def _mlp_topk(fn, tabA, idxA, tabB, idxB, packed, k, seen, user_first, gmf):
+    """mlp_topk (``gmf`` None) and neumf_topk (``gmf`` = (gmfA, gmfB, w)): one marshalling, the entry and its workspace query differ."""
     lib = load_library()
-    args, (B, I, d, dev) = _mlp_operands("mlp_topk", tabA, idxA, tabB, idxB, packed, user_first)
+    args, (B, I, d, dev) = _mlp_operands(fn, tabA, idxA, tabB, idxB, packed, user_first, gmf)
     k = int(k)
     rowptr, col = _csr_pair(seen, B, dev, "seen")
-    nbytes = lib.ncf_mlp_topk_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, k)
+    if gmf is None:
+        entry, nbytes = lib.ncf_mlp_topk, lib.ncf_mlp_topk_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, k)
+    else:
+        entry, nbytes = lib.ncf_neumf_topk, lib.ncf_neumf_topk_workspace_bytes(B, I, packed.n_layers, d, gmf[0].shape[1], k)
     out_score, out_idx, out_count, ws = _topk_outputs(B, k, nbytes, dev)
-    _check(lib.ncf_mlp_topk(*args, _ptr(rowptr), _ptr(col), k, _ptr(out_score), _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes,
-                            _ptr(_oob_flag(dev)), _stream(tabA)))
+    _check(entry(*args, _ptr(rowptr), _ptr(col), k, _ptr(out_score), _ptr(out_idx), _ptr(out_count), _ptr(ws), nbytes,
+                 _ptr(_oob_flag(dev)), _stream(tabA)))
     return out_score, out_idx, out_count
 
 
@@ -2726,16 +2769,69 @@ def mlp_rank(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tenso
     """ncf_mlp_rank: exactly ``rank_rows(score_fused(...).view(B, I), targets, seen)`` over every (user, item) pair of an MLP readout
     (arguments as mlp_topk), without the pair id columns or the score matrix.  max_targets and the overflow flag as dot_rank.  A
     shape without a fused instance or a bf16 blob raise NativeError (NCF_EUNSUPPORTED) and launch nothing.  No sync."""
+    return _mlp_rank("mlp_rank", tabA, idxA, tabB, idxB, packed, targets, max_targets, seen, user_first, rank, None)
+
+
+def _mlp_rank(fn, tabA, idxA, tabB, idxB, packed, targets, max_targets, seen, user_first, rank, gmf):
+    """mlp_rank (``gmf`` None) and neumf_rank (``gmf`` = (gmfA, gmfB, w)), as _mlp_topk."""
     lib = load_library()
-    args, (B, I, d, dev) = _mlp_operands("mlp_rank", tabA, idxA, tabB, idxB, packed, user_first)
+    args, (B, I, d, dev) = _mlp_operands(fn, tabA, idxA, tabB, idxB, packed, user_first, gmf)
     rowptr, col = _csr_pair(seen, B, dev, "seen")
     trow, tcol = _csr_pair(targets, B, dev, "targets", required=True)
     n, max_targets = tcol.numel(), int(max_targets)
-    nbytes = lib.ncf_mlp_rank_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, n, max_targets)
+    if gmf is None:
+        entry, nbytes = lib.ncf_mlp_rank, lib.ncf_mlp_rank_workspace_bytes(B, I, 1 if user_first else 0, packed.n_layers, d, n, max_targets)
+    else:
+        entry, nbytes = lib.ncf_neumf_rank, lib.ncf_neumf_rank_workspace_bytes(B, I, packed.n_layers, d, gmf[0].shape[1], n, max_targets)
     rank, ranked, ws, tcol, rank_arg = _rank_outputs(B, tcol, nbytes, dev, rank)
-    _check(lib.ncf_mlp_rank(*args, _ptr(rowptr), _ptr(col), _ptr(trow), _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws),
-                            nbytes, _ptr(_oob_flag(dev)), _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
+    _check(entry(*args, _ptr(rowptr), _ptr(col), _ptr(trow), _ptr(tcol), n, max_targets, _ptr(rank_arg), _ptr(ranked), _ptr(ws),
+                 nbytes, _ptr(_oob_flag(dev)), _ptr(_rank_overflow_flag(dev)), _stream(tabA)))
     return rank, ranked
+
+
+# ------------------------------------------------------------------ NeuMF: the MLP tower plus a GMF term (include/ncf_abi.h ncf_neumf_score)
+NEUMF_MAX_D = 128        # the GMF width: a multiple of 8 in 8 .. 128
+
+
+def neumf_supported(packed: PackedMLP, EA: int, EB: int, D: int) -> bool:
+    """Whether the NeuMF kernels take this packed tower (its last layer: predict.weight[:, D:] and predict.bias), split (EA, EB) and
+    GMF width D."""
+    return bool(load_library().ncf_neumf_supported(packed.dt, int(EA), int(EB), int(D), packed.n_layers, _dims_array(packed.dims)))
+
+
+def neumf_score(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], gmfA: torch.Tensor,
+                gmfB: torch.Tensor, packed: PackedMLP, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ncf_neumf_score: (B, 1) fp32 scores of the pairs (idxA[b], idxB[b]) (a list None: position b) — the tower over cat(tabA row,
+    tabB row) with ``packed``, plus the GMF term over the rows of gmfA / gmfB weighted by ``w`` (D floats), in the header's operation
+    order.  One launch, no sync.  A shape the kernel does not take raises NativeError (NCF_EUNSUPPORTED)."""
+    lib = load_library()
+    args, (B, I, d, dev) = _mlp_operands("neumf_score", tabA, idxA, tabB, idxB, packed, True, (gmfA, gmfB, w))
+    if idxA is not None and idxB is not None and B != I:
+        raise ValueError(f"neumf_score: {B} user ids and {I} item ids")
+    n = B if idxA is not None else I if idxB is not None else min(B, I)
+    if out is None:
+        out = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    _out1d("neumf_score", out, "out", torch.float32, n)
+    _dev(out, "out")
+    (dt, pA, rowsA, ldA, pB, rowsB, ldB, pGA, ldGA, pGB, ldGB, EA, EB, D, pU, pI, _, _, n_layers, d, blob, pw) = args
+    _check(lib.ncf_neumf_score(dt, pA, rowsA, ldA, pB, rowsB, ldB, pGA, ldGA, pGB, ldGB, pU, pI, n, EA, EB, D, n_layers, d, blob, pw,
+                               _ptr(out), _ptr(_oob_flag(dev)), _stream(tabA)))
+    return out
+
+
+def neumf_topk(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], gmfA: torch.Tensor,
+               gmfB: torch.Tensor, packed: PackedMLP, w: torch.Tensor, k: int, seen: Optional[tuple] = None):
+    """ncf_neumf_topk: exactly ``topk_rows(neumf_score over every (user, item) pair, k, seen)``, bit for bit, without the score
+    matrix; users first.  Arguments, results, limits and refusals as mlp_topk; ``ranking_plan("mlp_topk", ...)`` is its plan."""
+    return _mlp_topk("neumf_topk", tabA, idxA, tabB, idxB, packed, k, seen, True, (gmfA, gmfB, w))
+
+
+def neumf_rank(tabA: torch.Tensor, idxA: Optional[torch.Tensor], tabB: torch.Tensor, idxB: Optional[torch.Tensor], gmfA: torch.Tensor,
+               gmfB: torch.Tensor, packed: PackedMLP, w: torch.Tensor, targets: tuple, max_targets: int, seen: Optional[tuple] = None,
+               rank: Optional[torch.Tensor] = None):
+    """ncf_neumf_rank: exactly ``rank_rows(neumf_score over every (user, item) pair, targets, seen)``; as mlp_rank otherwise, and
+    ``ranking_plan("mlp_rank", ...)`` is its plan."""
+    return _mlp_rank("neumf_rank", tabA, idxA, tabB, idxB, packed, targets, max_targets, seen, True, rank, (gmfA, gmfB, w))
 
 
 # ncf_ranking_plan's entry (include/ncf_abi.h enum ncf_ranking_entry)

@@ -51,9 +51,11 @@ def _fused_ranks(model, r, users, seen, targets, max_targets):
         ops = _mlp_operands(model, r, users)
         if ops is None:
             return None
-        tabA, idxA, tabB, idxB, packed, user_first = ops
+        tabA, idxA, tabB, idxB, packed, user_first, gmf = ops
         if not native.mlp_rank_supported(packed, tabA.shape[1], tabB.shape[1], max_targets):
             return None
+        if gmf is not None:             # a NeuMF: the same waves with the GMF term
+            return native.neumf_rank(tabA, idxA, tabB, idxB, gmf[0], gmf[1], packed, gmf[2], targets, max_targets, seen)
         return native.mlp_rank(tabA, idxA, tabB, idxB, packed, targets, max_targets, seen, user_first=user_first)
 
 
@@ -65,7 +67,7 @@ def _scored_ranks(model, r, users, seen, targets, block_bytes):
 def rank_of_items(model, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, torch.Tensor], item_ids: Optional[torch.Tensor] = None,
                   exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, *, graph=None, fused: Optional[bool] = None,
                   max_targets: Optional[int] = None, block_bytes: int = BLOCK_BYTES, profiles=None):
-    """The exact rank of each user's held-out items against the whole ranked list, for a BasicNCF / MF / GraphNCF model.
+    """The exact rank of each user's held-out items against the whole ranked list, for a BasicNCF / MF / NeuMF / GraphNCF model.
 
     user_ids, item_ids, exclude, graph: as in ``top_k_items`` (int64 positions on the GPU; columns of the ranked list; a GraphNCF
     needs ``graph=``).  targets: the held-out items as a per-user CSR ``(rowptr (B + 1) int64, col int32)`` of columns of the
@@ -75,8 +77,8 @@ def rank_of_items(model, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, to
     other targets compete like any column; duplicate targets get the same rank; a target that is excluded or not a column of the
     list gets -1.  ranked[b] is the number of non-excluded columns of user b.
     fused: ``None`` ranks a dot-product readout (MF, GraphNCF-dot) with ``native.dot_rank`` and an MLP readout (BasicNCF,
-    GraphNCF-MLP) with ``native.mlp_rank``, neither of which writes a score matrix; what a fused kernel does not take (bf16
-    scoring, a folded first layer, an MLP shape without a fused instance, width > 256) and ``fused=False`` score the users block by
+    GraphNCF-MLP) with ``native.mlp_rank`` (a NeuMF with ``native.neumf_rank``), none of which writes a score matrix; what a fused
+    kernel does not take (bf16 scoring, a folded first layer, an MLP shape without a fused instance, width > 256) and ``fused=False`` score the users block by
     block through the model (score blocks under ``block_bytes``) and rank with ``native.rank_rows``.  All routes give the same
     integers.
     profiles: ``(item_features, ratings)`` for an AttentionNCF, as in ``top_k_items``: ``fused`` is then the route of

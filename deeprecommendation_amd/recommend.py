@@ -233,7 +233,7 @@ def _score_blocks(model, r: _RankedList, users, block_bytes):
 def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
                 exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES, *, graph=None,
                 fused: Optional[bool] = None, profiles=None):
-    """The ``k`` best items of every user in ``user_ids`` for a BasicNCF / MF / GraphNCF model (int64 position inputs).
+    """The ``k`` best items of every user in ``user_ids`` for a BasicNCF / MF / NeuMF / GraphNCF model (int64 position inputs).
 
     user_ids: (B,) int64 user positions on the GPU — for a GraphNCF node positions as in ``GraphNCF.forward`` (users come after
     the ``graph.num_items`` items).  item_ids: optional (I,) int64 item positions to rank (default: every item of the model; for
@@ -243,11 +243,12 @@ def top_k_items(model, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.
     for a GraphNCF and refused for any other model.
     fused: how the scores are ranked.  ``None``: GraphNCF-dot through the fused dot-product score-and-select kernel
     (``native.dot_topk``), and an MLP readout (BasicNCF, GraphNCF with ``use_dot_product=False``) through the fused MLP
-    score-and-select kernel (``native.mlp_topk``), neither of which writes a score matrix; MF score-then-select.  ``True``: the
+    score-and-select kernel (``native.mlp_topk``; a NeuMF through the same waves with its GMF term, ``native.neumf_topk``), none of
+    which writes a score matrix; MF score-then-select.  ``True``: the
     fused dot-product kernel for MF too (refused for a model with an MLP readout); ``False``: score-then-select everywhere.  All
     routes give the same bits.  Where a fused kernel's limits do not hold it falls back to score-then-select: k <= 128 for both;
     width <= 256 for the dot kernel; for the MLP kernel fp32 scoring, no folded first layer and an MLP shape with an
-    ``ncf_score_fused`` instance.
+    ``ncf_score_fused`` instance; for a NeuMF also at most two hidden layers and ``mf_dim`` a multiple of 8 up to 128.
     profiles: ``(item_features (I_c, F), ratings)`` for an AttentionNCF — required for that model and refused for any other.  The
     catalogue is both the candidate list and the rated-item list; ``ratings`` is a SparseRatings whose rows are users and whose
     columns are catalogue positions (``SparseDynamicProvider.device_state``), ``user_ids`` are rows of it, ``item_ids`` / ``exclude``
@@ -290,34 +291,49 @@ def _fused_top_k(model, r: _RankedList, k):
         return native.dot_topk(user_tab, r.users, item_tab, ids, k, r.seen)
 
 
+def _neumf_model(model) -> bool:
+    from .neural_collaborative_filtering.models.neumf import NeuMF
+    return isinstance(model, NeuMF)
+
+
 def _mlp_operands(model, r: _RankedList, users):
-    """``(tabA, idxA, tabB, idxB, packed, user_first)`` of a fused MLP readout over ``users`` and the ranked list — BasicNCF:
+    """``(tabA, idxA, tabB, idxB, packed, user_first, gmf)`` of a fused MLP readout over ``users`` and the ranked list — BasicNCF:
     cat(user table, item table), the users first; GraphNCF: cat(item node rows, user node rows) of the propagated table, the items
-    first.  None where no fused MLP kernel applies: non-fp32 scoring, a folded first layer, no packed MLP."""
+    first; NeuMF: its tower like a BasicNCF, with ``gmf`` = (GMF user table, GMF item table, w) for the NeuMF kernels (None for
+    the others).  None where no fused MLP kernel applies: non-fp32 scoring, a folded first layer, no packed MLP, a NeuMF shape
+    outside its kernels' limits."""
     if getattr(model, "scoring_dtype", torch.float32) != torch.float32 or model.fold_first_layer:
         return None
     cache = model._refresh()
+    if _neumf_model(model):
+        ops = model.kernel_operands(cache)
+        if ops is None:
+            return None
+        user_tab, item_tab, gmf_user, gmf_item, packed, w = ops
+        return user_tab, users, item_tab, None if r.all_items else r.items, packed, True, (gmf_user, gmf_item, w)
     packed = model._packed_mlp("MLP", cache)
     if packed is None:
         return None
     user_tab, item_tab, ids = _fused_tables(model, r, cache)
     if r.graph is None:
-        return user_tab, users, item_tab, ids, packed, True
-    return item_tab, ids, user_tab, users, packed, False
+        return user_tab, users, item_tab, ids, packed, True, None
+    return item_tab, ids, user_tab, users, packed, False, None
 
 
 def _fused_mlp_top_k(model, r: _RankedList, k):
-    """native.mlp_topk over the model's MLP readout; None where the fused kernel does not apply (_mlp_operands, an MLP shape
-    without a fused instance, k > 128); the caller then scores and selects, which gives the same bits."""
+    """native.mlp_topk (a NeuMF: native.neumf_topk) over the model's MLP readout; None where the fused kernel does not apply
+    (_mlp_operands, an MLP shape without a fused instance, k > 128); the caller then scores and selects, which gives the same bits."""
     if k > native.MLP_TOPK_MAX_K:
         return None
     with torch.no_grad():
         ops = _mlp_operands(model, r, r.users)
         if ops is None:
             return None
-        tabA, idxA, tabB, idxB, packed, user_first = ops
+        tabA, idxA, tabB, idxB, packed, user_first, gmf = ops
         if not native.mlp_topk_supported(packed, tabA.shape[1], tabB.shape[1], k):
             return None
+        if gmf is not None:
+            return native.neumf_topk(tabA, idxA, tabB, idxB, gmf[0], gmf[1], packed, gmf[2], k, r.seen)
         return native.mlp_topk(tabA, idxA, tabB, idxB, packed, k, r.seen, user_first=user_first)
 
 

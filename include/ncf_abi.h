@@ -1375,6 +1375,61 @@ int ncf_ranking_plan(int entry, int64_t rows, int64_t cols, int k_or_max_targets
                      int64_t* chunk_rows);
 
 /* ------------------------------------------------------------------------------------------------
+ * NeuMF (csrc/neumf.hip, csrc/gmf.h; fp32 only) — the fused model of He et al. 2017: an MLP tower over cat(user row, item row) and a
+ * GMF branch over a second pair of tables, under one 1-wide output layer `predict` over cat(p (.) q, phi).  Replaces: nothing in the
+ * reference, which has the two towers only as separate models.
+ * Operands: dev_tabA / dev_tabB are the tower's user / item tables (EA / EB wide), dev_gmfA / dev_gmfB the GMF tables of the same
+ *   users / items (D wide, leading dimensions ldGA / ldGB, as many rows as their side's tower table: rowsA / rowsB).
+ *   dev_packed = ncf_mlp_pack of [W1, (W2,) predict.weight[:, D:]] and [b1, (b2,) predict.bias] (n_layers, dims as there: dims[0] =
+ *   EA + EB, dims[n_layers] = 1);  dev_w = predict.weight[0, :D] (D floats, 16-byte aligned).
+ *   D is a multiple of 8 with 8 <= D <= 128.
+ * THE CONTRACT, per pair (u, i) with GMF rows p = gmfA[u], q = gmfB[i]:
+ *   s_mlp   the bits of the fused scorer's last sum: what ncf_score_fused returns for the pair with the same blob and a zero last
+ *           bias.  Layer 1 starts from b1 and runs its k-steps q ascending (the user table's, then the item table's), tiles
+ *           nt-major, j ascending; layer 2 and the last sum are the fused scorer's own code.
+ *   g       for lane half h in {0, 1} start a_h = +0.f; then for s = 0 .. D/8 - 1 and j = 0 .. 3, with d = 8 s + 4 h + j:
+ *               t = fl(w[d] * p[d]);   v = fl(t * q[d]);   a_h = fl(a_h + v)
+ *           and g = fl(a_0 + a_1).  Every product and sum is rounded on its own (no FMA).
+ *   score = fl(fl(s_mlp + g) + bl[0])        bl = predict.bias
+ *   An out-of-range user (item) id reads zero rows in both of that side's tables and sets *dev_oob_flag (when non-NULL).
+ *   s_mlp is never -0.0 (see ncf_mlp_topk) and a_h starts at +0, so g is never -0.0 and the score is -0.0 only if fl(s_mlp + g) and
+ *   bl both are: the ranking entries below recover the caller's bits from their keys for every non-NaN score.
+ * ncf_neumf_supported: dtype NCF_F32, a (K0 = EA + EB, dims) shape with an ncf_score_fused instance, EA and EB both >= 8 and
+ *   multiples of 8, D as above.  Every entry returns NCF_EUNSUPPORTED otherwise and launches nothing.
+ * ncf_neumf_score: dev_out[b] = score(dev_idxU[b], dev_idxI[b]) for b < B (an id list may be NULL: position b).  One wave per
+ *   32-pair tile, one launch form at every B, no host synchronisation: the call captures into a HIP graph.  Tables 16-byte aligned
+ *   with ld % 4 == 0 (NCF_EINVAL otherwise).
+ * ncf_neumf_topk / ncf_neumf_rank: ncf_mlp_topk / ncf_mlp_rank over NeuMF's score, users first (user_first is not an argument):
+ *   exactly ncf_topk_rows / ncf_rank_rows over the matrix of ncf_neumf_score's scores, bit for bit, without that matrix.  Same
+ *   output layout, limits (k <= 128, cols <= 2^24, rows <= 65536, max_targets <= 128), exclusion CSR, target CSR and overflow flag
+ *   as the MLP entries, and the same waves: the column ranges, merge plan and row chunks are theirs, so
+ *   ncf_ranking_plan(NCF_RANKING_MLP_TOPK / NCF_RANKING_MLP_RANK, ...) answers for these two entries as well.  The workspace
+ *   (ncf_neumf_topk_workspace_bytes / ncf_neumf_rank_workspace_bytes) is the MLP entry's plus D floats per listed user: the rounded
+ *   row t = w (.) p_u, written once per call behind the layer-1 state.
+ * ------------------------------------------------------------------------------------------------ */
+int ncf_neumf_supported(int dtype, int EA, int EB, int D, int n_layers, const int* dims);
+int ncf_neumf_score(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, const void* dev_tabB, int64_t rowsB, int64_t ldB,
+                    const float* dev_gmfA, int64_t ldGA, const float* dev_gmfB, int64_t ldGB, const int64_t* dev_idxU,
+                    const int64_t* dev_idxI, int64_t B, int EA, int EB, int D, int n_layers, const int* dims, const void* dev_packed,
+                    const float* dev_w, float* dev_out, int32_t* dev_oob_flag, ncf_stream_t stream);
+size_t ncf_neumf_topk_workspace_bytes(int64_t rows, int64_t cols, int n_layers, const int* dims, int D, int k);
+int ncf_neumf_topk(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, const void* dev_tabB, int64_t rowsB, int64_t ldB,
+                   const float* dev_gmfA, int64_t ldGA, const float* dev_gmfB, int64_t ldGB, int EA, int EB, int D,
+                   const int64_t* dev_user_ids, const int64_t* dev_item_ids, int64_t rows, int64_t cols, int n_layers, const int* dims,
+                   const void* dev_packed, const float* dev_w, const int64_t* dev_seen_rowptr, const int32_t* dev_seen_col, int k,
+                   float* dev_out_score, int32_t* dev_out_idx, int32_t* dev_out_count, void* dev_workspace, size_t workspace_bytes,
+                   int32_t* dev_oob_flag, ncf_stream_t stream);
+size_t ncf_neumf_rank_workspace_bytes(int64_t rows, int64_t cols, int n_layers, const int* dims, int D, int64_t n_targets,
+                                      int max_targets);
+int ncf_neumf_rank(int dtype, const void* dev_tabA, int64_t rowsA, int64_t ldA, const void* dev_tabB, int64_t rowsB, int64_t ldB,
+                   const float* dev_gmfA, int64_t ldGA, const float* dev_gmfB, int64_t ldGB, int EA, int EB, int D,
+                   const int64_t* dev_user_ids, const int64_t* dev_item_ids, int64_t rows, int64_t cols, int n_layers, const int* dims,
+                   const void* dev_packed, const float* dev_w, const int64_t* dev_seen_rowptr, const int32_t* dev_seen_col,
+                   const int64_t* dev_tgt_rowptr, const int32_t* dev_tgt_col, int64_t n_targets, int max_targets, int32_t* dev_rank,
+                   int32_t* dev_ranked, void* dev_workspace, size_t workspace_bytes, int32_t* dev_oob_flag, int32_t* dev_overflow_flag,
+                   ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Full-catalogue softmax cross-entropy for a dot-product readout, without a rows x cols matrix (csrc/dot_softmax.hip; fp32 only).
  * Operands as ncf_dot_topk: listed row b is dev_tabA[dev_idxA[b]] (dev_tabA[b] with dev_idxA NULL), catalogue column j is
  * dev_tabB[dev_idxB[j]] (dev_tabB[j] with dev_idxB NULL), D = 1 .. 256, rows <= 65536, cols <= 2^24.

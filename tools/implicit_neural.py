@@ -1,5 +1,5 @@
-"""Implicit-feedback MF (sampled loss and full-catalogue softmax) and BasicNCF beside the ImplicitALS baseline, all under one
-evaluation, on the device.
+"""Implicit-feedback MF (sampled loss and full-catalogue softmax), BasicNCF and NeuMF (from scratch, and initialised from the fitted
+MF + BasicNCF by ``NeuMF.from_pretrained``) beside the ImplicitALS baseline, all under one evaluation, on the device.
 
     python tools/implicit_neural.py RATINGS [--min-rating 0] [--negatives 4] [--loss bce] [--epochs 20] [--batch-size 65536]
                                             [--lr 0.001] [--factors 64] [--candidates 99] [--als-iters 15] [--seed 0]
@@ -7,7 +7,7 @@ evaluation, on the device.
 
 RATINGS is a sample file (CSV with userId, movieId, rating and, optionally, timestamp columns; ``.csv`` may be left off).  Every
 rating of at least ``--min-rating`` is an interaction.  ``leave_one_out`` holds out one item per user (the latest with a timestamp
-column, a seeded pick without), the rest trains: MF and BasicNCF by ``fit_implicit`` (``--negatives`` unseen items per positive, redrawn
+column, a seeded pick without), the rest trains: MF, BasicNCF and the two NeuMF by ``fit_implicit`` (``--negatives`` unseen items per positive, redrawn
 every epoch on the device), a second MF by ``fit_implicit(loss="softmax")`` (each positive against the whole catalogue, no
 negatives; ``--softmax-scale`` multiplies the logits), ImplicitALS by its own solver on the same pairs with value 1.  Each model is then reported twice: by
 ``eval_sampled`` (the held-out item among ``--candidates`` sampled unseen items, the same lists for every model) and by
@@ -26,6 +26,7 @@ from deeprecommendation_amd import (ImplicitALS, ImplicitFeedback, eval_full_ran
                                     sampled_candidates)
 from deeprecommendation_amd.neural_collaborative_filtering.models.basic_ncf import BasicNCF  # noqa: E402
 from deeprecommendation_amd.neural_collaborative_filtering.models.mf import MF  # noqa: E402
+from deeprecommendation_amd.neural_collaborative_filtering.models.neumf import NeuMF  # noqa: E402
 
 
 def fmt(m):
@@ -71,9 +72,16 @@ def main():
 
     torch.manual_seed(args.seed)
     F = args.factors
-    for name, model in (("MF", MF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F)),
-                        ("BasicNCF", BasicNCF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F, mlp_dense_layers=[2 * F, F])),
-                        ("MF softmax", MF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F))):
+    fitted = {}
+    # the paper's table: its two ablations (MF as GMF, BasicNCF as the MLP tower), then NeuMF from scratch and NeuMF initialised from
+    # the two fitted ablations (its Eq. 13, alpha = 0.5)
+    for name, make in (("MF", lambda: MF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F)),
+                       ("BasicNCF", lambda: BasicNCF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F, mlp_dense_layers=[2 * F, F])),
+                       ("NeuMF", lambda: NeuMF(item_dim=n_items, user_dim=n_users, mf_dim=F, item_emb=F, user_emb=F,
+                                               mlp_dense_layers=[2 * F, F])),
+                       ("NeuMF pretrained", lambda: NeuMF.from_pretrained(fitted["MF"], fitted["BasicNCF"], alpha=0.5)),
+                       ("MF softmax", lambda: MF(item_dim=n_items, user_dim=n_users, item_emb=F, user_emb=F))):
+        model = fitted[name] = make()
         def on_epoch(epoch, m, name=name):
             print(f"{name} epoch {epoch + 1}: sampled HR@10 {eval_sampled(m, users, held, candidates)['hr@10']:.4f}", flush=True)
         loss = "softmax" if name == "MF softmax" else args.loss
