@@ -2,9 +2,9 @@
 implicit-feedback protocol are re-exported here, imported on first use."""
 _RECOMMEND = ("top_k_items", "recommend_for_user", "seen_items", "rated_exclusion", "explain_items", "content_cosine_top_k",
               "content_cosine_ranks", "attention_statistics", "attention_stat_ratios", "AttentionStats", "diversify_top_k", "item_vectors",
-              "item_knn_top_k", "item_knn_ranks", "ease_top_k", "ease_ranks")
+              "item_knn_top_k", "item_knn_ranks", "ease_top_k", "ease_ranks", "slim_top_k", "slim_ranks")
 _RANKING_EVAL = ("rank_of_items", "ranking_metrics", "eval_full_ranking", "held_out_items", "intra_list_diversity", "catalogue_coverage")
-_BASELINES = ("KernelMF", "ItemKNN", "ImplicitALS", "EASE")
+_BASELINES = ("KernelMF", "ItemKNN", "ImplicitALS", "EASE", "SLIM")
 _IMPLICIT = ("leave_one_out", "ImplicitFeedback", "fit_implicit", "sampled_candidates", "eval_sampled", "rank_sampled")
 
 

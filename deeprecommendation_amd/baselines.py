@@ -20,8 +20,14 @@ such solve against the fixed item table.
 ``EASE`` is the closed-form item-item baseline that most often wins that comparison (Steck 2019, "Embarrassingly Shallow Autoencoders
 for Sparse Data"): W = the off-diagonal of (X^T X + reg 1)^-1 with every column divided by minus its diagonal entry, scores X W.  No
 epochs, no seeds, one hyper-parameter; the Gram matrix, its inversion (a blocked Gauss-Jordan elimination whose updates are fp32
-MFMA GEMMs), the weights and the scores all run on the device (csrc/ease.hip, THE CONTRACT in include/ncf_abi.h)."""
+MFMA GEMMs), the weights and the scores all run on the device (csrc/ease.hip, THE CONTRACT in include/ncf_abi.h).
+
+``SLIM`` is the model EASE is measured against in its own paper (Ning & Karypis 2011, "SLIM: Sparse Linear Methods for Top-N
+Recommender Systems"): the same item-item regression X ~ X W with diag(W) = 0, solved under an L1 + L2 penalty (and W >= 0) instead
+of in closed form, which makes W sparse.  Every column is one cyclic coordinate descent on EASE's Gram matrix, one workgroup per
+column, with the bits of the serial loop (csrc/slim.hip, THE CONTRACT in include/ncf_abi.h); the weights are served by EASE's scorer."""
 import math
+import numbers
 from types import SimpleNamespace
 from typing import Optional, Sequence
 
@@ -542,8 +548,65 @@ class ImplicitALS(_Baseline):
         return recommend.top_k_items(_mf_of_tables(vectors, self.item_factors_), users, k, exclude=exclude, **top_k_args)
 
 
-# ---------------------------------------------------------------------------------------- EASE
-class EASE(_Baseline):
+# ---------------------------------------------------------------------------------------- EASE and SLIM
+def _gram_matrix(rowptr, col, val, I, dev, block_bytes):
+    """The dense (I, I) fp32 Gram matrix X^T X of a checked user CSR: ncf_ease_gram over ``block_bytes`` of rows at a time, which
+    changes no bit."""
+    colptr, row, tval = build_transpose(rowptr, col, val, I)
+    G = torch.empty((I, I), dtype=torch.float32, device=dev)
+    rows = max(1, int(block_bytes) // (4 * I))
+    for i0 in range(0, I, rows):
+        i1 = min(I, i0 + rows)
+        native.ease_gram(rowptr, col, val, colptr, row, tval, (i0, i1), out=G[i0:i1])
+    return G
+
+
+class _ItemItem(_Baseline):
+    """What the models with a dense item-item matrix ``weights_`` (I, I) fp32, rows = source items, share: ``fit`` from samples,
+    the Gram-side checks, and the serving through ncf_ease_scores / ncf_ease_predict / topk_rows.  ``binary`` models read every
+    stored entry as 1.0."""
+
+    def fit(self, user_pos, item_pos, rating, num_users, num_items, **fit_args):
+        """Fits on int64 positions and fp32 ratings that live on the GPU (KernelMF.fit's arguments): the CSR is built on the device by
+        a stable sort on (user, item).  A (user, item) pair given twice raises in check()."""
+        _, num_users, num_items, _ = self._samples(user_pos, item_pos, rating, num_users, num_items)
+        rowptr, col, val = build_csr(user_pos, item_pos, rating, num_users, num_items)
+        return self.fit_csr(rowptr, col, val, num_items, **fit_args)
+
+    def _fitted(self):
+        if self.weights_ is None:
+            raise RuntimeError(f"{type(self).__name__}: not fitted")
+
+    def _ratings(self, who, ratings):
+        rowptr, col, val = _ratings_csr(who, ratings)
+        return rowptr, col, (torch.ones_like(val) if self.binary else val)
+
+    def scores(self, ratings, user_rows, item_range=None, stage_cap: int = 0):
+        """(B, i1 - i0) fp32 scores of the rows ``user_rows`` (int64) of ``ratings`` — a SparseRatings or a (rowptr, col, val) tuple
+        over the fitted items, not necessarily the fitted ratings, so new users work — against the items ``item_range`` = (i0, i1)
+        (default: all).  A ``binary`` model reads every stored entry as 1.0."""
+        self._fitted()
+        rowptr, col, val = self._ratings(f"{type(self).__name__}.scores", ratings)
+        return native.ease_scores(rowptr, col, val, user_rows.contiguous() if torch.is_tensor(user_rows) else user_rows, self.weights_,
+                                  item_range, stage_cap)
+
+    def predict(self, ratings, user_rows, item_pos):
+        """(n,) fp32 scores of the pairs (row ``user_rows[k]`` of ``ratings``, item ``item_pos[k]``), int64 both: ``scores``' values bit
+        for bit."""
+        self._fitted()
+        rowptr, col, val = self._ratings(f"{type(self).__name__}.predict", ratings)
+        return native.ease_predict(rowptr, col, val, user_rows, item_pos, self.weights_)
+
+    def similar_items(self, item_pos, k: int):
+        """"More like this": ``(scores (n, k) fp32, item_positions (n, k) int64, counts (n,) int32)`` — the ``k`` largest entries of
+        the listed rows of ``weights_``, in ``top_k_items``' form and order (native.topk_rows)."""
+        self._fitted()
+        _positions(f"{type(self).__name__}.similar_items", item_pos, "item_pos")
+        s, idx, cnt = native.topk_rows(self.weights_.index_select(0, item_pos), k)
+        return s, idx.to(torch.int64), cnt
+
+
+class EASE(_ItemItem):
     """The closed-form item-item autoencoder (csrc/ease.hip, THE CONTRACT in include/ncf_abi.h): ``weights_`` = W with
     ``W[i][j] = -P[i][j] / P[j][j]`` off the diagonal and 0 on it, ``P = (X^T X + reg 1)^-1``, and scores ``X W``.  ``binary`` fits on
     1.0 for every stored entry.  ``fit`` / ``fit_dataset`` / ``fit_csr`` (with ``at_regs``: one model per reg from one Gram matrix);
@@ -573,12 +636,7 @@ class EASE(_Baseline):
             raise ValueError(f"EASE: {I} items (at most {native.EASE_MAX_ITEMS})")
         if self.binary:
             val = torch.ones_like(val)
-        colptr, row, tval = build_transpose(rowptr, col, val, I)
-        G = torch.empty((I, I), dtype=torch.float32, device=dev)
-        rows = max(1, int(block_bytes) // (4 * I))
-        for i0 in range(0, I, rows):
-            i1 = min(I, i0 + rows)
-            native.ease_gram(rowptr, col, val, colptr, row, tval, (i0, i1), out=G[i0:i1])
+        G = _gram_matrix(rowptr, col, val, I, dev, block_bytes)
         if regs is None:
             self._finish(G, I)
             return self
@@ -594,13 +652,6 @@ class EASE(_Baseline):
         self.weights_, self.num_items_ = native.ease_weights(native.ease_invert(G, self.reg)), I
         self.check()
 
-    def fit(self, user_pos, item_pos, rating, num_users, num_items, **fit_args):
-        """Fits on int64 positions and fp32 ratings that live on the GPU (KernelMF.fit's arguments): the CSR is built on the device by
-        a stable sort on (user, item).  A (user, item) pair given twice raises in check()."""
-        _, num_users, num_items, _ = self._samples(user_pos, item_pos, rating, num_users, num_items)
-        rowptr, col, val = build_csr(user_pos, item_pos, rating, num_users, num_items)
-        return self.fit_csr(rowptr, col, val, num_items, **fit_args)
-
     def check(self):
         """Synchronises.  Raises ValueError when a fit walked a row whose columns do not strictly ascend or met a pivot that is not
         positive and finite (the weights are then zeros), and IndexError when a kernel of this device met an id outside its range;
@@ -610,35 +661,97 @@ class EASE(_Baseline):
         native.check_ease(dev)
         native.check_oob(dev)
 
-    def _fitted(self):
-        if self.weights_ is None:
-            raise RuntimeError("EASE: not fitted")
 
-    # ------------------------------------------------------------------ scoring
-    def _ratings(self, who, ratings):
-        rowptr, col, val = _ratings_csr(who, ratings)
-        return rowptr, col, (torch.ones_like(val) if self.binary else val)
+# ---------------------------------------------------------------------------------------- SLIM
+class SLIM(_ItemItem):
+    """Sparse linear item-item weights (csrc/slim.hip, THE CONTRACT in include/ncf_abi.h): column j of ``weights_`` minimises
+    ``1/2 |x_j - X w|^2 + 1/2 l2_reg |w|^2 + l1_reg |w|_1`` with ``w[j] = 0`` — and ``w >= 0`` with ``positive`` — by cyclic
+    coordinate descent on the Gram matrix, at most ``max_sweeps`` sweeps, until a sweep moves no weight by more than ``tol``.
+    ``binary`` fits on 1.0 for every stored entry.  ``fit`` / ``fit_dataset`` / ``fit_csr`` (with ``at_regs``: one model per
+    (l1, l2) from one Gram matrix); then ``scores``, ``predict``, ``similar_items``; ``recommend.slim_top_k`` / ``slim_ranks`` rank
+    with it.  After a fit: ``sweeps_`` / ``steps_`` (I,) int32 and ``last_delta_`` (I,) fp32 per item's column, and, from
+    ``check()``, ``density_`` (the share of ``weights_`` that is not zero) and ``n_unconverged_`` (columns whose last sweep still
+    moved a weight by more than ``tol``; not an error).  A fit is a fixed function of its inputs, bit for bit the serial loop.
+    There is no host path."""
 
-    def scores(self, ratings, user_rows, item_range=None, stage_cap: int = 0):
-        """(B, i1 - i0) fp32 scores of the rows ``user_rows`` (int64) of ``ratings`` — a SparseRatings or a (rowptr, col, val) tuple
-        over the fitted items, not necessarily the fitted ratings, so new users work — against the items ``item_range`` = (i0, i1)
-        (default: all).  A ``binary`` model reads every stored entry as 1.0."""
+    def __init__(self, l1_reg, l2_reg, positive=True, max_sweeps=100, tol=1e-4, binary=False):
+        who = "SLIM"
+        self.l1_reg, self.l2_reg = _finite(who, l1_reg, "l1_reg", 0.0), _finite(who, l2_reg, "l2_reg", 0.0)
+        self.tol = _finite(who, tol, "tol", 0.0)
+        self.max_sweeps = _int_in(who, max_sweeps, "max_sweeps", 1, INT_MAX)
+        for v, what in ((positive, "positive"), (binary, "binary")):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"{who}: {what} = {v!r} is not a bool")
+        self.positive, self.binary = bool(positive), bool(binary)
+        self.weights_ = None                                # (I, I) fp32, rows = source items
+        self.num_items_ = None
+        self.sweeps_ = self.steps_ = self.last_delta_ = None
+        self.density_ = self.n_unconverged_ = None
+
+    @classmethod
+    def elastic_net(cls, alpha, l1_ratio, num_users, **kw):
+        """The model of scikit-learn's ``ElasticNet(alpha, l1_ratio)`` fitted per item on ``num_users`` rows, whose objective is this
+        one divided by the number of rows: ``l1_reg = alpha * l1_ratio * num_users``, ``l2_reg = alpha * (1 - l1_ratio) * num_users``."""
+        who = "SLIM.elastic_net"
+        alpha, l1_ratio = _finite(who, alpha, "alpha", 0.0), _finite(who, l1_ratio, "l1_ratio", 0.0)
+        if l1_ratio > 1:
+            raise ValueError(f"{who}: l1_ratio = {l1_ratio} is not in 0 .. 1")
+        U = _int_in(who, num_users, "num_users", 1, INT_MAX)
+        return cls(alpha * l1_ratio * U, alpha * (1.0 - l1_ratio) * U, **kw)
+
+    def _like(self, l1_reg, l2_reg):
+        return SLIM(l1_reg, l2_reg, positive=self.positive, max_sweeps=self.max_sweeps, tol=self.tol, binary=self.binary)
+
+    # ------------------------------------------------------------------ fit
+    def fit_csr(self, rowptr, col, val, num_items, block_bytes: int = 256 << 20, at_regs: Optional[Sequence] = None,
+                warm_path: bool = False):
+        """Fits on a user CSR on the GPU: ``rowptr`` (U + 1) int64, ``col`` int32 item positions strictly ascending inside a row,
+        ``val`` fp32 (SparseRatings' arrays as they are).  The Gram rows are computed ``block_bytes`` at a time, which changes no
+        bit; the columns are handed to the solver heaviest first (descending ``G[j][j]``, ties by position), which changes none
+        either.  With ``at_regs`` = [(l1, l2), ...] the Gram matrix is computed once and a list of fitted models is returned, one per
+        point, each a cold fit with the bits of its own fit.  With ``warm_path`` every point after the first starts from the
+        weights of the point before it: fewer sweeps along a path of falling penalties, but the bits of a point then depend on the
+        path that led to it.  Synchronises in check(), once per fitted model."""
+        if not isinstance(warm_path, (bool, np.bool_)):
+            raise ValueError(f"SLIM: warm_path = {warm_path!r} is not a bool")
+        if at_regs is not None and not all(isinstance(r, (tuple, list)) and len(r) == 2 for r in at_regs):
+            raise ValueError("SLIM: at_regs must hold (l1_reg, l2_reg) pairs")
+        models = None if at_regs is None else [self._like(*r) for r in at_regs]
+        if isinstance(num_items, bool) or not isinstance(num_items, numbers.Integral):
+            raise ValueError(f"SLIM: num_items = {num_items!r} is not an integer")
+        if num_items > native.SLIM_MAX_ITEMS:                # before anything is converted or allocated
+            raise ValueError(f"SLIM: {int(num_items)} items (at most {native.SLIM_MAX_ITEMS})")
+        rowptr, col, val, I, dev = self._csr(rowptr, col, val, num_items)
+        if self.binary:
+            val = torch.ones_like(val)
+        G = _gram_matrix(rowptr, col, val, I, dev, block_bytes)
+        order = torch.argsort(G.diagonal(), descending=True, stable=True).to(torch.int32)
+        Wt = None
+        for m in [self] if models is None else models:
+            warm = bool(warm_path) and Wt is not None
+            Wt = m._solve(G, order, Wt if warm else None)
+        return self if models is None else models
+
+    def _solve(self, G, order, Wt):
+        """One solve of every column, warm from ``Wt`` (then updated in place) when given; sets the fitted attributes and checks."""
+        warm = Wt is not None
+        if not warm:                                         # `order` lists every column once, and a cold solve writes the whole of each listed row
+            Wt = torch.empty_like(G)
+        Wt, sweeps, steps, last = native.slim_solve(G, self.l1_reg, self.l2_reg, order, self.positive, warm, self.max_sweeps, self.tol,
+                                                    out=Wt)
+        by_item = order.to(torch.int64)
+        self.sweeps_, self.steps_, self.last_delta_ = (torch.empty_like(t).index_copy_(0, by_item, t) for t in (sweeps, steps, last))
+        self.weights_, self.num_items_ = Wt.t().contiguous(), G.shape[0]
+        self.check()
+        return Wt
+
+    def check(self):
+        """Synchronises.  Raises ValueError when a fit walked a row whose columns do not strictly ascend, and IndexError when a kernel
+        of this device met an id outside its range; each raises once and is then cleared.  A column that met ``max_sweeps`` raises
+        nothing: it is counted in ``n_unconverged_``, which this sets together with ``density_``."""
         self._fitted()
-        rowptr, col, val = self._ratings("EASE.scores", ratings)
-        return native.ease_scores(rowptr, col, val, user_rows.contiguous() if torch.is_tensor(user_rows) else user_rows, self.weights_,
-                                  item_range, stage_cap)
-
-    def predict(self, ratings, user_rows, item_pos):
-        """(n,) fp32 scores of the pairs (row ``user_rows[k]`` of ``ratings``, item ``item_pos[k]``), int64 both: ``scores``' values bit
-        for bit."""
-        self._fitted()
-        rowptr, col, val = self._ratings("EASE.predict", ratings)
-        return native.ease_predict(rowptr, col, val, user_rows, item_pos, self.weights_)
-
-    def similar_items(self, item_pos, k: int):
-        """"More like this": ``(scores (n, k) fp32, item_positions (n, k) int64, counts (n,) int32)`` — the ``k`` largest entries of
-        the listed rows of ``weights_``, in ``top_k_items``' form and order (native.topk_rows)."""
-        self._fitted()
-        _positions("EASE.similar_items", item_pos, "item_pos")
-        s, idx, cnt = native.topk_rows(self.weights_.index_select(0, item_pos), k)
-        return s, idx.to(torch.int64), cnt
+        dev = self.weights_.device
+        native.check_ease(dev)
+        native.check_oob(dev)
+        self.density_ = float(torch.count_nonzero(self.weights_).item()) / float(self.weights_.numel())
+        self.n_unconverged_ = int((self.last_delta_ > self.tol).sum().item())

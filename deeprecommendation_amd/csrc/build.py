@@ -10,7 +10,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ["abi.hip", "gather.hip", "mlp_fused.hip", "linear.hip", "spmm.hip", "edge_softmax.hip", "attn.hip", "attn_split.hip", "attn_cand.hip", "attn_tail.hip", "attn_cross.hip", "attn_explain.hip", "attn_stats.hip", "mlp_bf16.hip", "mlp_bf16_ws8.hip", "backward.hip", "adam_rows.hip", "exchange.hip", "dense_csr.hip", "pair_rows.hip", "probe.hip", "topk.hip", "dot_topk.hip", "dot_softmax.hip", "mlp_topk.hip", "neumf.hip", "mlp_partial.hip", "negsample.hip", "rank.hip", "edge_keep.hip", "gat.hip", "user_profiles.hip", "kmf.hip", "mmr.hip", "knn.hip", "als.hip", "unseen.hip", "ease.hip"]
+SOURCES = ["abi.hip", "gather.hip", "mlp_fused.hip", "linear.hip", "spmm.hip", "edge_softmax.hip", "attn.hip", "attn_split.hip", "attn_cand.hip", "attn_tail.hip", "attn_cross.hip", "attn_explain.hip", "attn_stats.hip", "mlp_bf16.hip", "mlp_bf16_ws8.hip", "backward.hip", "adam_rows.hip", "exchange.hip", "dense_csr.hip", "pair_rows.hip", "probe.hip", "topk.hip", "dot_topk.hip", "dot_softmax.hip", "mlp_topk.hip", "neumf.hip", "mlp_partial.hip", "negsample.hip", "rank.hip", "edge_keep.hip", "gat.hip", "user_profiles.hip", "kmf.hip", "mmr.hip", "knn.hip", "als.hip", "unseen.hip", "ease.hip", "slim.hip"]
 LIB = os.path.join(PKG, "libncf_hip.so")
 ARCH = "gfx950"
 # per-file flags.  mlp_bf16.hip: MFMA accumulators in VGPRs instead of AGPRs (the ReLU / bf16 conversion of the hidden
@@ -24,10 +24,11 @@ ARCH = "gfx950"
 # (tests/als_ref.py, bit for bit)
 # ease.hip: the same — every product, sum and quotient of a Gram row, a weight and a score (tests/ease_ref.py, bit for bit); the MFMA
 # builtins of its inversion are not touched by the flag
+# slim.hip: the same — every product, sum and quotient of a coordinate update and of its axpy (tests/slim_ref.py, bit for bit)
 EXTRA_FLAGS = {"mlp_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "mlp_bf16_ws8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "user_profiles.hip": ["-ffp-contract=off"], "kmf.hip": ["-ffp-contract=off"], "mmr.hip": ["-ffp-contract=off"],
                "knn.hip": ["-ffp-contract=off"], "als.hip": ["-ffp-contract=off"],
-               "ease.hip": ["-ffp-contract=off"]}
+               "ease.hip": ["-ffp-contract=off"], "slim.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

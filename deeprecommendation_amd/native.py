@@ -167,6 +167,8 @@ SIGNATURES = {
     "ncf_ease_scores": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_p, _c_i64,
                                  _c_p, _c_p]),
     "ncf_ease_predict": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "ncf_slim_solve": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_i64, ctypes.c_float, ctypes.c_float, _c_int, _c_int, _c_int, ctypes.c_float,
+                                _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "ncf_mmr_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "ncf_mmr_rerank": (_c_int, [_c_p, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, ctypes.c_float, _c_int, _c_p, _c_p,
                                 _c_p, _c_p, _c_p]),
@@ -1938,6 +1940,51 @@ def ease_predict(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, use
         _check(lib.ncf_ease_predict(_ptr(rowptr), _ptr(col), _ptr(val), nnz, R, _ptr(users), _ptr(items), n, _ptr(W), I, ldw, _ptr(out),
                                     _ptr(_oob_flag(rowptr.device)), _stream(rowptr)))
     return out
+
+
+SLIM_MAX_ITEMS = 32768       # include/ncf_abi.h NCF_SLIM_MAX_ITEMS
+
+
+def slim_solve(G: torch.Tensor, l1: float, l2: float, cols: Optional[torch.Tensor] = None, positive: bool = True, warm: bool = False,
+               max_sweeps: int = 100, tol: float = 1e-4, out: Optional[torch.Tensor] = None):
+    """Columns ``cols`` (int32, default: all, in ascending order) of the SLIM weights of the square fp32 Gram matrix ``G`` by cyclic
+    coordinate descent (ncf_slim_solve, THE CONTRACT in include/ncf_abi.h): column j minimises 1/2 w^T G w - G[j]^T w +
+    1/2 l2 |w|^2 + l1 |w|_1 with w[j] = 0, and w >= 0 with ``positive``.  Returns ``(Wt, sweeps, steps, last)``: ``Wt`` (I, I) fp32
+    whose ROW j is column j of W (``out``: a tensor to write into, any row stride; rows that are not listed keep what they hold, and
+    are zeros in a tensor allocated here), and per listed column its sweeps (int32), its updates with delta != 0 (int32) and the
+    largest |delta| of its last sweep (fp32: above ``tol`` the column met ``max_sweeps`` first).  ``warm``: start from the rows of
+    ``out``.  One workgroup per listed column, started in list order; bit for bit tests/slim_ref.py.  A column outside the items
+    raises at the next check_oob().  Checked before the device is; two launches on the current stream."""
+    who = "slim_solve"
+    I, ldg = _ease_matrix(who, G, "G")
+    if I > SLIM_MAX_ITEMS:
+        raise ValueError(f"{who}: {I} items (at most {SLIM_MAX_ITEMS})")
+    l1, l2, tol = _finite(who, l1, "l1", 0.0), _finite(who, l2, "l2", 0.0), _finite(who, tol, "tol", 0.0)
+    max_sweeps = _int_in(who, max_sweeps, "max_sweeps", 1, 2 ** 31 - 1)
+    for v, what in ((positive, "positive"), (warm, "warm")):
+        if not isinstance(v, bool):
+            raise ValueError(f"{who}: {what} = {v!r} is not a bool")
+    if cols is not None:
+        _vec1d(who, cols, "cols", torch.int32)
+    if warm and out is None:
+        raise ValueError(f"{who}: a warm start reads its rows from out")
+    given = out is not None
+    out = _out2d(who, out, I, I, G, ((G, "G"), (cols, "cols")))
+    lib = load_library()
+    dev = G.device
+    if cols is None:
+        cols = torch.arange(I, dtype=torch.int32, device=dev)
+    elif not given:
+        out.zero_()
+    n = cols.numel()
+    sweeps = torch.empty(n, dtype=torch.int32, device=dev)
+    steps = torch.empty(n, dtype=torch.int32, device=dev)
+    last = torch.empty(n, dtype=torch.float32, device=dev)
+    if n:
+        _check(lib.ncf_slim_solve(_ptr(G), I, ldg, _ptr(cols), n, l1, l2, 1 if positive else 0, 1 if warm else 0, max_sweeps, tol, _ptr(out),
+                                  max(out.stride(0), I) if I > 1 else max(I, 1), _ptr(sweeps), _ptr(steps), _ptr(last),
+                                  _ptr(_oob_flag(dev)), _stream(G)))
+    return out, sweeps, steps, last
 
 
 ALS_MAX_FACTORS, ALS_GRAM_ROWS, ALS_SEG = 128, 256, 512       # include/ncf_abi.h NCF_ALS_*

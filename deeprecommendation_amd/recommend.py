@@ -11,6 +11,8 @@
                        the neighbourhood baseline: a fitted ``baselines.ItemKNN`` scored over the catalogue (ncf_knn_scores) and ranked.
 ``ease_top_k`` / ``ease_ranks``
                        the closed-form item-item baseline: a fitted ``baselines.EASE`` scored over the catalogue (ncf_ease_scores) and ranked.
+``slim_top_k`` / ``slim_ranks``
+                       the sparse item-item baseline: a fitted ``baselines.SLIM`` scored and ranked through the same scorer.
 ``diversify_top_k``    greedy MMR re-ranking of the pools those two return (native.mmr_rerank, one launch): relevance traded against the
                        similarity to what is already in the list.  ``item_vectors`` gives a model's own item space for it.
 ``seen_items``         the exclusion lists of a graph's users (their training interactions) for top_k_items.
@@ -454,10 +456,11 @@ def item_knn_ranks(model, ratings, user_ids: torch.Tensor, targets: Tuple[torch.
     return _rank_blocks(_knn_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), targets, exclude)
 
 
-# ---------------------------------------------------------------------------------------- EASE baseline
-def _ease_blocks(model, ratings, user_ids, item_ids, block_bytes):
-    """Yields ``(b0, b1, scores (b1 - b0, I))`` of the listed rows of ``ratings`` under a fitted ``baselines.EASE``: one ncf_ease_scores
-    launch per block of users over the whole catalogue, the ranked list's columns gathered from it."""
+# ---------------------------------------------------------------------------------------- EASE and SLIM baselines
+def _item_item_blocks(model, ratings, user_ids, item_ids, block_bytes):
+    """Yields ``(b0, b1, scores (b1 - b0, I))`` of the listed rows of ``ratings`` under a fitted model with a dense item-item matrix
+    (``baselines.EASE``, ``baselines.SLIM``: ``_fitted()``, ``num_items_`` and ``scores``): one ncf_ease_scores launch per block of
+    users over the whole catalogue, the ranked list's columns gathered from it."""
     _position_lists(user_ids=user_ids, item_ids=item_ids)
     model._fitted()
     require_gpu(user_ids, item_ids)
@@ -473,7 +476,7 @@ def ease_top_k(model, ratings, user_ids: torch.Tensor, k: int, item_ids: Optiona
     ``baselines.EASE``; every other argument and the returned ``(scores (B, k), item_positions (B, k) int64, counts (B,) int32)`` as in
     ``item_knn_top_k``."""
     model._fitted()
-    return _select_blocks(_ease_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), k, exclude, item_ids,
+    return _select_blocks(_item_item_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), k, exclude, item_ids,
                           user_ids.device)
 
 
@@ -483,7 +486,26 @@ def ease_ranks(model, ratings, user_ids: torch.Tensor, targets: Tuple[torch.Tens
     """The ranks twin of ``ease_top_k``: ``(rank (n_targets,) int32, ranked (B,) int32)`` of each listed user's held-out items under
     the EASE scores, with the meaning ``rank_of_items`` gives them (``ranking_metrics`` takes them as they are)."""
     model._fitted()
-    return _rank_blocks(_ease_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), targets, exclude)
+    return _rank_blocks(_item_item_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), targets, exclude)
+
+
+def slim_top_k(model, ratings, user_ids: torch.Tensor, k: int, item_ids: Optional[torch.Tensor] = None,
+               exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, block_bytes: int = BLOCK_BYTES):
+    """The SLIM baseline's recommendations: the ``k`` items with the largest SLIM score for each listed user.  model: a fitted
+    ``baselines.SLIM``; every other argument and the returned ``(scores (B, k), item_positions (B, k) int64, counts (B,) int32)`` as in
+    ``item_knn_top_k``."""
+    model._fitted()
+    return _select_blocks(_item_item_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), k, exclude, item_ids,
+                          user_ids.device)
+
+
+def slim_ranks(model, ratings, user_ids: torch.Tensor, targets: Tuple[torch.Tensor, torch.Tensor],
+               item_ids: Optional[torch.Tensor] = None, exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               block_bytes: int = BLOCK_BYTES):
+    """The ranks twin of ``slim_top_k``: ``(rank (n_targets,) int32, ranked (B,) int32)`` of each listed user's held-out items under
+    the SLIM scores, with the meaning ``rank_of_items`` gives them (``ranking_metrics`` takes them as they are)."""
+    model._fitted()
+    return _rank_blocks(_item_item_blocks(model, ratings, user_ids, item_ids, block_bytes), user_ids.numel(), targets, exclude)
 
 
 # ---------------------------------------------------------------------------------------- diversified top-K

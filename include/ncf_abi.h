@@ -1044,6 +1044,49 @@ int ncf_ease_predict(const int64_t* dev_rowptr, const int32_t* dev_col, const fl
                      float* dev_out, int32_t* dev_oob_flag, ncf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SLIM (csrc/slim.hip) — the sparse item-item baseline EASE is measured against (Ning & Karypis 2011, "SLIM: Sparse Linear Methods
+ * for Top-N Recommender Systems"): the same regression X ~ X W, diag(W) = 0, with an L1 + L2 penalty (and W >= 0) instead of a closed
+ * form.  Column j of W minimises
+ *       1/2 w^T G w - G[j]^T w + 1/2 l2 |w|^2 + l1 |w|_1,   w[j] = 0   (and w >= 0 when `positive`),     G = X^T X
+ * by cyclic coordinate descent on the Gram matrix of ncf_ease_gram; W is scored by ncf_ease_scores / ncf_ease_predict.
+ * Replaces: nothing in the reference; on a host it is scikit-learn's ElasticNet once per item, and the torch composition updates
+ * all columns at once with one dense rank-1 update of an I x I matrix per coordinate.
+ * THE CONTRACT (csrc/slim.hip is built with -ffp-contract=off and without any fast-math flag; the division is the correctly rounded
+ * one).  State of a column: w (I) and q = G w (I), both +0.0f at a cold start, and d[k] = G[k][k].  One sweep visits k = 0 .. I - 1
+ * in ascending order and skips k == j:
+ *       t = d[k] * w[k];  r = q[k] - t;  rho = G[j][k] - r;  den = d[k] + l2
+ *       positive:  a = rho - l1;  wn = (a > 0 && den > 0) ? a / den : +0.0f
+ *       signed:    rho >  l1 && den > 0 -> (rho - l1) / den
+ *                  rho < -l1 && den > 0 -> (rho + l1) / den
+ *                  else +0.0f
+ *       delta = wn - w[k]
+ *       if delta != 0:  for every i: q[i] = q[i] + delta * G[k][i];  w[k] = wn;  steps += 1
+ *   every product, sum and quotient rounded on its own.
+ *   Stopping: a column stops after the first sweep whose largest |delta| is <= tol, or after max_sweeps.
+ *   Warm start (warm != 0): w is taken from the output row, with w[j] = +0.0f, and q is rebuilt as
+ *       q = +0;  for k ascending with w[k] != 0:  q = q + w[k] * G[k]
+ *     before the first sweep.
+ *   Per-column outputs: the row of w, sweeps (int32), steps (int32, the updates with delta != 0) and last (fp32, the largest |delta|
+ *     of the last sweep; last > tol says the column met max_sweeps first — there is no error bit for that).
+ *   No reduction over floats occurs anywhere in this, so the result is ONE function of the inputs that a host restates bit for bit
+ *   (tests/slim_ref.py), sweeps and steps included, whatever the workgroup size.  The kernel screens a block of coordinates side by
+ *   side against an unchanged q and applies the first one with delta != 0, which is the one the serial loop would have applied.
+ * dev_G: (I, I) fp32, rows of ldg floats.  dev_cols: (n,) int32, the columns to solve, in the order their workgroups start (the host
+ * lists the heaviest, by d[j], first).  dev_Wt: (I, ldw) fp32 — row dev_cols[c] receives COLUMN dev_cols[c] of W; rows that are not
+ * listed and the floats of a row past I are not touched.  dev_sweeps / dev_steps / dev_last: (n,), indexed by c.  A column outside
+ * [0, I) sets the sticky *dev_oob_flag (when non-NULL), touches no row and reports 0 / 0 / +0.0f.  A column listed again is solved
+ * once: every listing reports the first listing's three outputs.  q lives in LDS, 4 I bytes of it (above 64 KiB the dynamic-LDS
+ * limit is raised): NCF_SLIM_MAX_ITEMS is what fits beside the ballot slots.
+ * Refusals, before any launch, with the entry's name in ncf_last_error(): NCF_EINVAL for a negative size, ld below the width, l1 or
+ * l2 negative or not finite, tol negative or not finite, max_sweeps < 1, a misaligned array, or a NULL array that the sizes say is
+ * read or written; NCF_EUNSUPPORTED for I > NCF_SLIM_MAX_ITEMS.  n == 0 returns NCF_OK without a launch.
+ * ------------------------------------------------------------------------------------------------ */
+#define NCF_SLIM_MAX_ITEMS 32768
+int ncf_slim_solve(const float* dev_G, int64_t I, int64_t ldg, const int32_t* dev_cols, int64_t n, float l1, float l2, int positive,
+                   int warm, int max_sweeps, float tol, float* dev_Wt, int64_t ldw, int32_t* dev_sweeps, int32_t* dev_steps,
+                   float* dev_last, int32_t* dev_oob_flag, ncf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Diversified top-K (csrc/mmr.hip) — greedy Maximal Marginal Relevance (MMR) re-ranking of one candidate pool per user, the pools
  * being what ncf_topk_rows / ncf_dot_topk / ncf_mlp_topk return.  Replaces: nothing in the reference, which stops at the relevance
  * list; a torch composition needs a (B, N, N) Gram tensor and K rounds of masked arg-max launches.
